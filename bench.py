@@ -27,6 +27,7 @@ libamdhip64) and the librccl next to that runtime are all it maps (config.ranks[
 The JSON line: the contract's keys, `roofline` (dominant kernel alone on the GPU by HIP events on its own stream; inside it, because
 the driver's record keeps that object whole: other_kernels, whole_step, other_configs = BASELINE configs[1..3] + the dense-matrix form of
 configs[3], pcie_inclusive_value, four_beads_in_flight) and `cpu_baseline` (the reference's own object code on one host core).
+--dump-outputs DIR also writes what the last timed step computed as .npy files (dump_outputs), for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -139,6 +140,45 @@ def cpu_baseline(kind: str, atoms, basis, opts, workdir: str, gpu_bead0):
         out["parity_rel_err_by_term"] = errs
         out["gpu_energy_same_configuration"] = gpu_bead0["energy"]
     return out
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: cap of all files together
+DUMP_SAMPLE_SEED = 1234  # atoms of the per-atom arrays when every atom would pass the cap
+BEAD_TERMS = ("energy", "rd_energy", "coulombic_energy", "polarization_energy", "vdw_energy")
+
+
+def dump_outputs(outdir: str, v: float, obs, per, beads, bead_ids) -> list:
+    """--dump-outputs: what the last timed step handed back, one float64 .npy per array.  With the same arguments the inputs are the same
+    from run to run (seeded box, seeded bead displacements), so two builds can be compared output for output.
+      potential.npy          ()          V of PI_calculate_potential (K)
+      observables.npy        (4,)        the bead averages of {rd, coulombic, polarization, vdw} it returns with V
+      bead_ids.npy           (b,)        the beads this process evaluated (all P of them on one GPU)
+      bead_energies.npy      (b, 5)      per bead: BEAD_TERMS
+      dipole_atoms.npy       (k,)        atom indices of the two arrays below: every atom, or a fixed seeded sample where every atom would pass
+                                         DUMP_MAX_BYTES
+      bead_dipoles.npy       (b, k, 3)   induced dipoles of every bead (polarizable boxes only)
+      bead_static_field.npy  (b, k, 3)   static field of every bead (polarizable boxes only)"""
+    from mpmcxx_amd import energy
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"potential": np.float64(v), "observables": np.asarray(obs, dtype=np.float64),
+              "bead_ids": np.asarray(bead_ids, dtype=np.float64),
+              "bead_energies": np.array([[p[k] for k in BEAD_TERMS] for p in per], dtype=np.float64).reshape(-1, len(BEAD_TERMS))}
+    try:
+        fields = [s.dipoles()[:2] for s in beads]
+    except energy.MpmcError:
+        fields = []  # (no polarization evaluation in this configuration)
+    if fields:
+        n = beads[0].n
+        fixed = sum(a.nbytes for a in arrays.values()) + 4096
+        k = min(n, (DUMP_MAX_BYTES - fixed) // (len(beads) * 2 * 3 * 8 + 8))
+        idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+        arrays["dipole_atoms"] = idx.astype(np.float64)
+        arrays["bead_dipoles"] = np.stack([mu[idx] for mu, _ in fields])
+        arrays["bead_static_field"] = np.stack([e[idx] for _, e in fields])
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
+    return sorted(f"{name}.npy" for name in arrays)
 
 
 def sweep_flops(ps, cut: float, polar: bool) -> float:
@@ -310,7 +350,11 @@ def main():
                     help="one GPU, N beads in flight on it -- the per-GPU load of an (--beads / N)-GPU run, everything else as in that run; NOT the headline")
     ap.add_argument("--configure", action="append", default=[], metavar="KEY=VALUE",
                     help="measurement switch for every context of this run (mpmc_debug_configure, e.g. side_stream=0 pair_kernel=1); repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     inprocess = args.launch == "inprocess" and args.gpus > 1
     from mpmcxx_amd import ranks  # (pure Python: no GPU runtime is loaded by this import)
@@ -492,6 +536,9 @@ def main():
         s.timings(reset=True)
     dt, v, obs = timed(args.steps)
     gpu_bead0 = dict(state["per"][0]) if (rank == 0 and state["per"]) else None
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before the passes below evaluate the beads again
+        dumped = dump_outputs(args.dump_outputs, v, obs, state["per"], beads, mine)
     extra = not args.no_extra_passes
     if not events_in_region and extra:
         # what the kernels look like with the other beads in flight: a SEPARATE short pass behind the timed region, events on bead 0's stream
@@ -707,6 +754,8 @@ def main():
                                           f"{args.beads}-bead ensemble, without the 4-double collective.  NOT the headline workload")
         if pcie is not None:
             out["pcie_inclusive_value"] = pcie["value"]
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         if args.host_positions:
             out["note_host_positions"] = "positions of every bead handed over in host memory inside every timed step (PCIe-inclusive rate, not the headline)"
         if n_gpus == 1 and args.cpu_baseline != "none":

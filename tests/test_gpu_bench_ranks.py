@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import util
@@ -131,3 +132,23 @@ def test_inprocess_launch_on_two_devices():
     a, b = last_json(one.stdout), last_json(inp.stdout)
     assert all(r["comm_n_ranks"] == 2 and r["distinct_devices"] == 2 for r in b["config"]["ranks"])
     assert a["V_mean_K"] == b["V_mean_K"]
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_run_to_run(single, tmp_path):
+    """--dump-outputs DIR: the arrays of the last timed step as float64 .npy files -- the potential and observables of the JSON line, per-bead
+    energies, induced dipoles and static fields of every bead -- and with the same arguments the same arrays bit for bit in a second run."""
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / str(k))
+        r = run([sys.executable, "bench.py", "--gpus", "1", "--no-extra-passes", "--dump-outputs", d] + ARGS, clean_env())
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = last_json(r.stdout)
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and sorted(res["dumped_outputs"]["files"]) == sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert arrays["potential"] == res["V_mean_K"] == single["V_mean_K"] and arrays["observables"].tolist() == res["obs_rd_es_pol_vdw"]
+        dumps.append(arrays)
+    a, b = dumps
+    assert a["bead_ids"].tolist() == [0, 1, 2, 3] and a["bead_energies"].shape == (4, 5)
+    assert a["bead_dipoles"].shape == a["bead_static_field"].shape == (4, 1000, 3) and np.abs(a["bead_dipoles"]).max() > 0
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
