@@ -203,9 +203,14 @@ int mpmc_hint_in_flight(mpmc_ctx *ctx, int n_evaluations);
  * The reference re-evaluates only the pairs whose displacement changed (Pair::recalculate_energy, src/System.cpp:1211-1224,
  * src/System.Energy.cpp:925,1484).  After a full mpmc_energy() of the accepted configuration:
  *   mpmc_trial_begin  : atoms [first, first+count) (original order; typically one molecule) get trial positions
- *   mpmc_trial_energy : energy of the trial configuration.  Non-polarizable boxes: O(count * N) pair terms (old and new
- *                       geometry of every pair that involves a moved atom) + O(K * count) structure-factor update, added
- *                       to the accepted totals.  Polarizable boxes: a full evaluation (the dipole solve is global).
+ *   mpmc_trial_energy : energy of the trial configuration.  For count <= MPMC_TRIAL_MAX_ATOMS: O(count * N) pair terms (old
+ *                       and new geometry of every pair that involves a moved atom) + O(K * count) structure-factor update,
+ *                       added to the accepted totals.  Polarizable boxes without Wolf take the same delta path for the
+ *                       pair energies and the real-space static field, rebuild the Thole tensors of the moved atoms' tiles
+ *                       and solve the dipoles again (the solve is global).  A full evaluation of the trial configuration
+ *                       runs instead for count > MPMC_TRIAL_MAX_ATOMS; for polarizable boxes under Wolf; with the tuning
+ *                       switch polar_delta = 0; and, in a polarizable box, after a rejected full trial until the next
+ *                       accepted trial or mpmc_energy().
  *   mpmc_trial_accept : the trial configuration becomes the accepted one / mpmc_trial_reject : it is discarded.
  * A full mpmc_energy() at any time re-bases the totals (the reference's flag_all_pairs, src/System.cpp:1284).
  * Trial positions equal to the accepted ones cost nothing: the trial totals are the accepted totals, no kernel runs. */

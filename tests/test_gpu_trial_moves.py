@@ -12,16 +12,8 @@ from mpmcxx_amd import energy
 pytestmark = pytest.mark.gpu
 
 
-def molecules(atoms):
-    ids = atoms["mol_id"]
-    starts = [0] + [i for i in range(1, len(ids)) if ids[i] != ids[i - 1]] + [len(ids)]
-    return [(starts[k], starts[k + 1]) for k in range(len(starts) - 1)]
-
-
-def nonpolar(opts):
-    o = dict(opts)
-    o.update(polarization=0, polar_iterative=0)
-    return o
+molecules = util.molecules
+nonpolar = util.nonpolar
 
 
 @pytest.mark.parametrize("name,polar", [("lj64", False), ("ion64_es", False), ("water64_polar", False), ("ion216_triclinic", False),
@@ -32,6 +24,7 @@ def nonpolar(opts):
 def test_trial_moves_track_full_evaluations(name, polar):
     from oracle import OracleSystem
 
+    # Per component: 1e-11 relative against a fresh context, 1e-9 relative against the oracle, no absolute floor (util.component_errors)
     atoms, basis, opts = util.load_fixture(name)
     if not polar:
         opts = nonpolar(opts)
@@ -51,24 +44,10 @@ def test_trial_moves_track_full_evaluations(name, polar):
         assert not S.last_trial_was_full(), name
         full_pos = pos.copy()
         full_pos[a:b] = trial
-        at2 = dict(atoms)
-        at2["pos"] = full_pos
-        T = energy.System(at2, basis, opts)
-        e_full = T.energy()
-        for k in ("energy", "rd_energy", "coulombic_energy", "es_real", "es_recip", "lj_pairs"):
-            x, y = S.trial_observables[k], T.observables[k]
-            assert abs(x - y) <= 1e-11 * max(abs(y), abs(T.observables["energy"]) * 1e-3) + 1e-9, (name, step, k, x, y)
-        assert S.trial_observables["n_lj_in_cutoff"] == T.observables["n_lj_in_cutoff"]
-        assert S.trial_observables["n_es_in_cutoff"] == T.observables["n_es_in_cutoff"]
-        assert util.close(e_trial, e_full, 1e-11)
-        T.close()
-        # ... and the ORACLE on the same trial configuration, every step (1e-9, counts bit-exact)
-        ref_t = OracleSystem(at2, basis, opts).energy(want_atoms=False)
-        for k in ("energy", "rd_energy", "coulombic_energy", "polarization_energy"):
-            assert abs(S.trial_observables[k] - ref_t[k]) <= 1e-9 * max(abs(ref_t[k]), 1e-3 * abs(ref_t["energy"])), (name, step, k)
-        assert S.trial_observables["n_lj_in_cutoff"] == ref_t["n_lj_in_cutoff"]
-        if polar:
-            assert S.trial_observables["polar_iterations"] == ref_t["polar_iterations"]
+        util.check_trial_against_fresh(S, atoms, basis, opts, full_pos, rel=1e-11, label=f"{name} step {step}")
+        # ... and the ORACLE on the same trial configuration, every step (1e-9 per component, counts bit-exact)
+        ref_t = util.check_trial_against_oracle(S.trial_observables, atoms, basis, opts, full_pos, label=f"{name} step {step}")
+        assert util.close(e_trial, ref_t["energy"])
         if rng.random() < 0.5:
             S.accept()
             pos = full_pos

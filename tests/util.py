@@ -71,3 +71,78 @@ def max_rel(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     scale = np.abs(b).max()
     return float(np.abs(a - b).max() / scale) if scale > 0 else float(np.abs(a).max())
+
+
+# ---- trial moves (mpmc_trial_*): shared by test_gpu_trial_moves and test_gpu_trial_branches -------------------------------------------
+TRIAL_KEYS = ["energy", "rd_energy", "coulombic_energy", "polarization_energy", "es_real", "es_recip", "lj_pairs"]
+
+
+def molecules(atoms):
+    """(first, end) of every molecule: consecutive atoms with one mol_id"""
+    ids = atoms["mol_id"]
+    starts = [0] + [i for i in range(1, len(ids)) if ids[i] != ids[i - 1]] + [len(ids)]
+    return [(starts[k], starts[k + 1]) for k in range(len(starts) - 1)]
+
+
+def nonpolar(opts):
+    o = dict(opts)
+    o.update(polarization=0, polar_iterative=0)
+    return o
+
+
+def moved(atoms, first, m, seed, sigma=0.3):
+    """trial positions of atoms [first, first + m): seeded per-atom Gaussian noise, so intramolecular distances change too"""
+    rng = np.random.default_rng(seed)
+    return atoms["pos"][first:first + m] + rng.normal(scale=sigma, size=(m, 3))
+
+
+def with_positions(atoms, pos):
+    a = dict(atoms)
+    a["pos"] = pos
+    return a
+
+
+def component_errors(got, ref, keys, rel):
+    """the components of `keys` where |got - ref| > rel * |ref|.  Relative per component, with no absolute floor: a component that is
+    identically zero (the polarization energy of a non-polarizable box, the Ewald parts under Wolf) must be exactly 0.0 on both sides,
+    so a delta that leaves a residue where there is no term fails.  None of the boxes of the trial tests has a component small enough
+    against its terms for rounding to reach these tolerances (1e-11 against a fresh context, 1e-9 against the oracle); a case that
+    needs a floor has to state it, with its bound, next to the comparison."""
+    return [f"{k}: {got[k]!r} vs {ref[k]!r} (rel {abs(got[k] - ref[k]) / abs(ref[k]) if ref[k] else float('inf'):.2e})"
+            for k in keys if not abs(got[k] - ref[k]) <= rel * abs(ref[k])]
+
+
+def check_trial_against_fresh(S, atoms, basis, opts, pos, rel=1e-11, label=""):
+    """S's last trial against a stateless evaluation of the trial configuration `pos` in a new context: every energy component at `rel`,
+    the in-cutoff counts exactly.  Returns the fresh context's dipoles (mu, E0, E_ind) for polarizable boxes (None otherwise)."""
+    from mpmcxx_amd import energy
+
+    T = energy.System(with_positions(atoms, pos), basis, opts)
+    try:
+        T.energy()
+        got, ref = S.trial_observables, T.observables
+        bad = component_errors(got, ref, TRIAL_KEYS, rel)
+        assert not bad, f"{label}: trial vs fresh context (rel {rel}): " + "; ".join(bad)
+        for k in ("n_lj_in_cutoff", "n_es_in_cutoff", "polar_iterations"):
+            assert got[k] == ref[k], (label, k, got[k], ref[k])
+        return T.dipoles() if opts.get("polarization") and not opts.get("rd_only") else None
+    finally:
+        T.close()
+
+
+def check_trial_against_oracle(obs, atoms, basis, opts, pos, rel=REL_TOL, label=""):
+    """trial observables against the oracle on the trial configuration: per component at `rel`, counts bit-exact, the same number of
+    dipole iterations.  (Under Wolf the oracle reports the Coulomb energy alone, no Ewald parts and no count.)"""
+    from oracle import OracleSystem
+
+    ref = OracleSystem(with_positions(atoms, pos), basis, opts).energy(want_atoms=False)
+    wolf = bool(opts.get("wolf"))
+    keys = [k for k in TRIAL_KEYS if not (wolf and k in ("es_real", "es_recip"))]
+    bad = component_errors(obs, ref, keys, rel)
+    assert not bad, f"{label}: trial vs oracle (rel {rel}): " + "; ".join(bad)
+    assert obs["n_lj_in_cutoff"] == ref["n_lj_in_cutoff"], (label, obs["n_lj_in_cutoff"], ref["n_lj_in_cutoff"])
+    if not wolf:
+        assert obs["n_es_in_cutoff"] == ref["n_es_in_cutoff"], (label, obs["n_es_in_cutoff"], ref["n_es_in_cutoff"])
+    if opts.get("polarization") and not opts.get("rd_only"):
+        assert obs["polar_iterations"] == ref["polar_iterations"], (label, obs["polar_iterations"], ref["polar_iterations"])
+    return ref
