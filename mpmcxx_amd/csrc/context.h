@@ -30,8 +30,6 @@ struct EvPair {
 	int cls;
 };
 
-// Measurement / A-B switches (mpmc_debug_configure; the library reads no environment variable for any of them).  The defaults are the
-// production path; none of them changes a result beyond the last bits (tests/test_gpu_round3_fixes.py holds every one to the reference).
 // Pinned host memory comes from the HIP runtime's own pool: an address freed by one context is handed to the next.  The runtime is not
 // instrumented, so the sanitizer build (tools/host_tsan.sh) is told here what the pool's lock orders: every release happens before every
 // later allocation -- otherwise the old owner's writes and the new owner's count as a race between two threads that never shared anything.
@@ -55,6 +53,8 @@ inline hipError_t pinned_free(void *p) {
 	return hipHostFree(p);
 }
 
+// Measurement / A-B switches (mpmc_debug_configure; the library reads no environment variable for any of them).  The defaults are the
+// production path; none of them changes a result beyond the last bits (tests/test_gpu_round3_fixes.py holds every one to the reference).
 struct mpmc_tuning {
 	int stream_mode = -1;   // "side_stream": -1 by table size (kOneStreamMaxPairs), 0 never fork the side stream, 1 always
 	int pair_kernel = 0;    // "pair_kernel": 0 the fast sweep (kernels_pair.hip) where it applies and the table is large, 1 never, 2 wherever it applies
@@ -66,21 +66,15 @@ struct mpmc_tuning {
 	                              // hardware queues to streams in turn, and an ensemble that never forks then has its main streams on all four (+0.6 %)
 	bool poll_retire = true;      // "poll_retire": a polled-for evaluation queries its streams afterwards so that the runtime retires the finished commands
 	bool poll_long = true;        // "poll_long": evaluations of large tables are polled for before the wait synchronises the stream (0: rounds 1-3)
-	bool tail_fused = true;       // "tail_fused": polarization energy and the fold of the pair partials in one launch (0: the fold forks the side stream)
 	bool dense_symmetric = true; // "dense_symmetric": the dense solver reads the upper block triangle of A only (0: rounds 1-3, the whole matrix)
 	bool fast_geometry = true; // "fast_geometry": fused minimum image in the pair sweep, the reference's form only inside a 1e-9 band around the cutoff (0: everywhere)
 	int pair_split = -1;    // "pair_split": two waves per tile pair in the fast sweep (half-length workgroups): -1 the last part of the table (round 5), 0 never | 1 everywhere
 	int pair_split_tail = -1; // "pair_split_tail": per mille of the sweep's work table that is halved under pair_split = -1 (default kSweepSplitTailPermille)
 	int sweep_order = 1; // "sweep_order": the pair sweep's work table by descending j-tile (1, round 5: the short rows with their partial entries end the launch; -2 to -4 % per lone
 	                     // launch without field and store, level with them) | 0 ascending (rounds 3-4)
-	int update_waves = 0; // "update_waves": waves per workgroup of the dipole update launch: 0 = 4 (round 5) | 1 | 2 | 4 | 16 (rounds 2-4).  A 16-wave workgroup needs
-	                      // sixteen free wave slots on ONE CU at once: with 32 beads in flight the launch waited ~170 us for them (0.02 ms with four waves, +2.3 %
-	                      // evaluations/s); alone four waves are faster too (1008 against 1019 us per evaluation): profiles/r05_update_waves.txt
 	int sweep_lds_pad = 2048; // "sweep_lds_pad": bytes of unused dynamic LDS on the pair sweep's launch when the side stream runs beside it: four
 	                          // workgroups per CU instead of five (no loss: 133 -> 131 us) leave 30 KB of LDS for the reciprocal-space kernels, which otherwise
 	                          // wait for sweep workgroups to retire (k_recip_sf_tab 68 -> 53 us beside the sweep; profiles/r05_one_evaluation_timeline.txt)
-	int fused_update = 0; // "fused_update" = 1 (2: measurement only, arrivals without the update -- results invalid): the dipole update rides the panel launch (last-arriving workgroup per tile); 0 (default): its own launch per iteration -- measured in round 5, profiles/r05_fused_update.txt
-	bool panel_reverse = true; // "panel_reverse": panel entries launched in descending j-tile order; 0: table order (rounds 2-4)
 	bool use_panels = true; // "panels": panel form of the Jacobi contraction (orthorhombic cells, stored tensors); 0: one tile pair per workgroup
 	bool no_uniform = false;   // "uniform_images" = 0: no tile-pair-wide periodic images
 	bool no_classes = false;   // "tile_classes" = 0: every tile pair is "near" (nothing skipped, every tensor stored)
@@ -141,7 +135,6 @@ struct mpmc_ctx {
 	int4 *d_panels = nullptr;        // work table of the panel form of the Jacobi contraction (k_build_panels), rebuilt every evaluation
 	int *d_seg = nullptr;            // [n_tiles + 1] first entry of every j-tile's segment of that table
 	double *d_gpart = nullptr;       // [entries][3][64] j-side partial sums, one slot per entry of the table
-	int *d_arrive = nullptr;         // [n_tiles] arrival counters of the fused dipole update (zero between launches)
 	size_t cap_panels = 0, cap_seg = 0;
 	long long *d_trace = nullptr;    // measurement only (tune.trace_panel): [entries][4] start / end ticks, HW_ID, XCC_ID of every workgroup of the LAST panel launch
 	int n_panel_entries = 0, seg_tiles = -1; // entries of the table / the tile count its layout was made for

@@ -24,17 +24,11 @@
 // rint and the lattice vector per pair (TRI, instantiated per mask for the far-field walk).
 // Partial sums: F_k -> part[J][I_k atoms] (i-side), the entry's combined G -> gpart[entry] (j-side), each written exactly once per
 // iteration.  Inside this path a slot holds its 64 x 3 doubles COMPONENT-major ([3][64]): every store instruction of the closing wave
-// writes four whole 128-byte lines (what a write-through store wants) and every load of the update is unit-stride.
+// writes four whole 128-byte lines and every load of the update is unit-stride.
 //
-// The update of the dipoles rides the same launch (round 5): the workgroup that delivers the LAST contribution to tile X -- the nt - X
-// i-side slots part[S][X], S >= X, and the slots of the entries of X's segment -- runs new_mu = alpha (E0 + F) for X's 64 atoms, sums
-// taken from the slots in the fixed (group, slot) order of k_dipole_update_panel, so the result does not depend on who arrives last.
-// Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): the closing wave stores its slots write-through (sc1), waits for its own
-// stores (s_waitcnt vmcnt(0)), then adds to the tiles' arrival counters (agent-scope atomics; the add whose return value completes the
-// count is the last one); the arriving workgroup takes ONE agent-scope acquire, waits for it, and passes a workgroup barrier before any
-// of its waves loads a slot (sc1 loads on top: L1 is not trusted).  The entries are launched in DESCENDING j-tile order: tile X is
-// complete when segment X is (its i-side pairs (X, S) live in the segments S > X), so the updates spread over the whole launch and the
-// longest segments start first; iteration k + 1 still starts at the kernel boundary.
+// The update of the dipoles, new_mu = alpha (E0 + F), is a launch of its own (k_dipole_update_panel, one workgroup per tile) behind every
+// contraction: the kernel boundary is what makes every slot visible to it.  The entries are launched in DESCENDING j-tile order (the table
+// is ascending): segment J holds J / 2 + 3 entries, so the longest segments start first and the launch ends on the short ones.
 #include "kernels.h"
 #include "device_math.h"
 
@@ -65,12 +59,10 @@ __device__ __forceinline__ int tp_index(int I, int J, int nt) { return I * nt - 
 // is carried to the next chunk of 64 as that class's pending member.  At the end the pending members of equal kind (stored / far)
 // pair up across classes -- the panel then keeps only the dimensions uniform for BOTH -- and what is still single becomes a
 // one-member entry.  Every step is wave-uniform or a fixed function of the lane: the table is the same whatever the timing.
-__global__ __launch_bounds__(64) void k_build_panels(const int *__restrict__ cls, int nt, const int *__restrict__ seg, int4 *__restrict__ panels,
-                                                     int *__restrict__ arrive /*[nt] arrival counters of the fused update: left at zero*/) {
+__global__ __launch_bounds__(64) void k_build_panels(const int *__restrict__ cls, int nt, const int *__restrict__ seg, int4 *__restrict__ panels) {
 	__shared__ int s_odd[16][33]; // the odd-rank member of every pair of one chunk, by class and pair index
 	const int J = blockIdx.x, lane = threadIdx.x;
 	if (J >= nt) return;
-	if (arrive && lane == 0) arrive[J] = 0; // (an evaluation that failed half way may have left a count behind)
 	int4 *out = panels + seg[J];
 	const int cap = seg[J + 1] - seg[J];
 	int n = 0; // entries written so far (wave-uniform)
@@ -132,18 +124,6 @@ __global__ __launch_bounds__(64) void k_build_panels(const int *__restrict__ cls
 		}
 		for (; n < cap; ++n) out[n] = make_int4(-1, -1, 0, J);
 	}
-}
-
-// write-through store / L1-bypassing load (global_store / global_load ... sc1): the hand-off of the partial slots between workgroups
-template <bool SC1>
-__device__ __forceinline__ void st_slot(double *p, double v) {
-	if (SC1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	else *p = v;
-}
-template <bool SC1>
-__device__ __forceinline__ double ld_slot(const double *p) {
-	if (SC1) return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	return *p;
 }
 
 template <int NI>
@@ -284,7 +264,7 @@ __device__ __forceinline__ void pan_walk(const Box &bx, const double2 *__restric
 	}
 }
 
-template <int PIPE, int NI, bool ORTHO, bool FUSED>
+template <int PIPE, int NI, bool ORTHO>
 __device__ __forceinline__ void panel_block(const AtomsDev &at, const Box &bx, const double *__restrict__ mu, const int2 *__restrict__ tile_pairs,
                                             const double4 *__restrict__ tp_shift, const double2 *__restrict__ ab, double *__restrict__ part,
                                             double *__restrict__ gslot, const int tpA, const int tpB, const int flags, const int J,
@@ -436,37 +416,39 @@ __device__ __forceinline__ void panel_block(const AtomsDev &at, const Box &bx, c
 			}
 		}
 		double *oi = part + (size_t)J * nt_pad3 + 3 * (size_t)(Is[k] * kTile) + lane; // slot [J][I_k atoms], component-major
-		st_slot<FUSED>(oi + p0 * kTile, f[0]);
-		st_slot<FUSED>(oi + p1 * kTile, f[1]);
-		st_slot<FUSED>(oi + p2 * kTile, f[2]);
+		oi[p0 * kTile] = f[0];
+		oi[p1 * kTile] = f[1];
+		oi[p2 * kTile] = f[2];
 	}
-	st_slot<FUSED>(gslot + p0 * kTile + lane, g[0]);
-	st_slot<FUSED>(gslot + p1 * kTile + lane, g[1]);
-	st_slot<FUSED>(gslot + p2 * kTile + lane, g[2]);
+	*(gslot + p0 * kTile + lane) = g[0];
+	*(gslot + p1 * kTile + lane) = g[1];
+	*(gslot + p2 * kTile + lane) = g[2];
 }
 
 // ---- new_mu = alpha (E0 + F) for the 64 atoms of tile X ------------------------------------------------------------------------------
 // F = sum of the panel kernel's slots of this tile: part[S][X atoms] for S = X .. nt-1 (i-side, the diagonal included) and gpart[e] for
 // the entries of X's segment of the work table (j-side).  Tail as k_dipole_update (contract_dipoles :3586-3593, calc_dipole_rrms
-// :3147-3177, are_we_done_yet :3227-3236).  The sums are taken in kUpdGroups strided groups -- group g: slots g, g + 16, ... of the i-side,
-// then of the j-side -- and the groups added in order: fixed by (g, t) alone, whoever runs it and with however many waves (NW waves take
-// kUpdGroups / NW groups each, with independent accumulators: the loads of a wave are in flight together).
+// :3147-3177, are_we_done_yet :3227-3236).  The slots are walked as ONE list t = 0 .. nF + nG - 1 (the nF i-side slots first, then the nG
+// j-side ones) in kUpdGroups strided groups -- group g takes t = g, g + 16, ... -- and the groups are added in order g = 0 .. 15: the sum
+// is fixed by (g, t) alone.  kUpdWaves waves take kUpdGroups / kUpdWaves groups each, with independent accumulators (the loads of a wave are
+// in flight together).
 constexpr int kUpdGroups = 16;
+// Four waves per workgroup: a sixteen-wave workgroup must find sixteen free wave slots on one CU, which an ensemble's other kernels rarely
+// leave (the launch then waits ~170 us for them), and is no faster alone (profiles/r05_update_waves.txt)
+constexpr int kUpdWaves = 4;
+constexpr int kUpdRounds = 2; // rounds of the wave's groups per trip
 struct PanelUpdate {
 	const double *e_static;
 	const int *seg;
-	double *mu_new, *e_induced /*may be null: not wanted (timing launches)*/, *rrms_atom;
+	double *mu_new, *e_induced /*may be null*/, *rrms_atom;
 	double allowed_sqerr;
 	int *ctl, *host_flag;
-	int *arrive; // [nt] arrival counters; null: the update is a launch of its own (k_dipole_update_panel)
-	int nt, it, want_rrms, reverse;
-	int probe; // measurement only: arrive, but skip the update (the producer side of the hand-off alone; results are NOT valid)
+	int nt, it, want_rrms;
 };
 
-template <int NW, bool SC1, int ROUNDS = ((8 * NW) / 16 > 0 ? (8 * NW) / 16 : 1)>
 __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const PanelUpdate &u, const double *__restrict__ part, const double *__restrict__ gpart,
                                                   const double *__restrict__ mu_old, const int X, double (*__restrict__ sh)[kTile][3]) {
-	constexpr int GW = kUpdGroups / NW; // groups per wave
+	constexpr int GW = kUpdGroups / kUpdWaves; // groups per wave
 	const int a = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int i = X * kTile + a;
 	const int nF = u.nt - X, wg0 = u.seg[X], nG = u.seg[X + 1] - wg0;
@@ -479,31 +461,30 @@ __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const Pane
 			mo[p] = mu_old[3 * (size_t)i + p];
 		}
 	}
-	// One list of T = nF + nG slots (i-side first); group g takes t = g, g + 16, ...  Every load is issued unconditionally (a slot index
-	// past the end is clamped and its value replaced by zero: no branch between the loads), ROUNDS rounds of the wave's groups per trip: 3 GW
-	// ROUNDS independent loads in flight per lane (24; 48 measured no faster) -- the update is
-	// a latency chain (few workgroups, data fresh from other CUs), not a bandwidth one.  The order of the additions does not depend on ROUNDS.
+	// Every load is issued unconditionally (a slot index past the end is clamped and its value replaced by zero: no branch between the
+	// loads), kUpdRounds rounds of the wave's groups per trip: 3 GW kUpdRounds = 24 independent loads in flight per lane (48 measured no
+	// faster) -- the update is a latency chain (few workgroups), not a bandwidth one.  The order of the additions does not depend on kUpdRounds.
 	double f[GW][3] = {};
 	const size_t n_pad = (size_t)at.n_pad;
 	const int T = nF + nG;
 	const double *__restrict__ pX = part + ((size_t)X * n_pad + (size_t)X * kTile) * 3 + a; // slot X, this tile's block; slot X + t is t * n_pad * 3 further
 	const double *__restrict__ gX = gpart + (size_t)wg0 * (kTile * 3) + a;
-	for (int t0 = 0; t0 < T; t0 += ROUNDS * kUpdGroups) {
-		double v[ROUNDS][GW][3];
+	for (int t0 = 0; t0 < T; t0 += kUpdRounds * kUpdGroups) {
+		double v[kUpdRounds][GW][3];
 #pragma unroll
-		for (int r = 0; r < ROUNDS; ++r) {
+		for (int r = 0; r < kUpdRounds; ++r) {
 #pragma unroll
 			for (int c = 0; c < GW; ++c) {
 				const int t = t0 + r * kUpdGroups + w * GW + c;
 				const int tc = t < T ? t : T - 1;
 				const double *__restrict__ q = tc < nF ? pX + (size_t)tc * n_pad * 3 : gX + (size_t)(tc - nF) * (kTile * 3);
-				v[r][c][0] = ld_slot<SC1>(q);
-				v[r][c][1] = ld_slot<SC1>(q + kTile);
-				v[r][c][2] = ld_slot<SC1>(q + 2 * kTile);
+				v[r][c][0] = q[0];
+				v[r][c][1] = q[kTile];
+				v[r][c][2] = q[2 * kTile];
 			}
 		}
 #pragma unroll
-		for (int r = 0; r < ROUNDS; ++r) {
+		for (int r = 0; r < kUpdRounds; ++r) {
 #pragma unroll
 			for (int c = 0; c < GW; ++c) {
 				const bool ok = t0 + r * kUpdGroups + w * GW + c < T;
@@ -569,29 +550,26 @@ __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const Pane
 	}
 }
 
-// (per FUSED two instantiations: the orthorhombic one reads three diagonal elements of the cell and its inverse, which keeps most of the
-// Box out of its scalar registers; the other holds the walks of skewed cells)
-constexpr int kPanelWalkDouble2 = 6 * kTile + kTile + (kPanelWaves * 2 * 3 * kTile + kPanelWaves * 3 * kTile) / 2; // j-tile image (every value twice), valid flags, s_F, s_G
-constexpr int kPanelLdsDouble2 = kPanelWalkDouble2; // (the fused update's group sums reuse the walk's LDS: with four waves and more it is large enough)
-template <int PIPE, bool ORTHO, bool FUSED>
+// (two instantiations: the orthorhombic one reads three diagonal elements of the cell and its inverse, which keeps most of the Box out of
+// its scalar registers; the other holds the walks of skewed cells)
+constexpr int kPanelLdsDouble2 = 6 * kTile + kTile + (kPanelWaves * 2 * 3 * kTile + kPanelWaves * 3 * kTile) / 2; // j-tile image (every value twice), valid flags, s_F, s_G
+template <int PIPE, bool ORTHO>
 __global__ __launch_bounds__(64 * kPanelWaves) void k_dipole_iter_panel(AtomsDev at, Box bx, const double *__restrict__ mu,
                                                                         const int2 *__restrict__ tile_pairs, const double4 *__restrict__ tp_shift,
                                                                         const int4 *__restrict__ panels, const double2 *__restrict__ ab,
                                                                         double *__restrict__ part, double *__restrict__ gpart /*[entries][3][64]*/,
                                                                         const int *__restrict__ converged /*null, or &ctl[1] of the precision-terminated solve*/,
-                                                                        long long *__restrict__ trace /*null; measurement only: [entries][4] = start, end (100 MHz ticks), HW_ID, XCC_ID*/,
-                                                                        const PanelUpdate u) {
+                                                                        long long *__restrict__ trace /*null; measurement only: [entries][4] = start, end (100 MHz ticks), HW_ID, XCC_ID*/) {
 	long long t_start = 0;
 	if (trace) t_start = wall_clock64();
-	__shared__ double2 s_all[(FUSED && kPanelLdsDouble2 * 2 < kUpdGroups * kTile * 3) ? (kUpdGroups * kTile * 3) / 2 : kPanelLdsDouble2];
-	__shared__ int s_todo[4];
+	__shared__ double2 s_all[kPanelLdsDouble2];
 	if (converged && *converged != 0) return; // an iteration enqueued ahead of the verdict: nothing to do
 	double2 *s_xy = s_all, *s_zm = s_all + 2 * kTile, *s_mm = s_all + 4 * kTile;
 	double *s_valid = reinterpret_cast<double *>(s_all + 6 * kTile);
 	double(*s_F)[2][3][kTile] = reinterpret_cast<double(*)[2][3][kTile]>(s_all + 7 * kTile);
 	double(*s_G)[3][kTile] = reinterpret_cast<double(*)[3][kTile]>(s_all + 7 * kTile + kPanelWaves * 2 * 3 * kTile / 2);
-	// entries in descending j-tile order (the table is ascending): the longest segments first, tile X complete when segment X is
-	const int ent = u.reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+	// entries in descending j-tile order (the table is ascending): the longest segments first
+	const int ent = (int)gridDim.x - 1 - (int)blockIdx.x;
 	const int4 e = panels[ent];
 	// everything that describes the entry is wave-uniform: keep it in scalar registers
 	const int tpA = __builtin_amdgcn_readfirstlane(e.x), tpB = __builtin_amdgcn_readfirstlane(e.y);
@@ -599,48 +577,16 @@ __global__ __launch_bounds__(64 * kPanelWaves) void k_dipole_iter_panel(AtomsDev
 	double *gslot = gpart + (size_t)ent * kTile * 3;
 	if (tpA < 0) { // unused entry of this j-tile's segment: its slot is read by the update all the same
 		if (threadIdx.x < kTile) {
-			st_slot<FUSED>(gslot + threadIdx.x, 0.0);
-			st_slot<FUSED>(gslot + kTile + threadIdx.x, 0.0);
-			st_slot<FUSED>(gslot + 2 * kTile + threadIdx.x, 0.0);
+			*(gslot + threadIdx.x) = 0.0;
+			*(gslot + kTile + threadIdx.x) = 0.0;
+			*(gslot + 2 * kTile + threadIdx.x) = 0.0;
 		}
 		if (trace && threadIdx.x == 0) trace[4 * (size_t)ent + 1] = 0; // no work: the reader drops entries whose end stamp is 0
-		if (!FUSED) return;
-	} else if (tpB >= 0) panel_block<PIPE, 2, ORTHO, FUSED>(at, bx, mu, tile_pairs, tp_shift, ab, part, gslot, tpA, tpB, flags, J, s_xy, s_zm, s_mm, s_valid, s_F, s_G);
-	else panel_block<PIPE, 1, ORTHO, FUSED>(at, bx, mu, tile_pairs, tp_shift, ab, part, gslot, tpA, tpB, flags, J, s_xy, s_zm, s_mm, s_valid, s_F, s_G);
-	if (FUSED) {
-		// arrival: wave 0 stored every slot of this entry; its lanes 0..2 add to the counters of the tiles those slots belong to
-		//   diagonal or unused entry: { J };  off-diagonal: { I_A, I_B (panels of two), J }
-		const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-		if (w == 0) {
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's write-through stores have been acknowledged
-			int target = -1;
-			const bool offdiag = tpA >= 0 && !(flags & kPanDiag);
-			if (lane == 0) target = J;
-			else if (lane == 1 && offdiag) target = tile_pairs[tpA].x;
-			else if (lane == 2 && offdiag && tpB >= 0) target = tile_pairs[tpB].x;
-			bool last = false;
-			if (target >= 0) {
-				const int expected = (u.nt - target) + (u.seg[target + 1] - u.seg[target] - 1);
-				last = __hip_atomic_fetch_add(&u.arrive[target], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == expected - 1;
-			}
-			if (lane < 3) s_todo[lane] = last ? target : -1;
-			if (__any(last)) { // ONE agent-scope acquire per arriving workgroup, complete before the barrier lets anybody load
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			}
-		}
-		__syncthreads();
-		double(*sh)[kTile][3] = reinterpret_cast<double(*)[kTile][3]>(s_all);
-#pragma unroll 1
-		for (int k = 0; k < 3; ++k) {
-			const int X = __builtin_amdgcn_readfirstlane(s_todo[k]);
-			if (X < 0) continue; // (block-uniform)
-			if (!u.probe) panel_update_tile<kPanelWaves, true>(at, u, part, gpart, mu, X, sh);
-			if (threadIdx.x == 0) u.arrive[X] = 0; // (nobody else touches it any more in this launch; the next one starts from zero)
-			__syncthreads();
-		}
+		return;
 	}
-	if (trace && threadIdx.x == 0 && tpA >= 0) { // (wave 0 is the last one to leave a workgroup: it folds the partial sums)
+	if (tpB >= 0) panel_block<PIPE, 2, ORTHO>(at, bx, mu, tile_pairs, tp_shift, ab, part, gslot, tpA, tpB, flags, J, s_xy, s_zm, s_mm, s_valid, s_F, s_G);
+	else panel_block<PIPE, 1, ORTHO>(at, bx, mu, tile_pairs, tp_shift, ab, part, gslot, tpA, tpB, flags, J, s_xy, s_zm, s_mm, s_valid, s_F, s_G);
+	if (trace && threadIdx.x == 0) { // (wave 0 is the last one to leave a workgroup: it folds the partial sums)
 		long long *o = trace + 4 * (size_t)ent;
 		o[0] = t_start;
 		o[1] = wall_clock64();
@@ -649,56 +595,36 @@ __global__ __launch_bounds__(64 * kPanelWaves) void k_dipole_iter_panel(AtomsDev
 	}
 }
 
-// the update as a launch of its own (the default; fused_update = 1 rides the contraction instead): one workgroup per tile, the same function,
-// the same sums whatever NW.  Four waves by default (update_waves): a sixteen-wave workgroup must find sixteen free wave slots on one CU,
-// which an ensemble's other kernels rarely leave (the launch then waits ~170 us for them), and is no faster alone.
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_dipole_update_panel(AtomsDev at, const double *__restrict__ part, const double *__restrict__ gpart,
-                                                                 const double *__restrict__ mu_old, const PanelUpdate u) {
+// the update: one workgroup per tile, launched behind every contraction
+__global__ __launch_bounds__(64 * kUpdWaves) void k_dipole_update_panel(AtomsDev at, const double *__restrict__ part, const double *__restrict__ gpart,
+                                                                        const double *__restrict__ mu_old, const PanelUpdate u) {
 	__shared__ double sh[kUpdGroups][kTile][3];
 	if (u.ctl && u.ctl[1] != 0) return; // converged in an earlier iteration (block-uniform)
-	panel_update_tile<NW, false>(at, u, part, gpart, mu_old, blockIdx.x, sh); // (48 loads per lane and trip instead of 24: no faster, round 5)
+	panel_update_tile(at, u, part, gpart, mu_old, blockIdx.x, sh);
 }
 
-void launch_build_panels(hipStream_t st, const int *cls, int n_tiles, const int *seg, int4 *panels, int *arrive) {
-	hipLaunchKernelGGL(k_build_panels, dim3(n_tiles), dim3(64), 0, st, cls, n_tiles, seg, panels, arrive);
+void launch_build_panels(hipStream_t st, const int *cls, int n_tiles, const int *seg, int4 *panels) {
+	hipLaunchKernelGGL(k_build_panels, dim3(n_tiles), dim3(64), 0, st, cls, n_tiles, seg, panels);
 }
 
 void launch_dipole_iter_panel(hipStream_t st, const AtomsDev &at, const Box &bx, const double *mu, const int2 *tile_pairs,
                               const double4 *tp_shift, const int4 *panels, int n_entries, const double2 *ab, double *part, double *gpart,
-                              const int *converged, long long *trace, int replicas, const PanelFuse *fuse) {
+                              const int *converged, long long *trace, int replicas) {
 	if (n_entries <= 0) return;
 	dim3 grid(n_entries, replicas > 1 ? replicas : 1), block(kTile * kPanelWaves); // (replicas: measurement only -- the same work blockIdx.y times)
-	PanelUpdate u{};
-	u.reverse = 1;
-	const bool fused = fuse && fuse->arrive && replicas <= 1;
-	if (fuse) u.reverse = fuse->reverse;
-	if (fused) {
-		u.e_static = fuse->e_static, u.seg = fuse->seg, u.mu_new = fuse->mu_new, u.e_induced = fuse->e_induced, u.rrms_atom = fuse->rrms_atom;
-		u.allowed_sqerr = fuse->allowed_sqerr, u.ctl = fuse->ctl, u.host_flag = fuse->host_flag, u.arrive = fuse->arrive;
-		u.nt = at.n_pad / kTile, u.it = fuse->it, u.want_rrms = fuse->want_rrms, u.probe = fuse->probe;
-	}
-#define MPMC_PANEL(O, F) hipLaunchKernelGGL((k_dipole_iter_panel<MPMC_PANEL_PIPE, O, F>), grid, block, 0, st, at, bx, mu, tile_pairs, tp_shift, panels, ab, part, gpart, converged, trace, u)
-	if (bx.ortho) {
-		if (fused) MPMC_PANEL(true, true);
-		else MPMC_PANEL(true, false);
-	} else {
-		if (fused) MPMC_PANEL(false, true);
-		else MPMC_PANEL(false, false);
-	}
-#undef MPMC_PANEL
+	if (bx.ortho)
+		hipLaunchKernelGGL((k_dipole_iter_panel<MPMC_PANEL_PIPE, true>), grid, block, 0, st, at, bx, mu, tile_pairs, tp_shift, panels, ab, part, gpart, converged, trace);
+	else
+		hipLaunchKernelGGL((k_dipole_iter_panel<MPMC_PANEL_PIPE, false>), grid, block, 0, st, at, bx, mu, tile_pairs, tp_shift, panels, ab, part, gpart, converged, trace);
 }
 
 void launch_dipole_update_panel(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, const double *gpart, const int *seg,
                                 const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr,
-                                int *ctl, int *host_flag, int it, int waves) {
+                                int *ctl, int *host_flag, int it) {
 	PanelUpdate u{};
 	u.e_static = e_static, u.seg = seg, u.mu_new = mu_new, u.e_induced = e_induced, u.rrms_atom = rrms_atom, u.allowed_sqerr = allowed_sqerr;
-	u.ctl = ctl, u.host_flag = host_flag, u.arrive = nullptr, u.nt = at.n_pad / kTile, u.it = it, u.want_rrms = want_rrms;
-	if (waves == 4) hipLaunchKernelGGL(k_dipole_update_panel<4>, dim3(at.n_pad / kTile), dim3(kTile * 4), 0, st, at, part, gpart, mu_old, u);
-	else if (waves == 2) hipLaunchKernelGGL(k_dipole_update_panel<2>, dim3(at.n_pad / kTile), dim3(kTile * 2), 0, st, at, part, gpart, mu_old, u);
-	else if (waves == 1) hipLaunchKernelGGL(k_dipole_update_panel<1>, dim3(at.n_pad / kTile), dim3(kTile), 0, st, at, part, gpart, mu_old, u);
-	else hipLaunchKernelGGL(k_dipole_update_panel<kUpdGroups>, dim3(at.n_pad / kTile), dim3(kTile * kUpdGroups), 0, st, at, part, gpart, mu_old, u);
+	u.ctl = ctl, u.host_flag = host_flag, u.nt = at.n_pad / kTile, u.it = it, u.want_rrms = want_rrms;
+	hipLaunchKernelGGL(k_dipole_update_panel, dim3(at.n_pad / kTile), dim3(kTile * kUpdWaves), 0, st, at, part, gpart, mu_old, u);
 }
 
 } // namespace mpmc

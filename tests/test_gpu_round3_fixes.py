@@ -77,6 +77,9 @@ def test_configure_rejects_unknown_keys_and_bad_values():
         S.configure("pair_kernel", 7)
     with pytest.raises(energy.MpmcError):
         S.configure("pair_waves", 3)
+    for retired in ("fused_update", "panel_reverse", "update_waves", "tail_fused"):  # launch variants removed after round 5
+        with pytest.raises(energy.MpmcError):
+            S.configure(retired, 1)
     S.close()
 
 

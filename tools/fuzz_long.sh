@@ -10,7 +10,6 @@ run timeout -k 10 280 python3 tools/fuzz_large.py 19000 200
 run timeout -k 10 280 python3 tools/fuzz_large.py 19500 200 sweep
 run timeout -k 10 280 python3 tools/fuzz_trial.py 19000 600
 run timeout -k 10 280 python3 tools/fuzz_trial.py 19700 600 polar
-run timeout -k 10 280 python3 tools/fuzz_large.py 29000 200 fused
 run timeout -k 10 200 python3 tools/fuzz_state.py 19000 200 4
 echo "== overall $rc_all"
 exit $rc_all
