@@ -78,7 +78,7 @@ void launch_recip_sf(hipStream_t st, const AtomsDev &at, const Box &bx, const Re
 // reciprocal energy + O(N) atom terms: coulombic_self, lj_lrc_self, and the PAIR long-range correction summed in O(N)
 // through moments of (sqrt(eps), |sigma|) (Lorentz-Berthelot makes the pair term a polynomial in sigma_i + sigma_j)
 // position-independent terms (pair LRC, self LRC, Ewald self) into their three slots of the scalar block; part_scratch: kAtomTermScratch doubles
-constexpr size_t kAtomTermScratch = 64 * 32;
+constexpr size_t kAtomTermScratch = 64 * 34;
 void launch_atom_terms(hipStream_t st, const AtomsDev &at, const Box &bx, double ewald_alpha, int rd_lrc, int do_es, double *part_scratch,
                        double *scal);
 

@@ -165,16 +165,17 @@ __device__ const double kBinom12[13] = {1, 12, 66, 220, 495, 792, 924, 792, 495,
 //   g_ij = (16 pi / 3V) eps_ij (sig_ij^12 / (3 rc^9) - sig_ij^6 / rc^3),  eps_ij = sqrt(eps_i) sqrt(eps_j),  sig_ij = (s_i + s_j)/2
 //   sum_{i<j} sqe_i sqe_j (s_i+s_j)^m = 1/2 [ sum_k C(m,k) M_k M_{m-k} - sum_i sqe_i^2 (2 s_i)^m ],   M_k = sum_i sqe_i s_i^k
 // over the atoms with eps != 0, sigma > 0 (sigma == 0 or < 0 gives sig_ij or eps_ij = 0), minus the same sum over the
-// frozen subset (frozen-frozen pairs are excluded, :1049).  O(N) instead of O(N^2), position independent.
+// frozen subset (frozen-frozen pairs are excluded, :1049).  O(N) instead of O(N^2), position independent.  Where no pair is left (at most one
+// such atom, or all of them frozen) the moments cancel only up to rounding: the term is then exactly 0, as the reference's empty sum is.
 // Two launches: the per-atom sums over as many 256-thread blocks as there are atoms for (one block looping over 10 000 atoms with thirteen
 // dependent multiplies each took 81 us -- most of an evaluation it rides along with after every insertion, removal or volume move),
-// 32 partial sums per block; then one wave adds the blocks' partials in block order (reproducible) and forms the three results.
-constexpr int kAtomTermSums = 32, kAtomTermBlocks = 64; // self, lrc, M_0..12, Mfrozen_0..12, d6, d12, df6, df12
+// 34 partial sums per block; then one wave adds the blocks' partials in block order (reproducible) and forms the three results.
+constexpr int kAtomTermSums = 34, kAtomTermBlocks = 64; // self, lrc, M_0..12, Mfrozen_0..12, d6, d12, df6, df12, atoms in M, frozen ones
 static_assert((size_t)kAtomTermSums * kAtomTermBlocks <= kAtomTermScratch, "scratch of launch_atom_terms");
 __global__ __launch_bounds__(256) void k_atom_terms_part(AtomsDev at, Box bx, double ewald_alpha, int rd_lrc, int do_es,
                                                          double *__restrict__ part /*[gridDim.x][kAtomTermSums]*/) {
 	double self = 0, lrc = 0;
-	double m[13], mf[13], d6 = 0, d12 = 0, df6 = 0, df12 = 0;
+	double m[13], mf[13], d6 = 0, d12 = 0, df6 = 0, df12 = 0, na = 0, nfa = 0;
 	for (int k = 0; k < 13; ++k) m[k] = mf[k] = 0;
 	for (int a = blockIdx.x * 256 + threadIdx.x; a < at.n; a += gridDim.x * 256) {
 		const int fl = at.mf[a].y;
@@ -190,9 +191,11 @@ __global__ __launch_bounds__(256) void k_atom_terms_part(AtomsDev at, Box bx, do
 			const double t2 = 2.0 * l.x, t6 = (t2 * t2 * t2) * (t2 * t2 * t2), e2 = l.y * l.y;
 			d6 += e2 * t6;
 			d12 += e2 * t6 * t6;
+			na += 1.0;
 			if (fr) {
 				df6 += e2 * t6;
 				df12 += e2 * t6 * t6;
+				nfa += 1.0;
 			}
 		}
 		if (fl & AF_FROZEN) continue;
@@ -218,6 +221,8 @@ __global__ __launch_bounds__(256) void k_atom_terms_part(AtomsDev at, Box bx, do
 	put(29, d12);
 	put(30, df6);
 	put(31, df12);
+	put(32, na);
+	put(33, nfa);
 	__syncthreads();
 	if (threadIdx.x < kAtomTermSums)
 		part[(size_t)blockIdx.x * kAtomTermSums + threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
@@ -246,7 +251,8 @@ __global__ __launch_bounds__(64) void k_atom_terms_finish(const double *__restri
 		const double p6 = (0.5 * (s6 - d6) - 0.5 * (f6 - df6)) / 64.0;       // sum_{pairs} eps_ij sig_ij^6
 		const double p12 = (0.5 * (s12 - d12) - 0.5 * (f12 - df12)) / 4096.0; // sum_{pairs} eps_ij sig_ij^12
 		const double rc3 = bx.cutoff * bx.cutoff * bx.cutoff, rc9 = rc3 * rc3 * rc3;
-		scal[S_LRC_PAIR] = rd_lrc ? (16.0 / 3.0) * kPi * (p12 / (3.0 * rc9) - p6 / rc3) / bx.volume : 0.0;
+		const bool no_pair = s[32] * (s[32] - 1.0) == s[33] * (s[33] - 1.0); // (counts: exact in fp64)
+		scal[S_LRC_PAIR] = (rd_lrc && !no_pair) ? (16.0 / 3.0) * kPi * (p12 / (3.0 * rc9) - p6 / rc3) / bx.volume : 0.0;
 		scal[S_ES_SELF] = s[0];
 		scal[S_LRC_SELF] = s[1];
 	}

@@ -6,7 +6,6 @@ import pytest
 
 import util
 from mpmcxx_amd import energy
-from oracle import OracleSystem
 
 pytestmark = pytest.mark.gpu
 
@@ -32,18 +31,39 @@ def build(case):
     return a, basis, opts
 
 
+def nearest_neighbour_field(a, basis):
+    """max |q_j| / d_nn^2: the field of the closest ion, the size of the largest term of any atom's static field in this orthorhombic cell"""
+    L = np.diag(basis)
+    f = (a["pos"][:, None, :] - a["pos"][None, :, :]) / L
+    r = np.linalg.norm((f - np.rint(f)) * L, axis=2)
+    np.fill_diagonal(r, np.inf)
+    return float(np.abs(a["charge"]).max() / r.min() ** 2)
+
+
 @pytest.mark.parametrize("solver", ["compact", "matrix_free"])
 @pytest.mark.parametrize("case", ["unwrapped", "anisotropic", "far_from_origin", "integer_grid_ties", "cell_smaller_than_a_tile"])
 def test_geometry_edge_cases(case, solver):
     a, basis, opts = build(case)
-    ref = OracleSystem(a, basis, opts).energy()
+    ref = util.oracle_energy(a, basis, opts)
     S = energy.System(a, basis, dict(opts, solver=solver))
-    S.energy()
-    r = S.observables
-    for k in ("rd_energy", "coulombic_energy", "polarization_energy", "energy"):
-        assert abs(r[k] - ref[k]) <= 1e-9 * max(abs(ref[k]), 1e-3 * abs(ref["energy"])), (case, k, r[k], ref[k])
-    assert int(r["n_lj_in_cutoff"]) == int(ref["n_lj_in_cutoff"]) and int(r["n_es_in_cutoff"]) == int(ref["n_es_in_cutoff"])
-    assert r["polar_iterations"] == ref["polar_iterations"]
-    mu = S.dipoles()[0]
-    assert np.abs(mu - ref["mu"]).max() <= 1e-9 * np.abs(ref["mu"]).max() + 1e-13
-    S.close()
+    try:
+        S.energy()
+        mu = S.dipoles()[0]
+        fields = absolute = None
+        if case == "integer_grid_ties":
+            # the perfect grid cancels the static field almost completely: |E_i| ~ 2e-6 on every ion, against terms up to the nearest
+            # neighbour's field q / d_nn^2 ~ 2.6.  What is left of E_i is the rounding residue of ~10^3 such terms (~10^3 x 1.1e-16 of
+            # the largest); measured on the MI355X: 1e-14 (5e-9 of |E_i| on 913 of the 1000 ions).  Held at 1e-13 q / d_nn^2 absolute on
+            # top of the standard bound.
+            # The induced field (|F_i| 2.8e-7 .. 5.0e-7) is a linear function of the static field after the fixed number of iterations,
+            # so it inherits E's relative uncertainty: delta_E = 1e-13 q / d_nn^2 / min|E_i| (1.3e-7 here) of max|F|, on top of the
+            # standard 1e-9 |F_i|.  Measured on the MI355X: max |d_i| = 1.6e-15, 5e-9 of |F_i| (delta_E max|F| = 6.4e-14).
+            # The dipoles keep the global 1e-9 max|mu| + 1e-13 this test held before.
+            s_nn = nearest_neighbour_field(a, basis)
+            delta_e = 1e-13 * s_nn / float(np.abs(ref["ef_static"]).max(axis=1).min())
+            fields = {"mu": (0.0, 1e-9), "ef_induced": (util.REL_TOL, delta_e)}
+            absolute = {"ef_static": 1e-13 * s_nn, "mu": 1e-13}
+        util.assert_matches_oracle(S.observables, S.dipoles(), ref, a, opts, label=(case, solver), fields=fields, absolute=absolute)
+        assert np.abs(mu - ref["mu"]).max() <= 1e-9 * np.abs(ref["mu"]).max() + 1e-13  # (the global bound this test held before, kept)
+    finally:
+        S.close()

@@ -2,8 +2,8 @@
 of the domain: ragged sizes around the 64-atom tile (1, 2, 63, 64, 65, 129 ...), multi-atom molecules (exclusions,
 intramolecular term), frozen atoms, zero / negative sigma, zero epsilon, zero charges ("es_excluded" inter-molecular
 pairs), zero polarizabilities, dispersion flags, orthorhombic and triclinic cells, every option combination of the
-path, and the solver fallbacks.  Tolerance 1e-9 relative per component (floored at 1e-12 of the largest component,
-for components that vanish by cancellation); pair counts bit-exact."""
+path, and the solver fallbacks.  Compared by util.assert_matches_oracle: 1e-9 relative per component with no floor, pair counts
+bit-exact, the per-atom fields atom by atom."""
 import numpy as np
 import pytest
 
@@ -86,37 +86,37 @@ def random_options(rng):
     return o
 
 
-def check(atoms, basis, opts, label, wolf=False):
-    from oracle import OracleSystem
-
-    ref = OracleSystem(atoms, basis, opts).energy()
+def check(atoms, basis, opts, label):
+    """one evaluation against the oracle (util.assert_matches_oracle: every component at 1e-9 relative with no floor, counts bit-exact,
+    the solver's results, ef_static / mu / ef_induced atom by atom)"""
+    ref = util.oracle_energy(atoms, basis, opts)
     S = energy.System(atoms, basis, opts)
-    S.energy()
-    r = S.observables
-    if not np.isfinite(ref["energy"]):
-        assert not np.isfinite(r["energy"]), label
+    try:
+        S.energy()
+        r = S.observables
+        if not np.isfinite(ref["energy"]):
+            assert not np.isfinite(r["energy"]), label
+            return
+        polar = opts["polarization"] and not opts["rd_only"]
+        absolute = None
+        if polar and len(atoms["charge"]) == 1:
+            # a lone atom: its static field vanishes by the inversion symmetry of its own periodic images, and both sides report the
+            # rounding residue of that cancellation (|E| ~ 1e-16 on the MI355X, polarization energies of 1e-35 .. 1e-32 that differ by
+            # 15-30 %).  The fields keep the absolute 1e-12 this test allowed before; the polarization energy -1/2 alpha |E|^2 of such a
+            # field, and the total it is all of when the atom has no other term, get 3 alpha (1e-12)^2
+            e_noise = 3.0 * float(np.max(atoms["polarizability"])) * 1e-24
+            absolute = {"ef_static": 1e-12, "mu": 1e-12, "ef_induced": 1e-12, "polarization_energy": e_noise, "energy": e_noise}
+        if polar and opts["polar_gs"]:
+            # Gauss-Seidel reports the induced field as the row sum recovered from its dipole, mu / alpha - E0 (kernels_gs.hip): exact
+            # up to the rounding of that difference and of the in-tile sweep that made mu, also where the row sum itself is exactly zero
+            # (seed 0: one polarizable atom among non-polarizable ones).  Allowed: 1e-12 max |E0| on top of the standard bound; this test
+            # did not compare the induced field before.  Measured on the MI355X, max |d_i| / max |E0| over the seeds of
+            # test_random_systems_gauss_seidel: 5.8e-18, 1.0e-15, 5.8e-14, 9.1e-14, 4.0e-13 and 6.3e-16 for seeds 0-4 and 7; the diverged
+            # precision solves of seeds 5 and 6 (|F| ~ 1e75) are held by the relative term
+            absolute = dict(absolute or {}, ef_induced=1e-12 * float(np.abs(ref["ef_static"]).max()))
+        util.assert_matches_oracle(r, S.dipoles() if polar else None, ref, atoms, opts, label=label, absolute=absolute)
+    finally:
         S.close()
-        return
-    keys = ["energy", "rd_energy", "coulombic_energy", "polarization_energy", "es_real", "es_recip", "es_self", "lj_pairs", "lrc_pair", "lrc_self"]
-    if wolf:  # coulombic_wolf has no real / reciprocal / self split (the oracle reports the total only)
-        keys = [k for k in keys if not k.startswith("es_")]
-    scale = max(abs(ref[k]) for k in keys)
-    for k in keys:
-        tol = 1e-9 * max(abs(ref[k]), 1e-3 * scale) + 1e-12  # absolute floor: a lone atom's energies are pure rounding noise
-        assert abs(r[k] - ref[k]) <= tol, (label, k, r[k], ref[k])
-    for k in ["n_pairs", "n_intra", "n_rd_excluded", "n_es_excluded", "n_frozen", "n_lj_in_cutoff"]:
-        assert int(r[k]) == int(ref[k]), (label, k, r[k], ref[k])
-    if not opts["rd_only"] and not wolf:  # (the oracle does not count the pairs of coulombic_wolf)
-        assert int(r["n_es_in_cutoff"]) == int(ref["n_es_in_cutoff"]), label
-    if opts["polarization"] and not opts["rd_only"]:
-        assert r["polar_iterations"] == ref["polar_iterations"], (label, r["polar_iterations"], ref["polar_iterations"])
-        assert r["iterator_failed"] == ref["iterator_failed"], label
-        mu, E, F = S.dipoles()
-        assert np.abs(E - ref["ef_static"]).max() <= 1e-9 * np.abs(ref["ef_static"]).max() + 1e-12, label
-        if not ref["iterator_failed"]:
-            assert np.abs(mu - ref["mu"]).max() <= 1e-8 * np.abs(ref["mu"]).max() + 1e-12, label
-        assert abs(r["dipole_rrms"] - ref["dipole_rrms"]) <= 1e-6 * abs(ref["dipole_rrms"]) + 1e-14, label
-    S.close()
 
 
 SIZES = [1, 2, 3, 17, 63, 64, 65, 127, 129, 200, 321]

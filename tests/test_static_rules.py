@@ -56,3 +56,32 @@ def test_every_kernel_launch_names_a_stream():
 def test_stale_references_are_gone():
     # pair_math.h used to cite a tests/hostcheck that never existed
     assert "tests/hostcheck" not in open(os.path.join(CSRC, "pair_math.h")).read()
+
+
+def test_size_ladder_finds_every_constant():
+    """test_gpu_size_ladder takes its rungs from the sources (util.size_ladder): every constant it parses is defined exactly once, every
+    switch is still written the way the rungs assume, and every rung comes out -- a renamed or removed constant fails here instead of
+    leaving the ladder with fewer rungs."""
+    c = util.ladder_constants()
+    assert set(c) == set(util.LADDER_CONSTANTS) and all(v > 0 for v in c.values()), c
+    for f, uses in util.LADDER_USES.items():
+        txt = util.csrc_text(f)
+        for pat in uses:
+            assert re.search(pat, txt), (f, pat)
+    rungs = util.size_ladder()
+    assert {"single_launch", "side_stream", "sweep", "pair_waves"} <= set(rungs), rungs
+    ks = sorted(k for k in rungs if k.startswith("ksplit_"))
+    # one k-slice switch per halving from kKSplitMax down to kKSplit
+    assert len(ks) == (c["kKSplitMax"] // c["kKSplit"]).bit_length() - 1, ks
+    for name, (lo, hi) in rungs.items():
+        assert hi == lo + 1 and lo >= 1, (name, lo, hi)
+        n_lo, n_hi = util.rung_sizes(lo)
+        assert -(-n_lo // c["kTile"]) == lo and -(-n_hi // c["kTile"]) == hi and n_hi % c["kTile"] == 1, (name, n_lo, n_hi)
+    pairs = lambda nt: nt * (nt + 1) // 2
+    for name, key in (("side_stream", "kOneStreamMaxPairs"), ("sweep", "kSweepMinPairs"), ("pair_waves", "kPairSplitMax")):
+        lo, hi = rungs[name]
+        assert pairs(lo) <= c[key] < pairs(hi), (name, lo, hi, c[key])
+    assert rungs["single_launch"] == (c["kSingleLaunchTiles"], c["kSingleLaunchTiles"] + 1)
+    for name in ks:
+        lo, hi = rungs[name]
+        assert util.recip_ksplit(lo, c) == 2 * util.recip_ksplit(hi, c) == 2 * int(name.split("_")[1]), (name, lo, hi)
