@@ -92,9 +92,9 @@ int main(int argc, char **argv) {
 		const double e = s.energy();
 		const mpmc::observables_t *o = s.observables;
 		std::printf("{\"natoms\": %d, \"total\": %.17g, \"rd\": %.17g, \"es\": %.17g, \"polar\": %.17g, \"es_real\": %.17g, \"es_recip\": %.17g, "
-		            "\"es_self\": %.17g, \"n_lj_in_cutoff\": %lld, \"n_es_in_cutoff\": %lld, \"polar_iterations\": %d, \"mu0\": [%.17g, %.17g, %.17g]}\n",
+		            "\"es_self\": %.17g, \"three_body\": %.17g, \"n_lj_in_cutoff\": %lld, \"n_es_in_cutoff\": %lld, \"polar_iterations\": %d, \"mu0\": [%.17g, %.17g, %.17g]}\n",
 		            s.natoms, e, o->rd_energy, o->coulombic_energy, o->polarization_energy, s.last_result.es_real, s.last_result.es_recip,
-		            s.last_result.es_self, (long long)s.last_result.n_lj_in_cutoff, (long long)s.last_result.n_es_in_cutoff,
+		            s.last_result.es_self, o->three_body_energy, (long long)s.last_result.n_lj_in_cutoff, (long long)s.last_result.n_es_in_cutoff,
 		            s.last_result.polar_iterations, s.atoms[0].mu[0], s.atoms[0].mu[1], s.atoms[0].mu[2]);
 	} catch (int code) {
 		std::printf("{\"error\": %d}\n", code);

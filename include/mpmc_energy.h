@@ -73,7 +73,7 @@ extern "C" {
 #define MPMC_FLAG_POLAR_ZODID (1ull << 12)
 #define MPMC_FLAG_NON_LB_MIXING (1ull << 13) /* waldmanhagler / halgren / c6_mixing / cdvdw_* */
 #define MPMC_FLAG_OTHER_RD (1ull << 14)      /* dreiding / lj_buffered_14_7 / disp_expansion / anharmonic / exp_repulsion */
-#define MPMC_FLAG_AXILROD_TELLER (1ull << 15)
+#define MPMC_FLAG_AXILROD_TELLER (1ull << 15) /* still refused here: the term is switched on by mpmc_set_axilrod_teller alone */
 #define MPMC_FLAG_CAVITY_AUTOREJECT (1ull << 16)
 #define MPMC_FLAG_POLAR_MATRIX_INVERSION (1ull << 17) /* polarization on with polar_iterative off */
 
@@ -111,7 +111,7 @@ typedef struct mpmc_result {
 	double coulombic_energy;    /* observables->coulombic_energy     (real + reciprocal + self)             */
 	double polarization_energy; /* observables->polarization_energy  (-1/2 sum mu.E0)                       */
 	double vdw_energy;          /* always 0 (polarvdw is out of scope)                                      */
-	double three_body_energy;   /* always 0                                                                 */
+	double three_body_energy;   /* observables->three_body_energy: Axilrod-Teller (mpmc_set_axilrod_teller), else 0 */
 	double kinetic_energy;      /* always 0 (gwp out of scope)                                              */
 	double es_real;             /* coulombic_real()                                                         */
 	double es_recip;            /* coulombic_reciprocal()                                                   */
@@ -142,6 +142,7 @@ typedef struct mpmc_result {
 #define MPMC_K_DIPOLE_ITER 4 /* Jacobi contraction, stored tensors streamed (one launch per iteration; MATRIX_FREE: its kernel) */
 #define MPMC_K_REDUCE 5      /* dipole update / final reductions / polarization energy */
 #define MPMC_K_DIPOLE_FAR 6  /* unused since ABI 4 (the two-kernel form of the Jacobi contraction is gone); the slot stays for layout stability */
+#define MPMC_K_THREE_BODY 6  /* the slot's use since: Axilrod-Teller sum / trial-move difference (0 for every context without the term) */
 #define MPMC_K_CLASSES 7     /* tile bounding boxes, tile-pair classes, panel table of the Jacobi contraction     */
 #define MPMC_K_COUNT 8
 typedef struct mpmc_timings {
@@ -222,6 +223,17 @@ int mpmc_trial_energy_async(mpmc_ctx *ctx);
 int mpmc_trial_energy_wait(mpmc_ctx *ctx, mpmc_result *out);
 int mpmc_trial_accept(mpmc_ctx *ctx);
 int mpmc_trial_reject(mpmc_ctx *ctx);
+
+/* ---- the Axilrod-Teller triple-dipole dispersion, System::axilrod_teller (src/System.Energy.cpp:129-136, 1653-1770) --------------------
+ * Sum over every unordered triple of distinct atoms that are not all in one molecule, no cutoff, frozen atoms included; each pair vector is
+ * that pair's own minimum image.  Added to energy (and NU) as three_body_energy; the path-integral sums stay {rd, coulombic, polarization,
+ * vdw} (PathIntegral.cpp:752-805), per_bead carries the field.  Cost O(N^3) per evaluation, O(m N^2) per trial move of m <= MPMC_TRIAL_MAX_ATOMS
+ * atoms.  Per-atom coefficients in the caller's atom order, length n of the current atom list: c6 is read only with midzuno_kihara_approx
+ * (c9_i = 3/4 alpha_i 6.7483345 c6_i), c9 only without it; either may then be NULL.  enabled = 0 switches the term off.  mpmc_set_atoms
+ * discards the coefficients (the setting stays): an evaluation with the term on and no coefficients fails with MPMC_ERR_ARG.  Position
+ * updates and accepted trials keep them. */
+int mpmc_set_axilrod_teller(mpmc_ctx *ctx, int enabled, int midzuno_kihara_approx, const double *c6, const double *c9);
+int mpmc_axilrod_teller(mpmc_ctx *ctx, double *out); /* System::axilrod_teller(), component entry like mpmc_lj */
 
 /* ---- public component entry points of the reference (src/System.h:346-402), for parity tests ----------- */
 int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj()                   */

@@ -108,6 +108,7 @@ inline void read_pqr(const std::string &path, System &s) {
 		if (t.size() > 16 && to_double(t[16], c)) a.c6 = c;
 		if (t.size() > 17 && to_double(t[17], c)) a.c8 = c;
 		if (t.size() > 18 && to_double(t[18], c)) a.c10 = c;
+		if (t.size() > 19 && to_double(t[19], c)) a.c9 = c;
 		s.atoms.push_back(a);
 	}
 	if (s.atoms.empty()) throw 3001; // no_molecules_in_system
@@ -127,7 +128,7 @@ inline std::string read_input(const std::string &path, System &s) {
 	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"waldmanhagler", MPMC_FLAG_NON_LB_MIXING},
 	    {"halgren_mixing", MPMC_FLAG_NON_LB_MIXING}, {"c6_mixing", MPMC_FLAG_NON_LB_MIXING}, {"dreiding", MPMC_FLAG_OTHER_RD},
 	    {"lj_buffered_14_7", MPMC_FLAG_OTHER_RD}, {"disp_expansion", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
-	    {"axilrod_teller", MPMC_FLAG_AXILROD_TELLER}, {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
+	    {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
 	    {"cavity_autoreject_absolute", MPMC_FLAG_CAVITY_AUTOREJECT}};
 	std::string pqr, line;
 	while (std::getline(f, line)) {
@@ -158,6 +159,8 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "polar_rrms") { need(1); s.polar_rrms = onoff(t[1]); }
 		else if (k == "wolf") { need(1); s.wolf = onoff(t[1]); }
 		else if (k == "feynman_hibbs") { need(1); s.feynman_hibbs = onoff(t[1]); }
+		else if (k == "axilrod_teller") { need(1); s.using_axilrod_teller = onoff(t[1]) != 0; }
+		else if (k == "midzuno_kihara_approx") { need(1); s.midzuno_kihara_approx = onoff(t[1]); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
 		else if (k == "polar_max_iter") { need(1); s.polar_max_iter = (int)dval(1); }

@@ -152,6 +152,7 @@ public:
 		mol_first.push_back((int)a.size());
 		for (SystemT *s : systems) {
 			if (s->atoms.size() != a.size()) throw 9000; // internal_error: images are not consistent (:1427)
+			if (uses_three_body(*s, 0)) throw 4004;     // unsupported_setting: the three-body term is not part of this driver (yet)
 			s->temperature = cfg.temperature;
 		}
 		pi.systems = systems;

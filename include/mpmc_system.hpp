@@ -55,11 +55,18 @@ struct nodestats_t {
 	double polarization_iterations = 0;
 };
 
+// whether a System-like type switches the Axilrod-Teller term on (the drivers are templates; a type without the member never does)
+template <class T>
+auto uses_three_body(const T &s, int) -> decltype(bool(s.using_axilrod_teller)) { return s.using_axilrod_teller; }
+template <class T>
+bool uses_three_body(const T &, long) { return false; }
+
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
 	double pos[3] = {0, 0, 0};
 	double mass = 0, charge = 0, polarizability = 0, epsilon = 0, sigma = 0;
 	double c6 = 0, c8 = 0, c10 = 0;
+	double c9 = 0; // Axilrod-Teller coefficient (PQR column 20, src/System.cpp:721)
 	int frozen = 0;
 	int molecule = 0; // index of the owning molecule (consecutive atoms with equal index form one Molecule)
 	int moltype = -1; // index into System::moltype_names (the molecule-type column of the PQR row; -1: not recorded)
@@ -75,6 +82,8 @@ public:
 	int damp_type = DAMPING_EXPONENTIAL;
 	int ewald_kmax = 7;
 	int wolf = 0, feynman_hibbs = 0, feynman_hibbs_order = 0;
+	bool using_axilrod_teller = false; // three-body dispersion (mpmc_set_axilrod_teller), src/System.h:659
+	int midzuno_kihara_approx = 0;     // its c9 from c6, src/System.h:655
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
 	double ewald_alpha = 0.5, polar_ewald_alpha = 0.5;
@@ -264,6 +273,8 @@ private:
 	int in_flight_hint_ = 1;
 	int capacity_ = 0;
 	bool atoms_dirty_ = true, box_dirty_ = true;
+	bool three_body_on_ = false; // what the context's three-body setting is (sync_state)
+	int three_body_mk_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
 	mpmc_result trial_result_{};
@@ -330,6 +341,15 @@ private:
 			check(mpmc_set_atoms(ctx_, n, pos.data(), q.data(), al.data(), ep.data(), sg.data(), mol.data(), fr.data(), dp.data(), ms.data()),
 			      "mpmc_set_atoms");
 			atoms_dirty_ = false;
+			three_body_on_ = false; // (the library discards the coefficients with the atom list)
+		}
+		// the three-body term after every upload of the atoms, and whenever the switch changed
+		if (using_axilrod_teller != three_body_on_ || (using_axilrod_teller && midzuno_kihara_approx != three_body_mk_)) {
+			std::vector<double> c6(n), c9(n);
+			for (int i = 0; i < n; i++) c6[i] = atoms[i].c6, c9[i] = atoms[i].c9;
+			check(mpmc_set_axilrod_teller(ctx_, using_axilrod_teller ? 1 : 0, midzuno_kihara_approx, c6.data(), c9.data()), "mpmc_set_axilrod_teller");
+			three_body_on_ = using_axilrod_teller;
+			three_body_mk_ = midzuno_kihara_approx;
 		}
 	}
 

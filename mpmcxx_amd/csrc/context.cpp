@@ -211,7 +211,7 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	void *ptrs[] = {c->d_atoms_blob, c->d_atom_part, c->d_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_scal,
 	                c->d_flag, c->d_counter, c->d_kvec, c->d_kw, c->d_sf, c->d_w_en, c->d_e_recip_part, c->d_part, c->d_e_static, c->d_mu[0], c->d_mu[1],
 	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
-	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list};
+	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (c->h_stage) (void)pinned_free(c->h_stage);
@@ -588,6 +588,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	}
 	c->h_pos_sorted = c->h_pos;        // where every atom stood when this order was made
 	c->atoms_dirty = false;
+	if (c->tb_have) c->tb_dirty = true; // (the three-body coefficients follow the order at the next evaluation that needs them)
 	return MPMC_OK;
 }
 
@@ -615,6 +616,8 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	f->n_poll_hits = c->n_poll_hits, f->n_poll_timeouts = c->n_poll_timeouts, f->n_stream_syncs = c->n_stream_syncs, f->n_poll_yields = c->n_poll_yields;
 	f->n_uploads_carried = c->n_uploads_carried; // (diagnostics survive the growth; the order itself does not: the new context sorts)
 	f->n_uploads_sorted = c->n_uploads_sorted;
+	f->tb_enabled = c->tb_enabled; // (the three-body setting survives; its coefficients go with the atom list that is being replaced)
+	f->tb_mk = c->tb_mk;
 	std::swap(*c, *f);
 	mpmc_ctx_destroy(f); // now owns the old, smaller buffers
 	return MPMC_OK;
@@ -725,6 +728,70 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->pending = false;
 	c->cache_valid = false;
 	c->trial_open = false;
+	c->tb_have = false; // per-atom three-body coefficients belong to the old list (mpmc_set_axilrod_teller again)
+	c->tb_dirty = false;
+	c->h_tb_au.clear();
+	return MPMC_OK;
+}
+
+// ---- Axilrod-Teller coefficients (System::axilrod_teller, src/System.Energy.cpp:1685-1709) ------------------------------------------------
+// Per atom a_i = 6.7483345 alpha_i and u_i = a_i^3 / c9_i, so that c9_abc = 3 a_a a_b a_c / (u_a + u_b + u_c) times the unit factor
+// (kThreeBodyScale).  The reference gives 0 for a triple with alpha = 0 (explicitly) or c9 = 0 (1 / (c9 / a^3) is infinite); such an atom
+// carries a = 0, u = 1 here, which gives the same 0 without an infinity on the device.
+static void three_body_coefficients(int n, const double *alpha, int mk, const double *c6, const double *c9, std::vector<double> &au) {
+	au.assign(2 * (size_t)n, 0.0);
+	for (int i = 0; i < n; i++) {
+		const double a = alpha[i] * 6.7483345;
+		const double c9i = mk ? 3.0 / 4.0 * alpha[i] * 6.7483345 * c6[i] : c9[i]; // (Midzuno-Kihara: :1693-1697)
+		const double u = 1.0 / (c9i / std::pow(a, 3));
+		const bool zero = (alpha[i] == 0.0) || !std::isfinite(u) || u == 0.0;
+		au[2 * (size_t)i] = zero ? 0.0 : a;
+		au[2 * (size_t)i + 1] = zero ? 1.0 : u;
+	}
+}
+
+extern "C" int mpmc_set_axilrod_teller(mpmc_ctx *c, int enabled, int mk, const double *c6, const double *c9) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: an evaluation or a trial move is open");
+	if (!enabled) {
+		if (c->tb_enabled) c->cache_valid = false; // (the accepted totals carry the term)
+		c->tb_enabled = c->tb_mk = c->tb_have = c->tb_dirty = false;
+		c->h_tb_au.clear();
+		return MPMC_OK;
+	}
+	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: set the atoms first (the coefficients are per atom)");
+	const double *src = mk ? c6 : c9;
+	if (!src) return fail(c, MPMC_ERR_ARG, mk ? "mpmc_set_axilrod_teller: midzuno_kihara_approx needs c6" : "mpmc_set_axilrod_teller: c9 is NULL");
+	for (int i = 0; i < c->n; i++)
+		if (!std::isfinite(src[i])) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_set_axilrod_teller: non-finite coefficient");
+	if (three_body_tile_triples(c->n_tiles) > 0x7fffffffLL)
+		return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: more tile triples than one launch can index");
+	three_body_coefficients(c->n, c->h_alpha.data(), mk, c6, c9, c->h_tb_au);
+	c->tb_enabled = c->tb_have = c->tb_dirty = true;
+	c->tb_mk = mk != 0;
+	c->cache_valid = false; // (the accepted totals of trial moves lack the term until the next mpmc_energy)
+	return MPMC_OK;
+}
+
+int mpmc::three_body_ready(mpmc_ctx *c) {
+	if (!c->tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the Axilrod-Teller term is off (mpmc_set_axilrod_teller)");
+	if (!c->tb_have)
+		return fail(c, MPMC_ERR_ARG, "the Axilrod-Teller term is on but has no coefficients for this atom list (mpmc_set_axilrod_teller after mpmc_set_atoms)");
+	int rc;
+	if (!c->d_tb_au) {
+		if ((rc = dev_alloc(c, &c->d_tb_au, (size_t)c->max_pad)) != MPMC_OK) return rc;
+		if ((rc = dev_alloc(c, &c->d_tb_part, (size_t)kThreeBodyBlocks)) != MPMC_OK) return rc;
+	}
+	if (c->tb_dirty) { // slot order, like every other per-atom array (upload_atoms)
+		std::vector<double2> au((size_t)c->n_pad, make_double2(0.0, 1.0));
+		for (int k = 0; k < c->n; k++) {
+			const int i = c->perm[k];
+			au[k] = make_double2(c->h_tb_au[2 * (size_t)i], c->h_tb_au[2 * (size_t)i + 1]);
+		}
+		HIP_TRY(c, hipMemcpyAsync(c->d_tb_au, au.data(), au.size() * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // (`au` dies here; once per upload of the atoms)
+		c->tb_dirty = false;
+	}
 	return MPMC_OK;
 }
 

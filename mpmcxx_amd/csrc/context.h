@@ -267,7 +267,7 @@ struct mpmc_ctx {
 	int touch_n = -1, touch[8] = {0}; // what enqueue(RUN_STORE) passes to the store-only sweep (-1: all tile pairs)
 	unsigned char *d_mv_blob = nullptr, *h_mv_blob = nullptr; // device / pinned host staging of a trial's moved-atom list
 	int cap_sf_trial = 0;
-	double *d_delta_out = nullptr, *h_delta_out = nullptr; // h: pinned [9] = 5 doubles, 2 int64 counts, spare, launch number (k_delta_finish posts it)
+	double *d_delta_out = nullptr, *h_delta_out = nullptr; // h: pinned [9] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it)
 	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
@@ -276,6 +276,14 @@ struct mpmc_ctx {
 	// how the host waits ended (mpmc_debug_wait_counters): polls that saw the device's post, polls that ran out of their budget (the
 	// wait then fell back to a stream synchronisation), plain stream synchronisations, and yields taken inside long polls
 	long long n_poll_hits = 0, n_poll_timeouts = 0, n_stream_syncs = 0, n_poll_yields = 0;
+
+	// Axilrod-Teller three-body term (mpmc_set_axilrod_teller, kernels_three_body.hip)
+	bool tb_enabled = false, tb_mk = false; // switched on; Midzuno-Kihara c9 (kept across mpmc_set_atoms and capacity growth)
+	bool tb_have = false;                   // coefficients set since the last mpmc_set_atoms
+	bool tb_dirty = false;                  // d_tb_au is older than h_tb_au or than the spatial order
+	std::vector<double> h_tb_au;            // [n][2] (a, u) per atom in original order (three_body_coefficients)
+	double2 *d_tb_au = nullptr;             // [max_pad] the same in slot order, padding (0, 1)
+	double *d_tb_part = nullptr;            // [kThreeBodyBlocks] per-workgroup partials
 
 	// profiling
 	bool prof = false;
@@ -433,8 +441,13 @@ inline void join_side(mpmc_ctx *c) {
 // ---- shared between the translation units ---------------------------------------------------------------------
 enum : unsigned {
 	RUN_PAIR = 1, RUN_PAIR_ES = 2, RUN_RECIP = 4, RUN_ATOMTERMS = 8, RUN_FIELD = 16, RUN_SOLVE = 32, RUN_WOLF = 64,
-	RUN_STORE = 128 // tile classes + the Thole tensor store alone (no energies, no field): trial moves of polarizable boxes
+	RUN_STORE = 128, // tile classes + the Thole tensor store alone (no energies, no field): trial moves of polarizable boxes
+	RUN_THREE_BODY = 256 // the Axilrod-Teller sum (contexts with the term switched on)
 };
+// 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
+// applied once to the sum of the per-triple terms
+constexpr double kThreeBodyScale = 3.0 * (0.0032539449 / (3.166811429 * 0.000001));
+int three_body_ready(mpmc_ctx *c); // the term is on and its coefficients are on the device in the current slot order (context.cpp)
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
 int enqueue(mpmc_ctx *c, unsigned mask);         // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp)
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)

@@ -251,6 +251,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	// stale position-independent terms ride along with this evaluation (an insertion / removal makes them stale every time)
 	int rc = prepare(c, true);
 	if (rc != MPMC_OK) return rc;
+	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
 	const bool static_ride = c->static_dirty;
 	c->static_ride_gen = 0;
 	const AtomsDev at = atoms_view(c);
@@ -591,6 +592,11 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		}
 		c->have_polar = true;
 	}
+	// ---- Axilrod-Teller, System::axilrod_teller (:129-136): into its slot of the scalar block, in front of the post below ----------------
+	if (mask & RUN_THREE_BODY) {
+		ProfScope p(c, MPMC_K_THREE_BODY);
+		launch_three_body(st, at, c->d_tb_au, c->box, kThreeBodyScale, c->d_tb_part, c->d_scal + S_THREE_BODY);
+	}
 	HIP_TRY(c, hipGetLastError());
 	// results to the pinned block by a kernel of ours (a blit and a stream synchronisation cost more than the whole reciprocal space of a
 	// small box): copy, zero the device block for the next evaluation, launch number last
@@ -751,6 +757,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	out->coulombic_energy = (out->es_real + out->es_recip) + out->es_self; // coulombic() :1412
 	out->polarization_energy = s[S_POLAR];
 	out->dipole_rrms = s[S_RRMS];
+	out->three_body_energy = (c->run_mask & RUN_THREE_BODY) ? s[S_THREE_BODY] : 0.0;
 	out->energy = out->rd_energy + out->coulombic_energy + out->polarization_energy + out->vdw_energy + out->three_body_energy; // :136
 	out->N = c->N_movable;
 	out->NU = out->N * out->energy; // :162
@@ -777,6 +784,7 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 		m |= c->opts.wolf ? RUN_WOLF : RUN_RECIP; // coulombic() :1404-1413: Wolf replaces real + reciprocal + self
 		if (c->opts.polarization) m |= RUN_FIELD | RUN_SOLVE;
 	}
+	if (c->tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
 	return m;
 }
 
@@ -846,6 +854,14 @@ extern "C" int mpmc_polar(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	int rc = run_piece(c, RUN_FIELD | RUN_SOLVE, &r);
 	if (rc == MPMC_OK && out) *out = r.polarization_energy;
+	return rc;
+}
+extern "C" int mpmc_axilrod_teller(mpmc_ctx *c, double *out) {
+	if (!c) return MPMC_ERR_ARG;
+	if (!c->tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_axilrod_teller: the term is off (mpmc_set_axilrod_teller)");
+	mpmc_result r;
+	int rc = run_piece(c, RUN_THREE_BODY, &r);
+	if (rc == MPMC_OK && out) *out = r.three_body_energy;
 	return rc;
 }
 // device per-atom vectors are in slot order; everything handed to the caller is in original atom order

@@ -41,6 +41,7 @@ enum : int {
 	S_LJ = 0, S_LRC_PAIR, S_ES_REAL, S_ES_INTRA, // pair kernel
 	S_ES_RECIP, S_ES_SELF, S_LRC_SELF,           // recip / atom kernel
 	S_POLAR, S_RRMS,                             // polarization
+	S_THREE_BODY,                                // Axilrod-Teller (kernels_three_body.hip)
 	S_COUNT = 16
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
@@ -259,6 +260,19 @@ void launch_delta_field(hipStream_t st, const AtomsDev &at, const Box &bx, doubl
                         const double4 *mv_new, int m, int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part);
 // resident positions of the moved atoms <-> mv_new (call again to undo)
 void launch_swap_positions(hipStream_t st, double4 *xyzq, const int *mv_slot, double4 *mv_new, int m);
+
+// ---- Axilrod-Teller three-body dispersion (kernels_three_body.hip) --------------------------------------------------------------
+// au[slot] = (a, u) per atom (context.cpp: three_body_coefficients; padding a = 0, u = 1).  Both launches leave kThreeBodyBlocks (or fewer)
+// partials in `part` and write scale * their fixed-order sum to out[0].
+constexpr int kThreeBodyBlocks = 8192;
+long long three_body_tile_triples(int n_tiles);
+int three_body_grid(long long work_items); // partials a launch over this many tile triples / tile pairs leaves
+// the full sum over unordered triples
+void launch_three_body(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, double *part, double *out);
+// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
+// kernels (marked and cleared again inside)
+void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, const int *mv_slot, const double4 *mv_new,
+                             int m, int *moved_idx, double *part, double *out);
 
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);

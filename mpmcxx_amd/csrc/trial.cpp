@@ -18,7 +18,7 @@ static int ensure_trial_buffers(mpmc_ctx *c) {
 		c->d_mv_slot = reinterpret_cast<int *>(c->d_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		c->d_mv_orig = c->d_mv_slot + MPMC_TRIAL_MAX_ATOMS;
 		if ((rc = dev_alloc(c, &c->d_moved_idx, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_delta_out, (size_t)8)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts
+		if ((rc = dev_alloc(c, &c->d_delta_out, (size_t)8)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body delta
 		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + 5);
 		HIP_TRY(c, hipMemsetAsync(c->d_moved_idx, 0xff, (size_t)c->max_pad * sizeof(int), c->stream)); // all -1; on our stream (ordered before the first delta kernel)
 		HIP_TRY(c, pinned_alloc(&c->h_delta_out, 9 * sizeof(double)));
@@ -92,7 +92,8 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// short moves of non-polarizable boxes travel in the kernel arguments: no staging copy (a trial is launch-bound on the host: every
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->tune.no_inline_move;
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline;
+	// (the three-body delta reads the moved atoms from the device lists: a box with the term always stages its move)
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->tb_enabled;
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -118,6 +119,14 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		HIP_TRY(c, hipMemcpyAsync(c->d_mv_blob, c->h_mv_blob, kMvBlobBytes, hipMemcpyHostToDevice, st));
 	}
 	const int do_es = o.rd_only ? 0 : 1;
+	if (c->tb_enabled) {
+		// Axilrod-Teller: the change of the triples with a moved atom, O(m N^2), with the accepted positions still resident; its sum lands in
+		// the spare slot 7 of the delta result block, which k_delta_finish copies out in front of the launch number it posts
+		if ((rc = three_body_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_THREE_BODY);
+		launch_three_body_delta(st, atoms_view(c), c->d_tb_au, c->box, kThreeBodyScale, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_tb_part,
+		                        c->d_delta_out + 7);
+	}
 	{
 		FusedParams fp{};
 		fp.ewald_alpha = c->ewald_alpha;
@@ -239,6 +248,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		r.polar_iterations = solved.polar_iterations;
 		r.iterator_failed = solved.iterator_failed;
 	}
+	if (c->tb_enabled) r.three_body_energy = a.three_body_energy + c->h_delta_out[7];
 	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
 	r.NU = r.N * r.energy;
 	c->trial_res = r;

@@ -110,6 +110,9 @@ def lib():
     L.mpmc_energy_wait.argtypes = [vp, C.POINTER(Result)]
     for name in ("mpmc_lj", "mpmc_coulombic", "mpmc_coulombic_real", "mpmc_coulombic_reciprocal", "mpmc_coulombic_self", "mpmc_polar"):
         getattr(L, name).argtypes = [vp, dp]
+    if hasattr(L, "mpmc_set_axilrod_teller") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no three-body term)
+        L.mpmc_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+        L.mpmc_axilrod_teller.argtypes = [vp, dp]
     L.mpmc_thole_field.argtypes = [vp, dp]
     L.mpmc_thole_amatrix.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_get_dipoles.argtypes = [vp, dp, dp, dp]
@@ -315,6 +318,20 @@ class System:
         self._check(self._L.mpmc_set_atoms(self._h, n, _dp(pos), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
                                            _dp(f("sigma")), _ip(g("mol_id")), _ip(g("frozen")), _ip(disp), _dp(mass)))
         self.n = n
+        # the library discards three-body coefficients with every atom list: the term follows the options (`axilrod_teller on`)
+        if self.options.get("axilrod_teller"):
+            mk = bool(self.options.get("midzuno_kihara_approx"))
+            key = "c6" if mk else "c9"
+            if key not in atoms:
+                raise ValueError(f"axilrod_teller is on but the atoms carry no {key!r} column")
+            self.set_axilrod_teller(True, atoms[key] if mk else None, None if mk else atoms[key], midzuno_kihara_approx=mk)
+
+    def set_axilrod_teller(self, enabled: bool, c6: Optional[np.ndarray] = None, c9: Optional[np.ndarray] = None,
+                           midzuno_kihara_approx: bool = False):
+        """switch the Axilrod-Teller three-body term on (per-atom c9, or c6 under the Midzuno-Kihara form) or off (mpmc_set_axilrod_teller)"""
+        a6 = None if c6 is None else np.ascontiguousarray(c6, dtype=np.float64)
+        a9 = None if c9 is None else np.ascontiguousarray(c9, dtype=np.float64)
+        self._check(self._L.mpmc_set_axilrod_teller(self._h, int(bool(enabled)), int(bool(midzuno_kihara_approx)), _dp(a6), _dp(a9)))
 
     def update_positions(self, first: int, pos: np.ndarray):
         p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
@@ -372,6 +389,9 @@ class System:
 
     def lj(self) -> float:
         return self._scalar(self._L.mpmc_lj)
+
+    def axilrod_teller(self) -> float:
+        return self._scalar(self._L.mpmc_axilrod_teller)
 
     def coulombic(self) -> float:
         return self._scalar(self._L.mpmc_coulombic)

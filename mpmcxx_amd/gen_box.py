@@ -37,13 +37,22 @@ class AtomRow:
     alpha: float
     eps: float
     sigma: float
+    # dispersion coefficients (reference PQR columns 17-20, src/System.cpp:587): only rows that carry them print them
+    c6: Optional[float] = None
+    c8: Optional[float] = None
+    c10: Optional[float] = None
+    c9: Optional[float] = None
 
     def line(self) -> str:
-        return (
+        s = (
             f"ATOM {self.atom_id:6d} {self.atomtype:<4s} {self.moltype:<4s} {self.flag} {self.mol_id:6d} "
             f"{self.x:12.6f} {self.y:12.6f} {self.z:12.6f} {self.mass:9.5f} {self.charge_e:9.5f} "
             f"{self.alpha:8.5f} {self.eps:10.5f} {self.sigma:8.5f} 0.00000 0.00000"
         )
+        coef = (self.c6, self.c8, self.c10, self.c9)
+        if any(v is not None for v in coef):
+            s += "".join(f" {(v or 0.0)!r}" for v in coef)
+        return s
 
 
 def lattice_box(
@@ -317,6 +326,56 @@ def fixture(name: str):
         for r, (x, y, z) in zip(rows, pos):
             r.x, r.y, r.z = float(x), float(y), float(z)
         return rows, cubic(86.0), dict(POLAR_OPTS)
+    if name in THREE_BODY_FIXTURES:
+        return _three_body_fixture(name)
+    raise KeyError(name)
+
+
+# ---- Axilrod-Teller three-body dispersion (`axilrod_teller on`, reference src/System.Energy.cpp:1653-1770) ----------------------------------
+# per-site c9 in hartree bohr^9 (the PQR's last column); c6 for the Midzuno-Kihara form (c9 = 3/4 alpha 6.7483345 c6)
+AT_C9 = {"Ar": 518.3, "O": 1200.0, "H": 25.0, "Xe": 6000.0}
+AT_C6 = {"Ar": 64.3}
+AT_OPTS = {"axilrod_teller": "on"}
+
+
+def _with_c9(rows: List[AtomRow], c9: Optional[Dict[str, float]] = None, c6: Optional[Dict[str, float]] = None) -> List[AtomRow]:
+    for r in rows:
+        r.c6, r.c8, r.c10 = (c6 or {}).get(r.atomtype, 0.0), 0.0, 0.0
+        r.c9 = (c9 or {}).get(r.atomtype, 0.0)
+    return rows
+
+
+def _three_body_fixture(name: str):
+    at = dict(AT_OPTS)
+    if name == "ar3_at":  # equilateral triangle (3,0,0) (0,3,0) (0,0,3), side sqrt(18) A, in a 10^4 A box: cos A cos B cos C = 1/8, LJ only
+        rows = [AtomRow(k + 1, "Ar", "Ar", "M", k + 1, *xyz, 39.948, 0.0, 1.6411, 119.8, 3.405)
+                for k, xyz in enumerate([(3.0, 0.0, 0.0), (0.0, 3.0, 0.0), (0.0, 0.0, 3.0)])]
+        return _with_c9(rows, AT_C9), cubic(10000.0), dict(at, rd_only="on")
+    if name == "ion216_at":  # single-site atoms, LJ + Ewald
+        return _with_c9(lattice_box(216, 24.0, 7), AT_C9), cubic(24.0), dict(at, ewald_kmax=7)
+    if name == "ion216_polar_at":
+        return _with_c9(lattice_box(216, 24.0, 7), AT_C9), cubic(24.0), dict(POLAR_OPTS, **at)
+    if name == "water64_at":  # 3-site molecules (same-molecule triples excluded), an alpha = 0 site, a neutral Xe
+        return _with_c9(molecular_box(64, 14.0, 5), AT_C9), cubic(14.0), dict(at, ewald_kmax=7)
+    if name == "ion216_framework_at":  # one frozen 150-site molecule + 66 mobile atoms
+        rows, basis, o = fixture("ion216_framework")
+        return _with_c9(rows, AT_C9), basis, dict(o, **at)
+    if name == "ion216_triclinic_at":
+        rows, basis, o = fixture("ion216_triclinic")
+        return _with_c9(rows, AT_C9), basis, dict(o, **at)
+    if name == "ion216_mk_at":  # Midzuno-Kihara c9 from the c6 column; the c9 column is 0 and must be ignored
+        return (_with_c9(lattice_box(216, 24.0, 7), None, AT_C6), cubic(24.0),
+                dict(at, ewald_kmax=7, midzuno_kihara_approx="on"))
+    if name == "grid_at":  # integer grid, spacing 2 in an 8 A box: every separation of 4 A is an exact half-box image tie
+        rows = []
+        for ix in range(4):
+            for iy in range(4):
+                for iz in range(4):
+                    k = len(rows) + 1
+                    rows.append(AtomRow(k, "Ar", "Ar", "M", k, 2.0 * ix - 4.0, 2.0 * iy - 4.0, 2.0 * iz - 4.0, 39.948, 0.0, 1.0, 50.0, 1.2))
+        return _with_c9(rows, {"Ar": 100.0}), cubic(8.0), dict(at, rd_only="on")
+    if name == "ion512_at":
+        return _with_c9(lattice_box(512, 32.0, 9), AT_C9), cubic(32.0), dict(at, ewald_kmax=7)
     raise KeyError(name)
 
 
@@ -339,7 +398,29 @@ SMALL_FIXTURES = [
     "ion216_wolf", "water64_fh2", "water64_fh4", "ion216_fh4_polar", "ion216_gs", "water64_gs_precision", "ion1000_gs", "ion216_framework",
     "ion1000_triclinic",
 ]
+# boxes with the Axilrod-Teller term: the C oracle (oracle/) has no three-body term, so they are kept apart from SMALL_FIXTURES
+THREE_BODY_FIXTURES = ["ar3_at", "ion216_at", "ion216_polar_at", "water64_at", "ion216_framework_at", "ion216_triclinic_at", "ion216_mk_at",
+                       "grid_at", "ion512_at"]
 LARGE_FIXTURES = ["ion10k_es", "ion10k_polar", "ion10k_polar_bead0", "ion10k_polar_bead1", "ion8000_triclinic"]
+
+
+def keep_three_body_golden(golden_dir: str) -> None:
+    """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>`: keep each box's scalar results (energies, counts, cell) and drop the
+    per-atom arrays and the box text.  The three-body tests compare nothing else, and they regenerate the boxes with `materialize`, which
+    writes the same bytes the reference read."""
+    import json
+
+    for name in THREE_BODY_FIXTURES:
+        path = os.path.join(golden_dir, f"{name}.json")
+        with open(path) as f:
+            res = json.load(f)
+        res = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+        with open(path, "w") as f:
+            json.dump(res, f, separators=(",", ":"))
+            f.write("\n")
+        for ext in (".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
 
 
 def materialize(name: str, outdir: str):
@@ -356,6 +437,9 @@ def materialize(name: str, outdir: str):
 if __name__ == "__main__":
     import sys
 
+    if sys.argv[1:2] == ["--keep-three-body-golden"]:
+        keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
     out = sys.argv[1] if len(sys.argv) > 1 else "."
     for nm in (sys.argv[2:] or SMALL_FIXTURES):
         print(materialize(nm, out))

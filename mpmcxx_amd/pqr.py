@@ -24,7 +24,7 @@ UNSUPPORTED_ON = [
     "rd_crystal", "spectre", "gwp", "sg", "polarvdw", "cdvdw", "polar_ewald_full",
     "polar_wolf", "polar_wolf_full", "polar_palmo", "polar_gs_ranked", "polar_sor", "polar_esor", "polar_zodid",
     "waldmanhagler", "halgren_mixing", "c6_mixing", "dreiding", "lj_buffered_14_7", "disp_expansion",
-    "axilrod_teller", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
+    "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
 ]
 
 
@@ -38,6 +38,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
     mol: List[int] = []
     frozen: List[int] = []
     disp: List[int] = []
+    c6: List[float] = []
+    c9: List[float] = []
     cur_mol_token = None
     mol_index = -1
     with open(path) as f:
@@ -68,6 +70,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
             frozen.append(1 if flag == "F" else 0)
             c = [float(x) for x in t[16:19]]
             disp.append(1 if any(v != 0.0 for v in c) else 0)
+            c6.append(c[0] if c else 0.0)  # (Axilrod-Teller: c6 feeds the Midzuno-Kihara c9, src/System.cpp:587, 721)
+            c9.append(float(t[19]) if len(t) > 19 else 0.0)
     return {
         "pos": np.ascontiguousarray(np.array(pos, dtype=np.float64).reshape(-1, 3)),
         "charge": np.array(q, dtype=np.float64),
@@ -78,6 +82,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
         "mol_id": np.array(mol, dtype=np.int32),
         "frozen": np.array(frozen, dtype=np.int32),
         "has_disp": np.array(disp, dtype=np.int32),
+        "c6": np.array(c6, dtype=np.float64),
+        "c9": np.array(c9, dtype=np.float64),
     }
 
 
@@ -117,6 +123,8 @@ def read_input(path: str) -> Dict[str, object]:
             elif k == "ensemble":
                 ensemble = v[0].lower()
             elif k in ("rd_only", "rd_lrc", "polarization", "polar_iterative", "polar_ewald", "polar_gs", "polar_rrms", "wolf", "feynman_hibbs"):
+                opts[k] = _onoff(v[0])
+            elif k in ("axilrod_teller", "midzuno_kihara_approx"):  # (set only when the input names them: other inputs load as before)
                 opts[k] = _onoff(v[0])
             elif k in ("polar_max_iter", "ewald_kmax", "feynman_hibbs_order"):
                 opts[k] = int(v[0])
