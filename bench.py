@@ -24,9 +24,12 @@ libamdhip64) and the librccl next to that runtime are all it maps (config.ranks[
   * --launch inprocess keeps ONE process that drives the N devices through mpmc_pi_allreduce (one host thread per device,
     ncclCommInitAll) -- the shape of the reference's OpenMP build (PathIntegral.cpp:772-779).
 
-The JSON line: the contract's keys, `roofline` (dominant kernel alone on the GPU by HIP events on its own stream; inside it, because
-the driver's record keeps that object whole: other_kernels, whole_step, other_configs = BASELINE configs[1..3] + the dense-matrix form of
-configs[3], pcie_inclusive_value, four_beads_in_flight) and `cpu_baseline` (the reference's own object code on one host core).
+The JSON line: the contract's keys, the run's configuration, the ensemble potential and `kernel_ms` (HIP events inside the timed region
+with --events-in-timed-region, else empty).  A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds the passes behind the timed region and their keys: `roofline` (dominant kernel alone on the GPU by HIP events on its own
+stream; inside it, because the driver's record keeps that object whole: other_kernels, whole_step, other_configs = BASELINE configs[1..3]
++ the dense-matrix form of configs[3], pcie_inclusive_value, four_beads_in_flight), `pcie_inclusive_value` and `cpu_baseline` (the
+reference's own object code on one host core).
 --dump-outputs DIR also writes what the last timed step computed as .npy files (dump_outputs), for comparing two builds output for output.
 """
 from __future__ import annotations
@@ -328,8 +331,12 @@ def main():
     ap.add_argument("--solver", default="auto")
     ap.add_argument("--concurrency", choices=["async", "serial"], default="async",
                     help="async: all local beads enqueued on their own streams before the first wait; serial: one bead at a time")
-    ap.add_argument("--cpu-baseline", choices=["auto", "port", "reference", "none"], default="auto",
-                    help="auto: the reference's own object code (oracle/_ref/ref_harness, ~25 s) where it was built, else the C port of the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also measure what the headline does not need: the kernel passes and the roofline, the "
+                         "PCIe-inclusive and four-bead rates, BASELINE configs[1..3] + dense, and the CPU baseline")
+    ap.add_argument("--cpu-baseline", choices=["auto", "port", "reference", "none"], default=None,
+                    help="auto: the reference's own object code (oracle/_ref/ref_harness, ~25 s) where it was built, else the C port of the oracle "
+                         "(default: auto with --full, none without)")
     ap.add_argument("--combine", choices=["gather", "reduce"], default="gather", help="reduce: only with --combine-impl torch")
     ap.add_argument("--combine-impl", choices=["cabi", "hub", "torch"], default="cabi",
                     help="cabi: ncclAllGather inside libmpmc_energy.so over a communicator from mpmc_comm_init_rank, torch-free ranks (falls back to "
@@ -339,8 +346,9 @@ def main():
                     help="seconds a rank waits for ncclCommInitRank + one probe all-gather (blocking collectives) before the job gives up on the run")
     ap.add_argument("--events-in-timed-region", action="store_true",
                     help="diagnostic: per-launch HIP events on one bead's stream INSIDE the timed region (by default it carries no instrumentation)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE configs[1..3] + dense pass (roofline.other_configs)")
-    ap.add_argument("--no-extra-passes", action="store_true", help="diagnostic: skip the isolated-kernel, PCIe-inclusive and 4-bead passes after the timed region")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the BASELINE configs[1..3] + dense pass (roofline.other_configs)")
+    ap.add_argument("--no-extra-passes", action="store_true",
+                    help="--full, diagnostic: skip the isolated-kernel, PCIe-inclusive and 4-bead passes after the timed region")
     ap.add_argument("--host-positions", action="store_true",
                     help="re-upload every bead's positions from host buffers inside each timed step (the PCIe-inclusive rate; the default run "
                          "measures it in a short extra pass and reports it as pcie_inclusive_value, never as value)")
@@ -448,17 +456,17 @@ def main():
     n = atoms["pos"].shape[0]
 
     mine = pi.beads_of_rank(P, rank, world)
+    host_pos = [np.ascontiguousarray(bead_positions(atoms["pos"], b)) for b in mine]  # (System copies them into the library)
     beads = []
     for k, b in enumerate(mine):
         a = dict(atoms)
-        a["pos"] = bead_positions(atoms["pos"], b)
+        a["pos"] = host_pos[k]
         beads.append(energy.System(a, basis, opts, device=devices[k % n_dev]))
     if inprocess and args.force_device is not None:
         # rehearsal on one GPU: bead k counts as living on "device" k mod N (the library's test hook "virtual_device"), so that the step below
         # runs the real thread-per-device path -- worker threads, hand-off, ordered combine -- with a host copy in RCCL's place
         for k, s in enumerate(beads):
             s.configure("virtual_device", k % n_dev)
-    host_pos = [np.ascontiguousarray(bead_positions(atoms["pos"], b)) for b in mine]
     state = {"host_positions": bool(args.host_positions), "per": None}
 
     def local_eval(systems=None, hp_all=None):
@@ -539,7 +547,7 @@ def main():
     dumped = None
     if args.dump_outputs and rank == 0:  # before the passes below evaluate the beads again
         dumped = dump_outputs(args.dump_outputs, v, obs, state["per"], beads, mine)
-    extra = not args.no_extra_passes
+    extra = args.full and not args.no_extra_passes
     if not events_in_region and extra:
         # what the kernels look like with the other beads in flight: a SEPARATE short pass behind the timed region, events on bead 0's stream
         beads[0].set_profiling(True)
@@ -551,8 +559,8 @@ def main():
         s.set_profiling(False)
     iters = int(beads[0].observables.get("polar_iterations", 0)) if beads else 0
     mem_total, mem_tensor = beads[0].memory_usage() if beads else (0, 0)
-    tiles = beads[0].tile_stats() if beads else {}
-    pairs = beads[0].pair_stats() if beads else {}
+    tiles = beads[0].tile_stats() if (beads and args.full) else {}
+    pairs = beads[0].pair_stats() if (beads and args.full) else {}
     single = n_gpus == 1 and extra  # the passes below keep nobody waiting in a barrier: one-GPU runs only
 
     # ---- PCIe-inclusive rate: the same step with every bead's positions handed over in host memory --------------------------
@@ -613,23 +621,6 @@ def main():
     if single and rank == 0 and not args.no_other_configs and not rehearsal and args.natoms == 10000:
         others = other_configs(P, P * args.steps / dt, local_rank, workdir)
 
-    pmc = {}  # per-launch PMC figures of the committed profiling passes (rocprofv3 cannot run inside this process): HBM bytes, executed flops
-    for rnd in ("r04", "r05"):
-        pth = os.path.join(ROOT, "profiles", f"{rnd}_traffic.json")
-        try:
-            with open(pth) as f:
-                for kname, rec in json.load(f).items():
-                    pmc[kname] = dict(rec, source=f"profiles/{rnd}_traffic.json (committed rocprofv3 --pmc passes of the builder, NOT counters of this run)")
-        except (OSError, ValueError):
-            pass
-    K = 709 if int(opts.get("ewald_kmax", 7)) == 7 else None
-    cut = float(gpu_bead0["n_es_in_cutoff"]) if gpu_bead0 else 0.0
-    flops_jacobi = (FLOP_JAC_STORED * pairs.get("pairs_stored", 0) + FLOP_JAC_FAR * pairs.get("pairs_far", 0)
-                    + FLOP_JAC_PER_NU * (pairs.get("nonuniform_dims_x_pairs_stored", 0) + pairs.get("nonuniform_dims_x_pairs_far", 0)))
-    flops_pair = sweep_flops(pairs, cut, True) if pairs else 0.0
-    flops_eval = flops_pair + iters * flops_jacobi + (FLOP_RECIP_PER_K_ATOM * K * n if K else 0.0)
-    bytes_jacobi = 16.0 * 4096 * pairs.get("tile_pairs_stored", 0) + n * 80.0
-
     my_info = {"rank": rank, "local_rank": local_rank, "device": f"hip:{local_rank}", "device_name": energy.device_name(local_rank), "pid": os.getpid(),
                "beads": mine, "comm_n_ranks": (comm.n_ranks if comm is not None else None), "torch_imported": "torch" in sys.modules,
                "rocm_libs": energy.loaded_rocm_libs()}
@@ -647,86 +638,105 @@ def main():
         n_local = len(beads)
         solver_used = "dense" if args.solver == "dense" else ("compact" if mem_tensor > 0 else "matrix_free")
         in_region = {k: round(tv["ms"] / max(tv["launches"], 1), 6) for k, tv in agg.items() if tv["launches"]}
-        alone = {k: round(tv["ms"] / max(tv["launches"], 1), 6) for k, tv in (iso or {}).items() if tv["launches"]}
-        src = alone if alone else in_region
+        roof = None
+        if args.full:
+            pmc = {}  # per-launch PMC figures of the committed profiling passes (rocprofv3 cannot run inside this process): HBM bytes, executed flops
+            for rnd in ("r04", "r05"):
+                pth = os.path.join(ROOT, "profiles", f"{rnd}_traffic.json")
+                try:
+                    with open(pth) as f:
+                        for kname, rec in json.load(f).items():
+                            pmc[kname] = dict(rec, source=f"profiles/{rnd}_traffic.json (committed rocprofv3 --pmc passes of the builder, NOT counters of this run)")
+                except (OSError, ValueError):
+                    pass
+            K = 709 if int(opts.get("ewald_kmax", 7)) == 7 else None
+            cut = float(gpu_bead0["n_es_in_cutoff"]) if gpu_bead0 else 0.0
+            flops_jacobi = (FLOP_JAC_STORED * pairs.get("pairs_stored", 0) + FLOP_JAC_FAR * pairs.get("pairs_far", 0)
+                            + FLOP_JAC_PER_NU * (pairs.get("nonuniform_dims_x_pairs_stored", 0) + pairs.get("nonuniform_dims_x_pairs_far", 0)))
+            flops_pair = sweep_flops(pairs, cut, True) if pairs else 0.0
+            flops_eval = flops_pair + iters * flops_jacobi + (FLOP_RECIP_PER_K_ATOM * K * n if K else 0.0)
+            bytes_jacobi = 16.0 * 4096 * pairs.get("tile_pairs_stored", 0) + n * 80.0
 
-        def compute_entry(kernel, cls_key, flops, launches_per_step):
-            """fp64 vector-issue roofline of one kernel.  avg_launch_ms: HIP events on the kernel's stream (alone on the GPU where the
-            isolated pass ran); achieved = algorithmic flops / that duration."""
-            ms = back_to_back.get(cls_key) or src.get(cls_key) or 1e30
-            e = fp64_entry(kernel, flops, ms,
-                           "median of three batches of 100 (pair sweep: 40) launches back to back between ONE pair of HIP events on the kernel's stream, "
-                           "per launch (kernel alone on the GPU)" if back_to_back.get(cls_key) else "HIP events around every launch on the kernel's stream")
-            e["algorithmic_flops_per_launch"] = e.pop("algorithmic_flops")
-            e.update({"traffic": None, "launches_per_step": launches_per_step, "consistent": bool(ms * launches_per_step <= ms_per_step),
-                      "frac_of_sustained_fma_rate": e["achieved"] / FP64_FMA_SUSTAINED_TFLOPS})
-            if back_to_back.get(cls_key):
-                e["avg_launch_ms_batches"] = back_to_back_runs.get(cls_key)
-                if src.get(cls_key):
-                    e["avg_launch_ms_event_pair_per_launch"] = src[cls_key]
-            t = pmc.get(kernel)
-            if t and t.get("natoms") == n:
-                e["traffic"] = t.get("hbm_bytes_per_launch")
-                e["traffic_source"] = t.get("source")
-                e["pmc"] = t
-                if t.get("trace_avg_launch_ms"):
-                    e["frac_by_trace_clock"] = flops / (t["trace_avg_launch_ms"] * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS
-                if t.get("valu_wave_insts_per_launch"):
-                    # every VALU instruction an FMA on 64 lanes would be 128 flops: the share of that which is algorithmic work, and the
-                    # ceiling of THIS instruction stream at the sustained issue rate
-                    e["algorithmic_flops_per_valu_slot"] = flops / (128.0 * t["valu_wave_insts_per_launch"])
-                    e["ceiling_frac_of_this_instruction_stream"] = e["algorithmic_flops_per_valu_slot"] * FP64_FMA_SUSTAINED_TFLOPS / FP64_VALU_PEAK_TFLOPS
-            return e
+            alone = {k: round(tv["ms"] / max(tv["launches"], 1), 6) for k, tv in (iso or {}).items() if tv["launches"]}
+            src = alone if alone else in_region
 
-        # dominant kernel: the one with the largest share of the device time of an evaluation (alone-on-the-GPU durations)
-        share = {"dipole_iter": (src.get("dipole_iter") or 0.0) * iters, "pair": src.get("pair") or 0.0}
-        dom = max(share, key=share.get) if any(share.values()) else "dipole_iter"
-        jac_kernel = "k_dipole_iter_panel" if solver_used == "compact" else "k_dipole_iter_hybrid"
-        if solver_used == "dense":
-            roof = dense_symv_entry(n, src.get("dipole_iter") or 1e30)
-            roof.update({"traffic": None, "launches_per_step": iters * n_local, "consistent": bool(roof["avg_launch_ms"] * iters * n_local <= ms_per_step)})
-        elif dom == "pair":
-            roof = compute_entry(pair_kernel_name, "pair", flops_pair, n_local)
-        else:
-            roof = compute_entry(jac_kernel, "dipole_iter", flops_jacobi, iters * n_local)
-            ms = roof["avg_launch_ms"]
-            roof["hbm_side"] = {"achieved": bytes_jacobi / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                "frac": bytes_jacobi / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": bytes_jacobi}
-        roof["measured"] = ("extra pass right after the timed region: ONE bead on ONE stream, every kernel alone on the GPU.  rocprofv3 --kernel-trace reports "
-                            "a little less for the same launch (profiles/*_serial_kernel_stats.csv; frac_by_trace_clock): its stamps leave out the dispatch "
-                            "and completion time between consecutive kernels of a stream" if alone else
-                            "HIP events on one bead's stream with the other beads in flight (stretched durations)")
-        roof["tile_pairs"] = tiles
-        roof["pairs"] = dict(pairs, in_cutoff=cut)
-        roof["flop_model"] = {"jacobi_stored": FLOP_JAC_STORED, "jacobi_far": FLOP_JAC_FAR, "jacobi_per_nonuniform_dim": FLOP_JAC_PER_NU,
-                              "sweep_base": FLOP_SWEEP_BASE, "sweep_per_nonuniform_dim": FLOP_SWEEP_PER_NU, "sweep_in_cutoff": FLOP_SWEEP_CUTOFF,
-                              "sweep_in_cutoff_no_field": FLOP_SWEEP_CUTOFF_NO_FIELD, "sweep_stored": FLOP_SWEEP_STORE,
-                              "what": "fp64 flops per unordered atom pair, FMA = 2 (top of bench.py, DESIGN.md section 3); pair counts are exact atom pairs "
-                                      "per tile-pair class (mpmc_debug_pair_stats)"}
-        roof["share_of_device_time_alone"] = share[dom] / max(sum((src.get(k) or 0.0) * (iters if k in ("dipole_iter", "reduce") else 1) for k in src), 1e-30)
-        # whole-step view, which overlap cannot distort: algorithmic flops of one evaluation x evaluations per second per GPU
-        roof["whole_step"] = {"algorithmic_flops_per_eval": flops_eval, "achieved": flops_eval * value / n_gpus / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
-                              "unit": "TFLOP/s", "frac": flops_eval * value / n_gpus / 1e12 / FP64_VALU_PEAK_TFLOPS,
-                              "what": "pair sweep + iterations x Jacobi contraction + reciprocal space, x evaluations/s per GPU"}
-        roof["in_timed_region"] = {"kernel_ms": in_region,
-                                   "measured": ("INSIDE the timed region (--events-in-timed-region)" if events_in_region else
-                                                "in a separate 2-step pass BEHIND the timed region (the timed region carries no events)"),
-                                   "note": f"{args.concurrency}: {n_local} beads in flight on this GPU, HIP events on one bead's stream; a launch here "
-                                           "shares the CUs with other beads' kernels, so its duration is stretched -- not a kernel time"}
-        other = {}
-        if alone.get("pair") and dom != "pair":
-            other["pair"] = compute_entry(pair_kernel_name, "pair", flops_pair, n_local)
-        if alone.get("dipole_iter") and dom == "pair" and solver_used != "dense":
-            other["dipole_iter"] = compute_entry(jac_kernel, "dipole_iter", flops_jacobi, iters * n_local)
-        roof["other_kernels"] = other
-        roof["alone_kernel_ms"] = alone
-        if others is not None:
-            roof["other_configs"] = others
-        if pcie is not None:
-            roof["pcie_inclusive_value"] = pcie["value"]
-            roof["pcie_inclusive"] = pcie
-        if four is not None:
-            roof["four_beads_in_flight"] = four
+            def compute_entry(kernel, cls_key, flops, launches_per_step):
+                """fp64 vector-issue roofline of one kernel.  avg_launch_ms: HIP events on the kernel's stream (alone on the GPU where the
+                isolated pass ran); achieved = algorithmic flops / that duration."""
+                ms = back_to_back.get(cls_key) or src.get(cls_key) or 1e30
+                e = fp64_entry(kernel, flops, ms,
+                               "median of three batches of 100 (pair sweep: 40) launches back to back between ONE pair of HIP events on the kernel's stream, "
+                               "per launch (kernel alone on the GPU)" if back_to_back.get(cls_key) else "HIP events around every launch on the kernel's stream")
+                e["algorithmic_flops_per_launch"] = e.pop("algorithmic_flops")
+                e.update({"traffic": None, "launches_per_step": launches_per_step, "consistent": bool(ms * launches_per_step <= ms_per_step),
+                          "frac_of_sustained_fma_rate": e["achieved"] / FP64_FMA_SUSTAINED_TFLOPS})
+                if back_to_back.get(cls_key):
+                    e["avg_launch_ms_batches"] = back_to_back_runs.get(cls_key)
+                    if src.get(cls_key):
+                        e["avg_launch_ms_event_pair_per_launch"] = src[cls_key]
+                t = pmc.get(kernel)
+                if t and t.get("natoms") == n:
+                    e["traffic"] = t.get("hbm_bytes_per_launch")
+                    e["traffic_source"] = t.get("source")
+                    e["pmc"] = t
+                    if t.get("trace_avg_launch_ms"):
+                        e["frac_by_trace_clock"] = flops / (t["trace_avg_launch_ms"] * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS
+                    if t.get("valu_wave_insts_per_launch"):
+                        # every VALU instruction an FMA on 64 lanes would be 128 flops: the share of that which is algorithmic work, and the
+                        # ceiling of THIS instruction stream at the sustained issue rate
+                        e["algorithmic_flops_per_valu_slot"] = flops / (128.0 * t["valu_wave_insts_per_launch"])
+                        e["ceiling_frac_of_this_instruction_stream"] = e["algorithmic_flops_per_valu_slot"] * FP64_FMA_SUSTAINED_TFLOPS / FP64_VALU_PEAK_TFLOPS
+                return e
+
+            # dominant kernel: the one with the largest share of the device time of an evaluation (alone-on-the-GPU durations)
+            share = {"dipole_iter": (src.get("dipole_iter") or 0.0) * iters, "pair": src.get("pair") or 0.0}
+            dom = max(share, key=share.get) if any(share.values()) else "dipole_iter"
+            jac_kernel = "k_dipole_iter_panel" if solver_used == "compact" else "k_dipole_iter_hybrid"
+            if solver_used == "dense":
+                roof = dense_symv_entry(n, src.get("dipole_iter") or 1e30)
+                roof.update({"traffic": None, "launches_per_step": iters * n_local, "consistent": bool(roof["avg_launch_ms"] * iters * n_local <= ms_per_step)})
+            elif dom == "pair":
+                roof = compute_entry(pair_kernel_name, "pair", flops_pair, n_local)
+            else:
+                roof = compute_entry(jac_kernel, "dipole_iter", flops_jacobi, iters * n_local)
+                ms = roof["avg_launch_ms"]
+                roof["hbm_side"] = {"achieved": bytes_jacobi / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": bytes_jacobi / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": bytes_jacobi}
+            roof["measured"] = ("extra pass right after the timed region: ONE bead on ONE stream, every kernel alone on the GPU.  rocprofv3 --kernel-trace reports "
+                                "a little less for the same launch (profiles/*_serial_kernel_stats.csv; frac_by_trace_clock): its stamps leave out the dispatch "
+                                "and completion time between consecutive kernels of a stream" if alone else
+                                "HIP events on one bead's stream with the other beads in flight (stretched durations)")
+            roof["tile_pairs"] = tiles
+            roof["pairs"] = dict(pairs, in_cutoff=cut)
+            roof["flop_model"] = {"jacobi_stored": FLOP_JAC_STORED, "jacobi_far": FLOP_JAC_FAR, "jacobi_per_nonuniform_dim": FLOP_JAC_PER_NU,
+                                  "sweep_base": FLOP_SWEEP_BASE, "sweep_per_nonuniform_dim": FLOP_SWEEP_PER_NU, "sweep_in_cutoff": FLOP_SWEEP_CUTOFF,
+                                  "sweep_in_cutoff_no_field": FLOP_SWEEP_CUTOFF_NO_FIELD, "sweep_stored": FLOP_SWEEP_STORE,
+                                  "what": "fp64 flops per unordered atom pair, FMA = 2 (top of bench.py, DESIGN.md section 3); pair counts are exact atom pairs "
+                                          "per tile-pair class (mpmc_debug_pair_stats)"}
+            roof["share_of_device_time_alone"] = share[dom] / max(sum((src.get(k) or 0.0) * (iters if k in ("dipole_iter", "reduce") else 1) for k in src), 1e-30)
+            # whole-step view, which overlap cannot distort: algorithmic flops of one evaluation x evaluations per second per GPU
+            roof["whole_step"] = {"algorithmic_flops_per_eval": flops_eval, "achieved": flops_eval * value / n_gpus / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
+                                  "unit": "TFLOP/s", "frac": flops_eval * value / n_gpus / 1e12 / FP64_VALU_PEAK_TFLOPS,
+                                  "what": "pair sweep + iterations x Jacobi contraction + reciprocal space, x evaluations/s per GPU"}
+            roof["in_timed_region"] = {"kernel_ms": in_region,
+                                       "measured": ("INSIDE the timed region (--events-in-timed-region)" if events_in_region else
+                                                    "in a separate 2-step pass BEHIND the timed region (the timed region carries no events)"),
+                                       "note": f"{args.concurrency}: {n_local} beads in flight on this GPU, HIP events on one bead's stream; a launch here "
+                                               "shares the CUs with other beads' kernels, so its duration is stretched -- not a kernel time"}
+            other = {}
+            if alone.get("pair") and dom != "pair":
+                other["pair"] = compute_entry(pair_kernel_name, "pair", flops_pair, n_local)
+            if alone.get("dipole_iter") and dom == "pair" and solver_used != "dense":
+                other["dipole_iter"] = compute_entry(jac_kernel, "dipole_iter", flops_jacobi, iters * n_local)
+            roof["other_kernels"] = other
+            roof["alone_kernel_ms"] = alone
+            if others is not None:
+                roof["other_configs"] = others
+            if pcie is not None:
+                roof["pcie_inclusive_value"] = pcie["value"]
+                roof["pcie_inclusive"] = pcie
+            if four is not None:
+                roof["four_beads_in_flight"] = four
 
         out = {
             "metric": "energy-evals/sec (10k-atom LJ+Ewald+polar box); 1/2/4/8-GPU scaling",
@@ -745,8 +755,9 @@ def main():
                        "rccl_version": rccl_ver, "rccl_library": rccl_path, "configure": args.configure, "ranks": infos},
             "V_mean_K": v, "obs_rd_es_pol_vdw": [float(x) for x in obs],
             "kernel_ms": in_region, "device_bytes_per_bead": mem_total, "instrumented_in_timed_region": events_in_region,
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if comm_failed_why:
             out["cabi_comm_failed"] = comm_failed_why  # (an error RCCL returned, no thread left inside it: the run is timed with the hub's host all-gather)
         if rehearsal:
@@ -758,8 +769,9 @@ def main():
             out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         if args.host_positions:
             out["note_host_positions"] = "positions of every bead handed over in host memory inside every timed step (PCIe-inclusive rate, not the headline)"
-        if n_gpus == 1 and args.cpu_baseline != "none":
-            cpu = cpu_baseline(args.cpu_baseline, {**atoms, "pos": bead_positions(atoms["pos"], 0)}, basis, opts, workdir, gpu_bead0)
+        cpu_kind = args.cpu_baseline or ("auto" if args.full else "none")
+        if n_gpus == 1 and cpu_kind != "none":
+            cpu = cpu_baseline(cpu_kind, {**atoms, "pos": bead_positions(atoms["pos"], 0)}, basis, opts, workdir, gpu_bead0)
             if cpu is not None:
                 out["cpu_baseline"] = cpu
         print(json.dumps(out), flush=True)

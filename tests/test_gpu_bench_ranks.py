@@ -42,12 +42,29 @@ def single():
     return last_json(one.stdout)
 
 
-def test_bare_multi_gpu_command_starts_its_own_torch_free_ranks(single):
-    """`python3 bench.py --gpus 2 ...` with no launcher: the parent starts the two ranks itself (plain children, never an exec), relays rank
-    0's line and the exit code; the ranks carry one ROCm each; same ensemble potential as one process, bit for bit."""
-    two = run([sys.executable, "bench.py", "--gpus", "2", "--combine-impl", "hub", "--force-device", "0"] + ARGS, clean_env())
+@pytest.fixture(scope="module")
+def single_full():
+    one = run([sys.executable, "bench.py", "--gpus", "1", "--full"] + ARGS, clean_env())
+    assert one.returncode == 0, one.stderr[-2000:]
+    return last_json(one.stdout)
+
+
+def test_a_plain_run_stops_at_the_headline(single, single_full):
+    """without --full the line carries the headline and the run's configuration, none of the passes behind the timed region; with it,
+    the roofline as well.  The timed steps are the same: same ensemble potential, bit for bit."""
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in single and k in single_full, k
+    assert "roofline" not in single and "pcie_inclusive_value" not in single and "cpu_baseline" not in single and single["kernel_ms"] == {}
+    assert "roofline" in single_full and single_full["roofline"]["alone_kernel_ms"]
+    assert single["V_mean_K"] == single_full["V_mean_K"] and single["obs_rd_es_pol_vdw"] == single_full["obs_rd_es_pol_vdw"]
+
+
+def test_bare_multi_gpu_command_starts_its_own_torch_free_ranks(single_full):
+    """`python3 bench.py --gpus 2 --full ...` with no launcher: the parent starts the two ranks itself (plain children, never an exec),
+    relays rank 0's line and the exit code; the ranks carry one ROCm each; same ensemble potential as one process, bit for bit."""
+    two = run([sys.executable, "bench.py", "--gpus", "2", "--combine-impl", "hub", "--force-device", "0", "--full"] + ARGS, clean_env())
     assert two.returncode == 0, two.stderr[-2000:]
-    a, b = single, last_json(two.stdout)
+    a, b = single_full, last_json(two.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in a and k in b, k
     assert a["n_gpus"] == 1 and b["n_gpus"] == 2 and b["value"] > 0 and b["config"]["beads_per_gpu"] == 2

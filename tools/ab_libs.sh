@@ -2,14 +2,14 @@
 # same-box A/B of two BUILDS of the library: tools/ab_libs.sh <label>=<path to .so> ...   (bench.py --steps 10, three times, interleaved).
 # Prints the headline (32 beads in flight), the PCIe-inclusive rate, one system at a time for configs[2] / configs[3], and the two hot kernels
 # alone on the GPU (back-to-back HIP events).  Older builds go under mpmcxx_amd/.abl/ (git-ignored, travels with gpurun).
-mkdir -p gpurun_out
+out=${OUT_DIR:-$(mktemp -d)}; mkdir -p $out  # the JSON lines of every run
 for rep in 1 2 3; do
 for spec in "$@"; do
   label="${spec%%=*}"; lib="${spec#*=}"
-  MPMC_ENERGY_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --cpu-baseline none > gpurun_out/abl_${label}_${rep}.json 2>gpurun_out/abl_${label}_${rep}.err || { echo "rep${rep} ${label}: bench failed"; tail -3 gpurun_out/abl_${label}_${rep}.err; continue; }
+  MPMC_ENERGY_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-baseline none > $out/abl_${label}_${rep}.json 2>$out/abl_${label}_${rep}.err || { echo "rep${rep} ${label}: bench failed"; tail -3 $out/abl_${label}_${rep}.err; continue; }
   python - <<PY
 import json
-d=json.load(open("gpurun_out/abl_${label}_${rep}.json"))
+d=json.load(open("$out/abl_${label}_${rep}.json"))
 r=d["roofline"]
 oc={o["workload"][:10]: o for o in (r.get("other_configs") or d.get("other_configs", []))}
 pair=(r.get("other_kernels") or {}).get("pair", {})
