@@ -936,3 +936,237 @@ double orc_time_sample(const orc_system *s, int stride, double out_sec[7]) {
 	(void)sink;
 	return now_sec() - t_begin;
 }
+
+/* ---------------------------------------------------------------------------------------------
+ * The Axilrod-Teller three-body energy with EXACT sums (CPU only; the measuring stick of kernels_three_body.hip).  Written from the
+ * contract of tests/three_body_ref.py (System::axilrod_teller, System.Energy.cpp:1653-1770), not from the kernels: every unordered
+ * triple {i < j < k} of distinct atoms not all in one molecule, no cutoff, frozen atoms included; each pair vector is that pair's own
+ * minimum image (orc_minimum_image, i.e. img(x_i - x_j)); the term
+ *     c9_ijk (1 + 3 cos A cos B cos C) / (r_ij r_ik r_jk)^3,   c9_ijk = UNIT (a_i^3 a_j^3 a_k^3)^(1/3) 3 / (1/u_i + 1/u_j + 1/u_k)
+ * with a_i = 6.7483345 alpha_i, 1/u_i = 1 / (c9_i / a_i^3) (:1685-1709) and the cosine at each corner taken between the two vectors that
+ * leave it.  Every term is evaluated in long double from the fp64 image vectors (the cube root of the product of cubes is the product
+ * a_i a_j a_k); the sums are long double + Neumaier.  A triple with an atom whose term vanishes (alpha = 0, or c9 = 0: the reference's
+ * coefficient is exactly 0) adds exactly nothing and is skipped, so a box where few atoms carry the term costs the triples of those only.
+ * out4 = { E3 (K), sum of |term|, the number of triples with a non-zero coefficient that were summed,
+ *          sum of the term scales |c9_ijk| (1 + 3 |cos A cos B cos C|) / (r_ij r_ik r_jk)^3: what bounds the rounding of one fp64 term }
+ * OpenMP over the outer atom on OMP_NUM_THREADS threads (1 if it is unset); each outer atom's row is summed by one thread and the rows are
+ * combined in atom order, so the result does not depend on the thread count.
+ * ------------------------------------------------------------------------------------------- */
+static const double AT_A_SCALE = 6.7483345;                         /* alpha -> a.u. (:1693) */
+static const double AT_UNIT = 0.0032539449 / (3.166811429 * 0.000001); /* hartree bohr^9 -> K A^9 (:1709) */
+#define AT_PRECOMPUTE_PAIRS (1u << 24) /* image vectors of at most this many pairs are computed once (24 bytes each) */
+
+typedef struct { long double a, inv_u; } at_coef;
+typedef struct { long double abs, scale; long long count; } at_row;
+
+static void ksum_addl(orc_ksum *k, long double x) {
+	long double t = k->s + x;
+	if (fabsl(k->s) >= fabsl(x)) k->c += (k->s - t) + x;
+	else k->c += (x - t) + k->s;
+	k->s = t;
+}
+static int at_threads(void) {
+	const char *e = getenv("OMP_NUM_THREADS");
+	int t = e ? atoi(e) : 1;
+	return t > 0 ? t : 1;
+}
+static long double dotl(const double *u, const double *v) {
+	return (long double)u[0] * v[0] + (long double)u[1] * v[1] + (long double)u[2] * v[2];
+}
+/* the active atoms (the ones whose triples can be non-zero) and their coefficients; returns their number */
+static int at_active(const orc_system *s, const double *c9_atom, int *act, at_coef *co) {
+	int na = 0;
+	for (int i = 0; i < s->n; i++) {
+		if (s->polarizability[i] == 0.0 || c9_atom[i] == 0.0) continue;
+		const long double a = (long double)s->polarizability[i] * AT_A_SCALE;
+		co[na].a = a;
+		co[na].inv_u = (a * a * a) / (long double)c9_atom[i];
+		act[na++] = i;
+	}
+	return na;
+}
+static size_t at_tri(size_t na, size_t p, size_t q) { return p * na - p * (p + 1) / 2 + (q - p - 1); } /* p < q */
+/* image vectors of every pair p < q of the active list in geometry s, or NULL when there are too many */
+static double *at_pair_vectors(const orc_system *s, const int *act, int na, int nt) {
+	const size_t np = (size_t)na * (na > 0 ? na - 1 : 0) / 2;
+	if (np == 0 || np > AT_PRECOMPUTE_PAIRS) return NULL;
+	double *V = malloc(3 * np * sizeof(double));
+	if (!V) return NULL;
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nt)
+	for (int p = 0; p < na; p++)
+		for (int q = p + 1; q < na; q++) {
+			double r;
+			orc_minimum_image(s, act[p], act[q], V + 3 * at_tri(na, p, q), &r);
+		}
+	return V;
+}
+static void at_vec(const orc_system *s, const double *V, const int *act, int na, int p, int q, double d[3]) {
+	if (V) memcpy(d, V + 3 * at_tri(na, p, q), 3 * sizeof(double));
+	else {
+		double r;
+		orc_minimum_image(s, act[p], act[q], d, &r);
+	}
+}
+/* one triple from v_ij = img(x_i - x_j), v_ik = img(x_i - x_k), v_jk = img(x_j - x_k) and their lengths */
+static long double at_term(const at_coef *ci, const at_coef *cj, const at_coef *ck, const double *ij, long double rij, const double *ik, long double rik,
+                           const double *jk, long double rjk, long double *scale) {
+	const long double cos_i = dotl(ij, ik) / (rij * rik);  /* corner i: -v_ij and -v_ik */
+	const long double cos_j = -dotl(ij, jk) / (rij * rjk); /* corner j: v_ij and -v_jk */
+	const long double cos_k = dotl(ik, jk) / (rik * rjk);  /* corner k: v_ik and v_jk */
+	const long double c9 = (ci->a * cj->a * ck->a) * 3.0L / (ci->inv_u + cj->inv_u + ck->inv_u) * (long double)AT_UNIT;
+	const long double ccc = (cos_i * cos_j) * cos_k, r3 = (rij * rik) * rjk, inv9 = 1.0L / (r3 * r3 * r3);
+	*scale = fabsl(c9) * (1.0L + 3.0L * fabsl(ccc)) * inv9;
+	return c9 * (1.0L + 3.0L * ccc) * inv9;
+}
+static void at_row_add(at_row *row, long double t, long double scale) {
+	row->abs += fabsl(t), row->scale += scale, row->count++;
+}
+static void at_combine(const orc_ksum *rows_e, const at_row *rows, size_t nrows, double out4[4]) {
+	orc_ksum e = {0, 0}, a = {0, 0}, sc = {0, 0};
+	long long cnt = 0;
+	for (size_t r = 0; r < nrows; r++) {
+		ksum_addl(&e, rows_e[r].s);
+		ksum_addl(&e, rows_e[r].c);
+		ksum_addl(&a, rows[r].abs);
+		ksum_addl(&sc, rows[r].scale);
+		cnt += rows[r].count;
+	}
+	out4[0] = (double)(e.s + e.c);
+	out4[1] = (double)(a.s + a.c);
+	out4[2] = (double)cnt;
+	out4[3] = (double)(sc.s + sc.c);
+}
+
+void orc_axilrod_teller_exact(const orc_system *s, const double *c9_atom, double out4[4]) {
+	const int nt = at_threads();
+	int *act = malloc((size_t)(s->n + 1) * sizeof(int));
+	at_coef *co = malloc((size_t)(s->n + 1) * sizeof(at_coef));
+	const int na = at_active(s, c9_atom, act, co);
+	double *V = at_pair_vectors(s, act, na, nt);
+	orc_ksum *rows_e = calloc((size_t)na + 1, sizeof(orc_ksum));
+	at_row *rows = calloc((size_t)na + 1, sizeof(at_row));
+#pragma omp parallel num_threads(nt)
+	{
+		double *row_v = malloc((size_t)3 * (na + 1) * sizeof(double)); /* v_ik of the outer atom, k = act[p + 1 ..] */
+		long double *row_r = malloc((size_t)(na + 1) * sizeof(long double));
+#pragma omp for schedule(dynamic, 1)
+		for (int p = 0; p < na; p++) {
+			const int i = act[p];
+			for (int r = p + 1; r < na; r++) {
+				at_vec(s, V, act, na, p, r, row_v + 3 * r);
+				row_r[r] = sqrtl(dotl(row_v + 3 * r, row_v + 3 * r));
+			}
+			orc_ksum ke = {0, 0};
+			at_row row = {0, 0, 0};
+			for (int q = p + 1; q < na; q++) {
+				const int j = act[q];
+				const int same_ij = s->mol_id[i] == s->mol_id[j];
+				for (int r = q + 1; r < na; r++) {
+					const int k = act[r];
+					if (same_ij && s->mol_id[k] == s->mol_id[i]) continue;
+					double jk[3];
+					at_vec(s, V, act, na, q, r, jk);
+					long double sc;
+					const long double t = at_term(co + p, co + q, co + r, row_v + 3 * q, row_r[q], row_v + 3 * r, row_r[r], jk, sqrtl(dotl(jk, jk)), &sc);
+					ksum_addl(&ke, t);
+					at_row_add(&row, t, sc);
+				}
+			}
+			rows_e[p] = ke;
+			rows[p] = row;
+		}
+		free(row_v);
+		free(row_r);
+	}
+	at_combine(rows_e, rows, (size_t)na, out4);
+	free(rows_e);
+	free(rows);
+	free(V);
+	free(co);
+	free(act);
+}
+
+/* The change of E3 when atoms [first, first + m) move to new_pos [m][3], in O(m N^2): a triple that holds a moved atom is owned by its
+ * lowest moved atom a and pairs it with b < c from the atoms that are neither a nor a moved atom below a; every such triple is summed
+ * once in its old and once in its new geometry (each with orc_minimum_image), and the delta is the difference of the two exact sums.
+ * out4 = { delta (K), sum of |old term| + |new term|, the number of triples (each counted once), sum of the old and new term scales } */
+void orc_axilrod_teller_delta_exact(const orc_system *s, const double *c9_atom, int first, int m, const double *new_pos, double out4[4]) {
+	const int nt = at_threads();
+	const int n = s->n;
+	double *pos2 = malloc((size_t)3 * n * sizeof(double));
+	memcpy(pos2, s->pos, (size_t)3 * n * sizeof(double));
+	memcpy(pos2 + 3 * (size_t)first, new_pos, (size_t)3 * m * sizeof(double));
+	orc_system s2 = *s;
+	s2.pos = pos2;
+	int *act = malloc((size_t)(n + 1) * sizeof(int));
+	at_coef *co = malloc((size_t)(n + 1) * sizeof(at_coef));
+	const int na = at_active(s, c9_atom, act, co);
+	int lo = 0, hi = 0; /* active positions of the moved range: [lo, hi) */
+	while (lo < na && act[lo] < first) lo++;
+	hi = lo;
+	while (hi < na && act[hi] < first + m) hi++;
+	const int mo = hi - lo; /* owners */
+	double *V = at_pair_vectors(s, act, na, nt);
+	/* v_ax of every owner, old and new geometry */
+	double *ao = malloc((size_t)3 * (mo > 0 ? mo : 1) * (na + 1) * sizeof(double)), *an = malloc((size_t)3 * (mo > 0 ? mo : 1) * (na + 1) * sizeof(double));
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+	for (int o = 0; o < mo; o++)
+		for (int x = 0; x < na; x++) {
+			double r;
+			if (x == lo + o) continue;
+			orc_minimum_image(s, act[lo + o], act[x], ao + 3 * ((size_t)o * na + x), &r);
+			orc_minimum_image(&s2, act[lo + o], act[x], an + 3 * ((size_t)o * na + x), &r);
+		}
+	const size_t nrows = (size_t)mo * na;
+	orc_ksum *rows_o = calloc(nrows + 1, sizeof(orc_ksum)), *rows_n = calloc(nrows + 1, sizeof(orc_ksum));
+	at_row *rows = calloc(nrows + 1, sizeof(at_row));
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+	for (long long w = 0; w < (long long)nrows; w++) {
+		const int o = (int)(w / na), pb = (int)(w % na), pa = lo + o;
+		if (pb == pa || (pb >= lo && pb < pa)) continue; /* b is a, or a moved atom below a */
+		const int a = act[pa], b = act[pb];
+		const double *abo = ao + 3 * ((size_t)o * na + pb), *abn = an + 3 * ((size_t)o * na + pb);
+		const long double rabo = sqrtl(dotl(abo, abo)), rabn = sqrtl(dotl(abn, abn));
+		const int b_moved = pb >= lo && pb < hi, same_ab = s->mol_id[a] == s->mol_id[b];
+		orc_ksum ko = {0, 0}, kn = {0, 0};
+		at_row row = {0, 0, 0};
+		for (int pc = pb + 1; pc < na; pc++) {
+			if (pc == pa || (pc >= lo && pc < pa)) continue;
+			const int c = act[pc];
+			if (same_ab && s->mol_id[c] == s->mol_id[a]) continue;
+			const double *aco = ao + 3 * ((size_t)o * na + pc), *acn = an + 3 * ((size_t)o * na + pc);
+			double bco[3], bcn[3], r;
+			at_vec(s, V, act, na, pb, pc, bco);
+			if (b_moved || (pc >= lo && pc < hi)) orc_minimum_image(&s2, b, c, bcn, &r);
+			else memcpy(bcn, bco, sizeof bco);
+			/* the triple ordered (a, b, c): the term does not depend on the order of its atoms */
+			long double sco, scn;
+			const long double to = at_term(co + pa, co + pb, co + pc, abo, rabo, aco, sqrtl(dotl(aco, aco)), bco, sqrtl(dotl(bco, bco)), &sco);
+			const long double tn = at_term(co + pa, co + pb, co + pc, abn, rabn, acn, sqrtl(dotl(acn, acn)), bcn, sqrtl(dotl(bcn, bcn)), &scn);
+			ksum_addl(&ko, to);
+			ksum_addl(&kn, tn);
+			row.abs += fabsl(to) + fabsl(tn), row.scale += sco + scn, row.count++;
+		}
+		rows_o[w] = ko;
+		rows_n[w] = kn;
+		rows[w] = row;
+	}
+	orc_ksum eo = {0, 0}, en = {0, 0};
+	for (size_t w = 0; w < nrows; w++) {
+		ksum_addl(&eo, rows_o[w].s);
+		ksum_addl(&eo, rows_o[w].c);
+		ksum_addl(&en, rows_n[w].s);
+		ksum_addl(&en, rows_n[w].c);
+	}
+	at_combine(rows_o, rows, nrows, out4); /* (abs, count, scale) */
+	out4[0] = (double)((en.s + en.c) - (eo.s + eo.c));
+	free(rows_o);
+	free(rows_n);
+	free(rows);
+	free(ao);
+	free(an);
+	free(V);
+	free(co);
+	free(act);
+	free(pos2);
+}

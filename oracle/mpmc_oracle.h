@@ -65,6 +65,11 @@ int orc_energy(const orc_system *s, orc_result *out, double *ef_static, double *
 double orc_lj(const orc_system *s, orc_result *out);
 /* lj() with exactly rounded sums (long double + Neumaier) next to the reference's list-order sums; see mpmc_oracle.c.  CPU only. */
 void orc_lj_exact(const orc_system *s, double out7[7]);
+/* the Axilrod-Teller three-body energy with exactly rounded sums (see mpmc_oracle.c), c9_atom [n] = per-atom c9 after the Midzuno-Kihara
+ * rule.  out4 = {E3, sum |term|, triples summed, sum of term scales}.  CPU only, OpenMP on OMP_NUM_THREADS threads. */
+void orc_axilrod_teller_exact(const orc_system *s, const double *c9_atom, double out4[4]);
+/* its change when atoms [first, first + m) move to new_pos [m][3], O(m N^2); out4 as above over the old and the new terms */
+void orc_axilrod_teller_delta_exact(const orc_system *s, const double *c9_atom, int first, int m, const double *new_pos, double out4[4]);
 double orc_coulombic_real(const orc_system *s, orc_result *out);
 double orc_coulombic_reciprocal(const orc_system *s);
 double orc_coulombic_self(const orc_system *s);

@@ -90,6 +90,10 @@ def lib():
         L.orc_lj.restype = C.c_double
         L.orc_lj_exact.argtypes = [C.POINTER(OrcSystem), dp]
         L.orc_lj_exact.restype = None
+        L.orc_axilrod_teller_exact.argtypes = [C.POINTER(OrcSystem), dp, dp]
+        L.orc_axilrod_teller_exact.restype = None
+        L.orc_axilrod_teller_delta_exact.argtypes = [C.POINTER(OrcSystem), dp, C.c_int, C.c_int, dp, dp]
+        L.orc_axilrod_teller_delta_exact.restype = None
         L.orc_coulombic_real.argtypes = [C.POINTER(OrcSystem), C.POINTER(OrcResult)]
         L.orc_coulombic_real.restype = C.c_double
         L.orc_coulombic_reciprocal.argtypes = [C.POINTER(OrcSystem)]
@@ -199,6 +203,26 @@ class OracleSystem:
         lib().orc_lj_exact(C.byref(self.s), _dp(o))
         return {"lj_pairs_exact": o[0], "lrc_pair_exact": o[1], "lrc_self_exact": o[2], "rd_exact": o[3],
                 "rd_list_order": o[4], "lj_pairs_list_order": o[5], "lrc_pair_list_order": o[6]}
+
+    def axilrod_teller_exact(self, c9_atom: np.ndarray):
+        """the Axilrod-Teller energy with exactly rounded sums (orc_axilrod_teller_exact); c9_atom = per-atom c9 after the Midzuno-Kihara
+        rule (tests/three_body_ref.atom_c9).  {"e3", "abs": sum of |term|, "count": triples summed (those with a non-zero coefficient),
+        "scale": sum of |c9_ijk| (1 + 3 |cos A cos B cos C|) / (r_ij r_ik r_jk)^3}"""
+        c9 = np.ascontiguousarray(c9_atom, dtype=np.float64)
+        assert c9.shape == (self.n,), c9.shape
+        o = np.zeros(4)
+        lib().orc_axilrod_teller_exact(C.byref(self.s), _dp(c9), _dp(o))
+        return {"e3": o[0], "abs": o[1], "count": int(o[2]), "scale": o[3]}
+
+    def axilrod_teller_delta_exact(self, c9_atom: np.ndarray, first: int, new_pos: np.ndarray):
+        """the change of the Axilrod-Teller energy when atoms [first, first + m) move to new_pos (m, 3) (orc_axilrod_teller_delta_exact):
+        {"delta", "abs", "count", "scale"}, abs and scale over the old and the new terms of the triples that hold a moved atom"""
+        c9 = np.ascontiguousarray(c9_atom, dtype=np.float64)
+        new = np.ascontiguousarray(new_pos, dtype=np.float64).reshape(-1, 3)
+        assert c9.shape == (self.n,) and 0 <= first and first + new.shape[0] <= self.n, (c9.shape, first, new.shape)
+        o = np.zeros(4)
+        lib().orc_axilrod_teller_delta_exact(C.byref(self.s), _dp(c9), int(first), new.shape[0], _dp(new), _dp(o))
+        return {"delta": o[0], "abs": o[1], "count": int(o[2]), "scale": o[3]}
 
     def time_sample(self, stride: int):
         """(estimated seconds per stage of one full evaluation [7], wall seconds spent)"""

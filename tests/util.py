@@ -238,11 +238,14 @@ def assert_matches_oracle(obs, dipoles, ref, atoms, opts, label="", rel=REL_TOL,
 CSRC = os.path.join(ROOT, "mpmcxx_amd", "csrc")
 # the constants that choose kernels and launch shapes by the size of the tile-pair table, and where each is defined
 LADDER_CONSTANTS = {"kTile": "kernels.h", "kSingleLaunchTiles": "evaluate.cpp", "kOneStreamMaxPairs": "kernels.h", "kSweepMinPairs": "kernels.h",
-                    "kPairSplitMax": "kernels.h", "kKSplit": "kernels.h", "kKSplitMax": "kernels.h", "kKSplitWaves": "kernels.h"}
+                    "kPairSplitMax": "kernels.h", "kKSplit": "kernels.h", "kKSplitMax": "kernels.h", "kKSplitWaves": "kernels.h",
+                    "kThreeBodyBlocks": "kernels.h"}
 # how they are used: each switch as it is written in the sources (the rungs below assume these directions)
 LADDER_USES = {"evaluate.cpp": [r"c->n_tiles <= kSingleLaunchTiles", r"c->n_tile_pairs > kOneStreamMaxPairs", r"c->n_tile_pairs > kSweepMinPairs",
                                 r"c->n_tile_pairs <= kPairSplitMax \? 4 : 1"],
-               "kernels.h": [r"const int nt = n_pad / kTile;\s*int ks = kKSplit;\s*while \(ks < kKSplitMax && nt \* ks < kKSplitWaves\) ks \*= 2;\s*return ks;"]}
+               "kernels.h": [r"const int nt = n_pad / kTile;\s*int ks = kKSplit;\s*while \(ks < kKSplitMax && nt \* ks < kKSplitWaves\) ks \*= 2;\s*return ks;"],
+               # the three-body launches: one workgroup per tile triple (pair) up to kThreeBodyBlocks, a grid-stride loop above
+               "kernels_three_body.hip": [r"std::min<long long>\(work_items, kThreeBodyBlocks\)"]}
 
 
 def csrc_text(name):
@@ -286,6 +289,20 @@ def size_ladder():
         if recip_ksplit(nt + 1, c) != recip_ksplit(nt, c):
             rungs[f"ksplit_{recip_ksplit(nt + 1, c)}"] = nt
     return {k: (nt, nt + 1) for k, nt in rungs.items()}
+
+
+def three_body_ladder():
+    """The grid-stride thresholds of kernels_three_body.hip as tile counts: {"full": nt, "delta": nt}, the last tile count whose tile
+    triples (k_three_body) / tile pairs (k_three_body_delta) fit in kThreeBodyBlocks workgroups, one each; nt + 1 tiles stride."""
+    blocks = ladder_constants()["kThreeBodyBlocks"]
+
+    def last_within(count):
+        nt = 1
+        while count(nt + 1) <= blocks:
+            nt += 1
+        return nt
+
+    return {"full": last_within(lambda nt: nt * (nt + 1) * (nt + 2) // 6), "delta": last_within(lambda nt: nt * (nt + 1) // 2)}
 
 
 def rung_sizes(nt):
