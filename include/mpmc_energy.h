@@ -118,7 +118,7 @@ typedef struct mpmc_result {
 	double es_self;             /* coulombic_self()                                                         */
 	double lj_pairs;            /* sum of pair->rd_energy                                                   */
 	double lrc_pair;            /* sum of pair->lrc                                                         */
-	double lrc_self;            /* sum of lj_lrc_self                                                       */
+	double lrc_self;            /* sum of lj_lrc_self (disp-expansion: of disp_expansion_lrc_self)          */
 	double dipole_rrms;         /* observables->dipole_rrms                                                 */
 	double N;                   /* observables->N  (non-frozen molecules, countN System.cpp:909-931)        */
 	double NU;                  /* observables->NU = N * energy                                             */
@@ -135,7 +135,7 @@ typedef struct mpmc_result {
 
 /* accumulated device time of the kernels of one context, measured with HIP events on the context's stream
  * (only while profiling is enabled with mpmc_set_profiling).  Index with MPMC_K_*. */
-#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel                 */
+#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel; the disp-expansion sum / trial difference too */
 #define MPMC_K_RECIP 1       /* structure factors + reciprocal energy + atom terms  */
 #define MPMC_K_FIELD 2       /* static field (recip + real, or nopbc)               */
 #define MPMC_K_TENSOR 3      /* dense thole_amatrix rows (mpmc_thole_amatrix)        */
@@ -234,6 +234,23 @@ int mpmc_trial_reject(mpmc_ctx *ctx);
  * updates and accepted trials keep them. */
 int mpmc_set_axilrod_teller(mpmc_ctx *ctx, int enabled, int midzuno_kihara_approx, const double *c6, const double *c9);
 int mpmc_axilrod_teller(mpmc_ctx *ctx, double *out); /* System::axilrod_teller(), component entry like mpmc_lj */
+
+/* ---- the dispersion-expansion repulsion/dispersion term, System::disp_expansion (src/System.Energy.cpp:1939-2080) ----------------------
+ * `disp_expansion on`: replaces lj() in rd_energy.  The atoms' epsilon is the repulsion exponent alpha (1/A), sigma is r0 (A); c6, c8, c10
+ * per atom in atomic units, in the caller's atom order, length n of the current atom list (c10 may be NULL: zeros).  Negative or non-finite
+ * coefficients are refused with MPMC_ERR_INVALID_DATUM: unlike the reference, which would take sqrt of the product of two negative c's.
+ * Every pair that is neither rd_excluded nor frozen contributes at its minimum-image distance, with no cutoff:
+ *   315.775 exp(-alpha_ij (r - r0_ij)) - c6_ij / r^6 - c8_ij / r^8 - c10_ij / r^10   (Tang-Toennies damped under MPMC_DISP_DAMP)
+ * With rd_lrc, lrc_pair holds disp_expansion_lrc summed over every non-frozen pair and lrc_self disp_expansion_lrc_self over every
+ * non-frozen atom; lj_pairs holds the pair sum and rd_energy their total.  The counts keep their meaning.  Cost O(N^2) per evaluation,
+ * O(m N) per trial move of m <= MPMC_TRIAL_MAX_ATOMS atoms.  enabled = 0 switches the term off.  mpmc_set_atoms discards the coefficients
+ * (the setting stays): an evaluation with the term on and no coefficients fails with MPMC_ERR_ARG.  Position updates, accepted trials and
+ * capacity growth keep them.  MPMC_FLAG_OTHER_RD (the keyword through mpmc_check_flags) is still refused. */
+#define MPMC_DISP_DAMP 1            /* damp_dispersion: Tang-Toennies damping of the three dispersion terms  */
+#define MPMC_DISP_EXTRAPOLATE_C10 2 /* extrapolate_disp_coeffs: c10_ij = 49/40 c8_ij^2 / c6_ij                */
+#define MPMC_DISP_SCHMIDT 4         /* schmidt_ff: alpha_ij = (a_i + a_j) a_i a_j / (a_i^2 + a_j^2)            */
+int mpmc_set_disp_expansion(mpmc_ctx *ctx, int enabled, int flags, const double *c6, const double *c8, const double *c10);
+int mpmc_disp_expansion(mpmc_ctx *ctx, double *out); /* System::disp_expansion() (rd_energy of the term), component entry like mpmc_lj */
 
 /* ---- public component entry points of the reference (src/System.h:346-402), for parity tests ----------- */
 int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj()                   */

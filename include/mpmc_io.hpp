@@ -127,7 +127,7 @@ inline std::string read_input(const std::string &path, System &s) {
 	    {"polar_palmo", MPMC_FLAG_POLAR_PALMO}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED}, {"polar_sor", MPMC_FLAG_POLAR_SOR},
 	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"waldmanhagler", MPMC_FLAG_NON_LB_MIXING},
 	    {"halgren_mixing", MPMC_FLAG_NON_LB_MIXING}, {"c6_mixing", MPMC_FLAG_NON_LB_MIXING}, {"dreiding", MPMC_FLAG_OTHER_RD},
-	    {"lj_buffered_14_7", MPMC_FLAG_OTHER_RD}, {"disp_expansion", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
+	    {"lj_buffered_14_7", MPMC_FLAG_OTHER_RD}, {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
 	    {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
 	    {"cavity_autoreject_absolute", MPMC_FLAG_CAVITY_AUTOREJECT}};
 	std::string pqr, line;
@@ -161,6 +161,10 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "feynman_hibbs") { need(1); s.feynman_hibbs = onoff(t[1]); }
 		else if (k == "axilrod_teller") { need(1); s.using_axilrod_teller = onoff(t[1]) != 0; }
 		else if (k == "midzuno_kihara_approx") { need(1); s.midzuno_kihara_approx = onoff(t[1]); }
+		else if (k == "disp_expansion") { need(1); s.using_disp_expansion = onoff(t[1]) != 0; }
+		else if (k == "damp_dispersion") { need(1); s.damp_dispersion = onoff(t[1]); }
+		else if (k == "extrapolate_disp_coeffs") { need(1); s.extrapolate_disp_coeffs = onoff(t[1]); }
+		else if (k == "schmidt_ff") { need(1); s.schmidt_ff = onoff(t[1]); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
 		else if (k == "polar_max_iter") { need(1); s.polar_max_iter = (int)dval(1); }

@@ -60,6 +60,11 @@ template <class T>
 auto uses_three_body(const T &s, int) -> decltype(bool(s.using_axilrod_teller)) { return s.using_axilrod_teller; }
 template <class T>
 bool uses_three_body(const T &, long) { return false; }
+// the same for the disp-expansion term
+template <class T>
+auto uses_disp_expansion(const T &s, int) -> decltype(bool(s.using_disp_expansion)) { return s.using_disp_expansion; }
+template <class T>
+bool uses_disp_expansion(const T &, long) { return false; }
 
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
@@ -84,6 +89,8 @@ public:
 	int wolf = 0, feynman_hibbs = 0, feynman_hibbs_order = 0;
 	bool using_axilrod_teller = false; // three-body dispersion (mpmc_set_axilrod_teller), src/System.h:659
 	int midzuno_kihara_approx = 0;     // its c9 from c6, src/System.h:655
+	bool using_disp_expansion = false; // disp-expansion repulsion/dispersion in place of lj() (mpmc_set_disp_expansion), src/System.h:661
+	int damp_dispersion = 0, extrapolate_disp_coeffs = 0, schmidt_ff = 0; // its switches, src/System.h:649-656
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
 	double ewald_alpha = 0.5, polar_ewald_alpha = 0.5;
@@ -275,6 +282,8 @@ private:
 	bool atoms_dirty_ = true, box_dirty_ = true;
 	bool three_body_on_ = false; // what the context's three-body setting is (sync_state)
 	int three_body_mk_ = 0;
+	bool disp_on_ = false; // what the context's disp-expansion setting is (sync_state)
+	int disp_flags_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
 	mpmc_result trial_result_{};
@@ -342,6 +351,7 @@ private:
 			      "mpmc_set_atoms");
 			atoms_dirty_ = false;
 			three_body_on_ = false; // (the library discards the coefficients with the atom list)
+			disp_on_ = false;
 		}
 		// the three-body term after every upload of the atoms, and whenever the switch changed
 		if (using_axilrod_teller != three_body_on_ || (using_axilrod_teller && midzuno_kihara_approx != three_body_mk_)) {
@@ -350,6 +360,15 @@ private:
 			check(mpmc_set_axilrod_teller(ctx_, using_axilrod_teller ? 1 : 0, midzuno_kihara_approx, c6.data(), c9.data()), "mpmc_set_axilrod_teller");
 			three_body_on_ = using_axilrod_teller;
 			three_body_mk_ = midzuno_kihara_approx;
+		}
+		// the disp-expansion term likewise
+		const int dflags = (damp_dispersion ? MPMC_DISP_DAMP : 0) | (extrapolate_disp_coeffs ? MPMC_DISP_EXTRAPOLATE_C10 : 0) | (schmidt_ff ? MPMC_DISP_SCHMIDT : 0);
+		if (using_disp_expansion != disp_on_ || (using_disp_expansion && dflags != disp_flags_)) {
+			std::vector<double> c6(n), c8(n), c10(n);
+			for (int i = 0; i < n; i++) c6[i] = atoms[i].c6, c8[i] = atoms[i].c8, c10[i] = atoms[i].c10;
+			check(mpmc_set_disp_expansion(ctx_, using_disp_expansion ? 1 : 0, dflags, c6.data(), c8.data(), c10.data()), "mpmc_set_disp_expansion");
+			disp_on_ = using_disp_expansion;
+			disp_flags_ = dflags;
 		}
 	}
 

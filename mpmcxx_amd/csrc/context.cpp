@@ -211,7 +211,8 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	void *ptrs[] = {c->d_atoms_blob, c->d_atom_part, c->d_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_scal,
 	                c->d_flag, c->d_counter, c->d_kvec, c->d_kw, c->d_sf, c->d_w_en, c->d_e_recip_part, c->d_part, c->d_e_static, c->d_mu[0], c->d_mu[1],
 	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
-	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part};
+	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part,
+	                c->d_de_co, c->d_de_t10, c->d_de_part};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (c->h_stage) (void)pinned_free(c->h_stage);
@@ -498,7 +499,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 			int fl = 0;
 			if (c->h_frozen[i]) fl |= AF_FROZEN;
 			if (c->h_eps[i] == 0.0 || c->h_sigma[i] == 0.0) fl |= AF_NULL_RD;
-			if (c->h_disp[i]) fl |= AF_HAS_DISP;
+			if (c->h_disp[i]) fl |= c->de_enabled ? AF_DISP_RD : AF_HAS_DISP; // (disp-expansion: LJ mixing no longer matters, pair_math.h)
 			if (c->h_sigma[i] < 0.0) fl |= AF_NEG_SIGMA;
 			if (c->h_sigma[i] == 0.0) fl |= AF_ZERO_SIGMA;
 			if (c->h_q[i] == 0.0) fl |= AF_ZERO_Q;
@@ -589,6 +590,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	c->h_pos_sorted = c->h_pos;        // where every atom stood when this order was made
 	c->atoms_dirty = false;
 	if (c->tb_have) c->tb_dirty = true; // (the three-body coefficients follow the order at the next evaluation that needs them)
+	if (c->de_have) c->de_dirty = true; // (so do the disp-expansion coefficients)
 	return MPMC_OK;
 }
 
@@ -618,6 +620,8 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	f->n_uploads_sorted = c->n_uploads_sorted;
 	f->tb_enabled = c->tb_enabled; // (the three-body setting survives; its coefficients go with the atom list that is being replaced)
 	f->tb_mk = c->tb_mk;
+	f->de_enabled = c->de_enabled; // (the disp-expansion setting likewise)
+	f->de_flags = c->de_flags;
 	std::swap(*c, *f);
 	mpmc_ctx_destroy(f); // now owns the old, smaller buffers
 	return MPMC_OK;
@@ -731,6 +735,9 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->tb_have = false; // per-atom three-body coefficients belong to the old list (mpmc_set_axilrod_teller again)
 	c->tb_dirty = false;
 	c->h_tb_au.clear();
+	c->de_have = c->de_dirty = c->de_lrc_valid = false; // so do the disp-expansion coefficients (mpmc_set_disp_expansion again)
+	c->h_de.clear();
+	c->h_de_raw.clear();
 	return MPMC_OK;
 }
 
@@ -770,6 +777,126 @@ extern "C" int mpmc_set_axilrod_teller(mpmc_ctx *c, int enabled, int mk, const d
 	c->tb_enabled = c->tb_have = c->tb_dirty = true;
 	c->tb_mk = mk != 0;
 	c->cache_valid = false; // (the accepted totals of trial moves lack the term until the next mpmc_energy)
+	return MPMC_OK;
+}
+
+// ---- disp-expansion coefficients (System::disp_expansion, src/System.Energy.cpp:1939-2080; mixing src/System.cpp:1139-1156) ------------------
+// Per atom (alpha, r0) = (epsilon, sigma) of the atom list and s_n = sqrt(k_n c_n) for n = 6, 8, so that c_n,ij = s_n,i s_n,j carries the
+// unit factor k_n (pair_math.h); s10 = sqrt(k10 c10), or under extrapolate_disp_coeffs sqrt(49/40 k8^2 / k6) c8 / sqrt(c6) (0 when c6 or c8
+// is 0), so that s10_i s10_j is the pair's 49/40 c8_ij^2 / c6_ij.
+static void disp_coefficients(int n, const double *alpha, const double *r0, int flags, const double *c6, const double *c8, const double *c10,
+                              std::vector<double> &de, std::vector<double> &raw) {
+	const double q6 = std::sqrt(kDispK6), q8 = std::sqrt(kDispK8), q10 = std::sqrt(kDispK10);
+	const double q10x = std::sqrt(49.0 / 40.0) * kDispK8 / q6;
+	de.assign(5 * (size_t)n, 0.0);
+	raw.assign(3 * (size_t)n, 0.0);
+	for (int i = 0; i < n; i++) {
+		const double a6 = c6[i], a8 = c8[i], a10 = c10 ? c10[i] : 0.0;
+		double *d = &de[5 * (size_t)i];
+		d[0] = alpha[i];
+		d[1] = r0[i];
+		d[2] = q6 * std::sqrt(a6);
+		d[3] = q8 * std::sqrt(a8);
+		d[4] = (flags & MPMC_DISP_EXTRAPOLATE_C10) ? ((a6 != 0.0 && a8 != 0.0) ? q10x * (a8 / std::sqrt(a6)) : 0.0) : q10 * std::sqrt(a10);
+		raw[3 * (size_t)i] = a6, raw[3 * (size_t)i + 1] = a8, raw[3 * (size_t)i + 2] = a10;
+	}
+}
+
+DispParams mpmc::disp_params(const mpmc_ctx *c) {
+	DispParams dp;
+	dp.damp = (c->de_flags & MPMC_DISP_DAMP) ? 1 : 0;
+	dp.schmidt = (c->de_flags & MPMC_DISP_SCHMIDT) ? 1 : 0;
+	return dp;
+}
+
+// the two long-range corrections (disp_expansion_lrc over every pair that is not frozen -- rd_excluded ones included -- and
+// disp_expansion_lrc_self over every atom that is not frozen, with the atom's unconverted coefficients, :2022-2034, :2056-2080).  The pair
+// sum is the moment form sum_{i<j} s_i s_j = ((sum s)^2 - sum s^2) / 2 over all atoms minus the same over the frozen ones, in long double.
+static void disp_lrc(mpmc_ctx *c) {
+	c->de_lrc[0] = c->de_lrc[1] = 0.0;
+	if (c->opts.rd_lrc) {
+		const double rc = c->box.cutoff, V = c->box.volume;
+		long double S[3][2] = {{0, 0}, {0, 0}, {0, 0}}, Q[3][2] = {{0, 0}, {0, 0}, {0, 0}}; // [coefficient][all, frozen]
+		double self = 0.0;
+		const bool ex = (c->de_flags & MPMC_DISP_EXTRAPOLATE_C10) != 0;
+		for (int i = 0; i < c->n; i++) {
+			const double *d = &c->h_de[5 * (size_t)i];
+			const bool fr = c->h_frozen[i] != 0;
+			for (int k = 0; k < 3; k++) {
+				const long double v = d[2 + k];
+				S[k][0] += v, Q[k][0] += v * v;
+				if (fr) S[k][1] += v, Q[k][1] += v * v;
+			}
+			if (!fr) {
+				const double *r = &c->h_de_raw[3 * (size_t)i];
+				const double c10 = ex ? ((r[0] != 0.0 && r[1] != 0.0) ? 49.0 / 40.0 * r[1] * r[1] / r[0] : 0.0) : r[2];
+				self += disp_lrc_term(r[0], r[1], c10, rc, V);
+			}
+		}
+		double P[3];
+		for (int k = 0; k < 3; k++) P[k] = (double)(((S[k][0] * S[k][0] - Q[k][0]) - (S[k][1] * S[k][1] - Q[k][1])) * 0.5L);
+		c->de_lrc[0] = disp_lrc_term(P[0], P[1], P[2], rc, V); // (the unit factors ride in the per-atom values)
+		c->de_lrc[1] = self;
+	}
+	c->de_lrc_volume = c->box.volume;
+	c->de_lrc_cutoff = c->box.cutoff;
+	c->de_lrc_rd_lrc = c->opts.rd_lrc;
+	c->de_lrc_valid = true;
+}
+
+extern "C" int mpmc_set_disp_expansion(mpmc_ctx *c, int enabled, int flags, const double *c6, const double *c8, const double *c10) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: an evaluation or a trial move is open");
+	if (flags & ~(MPMC_DISP_DAMP | MPMC_DISP_EXTRAPOLATE_C10 | MPMC_DISP_SCHMIDT)) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: unknown flag bits");
+	if (!enabled) {
+		if (c->de_enabled) c->cache_valid = false, c->atoms_dirty = true; // (the accepted totals carry the term; the atoms' flags change back)
+		c->de_enabled = c->de_have = c->de_dirty = c->de_lrc_valid = false;
+		c->de_flags = 0;
+		c->h_de.clear();
+		c->h_de_raw.clear();
+		return MPMC_OK;
+	}
+	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: set the atoms first (the coefficients are per atom)");
+	if (!c6 || !c8) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: c6 and c8 are required (c10 may be NULL: zeros)");
+	for (int i = 0; i < c->n; i++) {
+		const double v[3] = {c6[i], c8[i], c10 ? c10[i] : 0.0};
+		for (double x : v)
+			if (!std::isfinite(x) || x < 0.0) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_set_disp_expansion: coefficients must be finite and >= 0");
+	}
+	disp_coefficients(c->n, c->h_eps.data(), c->h_sigma.data(), flags, c6, c8, c10, c->h_de, c->h_de_raw);
+	if (!c->de_enabled) c->atoms_dirty = true; // (the atoms' dispersion flag becomes AF_DISP_RD: upload_atoms)
+	c->de_enabled = c->de_have = c->de_dirty = true;
+	c->de_lrc_valid = false;
+	c->de_flags = flags;
+	c->cache_valid = false; // (the accepted totals of trial moves lack the term until the next mpmc_energy)
+	return MPMC_OK;
+}
+
+int mpmc::disp_ready(mpmc_ctx *c) {
+	if (!c->de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the disp-expansion term is off (mpmc_set_disp_expansion)");
+	if (!c->de_have)
+		return fail(c, MPMC_ERR_ARG, "the disp-expansion term is on but has no coefficients for this atom list (mpmc_set_disp_expansion after mpmc_set_atoms)");
+	int rc;
+	if (!c->d_de_co) {
+		if ((rc = dev_alloc(c, &c->d_de_co, (size_t)c->max_pad)) != MPMC_OK) return rc;
+		if ((rc = dev_alloc(c, &c->d_de_t10, (size_t)c->max_pad)) != MPMC_OK) return rc;
+		if ((rc = dev_alloc(c, &c->d_de_part, (size_t)kDispBlocks)) != MPMC_OK) return rc;
+	}
+	if (c->de_dirty) { // slot order, like every other per-atom array (upload_atoms)
+		std::vector<double4> co((size_t)c->n_pad, make_double4(0.0, 0.0, 0.0, 0.0));
+		std::vector<double> t10((size_t)c->n_pad, 0.0);
+		for (int k = 0; k < c->n; k++) {
+			const double *d = &c->h_de[5 * (size_t)c->perm[k]];
+			co[k] = make_double4(d[0], d[1], d[2], d[3]);
+			t10[k] = d[4];
+		}
+		HIP_TRY(c, hipMemcpyAsync(c->d_de_co, co.data(), co.size() * sizeof(double4), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(c->d_de_t10, t10.data(), t10.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // (`co`, `t10` die here; once per upload of the atoms)
+		c->de_dirty = false;
+	}
+	// the corrections follow the box (mpmc_set_box: volume moves) and rd_lrc, never the positions
+	if (!c->de_lrc_valid || c->de_lrc_volume != c->box.volume || c->de_lrc_cutoff != c->box.cutoff || c->de_lrc_rd_lrc != c->opts.rd_lrc) disp_lrc(c);
 	return MPMC_OK;
 }
 

@@ -267,7 +267,7 @@ struct mpmc_ctx {
 	int touch_n = -1, touch[8] = {0}; // what enqueue(RUN_STORE) passes to the store-only sweep (-1: all tile pairs)
 	unsigned char *d_mv_blob = nullptr, *h_mv_blob = nullptr; // device / pinned host staging of a trial's moved-atom list
 	int cap_sf_trial = 0;
-	double *d_delta_out = nullptr, *h_delta_out = nullptr; // h: pinned [9] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it)
+	double *d_delta_out = nullptr, *h_delta_out = nullptr; // h: pinned [10] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8])
 	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
@@ -284,6 +284,20 @@ struct mpmc_ctx {
 	std::vector<double> h_tb_au;            // [n][2] (a, u) per atom in original order (three_body_coefficients)
 	double2 *d_tb_au = nullptr;             // [max_pad] the same in slot order, padding (0, 1)
 	double *d_tb_part = nullptr;            // [kThreeBodyBlocks] per-workgroup partials
+
+	// dispersion-expansion term (mpmc_set_disp_expansion, kernels_disp.hip): replaces the LJ sums of rd_energy
+	bool de_enabled = false;   // switched on (kept across mpmc_set_atoms and capacity growth); the atoms' dispersion flag is AF_DISP_RD then
+	int de_flags = 0;          // MPMC_DISP_* (kept likewise)
+	bool de_have = false;      // coefficients set since the last mpmc_set_atoms
+	bool de_dirty = false;     // d_de_co / d_de_t10 are older than h_de or than the spatial order
+	std::vector<double> h_de;  // [n][5] (alpha, r0, sqrt c6, sqrt c8, t10) per atom in original order (disp_coefficients)
+	std::vector<double> h_de_raw; // [n][3] c6, c8, c10 as given: the self LRC takes the unconverted values
+	bool de_lrc_valid = false; // de_lrc holds the two long-range corrections of the volume / cutoff / rd_lrc below
+	double de_lrc[2] = {0, 0}, de_lrc_volume = 0, de_lrc_cutoff = 0;
+	int de_lrc_rd_lrc = 0;
+	double4 *d_de_co = nullptr; // [max_pad] (alpha, r0, sqrt c6, sqrt c8) in slot order, padding zeros
+	double *d_de_t10 = nullptr; // [max_pad]
+	double *d_de_part = nullptr; // [kDispBlocks] per-workgroup partials
 
 	// profiling
 	bool prof = false;
@@ -442,12 +456,15 @@ inline void join_side(mpmc_ctx *c) {
 enum : unsigned {
 	RUN_PAIR = 1, RUN_PAIR_ES = 2, RUN_RECIP = 4, RUN_ATOMTERMS = 8, RUN_FIELD = 16, RUN_SOLVE = 32, RUN_WOLF = 64,
 	RUN_STORE = 128, // tile classes + the Thole tensor store alone (no energies, no field): trial moves of polarizable boxes
-	RUN_THREE_BODY = 256 // the Axilrod-Teller sum (contexts with the term switched on)
+	RUN_THREE_BODY = 256, // the Axilrod-Teller sum (contexts with the term switched on)
+	RUN_DISP = 512        // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
 };
 // 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
 // applied once to the sum of the per-triple terms
 constexpr double kThreeBodyScale = 3.0 * (0.0032539449 / (3.166811429 * 0.000001));
 int three_body_ready(mpmc_ctx *c); // the term is on and its coefficients are on the device in the current slot order (context.cpp)
+int disp_ready(mpmc_ctx *c);       // the same for the disp-expansion term, and its long-range corrections for the current box (context.cpp)
+DispParams disp_params(const mpmc_ctx *c);
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
 int enqueue(mpmc_ctx *c, unsigned mask);         // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp)
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)

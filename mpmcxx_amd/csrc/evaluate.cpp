@@ -252,6 +252,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	int rc = prepare(c, true);
 	if (rc != MPMC_OK) return rc;
 	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	const bool static_ride = c->static_dirty;
 	c->static_ride_gen = 0;
 	const AtomsDev at = atoms_view(c);
@@ -597,6 +598,12 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		ProfScope p(c, MPMC_K_THREE_BODY);
 		launch_three_body(st, at, c->d_tb_au, c->box, kThreeBodyScale, c->d_tb_part, c->d_scal + S_THREE_BODY);
 	}
+	// ---- disp-expansion, System::disp_expansion (:121-122, 1939-2018): pair sum and the cached corrections into their three slots ----------
+	if (mask & RUN_DISP) {
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_disp_expansion(st, at, c->d_de_co, c->d_de_t10, c->d_tile_pairs, c->n_tile_pairs, c->box, disp_params(c), c->de_lrc[0], c->de_lrc[1],
+		                      c->d_de_part, c->d_scal + S_DISP);
+	}
 	HIP_TRY(c, hipGetLastError());
 	// results to the pinned block by a kernel of ours (a blit and a stream synchronisation cost more than the whole reciprocal space of a
 	// small box): copy, zero the device block for the next evaluation, launch number last
@@ -746,10 +753,16 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		}
 		c->static_ride_gen = 0;
 	}
-	const bool lrc = (c->run_mask & RUN_ATOMTERMS) && c->opts.rd_lrc;
-	out->lj_pairs = s[S_LJ];
-	out->lrc_pair = lrc ? c->h_static[0] : 0.0;
-	out->lrc_self = lrc ? c->h_static[1] : 0.0;
+	if (c->run_mask & RUN_DISP) { // disp_expansion() replaces lj() (:121-122): the LJ sums of the pair kernels are not used
+		out->lj_pairs = s[S_DISP];
+		out->lrc_pair = s[S_DISP_LRC_PAIR];
+		out->lrc_self = s[S_DISP_LRC_SELF];
+	} else {
+		const bool lrc = (c->run_mask & RUN_ATOMTERMS) && c->opts.rd_lrc;
+		out->lj_pairs = s[S_LJ];
+		out->lrc_pair = lrc ? c->h_static[0] : 0.0;
+		out->lrc_self = lrc ? c->h_static[1] : 0.0;
+	}
 	out->rd_energy = (out->lj_pairs + out->lrc_pair) + out->lrc_self;
 	out->es_real = s[S_ES_REAL] - s[S_ES_INTRA];
 	out->es_recip = s[S_ES_RECIP];
@@ -785,6 +798,7 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 		if (c->opts.polarization) m |= RUN_FIELD | RUN_SOLVE;
 	}
 	if (c->tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
+	if (c->de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
 	return m;
 }
 
@@ -862,6 +876,14 @@ extern "C" int mpmc_axilrod_teller(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	int rc = run_piece(c, RUN_THREE_BODY, &r);
 	if (rc == MPMC_OK && out) *out = r.three_body_energy;
+	return rc;
+}
+extern "C" int mpmc_disp_expansion(mpmc_ctx *c, double *out) {
+	if (!c) return MPMC_ERR_ARG;
+	if (!c->de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_disp_expansion: the term is off (mpmc_set_disp_expansion)");
+	mpmc_result r;
+	int rc = run_piece(c, RUN_DISP, &r);
+	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }
 // device per-atom vectors are in slot order; everything handed to the caller is in original atom order

@@ -42,6 +42,7 @@ enum : int {
 	S_ES_RECIP, S_ES_SELF, S_LRC_SELF,           // recip / atom kernel
 	S_POLAR, S_RRMS,                             // polarization
 	S_THREE_BODY,                                // Axilrod-Teller (kernels_three_body.hip)
+	S_DISP, S_DISP_LRC_PAIR, S_DISP_LRC_SELF,    // disp-expansion pair sum and its two long-range corrections (kernels_disp.hip)
 	S_COUNT = 16
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
@@ -273,6 +274,22 @@ void launch_three_body(hipStream_t st, const AtomsDev &at, const double2 *au, co
 // kernels (marked and cleared again inside)
 void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, const int *mv_slot, const double4 *mv_new,
                              int m, int *moved_idx, double *part, double *out);
+
+// ---- dispersion-expansion repulsion/dispersion (kernels_disp.hip) ---------------------------------------------------------------
+// co[slot] = (alpha, r0, s6, s8), t10[slot] = s10 with c_n,ij = s_n,i s_n,j (unit factors included; context.cpp: disp_coefficients;
+// padding zeros).  Both launches leave kDispBlocks (or fewer) partials in `part` and write their
+// fixed-order sum to out[0]; the full sum also writes lrc_pair and lrc_self to out[1] and out[2].
+constexpr int kDispBlocks = 16384; // (12 403 tile pairs at 10 000 atoms: one per workgroup, no tail of doubled waves)
+struct DispParams {
+	int damp, schmidt; // damp_dispersion, schmidt_ff
+};
+int disp_grid(long long work_items); // partials a launch over this many tile pairs / (moved atom, tile) items leaves
+void launch_disp_expansion(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const int2 *tile_pairs, int n_tile_pairs,
+                           const Box &bx, const DispParams &dp, double lrc_pair, double lrc_self, double *part, double *out);
+// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
+// kernels (marked and cleared again inside)
+void launch_disp_expansion_delta(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const Box &bx, const DispParams &dp,
+                                 const int *mv_slot, const double4 *mv_new, int m, int *moved_idx, double *part, double *out);
 
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);

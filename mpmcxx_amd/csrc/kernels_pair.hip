@@ -74,7 +74,7 @@ __device__ __forceinline__ void sweep_finish(const double2 *__restrict__ s_se, c
 	if (MODE == 2) {
 		const int any = I.fl | mfj.y, both = I.fl & mfj.y;
 		frozen = (both & AF_FROZEN) != 0;
-		excl_rd = intra || (any & AF_NULL_RD) != 0;
+		excl_rd = intra || (any & (AF_NULL_RD | AF_DISP_RD)) == AF_NULL_RD; // (AF_HAS_DISP never reaches the sweep: kUnmaskable)
 		excl_es = intra || (any & AF_ZERO_Q) != 0;
 		no_field = (both & AF_ZERO_Q) != 0 || (ri2 == 0.0);
 	}

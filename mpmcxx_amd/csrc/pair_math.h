@@ -36,7 +36,9 @@ enum : int {
 	AF_ZERO_SIGMA = 16,// sigma == 0                   (System.cpp:1170)
 	AF_ZERO_Q = 32,    // charge == 0                  (System.cpp:1059)
 	AF_ZERO_ALPHA = 64,// polarizability == 0
-	AF_PAD = 128       // padding slot beyond n (never a real atom)
+	AF_PAD = 128,      // padding slot beyond n (never a real atom)
+	AF_DISP_RD = 256   // AF_HAS_DISP of a context whose disp-expansion term replaces LJ: the same exclusion role, but lj_mix no longer
+	                   // matters (the LJ sums are not used there), so the fast pair sweep keeps these tile pairs (context.cpp: upload_atoms)
 };
 // Atoms whose flags change the MIXING of lj_mix (sigma < 0: attractive only; dispersion coefficients), not just the masks of
 // pair_exclusions: a tile pair that contains one is left to k_pair_fused.  ONE definition for the host list (context.cpp: upload_atoms)
@@ -151,7 +153,7 @@ MPMC_HD PairFlags pair_flags(int mol_i, int fl_i, int mol_j, int fl_j) {
 	int any = fl_i | fl_j;
 	f.intra = (mol_i == mol_j);
 	f.frozen = (fl_i & fl_j & AF_FROZEN) != 0;
-	f.rd_excluded = f.intra || ((any & AF_NULL_RD) && !(any & AF_HAS_DISP));
+	f.rd_excluded = f.intra || ((any & AF_NULL_RD) && !(any & (AF_HAS_DISP | AF_DISP_RD)));
 	f.es_excluded = f.intra || (any & AF_ZERO_Q);
 	f.attractive_only = (any & AF_NEG_SIGMA) != 0;
 	return f;
@@ -213,6 +215,66 @@ MPMC_HD double fh_es_corr(int order, double c2, double c4, double imu, double al
 		corr += c4 * (imu * imu) * (15.0 * du * ir3 + 4.0 * d3u * ir + d4u);
 	}
 	return corr;
+}
+
+// ---- disp_expansion, reference System.Energy.cpp:1939-2053 (mixing System.cpp:1139-1156) ----------------------------------------------
+// Per atom: alpha (the PQR epsilon column, 1/A), r0 (sigma, A) and s_n = sqrt(k_n c_n) with the unit factors k_n below, s10 under
+// extrapolate_disp_coeffs sqrt(49/40 k8^2 / k6) c8 / sqrt(c6) (0 when c6 or c8 is 0), so that c_n,ij = s_n,i s_n,j (context.cpp:
+// disp_coefficients).  The mixed alpha is formed per pair, as the reference does: alpha_i = alpha_j = 0 gives 0/0 = NaN, which keeps
+// the repulsion (NaN != 0) and zeroes the damping factors (NaN > 1e-9 is false) exactly like the reference.
+constexpr double kDispRepulsion = 315.7750382111558307123944638; // K (= 1e-3 hartree), System.Energy.cpp:1974
+constexpr double kDispUnit = 3.166811429 * 0.000001;             // hartree -> K
+constexpr double kDispK6 = 0.021958709 / kDispUnit;             // hartree bohr^6 -> K A^6
+constexpr double kDispK8 = 0.0061490647 / kDispUnit;
+constexpr double kDispK10 = 0.0017219135 / kDispUnit;
+
+MPMC_HD double disp_mix_alpha(double a_i, double a_j, bool schmidt) {
+	return schmidt ? ((a_i + a_j) * a_i * a_j) / (a_i * a_i + a_j * a_j) : (2.0 * a_i * a_j) / (a_i + a_j);
+}
+
+// the constants of the series below: 1/2 .. 1/10, the repulsion prefactor and the clamp.  A kernel may keep them in vector registers (a
+// loop that holds a skewed cell's 18 box doubles in scalar registers has no room for eleven more literals there)
+struct DispConst {
+	double inv[9], rep, tiny;
+};
+MPMC_HD DispConst disp_const() {
+	return DispConst{{0.5, 1.0 / 3.0, 0.25, 0.2, 1.0 / 6.0, 1.0 / 7.0, 0.125, 1.0 / 9.0, 0.1}, kDispRepulsion, 0.000000001};
+}
+
+// tt_damping for n = 6, 8, 10 at once (System.Energy.cpp:2037-2053): 1 - e^{-x} sum_{i<=n} x^i / i!, 0 unless > 1e-9
+MPMC_HD void disp_tt_damping(const DispConst &k, double x, double &f6, double &f8, double &f10) {
+	const double ex = exp(-x);
+	double t = x, s = 1.0 + x; // x^0 / 0! + x^1 / 1!
+	double s6 = 0.0, s8 = 0.0;
+	for (int i = 0; i < 9; i++) { // x^(i+2) / (i+2)!
+		t = (t * x) * k.inv[i];
+		s += t;
+		if (i == 4) s6 = s;
+		if (i == 6) s8 = s;
+	}
+	const double d6 = 1.0 - ex * s6, d8 = 1.0 - ex * s8, d10 = 1.0 - ex * s;
+	f6 = (d6 > k.tiny) ? d6 : 0.0;
+	f8 = (d8 > k.tiny) ? d8 : 0.0;
+	f10 = (d10 > k.tiny) ? d10 : 0.0;
+}
+
+// one pair's rd_energy at the minimum-image distance r (caller applied rd_excluded / frozen; there is no cutoff).  One reciprocal of r^2
+// serves the three powers (the reference divides three times: a few ulp apart, and r = 0 or c_n = 0 give the same infinities and NaNs)
+MPMC_HD double disp_expansion_pair(const DispConst &k, double r, double alpha_ij, double r0_ij, double c6, double c8, double c10, bool damp) {
+	const double ir2 = 1.0 / (r * r);
+	const double ir6 = (ir2 * ir2) * ir2;
+	const double ir8 = ir6 * ir2;
+	const double ir10 = ir8 * ir2;
+	const double rep = (alpha_ij != 0.0 && r0_ij != 0.0) ? k.rep * exp(-alpha_ij * (r - r0_ij)) : 0.0;
+	double f6 = 1.0, f8 = 1.0, f10 = 1.0;
+	if (damp) disp_tt_damping(k, alpha_ij * r, f6, f8, f10);
+	return ((-(f6 * c6) * ir6 - (f8 * c8) * ir8) - (f10 * c10) * ir10) + rep;
+}
+
+// disp_expansion_lrc / disp_expansion_lrc_self (:2022-2034, :2056-2080) with the coefficients c6, c8, c10 of a pair or of one atom
+MPMC_HD double disp_lrc_term(double c6, double c8, double c10, double cutoff, double volume) {
+	const double rc3 = cutoff * cutoff * cutoff, rc5 = rc3 * cutoff * cutoff, rc7 = rc5 * cutoff * cutoff;
+	return -4.0 * kPi * ((c6 / (3.0 * rc3) + c8 / (5.0 * rc5)) + c10 / (7.0 * rc7)) / volume;
 }
 
 // Thole exponential damping, reference System.Energy.cpp:2731-2757:  T = a*I - b*(d (x) d),

@@ -18,11 +18,11 @@ static int ensure_trial_buffers(mpmc_ctx *c) {
 		c->d_mv_slot = reinterpret_cast<int *>(c->d_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		c->d_mv_orig = c->d_mv_slot + MPMC_TRIAL_MAX_ATOMS;
 		if ((rc = dev_alloc(c, &c->d_moved_idx, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_delta_out, (size_t)8)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body delta
+		if ((rc = dev_alloc(c, &c->d_delta_out, (size_t)9)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body and disp-expansion deltas
 		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + 5);
 		HIP_TRY(c, hipMemsetAsync(c->d_moved_idx, 0xff, (size_t)c->max_pad * sizeof(int), c->stream)); // all -1; on our stream (ordered before the first delta kernel)
-		HIP_TRY(c, pinned_alloc(&c->h_delta_out, 9 * sizeof(double)));
-		c->h_delta_out[8] = 0.0;
+		HIP_TRY(c, pinned_alloc(&c->h_delta_out, 10 * sizeof(double)));
+		c->h_delta_out[8] = c->h_delta_out[9] = 0.0;
 		c->h_delta_cnt = reinterpret_cast<long long *>(c->h_delta_out + 5);
 		HIP_TRY(c, pinned_alloc(&c->h_mv_blob, kMvBlobBytes));
 	}
@@ -92,8 +92,8 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// short moves of non-polarizable boxes travel in the kernel arguments: no staging copy (a trial is launch-bound on the host: every
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->tune.no_inline_move;
-	// (the three-body delta reads the moved atoms from the device lists: a box with the term always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->tb_enabled;
+	// (the three-body and disp-expansion deltas read the moved atoms from the device lists: a box with either term always stages its move)
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->tb_enabled && !c->de_enabled;
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -126,6 +126,14 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_THREE_BODY);
 		launch_three_body_delta(st, atoms_view(c), c->d_tb_au, c->box, kThreeBodyScale, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_tb_part,
 		                        c->d_delta_out + 7);
+	}
+	if (c->de_enabled) {
+		// disp-expansion: the change of the pairs with a moved atom, O(m N), old positions still resident; into slot 8 of the delta result
+		// block, which k_delta_finish copies out behind the launch number's slot (h_delta_out[9]).  It replaces the LJ delta of launch_delta.
+		if ((rc = disp_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_disp_expansion_delta(st, atoms_view(c), c->d_de_co, c->d_de_t10, c->box, disp_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx,
+		                            c->d_de_part, c->d_delta_out + 8);
 	}
 	{
 		FusedParams fp{};
@@ -233,7 +241,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	const int do_es = c->opts.rd_only ? 0 : 1;
 	const mpmc_result &a = c->last_full;
 	mpmc_result r = a;
-	r.lj_pairs = a.lj_pairs + c->h_delta_out[0];
+	r.lj_pairs = a.lj_pairs + (c->de_enabled ? c->h_delta_out[9] : c->h_delta_out[0]); // (with the disp-expansion term lj_pairs holds its pair sum)
 	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {

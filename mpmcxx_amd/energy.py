@@ -24,6 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 MPMC_OK = 0
 ERR_UNSUPPORTED = 4004
 ERR_INVALID_SETTING = 4000
+DISP_DAMP, DISP_EXTRAPOLATE_C10, DISP_SCHMIDT = 1, 2, 4  # MPMC_DISP_* (mpmc_set_disp_expansion)
 ERR_NO_DEVICE = -1
 DAMPING = {"off": 0, "linear": 1, "exponential": 2, None: 2}
 SOLVER = {"auto": 0, "matrix_free": 1, "compact": 2, "dense": 3}
@@ -113,6 +114,9 @@ def lib():
     if hasattr(L, "mpmc_set_axilrod_teller") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no three-body term)
         L.mpmc_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, dp, dp]
         L.mpmc_axilrod_teller.argtypes = [vp, dp]
+    if hasattr(L, "mpmc_set_disp_expansion") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the disp-expansion term)
+        L.mpmc_set_disp_expansion.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
+        L.mpmc_disp_expansion.argtypes = [vp, dp]
     L.mpmc_thole_field.argtypes = [vp, dp]
     L.mpmc_thole_amatrix.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_get_dipoles.argtypes = [vp, dp, dp, dp]
@@ -325,6 +329,22 @@ class System:
             if key not in atoms:
                 raise ValueError(f"axilrod_teller is on but the atoms carry no {key!r} column")
             self.set_axilrod_teller(True, atoms[key] if mk else None, None if mk else atoms[key], midzuno_kihara_approx=mk)
+        # likewise the disp-expansion coefficients (`disp_expansion on`)
+        if self.options.get("disp_expansion"):
+            for key in ("c6", "c8", "c10"):
+                if key not in atoms:
+                    raise ValueError(f"disp_expansion is on but the atoms carry no {key!r} column")
+            o = self.options
+            self.set_disp_expansion(True, atoms["c6"], atoms["c8"], atoms["c10"], damp=bool(o.get("damp_dispersion")),
+                                    extrapolate_c10=bool(o.get("extrapolate_disp_coeffs")), schmidt=bool(o.get("schmidt_ff")))
+
+    def set_disp_expansion(self, enabled: bool, c6: Optional[np.ndarray] = None, c8: Optional[np.ndarray] = None, c10: Optional[np.ndarray] = None,
+                           damp: bool = False, extrapolate_c10: bool = False, schmidt: bool = False):
+        """switch the disp-expansion repulsion/dispersion term on (per-atom c6, c8, c10 in atomic units; the atoms' epsilon / sigma are its
+        alpha / r0) or off (mpmc_set_disp_expansion).  It replaces the LJ part of rd_energy."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (c6, c8, c10)]
+        flags = (DISP_DAMP if damp else 0) | (DISP_EXTRAPOLATE_C10 if extrapolate_c10 else 0) | (DISP_SCHMIDT if schmidt else 0)
+        self._check(self._L.mpmc_set_disp_expansion(self._h, int(bool(enabled)), flags, _dp(a[0]), _dp(a[1]), _dp(a[2])))
 
     def set_axilrod_teller(self, enabled: bool, c6: Optional[np.ndarray] = None, c9: Optional[np.ndarray] = None,
                            midzuno_kihara_approx: bool = False):
@@ -392,6 +412,9 @@ class System:
 
     def axilrod_teller(self) -> float:
         return self._scalar(self._L.mpmc_axilrod_teller)
+
+    def disp_expansion(self) -> float:
+        return self._scalar(self._L.mpmc_disp_expansion)
 
     def coulombic(self) -> float:
         return self._scalar(self._L.mpmc_coulombic)

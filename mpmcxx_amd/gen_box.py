@@ -328,6 +328,77 @@ def fixture(name: str):
         return rows, cubic(86.0), dict(POLAR_OPTS)
     if name in THREE_BODY_FIXTURES:
         return _three_body_fixture(name)
+    if name in DISP_FIXTURES:
+        return _disp_fixture(name)
+    raise KeyError(name)
+
+
+# ---- dispersion-expansion repulsion/dispersion (`disp_expansion on`, reference src/System.Energy.cpp:1939-2080) -----------------------------
+# per species: alpha (1/A) and r0 (A) in the PQR's epsilon / sigma columns, c6 / c8 / c10 in atomic units.  Repulsion and dispersion partly
+# cancel at contact (two A atoms at 3.8 A: +124 K of repulsion against -262 K of undamped dispersion).  Lattice rows alternate A / B (the
+# mixing rules see two species); in the molecular box the first H has alpha = 0 but c6 != 0 and the second H is a null site.
+DISP_SPECIES = {
+    "A": (3.10, 3.45, 64.3, 1623.0, 49060.0),
+    "B": (2.85, 3.70, 129.6, 4187.0, 155500.0),
+    "O": (3.60, 3.20, 15.0, 250.0, 5000.0),
+    "H1": (0.0, 0.0, 2.5, 0.0, 0.0),
+    "H2": (0.0, 0.0, 0.0, 0.0, 0.0),
+    "Xe": (2.60, 4.30, 285.9, 11000.0, 500000.0),
+}
+DISP_OPTS = {"disp_expansion": "on"}
+
+
+def _with_disp(rows: List[AtomRow], zero_c6_every: int = 0, zero_c8_every: int = 0) -> List[AtomRow]:
+    """every row gets its species' parameters and all four coefficient columns (c9 = 0)"""
+    prev = None
+    for r in rows:
+        if r.atomtype == "H":
+            sp = "H1" if prev == "O" else "H2"
+        elif r.atomtype in ("O", "Xe"):
+            sp = r.atomtype
+        else:
+            sp = "A" if r.atom_id % 2 == 1 else "B"
+        prev = r.atomtype
+        r.eps, r.sigma, r.c6, r.c8, r.c10 = DISP_SPECIES[sp]
+        r.c9 = 0.0
+        if zero_c6_every and r.atom_id % zero_c6_every == 0:
+            r.c6 = 0.0
+        if zero_c8_every and r.atom_id % zero_c8_every == 0:
+            r.c8 = 0.0
+    return rows
+
+
+def _disp_fixture(name: str):
+    d = dict(DISP_OPTS)
+    damped = dict(d, damp_dispersion="on")
+    if name.startswith("ar2_disp_"):  # two atoms (species A and B) at 3.2, 3.8 or 6.0 A in a 10^4 A box
+        r = {"ar2_disp_32": 3.2, "ar2_disp_38": 3.8, "ar2_disp_60": 6.0}[name]
+        rows = [AtomRow(1, "Ar", "Ar", "M", 1, 0.0, 0.0, -r / 2, 39.948, 0.0, 0.0, 0.0, 0.0),
+                AtomRow(2, "Ar", "Ar", "M", 2, 0.0, 0.0, r / 2, 39.948, 0.0, 0.0, 0.0, 0.0)]
+        return _with_disp(rows), cubic(10000.0), dict(d if name == "ar2_disp_32" else damped, rd_only="on")
+    if name == "ar216_disp":  # noble-gas lattice, rd_only, damped
+        return _with_disp(lattice_box(216, 24.0, 7, charged=False, alpha=0.0)), cubic(24.0), dict(damped, rd_only="on")
+    if name == "ion216_disp":  # Ewald, undamped
+        return _with_disp(lattice_box(216, 24.0, 7)), cubic(24.0), dict(d, ewald_kmax=7)
+    if name == "ion216_polar_disp":
+        return _with_disp(lattice_box(216, 24.0, 7)), cubic(24.0), dict(POLAR_OPTS, **damped)
+    if name == "water64_disp":  # 3-site molecules, an alpha = 0 site with c6, a null site, a neutral Xe; undamped
+        return _with_disp(molecular_box(64, 14.0, 5)), cubic(14.0), dict(d, ewald_kmax=7)
+    if name == "ion216_framework_disp":  # one frozen 150-site molecule + 66 mobile atoms
+        rows, basis, o = fixture("ion216_framework")
+        return _with_disp(rows), basis, dict(o, **damped)
+    if name == "ion216_triclinic_disp":
+        rows, basis, o = fixture("ion216_triclinic")
+        return _with_disp(rows), basis, dict(o, **damped)
+    if name == "ion216_extrap_disp":  # extrapolated c10, with atoms whose c6 or c8 is 0
+        return (_with_disp(lattice_box(216, 24.0, 7), zero_c6_every=7, zero_c8_every=11), cubic(24.0),
+                dict(damped, extrapolate_disp_coeffs="on", ewald_kmax=7))
+    if name == "ion216_schmidt_disp":
+        return _with_disp(lattice_box(216, 24.0, 7)), cubic(24.0), dict(d, schmidt_ff="on", ewald_kmax=7)
+    if name == "ion216_nolrc_disp":
+        return _with_disp(lattice_box(216, 24.0, 7)), cubic(24.0), dict(damped, rd_lrc="off", ewald_kmax=7)
+    if name == "ion4000_polar_disp":  # 63 tiles: beyond the single-launch size, Ewald + polarization
+        return _with_disp(lattice_box(4000, 64.0, 17)), cubic(64.0), dict(POLAR_OPTS, **damped)
     raise KeyError(name)
 
 
@@ -402,15 +473,19 @@ SMALL_FIXTURES = [
 THREE_BODY_FIXTURES = ["ar3_at", "ion216_at", "ion216_polar_at", "water64_at", "ion216_framework_at", "ion216_triclinic_at", "ion216_mk_at",
                        "grid_at", "ion512_at"]
 LARGE_FIXTURES = ["ion10k_es", "ion10k_polar", "ion10k_polar_bead0", "ion10k_polar_bead1", "ion8000_triclinic"]
+# boxes with the disp-expansion term (the C oracle has no such term): kept apart like THREE_BODY_FIXTURES
+DISP_FIXTURES = ["ar2_disp_32", "ar2_disp_38", "ar2_disp_60", "ar216_disp", "ion216_disp", "ion216_polar_disp", "water64_disp",
+                 "ion216_framework_disp", "ion216_triclinic_disp", "ion216_extrap_disp", "ion216_schmidt_disp", "ion216_nolrc_disp",
+                 "ion4000_polar_disp"]
 
 
-def keep_three_body_golden(golden_dir: str) -> None:
-    """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>`: keep each box's scalar results (energies, counts, cell) and drop the
-    per-atom arrays and the box text.  The three-body tests compare nothing else, and they regenerate the boxes with `materialize`, which
-    writes the same bytes the reference read."""
+def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
+    results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
+    they regenerate the boxes with `materialize`, which writes the same bytes the reference read."""
     import json
 
-    for name in THREE_BODY_FIXTURES:
+    for name in (names or THREE_BODY_FIXTURES):
         path = os.path.join(golden_dir, f"{name}.json")
         with open(path) as f:
             res = json.load(f)
@@ -439,6 +514,9 @@ if __name__ == "__main__":
 
     if sys.argv[1:2] == ["--keep-three-body-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-disp-golden"]:
+        keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)
         sys.exit(0)
     out = sys.argv[1] if len(sys.argv) > 1 else "."
     for nm in (sys.argv[2:] or SMALL_FIXTURES):

@@ -23,8 +23,8 @@ E2REDUCED = 408.7816  # reference src/constants.h:35
 UNSUPPORTED_ON = [
     "rd_crystal", "spectre", "gwp", "sg", "polarvdw", "cdvdw", "polar_ewald_full",
     "polar_wolf", "polar_wolf_full", "polar_palmo", "polar_gs_ranked", "polar_sor", "polar_esor", "polar_zodid",
-    "waldmanhagler", "halgren_mixing", "c6_mixing", "dreiding", "lj_buffered_14_7", "disp_expansion",
-    "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
+    "waldmanhagler", "halgren_mixing", "c6_mixing", "dreiding", "lj_buffered_14_7",
+    "disp_expansion_mbvdw", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
 ]
 
 
@@ -39,6 +39,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
     frozen: List[int] = []
     disp: List[int] = []
     c6: List[float] = []
+    c8: List[float] = []
+    c10: List[float] = []
     c9: List[float] = []
     cur_mol_token = None
     mol_index = -1
@@ -71,6 +73,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
             c = [float(x) for x in t[16:19]]
             disp.append(1 if any(v != 0.0 for v in c) else 0)
             c6.append(c[0] if c else 0.0)  # (Axilrod-Teller: c6 feeds the Midzuno-Kihara c9, src/System.cpp:587, 721)
+            c8.append(c[1] if len(c) > 1 else 0.0)  # (disp_expansion: the rest of the dispersion series)
+            c10.append(c[2] if len(c) > 2 else 0.0)
             c9.append(float(t[19]) if len(t) > 19 else 0.0)
     return {
         "pos": np.ascontiguousarray(np.array(pos, dtype=np.float64).reshape(-1, 3)),
@@ -83,6 +87,8 @@ def read_pqr(path: str) -> Dict[str, np.ndarray]:
         "frozen": np.array(frozen, dtype=np.int32),
         "has_disp": np.array(disp, dtype=np.int32),
         "c6": np.array(c6, dtype=np.float64),
+        "c8": np.array(c8, dtype=np.float64),
+        "c10": np.array(c10, dtype=np.float64),
         "c9": np.array(c9, dtype=np.float64),
     }
 
@@ -125,6 +131,8 @@ def read_input(path: str) -> Dict[str, object]:
             elif k in ("rd_only", "rd_lrc", "polarization", "polar_iterative", "polar_ewald", "polar_gs", "polar_rrms", "wolf", "feynman_hibbs"):
                 opts[k] = _onoff(v[0])
             elif k in ("axilrod_teller", "midzuno_kihara_approx"):  # (set only when the input names them: other inputs load as before)
+                opts[k] = _onoff(v[0])
+            elif k in ("disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_ff"):  # (likewise)
                 opts[k] = _onoff(v[0])
             elif k in ("polar_max_iter", "ewald_kmax", "feynman_hibbs_order"):
                 opts[k] = int(v[0])
