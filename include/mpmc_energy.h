@@ -75,7 +75,8 @@ extern "C" {
 #define MPMC_FLAG_OTHER_RD (1ull << 14)      /* dreiding / lj_buffered_14_7 / disp_expansion / anharmonic / exp_repulsion */
 #define MPMC_FLAG_AXILROD_TELLER (1ull << 15) /* still refused here: the term is switched on by mpmc_set_axilrod_teller alone */
 #define MPMC_FLAG_CAVITY_AUTOREJECT (1ull << 16)
-#define MPMC_FLAG_POLAR_MATRIX_INVERSION (1ull << 17) /* polarization on with polar_iterative off */
+#define MPMC_FLAG_POLAR_MATRIX_INVERSION (1ull << 17) /* polarization on with polar_iterative off (now supported: the direct solve
+                                                       * below; the bit is accepted and ignored, polar_iterative == 0 selects the path) */
 
 typedef struct mpmc_ctx mpmc_ctx; /* opaque: device buffers + stream of one System */
 
@@ -84,7 +85,7 @@ typedef struct mpmc_options {
 	int32_t rd_only;          /* :977  skip electrostatics + polarization                                   */
 	int32_t rd_lrc;           /* :1003 LJ long-range correction (default on)                                */
 	int32_t polarization;     /* :653                                                                       */
-	int32_t polar_iterative;  /* :1240 (required when polarization is on)                                   */
+	int32_t polar_iterative;  /* :1240 on: Jacobi / Gauss-Seidel sweeps; off (the reference's default): the direct solve  */
 	int32_t polar_ewald;      /* :718/:1210 static field by Ewald (recip_term + real_term) instead of nopbc */
 	int32_t polar_max_iter;   /* :1303 fixed iteration count when polar_precision == 0                      */
 	int32_t polar_gs;         /* :1256 Gauss-Seidel: in-place sweeps in atom order (serial over 64-atom tiles)  */
@@ -263,6 +264,30 @@ int mpmc_thole_field(mpmc_ctx *ctx, double *ef_static /*[n][3] host, may be NULL
 /* System::thole_amatrix(): fills rows [row0, row0+nrows) of the dense 3N x 3N matrix into `a` (host, row-major
  * nrows x 3N).  Diagonal 1/alpha (1e40 when alpha == 0), off-diagonal blocks as src/System.Energy.cpp:2744-2764. */
 int mpmc_thole_amatrix(mpmc_ctx *ctx, int row0, int nrows, double *a);
+
+/* ---- `polar_iterative off`: the dipoles by a direct solve (System::polar :2590-2607: thole_field, thole_bmatrix, thole_bmatrix_dipoles) --
+ * With polarization on, rd_only off and polar_iterative == 0 an evaluation computes the static field as always, solves A mu = E0 on the
+ * device and returns polarization_energy = -1/2 sum mu . E0.  A is the matrix of thole_amatrix restricted to the polarizable atoms (atoms
+ * with alpha == 0 get mu = 0 exactly; the reference's 1e40 diagonal gives them dipoles of the order 1e-40 E).  A is symmetric and positive
+ * definite for a physical model: it is factored as L L^T (blocked Cholesky, trailing update on the fp64 matrix cores) where the reference
+ * inverts it by pivoted LU.  polar_iterations, dipole_rrms and iterator_failed stay 0 as in the reference; polar_max_iter, polar_precision,
+ * polar_gamma, polar_gs, polar_rrms and solver are ignored.
+ * Deliberate difference: when A is NOT positive definite (polarization catastrophe) the reference returns the unphysical LU answer; here the
+ * evaluation completes with iterator_failed = 1 (every driver rejects such a configuration), dipoles and polarization_energy 0, and
+ * mpmc_polar_direct_info names the pivot.
+ * Trial moves of such a context run a FULL evaluation of the trial configuration (as polarizable Wolf boxes do): the solve is global.
+ * mpmc_get_dipoles: ef_induced = mu / alpha - ef_static for polarizable atoms, 0 for the others (the reference leaves stale values there
+ * on this path).
+ * Memory: (3 n_pol rounded up to 192)^2 doubles for the factor (the lower triangle is used; the square is allocated); a factor that does
+ * not fit the free device memory fails the evaluation with MPMC_ERR_MEMORY and a text that names the size.  Time: the factorisation and
+ * the solves are counted in MPMC_K_DIPOLE_ITER, the build of A in MPMC_K_TENSOR. */
+typedef struct mpmc_direct_info {
+	int64_t n_unknowns;   /* 3 n_pol of the last direct solve of this context (0: none has run)                            */
+	int64_t status;       /* 0, or the 1-based index (among the unknowns, device order) of the first non-positive pivot       */
+	double residual;      /* max |E0 - A mu| / max |E0| over the unknowns, A mu from an independent matrix-free product       */
+	int64_t factor_bytes; /* device memory held by the factor (counted in mpmc_memory_usage's total)                          */
+} mpmc_direct_info;
+int mpmc_polar_direct_info(mpmc_ctx *ctx, mpmc_direct_info *out);
 
 /* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL */
 int mpmc_get_dipoles(mpmc_ctx *ctx, double *mu, double *ef_static, double *ef_induced /* each [n][3] */);

@@ -330,7 +330,7 @@ private:
 		o.polar_damp = polar_damp;
 		o.ewald_alpha = ewald_alpha;
 		o.polar_ewald_alpha = polar_ewald_alpha;
-		o.unsupported_flags = unsupported_flags | ((polarization && !polar_iterative) ? MPMC_FLAG_POLAR_MATRIX_INVERSION : 0);
+		o.unsupported_flags = unsupported_flags; // (polar_iterative off is the library's direct dipole solve: no flag)
 		check(mpmc_set_options(ctx_, &o), "mpmc_set_options");
 		if (atoms_dirty_) {
 			std::vector<double> pos(3 * (size_t)n), q(n), al(n), ep(n), sg(n), ms(n);

@@ -210,7 +210,7 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	for (auto &e : c->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
 	void *ptrs[] = {c->d_atoms_blob, c->d_atom_part, c->d_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_scal,
 	                c->d_flag, c->d_counter, c->d_kvec, c->d_kw, c->d_sf, c->d_w_en, c->d_e_recip_part, c->d_part, c->d_e_static, c->d_mu[0], c->d_mu[1],
-	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
+	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_chol, c->d_chol_v, c->d_chol_info, c->d_chol_list, c->d_chol_status, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
 	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part,
 	                c->d_de_co, c->d_de_t10, c->d_de_part};
 	for (void *p : ptrs)
@@ -225,6 +225,7 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	if (c->h_scal) (void)pinned_free(c->h_scal);
 	if (c->h_flag) (void)pinned_free(c->h_flag);
 	if (c->h_delta_out) (void)pinned_free(c->h_delta_out);
+	if (c->h_chol_info) (void)pinned_free(c->h_chol_info);
 	if (c->h_mv_blob) (void)pinned_free(c->h_mv_blob);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
@@ -276,21 +277,20 @@ extern "C" int mpmc_set_box(mpmc_ctx *c, const double basis[9], const double *re
 
 extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 	if (!c || !o) return MPMC_ERR_ARG;
-	if (o->unsupported_flags & ~(uint64_t)(MPMC_FLAG_WOLF | MPMC_FLAG_FEYNMAN_HIBBS)) { // (Wolf / Feynman-Hibbs travel in their own option fields)
+	// (Wolf / Feynman-Hibbs travel in their own option fields, matrix inversion is polar_iterative == 0)
+	if (o->unsupported_flags & ~(uint64_t)(MPMC_FLAG_WOLF | MPMC_FLAG_FEYNMAN_HIBBS | MPMC_FLAG_POLAR_MATRIX_INVERSION)) {
 		char buf[160];
 		std::snprintf(buf, sizeof buf, "mpmc_set_options: reference option(s) outside the energy hot path are ON (flag mask 0x%llx)",
 		              (unsigned long long)o->unsupported_flags);
 		return fail(c, MPMC_ERR_UNSUPPORTED, buf);
 	}
 	if (o->polarization && !o->rd_only) {
-		if (!o->polar_iterative)
-			return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_set_options: polarization by matrix inversion (polar_iterative off) is not supported");
 		if (o->damp_type != MPMC_DAMPING_EXPONENTIAL)
 			return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_set_options: only polar_damp_type exponential is supported");
-		if (o->polar_precision == 0.0 && o->polar_max_iter < 1)
+		if (o->polar_iterative && o->polar_precision == 0.0 && o->polar_max_iter < 1)
 			return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: polar_max_iter must be >= 1 when polar_precision is 0 (the reference never terminates)");
-		if (o->polar_precision < 0.0) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: polar_precision < 0");
-		if (o->solver < MPMC_SOLVER_AUTO || o->solver > MPMC_SOLVER_DENSE) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: bad solver");
+		if (o->polar_iterative && o->polar_precision < 0.0) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: polar_precision < 0");
+		if (o->polar_iterative && (o->solver < MPMC_SOLVER_AUTO || o->solver > MPMC_SOLVER_DENSE)) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: bad solver");
 	}
 	if (o->ewald_kmax < 0 || o->ewald_kmax > 64) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: ewald_kmax out of range");
 	if (o->feynman_hibbs) {
@@ -1094,6 +1094,7 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 // any of this.  Keys (value 1 = on, 0 = off unless said otherwise):
 //   side_stream -1 | 0 | 1     pair_kernel 0 | 1 | 2     pair_waves 0 | 1 | 4     panels     uniform_images     tile_classes
 //   single_launch     recip_table     spatial_sort     order_carry     polar_delta     inline_move     trace_panel     tensor_budget_mb N
+//   direct_budget_mb N (-1: free device memory)
 extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) {
 	if (!key) return MPMC_ERR_ARG;
 	std::unique_lock<std::mutex> tuning_lk(g_tuning_mu, std::defer_lock);
@@ -1164,6 +1165,8 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 	else if (k == "panel_replicas") {
 		if (!c || v < 1 || v > 64) return MPMC_ERR_ARG;
 		c->debug_panel_replicas = v;
+	} else if (k == "direct_budget_mb") {
+		t.direct_budget_mb = (long long)value;
 	} else if (k == "tensor_budget_mb") {
 		if (value < 0) return MPMC_ERR_ARG;
 		t.tensor_budget_mb = (long long)value;

@@ -88,6 +88,7 @@ struct mpmc_tuning {
 	int fail_next_wait = 0;      // "fail_next_wait" = 1: the next wait of this context fails as if the runtime had refused it (test of the recovery path)
 	bool trace_panel = false;    // "trace_panel" = 1: per-workgroup time stamps of the panel kernel (tools/panel_trace.py)
 	long long tensor_budget_mb = 4096; // "tensor_budget_mb": AUTO solver: largest tensor store it will allocate
+	long long direct_budget_mb = -1;   // "direct_budget_mb": direct dipole solve: largest factor it will allocate (-1: what the device has free)
 };
 
 struct mpmc_ctx {
@@ -230,6 +231,13 @@ struct mpmc_ctx {
 	double2 *d_ab = nullptr;
 	size_t cap_ab = 0; // in double2 elements
 	int solver_used = MPMC_SOLVER_MATRIX_FREE;
+	// direct dipole solve (`polar_iterative off`, kernels_chol.hip): the factor (np x np doubles, lower triangle), the slot list of the
+	// polarizable atoms, two vectors of np doubles, { status } on the device and { status, max |r|, max |E0| } on the device / pinned
+	double *d_chol = nullptr, *d_chol_v = nullptr, *d_chol_info = nullptr, *h_chol_info = nullptr;
+	int *d_chol_list = nullptr, *d_chol_status = nullptr;
+	size_t cap_chol = 0, cap_chol_v = 0, cap_chol_list = 0;
+	bool direct_ran = false;       // the pending / last evaluation solved the dipoles directly
+	mpmc_direct_info direct{};     // of the last such evaluation (filled by wait_and_fill)
 
 	Box box{};
 	double box_in[20] = {0}; // what mpmc_set_box was last called with (basis, reciprocal, volume, cutoff): an identical call is a no-op
@@ -469,6 +477,7 @@ int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (
 int enqueue(mpmc_ctx *c, unsigned mask);         // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp)
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options
+inline bool direct_solve(const mpmc_ctx *c) { return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative; } // `polar_iterative off`
 void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Feynman-Hibbs fields of the pair parameters (evaluate.cpp)
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);

@@ -126,6 +126,10 @@ static int ensure_polar_buffers(mpmc_ctx *c) {
 static int resolve_solver(mpmc_ctx *c) {
 	const size_t need = (size_t)c->n_tile_pairs * (kTile * kTile); // double2 elements, 16 B each
 	int want = c->opts.solver;
+	if (direct_solve(c)) { // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
+		c->solver_used = MPMC_SOLVER_MATRIX_FREE;
+		return MPMC_OK;
+	}
 	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
 	if (want == MPMC_SOLVER_AUTO) {
 		const size_t budget_mb = (size_t)c->tune.tensor_budget_mb;
@@ -243,6 +247,86 @@ static inline int sweep_split_tail(const mpmc_ctx *c) {
 	return (int)((long long)c->n_sweep_blocks * permille / 1000);
 }
 
+// `polar_iterative off` (System::polar :2590-2607): A mu = E0 solved directly (kernels_chol.hip), behind the static field.  Leaves the
+// dipoles in d_mu[mu_cur], mu / alpha - E0 in d_e_induced and { status, max |r|, max |E0| } on their way to the pinned info block.
+static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
+	hipStream_t st = c->stream;
+	int n_pol = 0;
+	for (int i = 0; i < c->n; i++) n_pol += (c->h_alpha[i] != 0.0) ? 1 : 0;
+	const int np = chol_padded(n_pol);
+	const size_t elems = (size_t)np * (size_t)np, bytes = elems * sizeof(double);
+	int rc;
+	if (!c->d_chol_status) {
+		if ((rc = dev_alloc(c, &c->d_chol_status, (size_t)4)) != MPMC_OK) return rc;
+		if ((rc = dev_alloc(c, &c->d_chol_info, (size_t)4)) != MPMC_OK) return rc;
+		HIP_TRY(c, pinned_alloc(&c->h_chol_info, 4 * sizeof(double)));
+	}
+	{ // size guard: the factor must fit what the device has free (or the budget of the tuning switch)
+		size_t free_b = 0, total_b = 0;
+		HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+		size_t avail = free_b + c->cap_chol * sizeof(double);
+		if (c->tune.direct_budget_mb >= 0) avail = std::min(avail, (size_t)c->tune.direct_budget_mb * (size_t)1048576);
+		if (bytes > avail) {
+			char buf[256];
+			std::snprintf(buf, sizeof buf, "direct dipole solve: the factor of %d unknowns needs %.1f MB (%d x %d doubles), %.1f MB are available", 3 * n_pol,
+			              (double)bytes / 1048576.0, np, np, (double)avail / 1048576.0);
+			return fail(c, MPMC_ERR_MEMORY, buf);
+		}
+	}
+	if (elems > c->cap_chol) {
+		dev_free(c, &c->d_chol, c->cap_chol);
+		c->cap_chol = 0;
+		if (dev_alloc(c, &c->d_chol, elems) != MPMC_OK) {
+			(void)hipGetLastError();
+			c->d_chol = nullptr;
+			return fail(c, MPMC_ERR_MEMORY, "direct dipole solve: cannot allocate the factor (" + std::to_string(bytes) + " bytes): " + c->err);
+		}
+		c->cap_chol = elems;
+	}
+	if ((size_t)2 * np > c->cap_chol_v) {
+		dev_free(c, &c->d_chol_v, c->cap_chol_v);
+		c->cap_chol_v = 0;
+		if ((rc = dev_alloc(c, &c->d_chol_v, (size_t)2 * np + 1)) != MPMC_OK) return rc;
+		c->cap_chol_v = (size_t)2 * np + 1;
+	}
+	if ((size_t)n_pol > c->cap_chol_list) {
+		dev_free(c, &c->d_chol_list, c->cap_chol_list);
+		c->cap_chol_list = 0;
+		if ((rc = dev_alloc(c, &c->d_chol_list, (size_t)c->max_pad)) != MPMC_OK) return rc;
+		c->cap_chol_list = (size_t)c->max_pad;
+	}
+	c->mu_cur = 0;
+	double *mu = c->d_mu[0], *v0 = c->d_chol_v, *v1 = c->d_chol_v + np;
+	HIP_TRY(c, hipMemsetAsync(c->d_chol_status, 0, sizeof(int), st));
+	HIP_TRY(c, hipMemsetAsync(mu, 0, 3 * (size_t)at.n_pad * sizeof(double), st));
+	if (n_pol > 0) {
+		{
+			ProfScope p(c, MPMC_K_TENSOR);
+			launch_chol_build(st, at, c->box, c->opts.polar_damp, c->d_chol_list, n_pol, np, c->d_chol);
+		}
+		{
+			ProfScope p(c, MPMC_K_DIPOLE_ITER);
+			launch_chol_rhs(st, c->d_chol_list, n_pol, np, c->d_e_static, v0, c->d_chol_status);
+			launch_chol_factor(st, c->d_chol, np, c->d_chol_status);
+			launch_chol_solve(st, c->d_chol, np, v0, v1, c->d_chol_status);
+			launch_chol_scatter(st, c->d_chol_list, n_pol, v0, mu, c->d_chol_status);
+		}
+	}
+	{ // the residual from an independent product: one matrix-free contraction, -(A_off mu) into d_e_induced (d_mu[1] is scratch)
+		ProfScope p(c, MPMC_K_REDUCE);
+		launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift,
+		                          c->n_tile_pairs, nullptr, c->d_part, c->opts.polar_damp, nullptr);
+		launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, c->d_mu[1], c->d_e_induced, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
+		launch_chol_finish(st, at, mu, c->d_e_static, c->d_e_induced, c->d_chol_status, c->d_chol_info);
+	}
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipMemcpyAsync(c->h_chol_info, c->d_chol_info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+	c->direct.n_unknowns = 3 * (int64_t)n_pol;
+	c->direct.factor_bytes = (int64_t)(c->cap_chol * sizeof(double));
+	c->direct_ran = true;
+	return MPMC_OK;
+}
+
 // which pieces of energy() to run
 
 int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
@@ -261,6 +345,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	hipStream_t st = c->stream;
 	c->run_mask = mask;
 	c->have_polar = false;
+	c->direct_ran = false;
 	c->iters = 0;
 	c->failed = 0;
 
@@ -463,7 +548,17 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	}
 
 	// ---- thole_iterative, reference src/System.Energy.cpp:3450-3543 ------------------------------------------------
-	if (mask & RUN_SOLVE) {
+	if ((mask & RUN_SOLVE) && direct_solve(c)) { // thole_bmatrix + thole_bmatrix_dipoles (:2596-2600) as a direct solve of A mu = E0
+		if ((rc = enqueue_direct_solve(c, at)) != MPMC_OK) return rc;
+		{
+			ProfScope p(c, MPMC_K_REDUCE);
+			if (reduce_in_tail)
+				launch_polar_energy_and_pairs(st, at, c->d_mu[c->mu_cur], c->d_e_static, nullptr, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal,
+				                              c->d_cnt);
+			else launch_polar_energy(st, at, c->d_mu[c->mu_cur], c->d_e_static, nullptr, c->d_scal);
+		}
+		c->have_polar = true;
+	} else if (mask & RUN_SOLVE) {
 		const bool by_precision = (o.polar_precision != 0.0);
 		const int want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
 		const double allowed = by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
@@ -741,6 +836,15 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	c->sync_stream = nullptr;
 	c->pending = false;
 	prof_harvest(c);
+	if (c->direct_ran) { // the direct solve's verdict came with the results (copied in front of the post)
+		c->direct.status = (int64_t)c->h_chol_info[0];
+		c->direct.residual = (c->h_chol_info[2] > 0.0) ? c->h_chol_info[1] / c->h_chol_info[2] : 0.0;
+		if (c->direct.status != 0) {
+			c->failed = 1; // A is not positive definite: the caller rejects the configuration
+			c->err = "direct dipole solve: the matrix is not positive definite (pivot " + std::to_string((long long)c->direct.status) + " of " +
+			         std::to_string((long long)c->direct.n_unknowns) + " is not positive): dipoles and polarization energy set to 0";
+		}
+	}
 	if (!out) return MPMC_OK;
 	std::memset(out, 0, sizeof(*out));
 	const double *s = c->h_scal;
@@ -929,6 +1033,13 @@ extern "C" int mpmc_thole_amatrix(mpmc_ctx *c, int row0, int nrows, double *a) {
 	HIP_TRY(c, hipMemcpyAsync(a, c->d_arows, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	prof_harvest(c);
+	return MPMC_OK;
+}
+
+extern "C" int mpmc_polar_direct_info(mpmc_ctx *c, mpmc_direct_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_direct_info: an evaluation is in flight");
+	*out = c->direct;
 	return MPMC_OK;
 }
 

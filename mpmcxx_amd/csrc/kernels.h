@@ -228,6 +228,24 @@ void launch_dense_symv(hipStream_t st, const double *a, int n_pad, const double 
 // part[chunk][n_pad][3] = - (rows of the chunk of A) . x  (A symmetric); k_dipole_update sums the chunks
 void launch_dense_matvec(hipStream_t st, const double *a, int n_pad, const double *x, int n_chunks, double *part);
 
+// ---- direct dipole solve (kernels_chol.hip): `polar_iterative off`, A mu = E0 by a blocked Cholesky factorisation -------------------
+constexpr int kCholNB = 64;     // block width: the diagonal block one workgroup factors in LDS, the tile of the trailing update
+constexpr int kCholPanel = 192; // panel width (three blocks = the rows of one atom tile): rank of the trailing update behind a panel
+// unknowns 3 n_pol rounded up to whole panels (the matrix is np x np doubles, lower triangle used)
+inline int chol_padded(int n_pol) { return (3 * n_pol + kCholPanel - 1) / kCholPanel * kCholPanel; }
+// pol_list[n_pol]: slots of the atoms with alpha != 0 (written here); m: the lower triangle of thole_amatrix restricted to them
+void launch_chol_build(hipStream_t st, const AtomsDev &at, const Box &bx, double polar_damp, int *pol_list, int n_pol, int np, double *m);
+// b[np] = E0 of the unknowns; clears status[0]
+void launch_chol_rhs(hipStream_t st, const int *pol_list, int n_pol, int np, const double *e_static, double *b, int *status);
+// m = L (in place); status[0] = 1-based index of the first non-positive pivot, else 0 (every later kernel then returns at once)
+void launch_chol_factor(hipStream_t st, double *m, int np, int *status);
+// v0 = right-hand side in, solution out; v1 = scratch (both np long)
+void launch_chol_solve(hipStream_t st, const double *m, int np, double *v0, double *v1, const int *status);
+void launch_chol_scatter(hipStream_t st, const int *pol_list, int n_pol, const double *x, double *mu /*zeroed by the caller*/, const int *status);
+// info[3] = { status, max |E0 + e_induced - mu / alpha|, max |E0| }; e_induced in: -(A_off mu) of one contraction, out: mu / alpha - E0
+void launch_chol_finish(hipStream_t st, const AtomsDev &at, const double *mu, const double *e_static, double *e_induced, const int *status,
+                        double *info);
+
 // ---- Gauss-Seidel sweeps (kernels_gs.hip): `polar_gs on`, identity atom order, matrix-free ---------------------------
 // one sweep over all tiles in atom order: mu is updated in place, e_induced receives each atom's induced field.  part: the slots of the
 // symmetric kernel [nt][n_pad][3]; U, L: [n_pad][3] (tiles above / below); tile_pairs, cls, tp_shift: this evaluation's tile-pair tables

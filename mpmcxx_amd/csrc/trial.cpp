@@ -72,8 +72,9 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	c->trial_polar_delta = false;
 	const bool no_polar_delta = c->tune.no_polar_delta;
 	// (Wolf electrostatics and the Feynman-Hibbs corrections are per-pair terms like the others: the delta kernels carry them; a
-	// polarizable box under Wolf keeps the full evaluation -- its static field is the Ewald one, outside the reference's own combinations)
-	const bool polar_delta = polar && c->e_real_valid && !no_polar_delta && m <= MPMC_TRIAL_MAX_ATOMS && !o.wolf;
+	// polarizable box under Wolf keeps the full evaluation -- its static field is the Ewald one, outside the reference's own combinations;
+	// so does a box whose dipoles are solved directly, polar_iterative off: the matrix is rebuilt and factored again anyway)
+	const bool polar_delta = polar && c->e_real_valid && !no_polar_delta && m <= MPMC_TRIAL_MAX_ATOMS && !o.wolf && !direct_solve(c);
 	if ((polar && !polar_delta) || m > MPMC_TRIAL_MAX_ATOMS) {
 		// the dipole solve couples every atom: evaluate the trial configuration in full (still on the device)
 		c->trial_keep = c->last_full;

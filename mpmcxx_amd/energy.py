@@ -69,6 +69,11 @@ class GibbsMove(C.Structure):
                 ("N", C.c_double * 2), ("volume", C.c_double * 2), ("checkpoint_volume_0", C.c_double)]
 
 
+class DirectInfo(C.Structure):
+    """mpmc_direct_info: the last direct dipole solve (`polar_iterative off`) of a context."""
+    _fields_ = [("n_unknowns", C.c_int64), ("status", C.c_int64), ("residual", C.c_double), ("factor_bytes", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -134,6 +139,8 @@ def lib():
     L.mpmc_get_timings.argtypes = [vp, C.POINTER(Timings), C.c_int]
     L.mpmc_synchronize.argtypes = [vp]
     L.mpmc_memory_usage.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "mpmc_polar_direct_info") or not os.environ.get("MPMC_ENERGY_LIB"):
+        L.mpmc_polar_direct_info.argtypes = [vp, C.POINTER(DirectInfo)]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -497,6 +504,13 @@ class System:
         a, b = C.c_int64(), C.c_int64()
         self._check(self._L.mpmc_memory_usage(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def direct_info(self) -> Dict[str, float]:
+        """the last direct dipole solve (`polar_iterative off`): unknowns, status (0, or the 1-based index of the first non-positive
+        pivot), relative residual max|E0 - A mu| / max|E0|, bytes held by the factor."""
+        d = DirectInfo()
+        self._check(self._L.mpmc_polar_direct_info(self._h, C.byref(d)))
+        return {f: getattr(d, f) for f, _ in d._fields_}
 
 
 class ResultList:

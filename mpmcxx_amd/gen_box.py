@@ -326,6 +326,9 @@ def fixture(name: str):
         for r, (x, y, z) in zip(rows, pos):
             r.x, r.y, r.z = float(x), float(y), float(z)
         return rows, cubic(86.0), dict(POLAR_OPTS)
+    if name in DIRECT_FIXTURES:  # the same boxes with the dipoles by matrix inversion (the reference's default, `polar_iterative off`)
+        rows, basis, o = fixture(name[:-len("_direct")])
+        return rows, basis, dict(o, polar_iterative="off")
     if name in THREE_BODY_FIXTURES:
         return _three_body_fixture(name)
     if name in DISP_FIXTURES:
@@ -479,6 +482,39 @@ DISP_FIXTURES = ["ar2_disp_32", "ar2_disp_38", "ar2_disp_60", "ar216_disp", "ion
                  "ion4000_polar_disp"]
 
 
+# boxes whose dipoles the reference solves by matrix inversion (thole_bmatrix): the direct solve of the library
+DIRECT_FIXTURES = ["ion216_polar_direct", "ion216_polar_nopbc_direct", "water64_polar_direct", "ion216_triclinic_direct",
+                   "ion216_framework_direct", "ion1000_polar_direct"]
+DIRECT_SAMPLE_EVERY = 16  # ion1000_polar_direct keeps the per-atom results of every 16th atom (63 atoms)
+
+
+def keep_direct_golden(golden_dir: str) -> None:
+    """After `python oracle/make_golden.py <DIRECT_FIXTURES>`: the box text is dropped (the tests regenerate it with `materialize`, which
+    writes the same bytes the reference read); the 1000-atom box keeps its scalars and the per-atom rows of every DIRECT_SAMPLE_EVERY-th
+    atom (`sample_atoms` lists them), the small boxes keep everything."""
+    import json
+
+    for name in DIRECT_FIXTURES:
+        path = os.path.join(golden_dir, f"{name}.json")
+        with open(path) as f:
+            res = json.load(f)
+        n = res["natoms"]
+        if n > 500 and "sample_atoms" not in res:
+            idx = list(range(0, n, DIRECT_SAMPLE_EVERY))
+            for k, v in list(res.items()):
+                if k in ("ef_static", "mu", "ef_induced"):  # flat [n][3]
+                    res[k] = [v[3 * i + p] for i in idx for p in range(3)]
+                elif isinstance(v, list) and len(v) > 64:
+                    del res[k]
+            res["sample_atoms"] = idx
+        with open(path, "w") as f:
+            json.dump(res, f, separators=(",", ":"))
+            f.write("\n")
+        for ext in (".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -514,6 +550,9 @@ if __name__ == "__main__":
 
     if sys.argv[1:2] == ["--keep-three-body-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-direct-golden"]:
+        keep_direct_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)
