@@ -97,6 +97,10 @@ int main(int argc, char **argv) {
 				std::printf("direct dipole solve: %lld unknowns, status %lld, residual %.3e, factor %.1f MB\n", (long long)di.n_unknowns,
 				            (long long)di.status, di.residual, (double)di.factor_bytes / 1048576.0);
 		}
+		if (s.polarization && !s.rd_only && s.polar_palmo) { // the Palmo-Krimm correction that is part of "polar" below
+			double corr = 0;
+			if (mpmc_polar_palmo_info(s.context(), &corr, nullptr) == MPMC_OK) std::printf("polar_palmo: correction %.17g K\n", corr);
+		}
 		std::printf("{\"natoms\": %d, \"total\": %.17g, \"rd\": %.17g, \"es\": %.17g, \"polar\": %.17g, \"es_real\": %.17g, \"es_recip\": %.17g, "
 		            "\"es_self\": %.17g, \"three_body\": %.17g, \"n_lj_in_cutoff\": %lld, \"n_es_in_cutoff\": %lld, \"polar_iterations\": %d, \"mu0\": [%.17g, %.17g, %.17g]}\n",
 		            s.natoms, e, o->rd_energy, o->coulombic_energy, o->polarization_energy, s.last_result.es_real, s.last_result.es_recip,

@@ -289,6 +289,37 @@ typedef struct mpmc_direct_info {
 } mpmc_direct_info;
 int mpmc_polar_direct_info(mpmc_ctx *ctx, mpmc_direct_info *out);
 
+/* ---- `polar_wolf`: the static field as a Wolf sum, System::thole_field_wolf (src/System.Energy.cpp:3337-3396) -----------------------------
+ * With polarization on and rd_only off the setting replaces the static field whenever mpmc_options.polar_ewald is off (polar_ewald wins
+ * when both are set, thole_field :3289-3294); the iterative solvers and the direct solve read the new field.  The pairs are those of
+ * thole_field_nopbc (different molecules, not both frozen, r - 1e-12 < R, r != 0, R the cutoff of the box); such a pair adds
+ * q_j f(r) d / r to atom i and -q_i f(r) d / r to atom j with
+ *   a > 0:  f(r) = erfc(a r) / r^2 + 2 a / sqrt(pi) exp(-a^2 r^2) / r - [the same at r = R]          a = 0:  f(r) = 1 / r^2 - 1 / R^2
+ * f vanishes at r = R and follows every change of the box.  polar_wolf_alpha outside [0, 1] or non-finite is refused with
+ * MPMC_ERR_INVALID_SETTING (SimulationControl.cpp:2652-2660).  Both setters follow the lifetime of mpmc_set_axilrod_teller's switch: the
+ * setting survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates, accepted trials and capacity growth; enabled = 0
+ * restores the behaviour of a context that never called them, to the bit.  MPMC_FLAG_POLAR_WOLF and MPMC_FLAG_POLAR_PALMO (the keywords
+ * through mpmc_check_flags / mpmc_set_options) are still refused.  Trial moves of up to MPMC_TRIAL_MAX_ATOMS atoms keep the O(m N) path
+ * unless mpmc_options.wolf is on.  Time: MPMC_K_FIELD.
+ * Not supported, and refused by the input readers: `polar_wolf_full`, which changes every block of thole_amatrix (:2735-2757), and
+ * `polar_wolf_alpha_lookup`, a table indexed by (int)(r * 1000): a different function of r that would need the reference's rounding of r
+ * for every pair.
+ *
+ * ---- `polar_palmo`: the Palmo-Krimm correction (palmo_contraction :3602-3627, thole_iterative :3517-3519, polar() :2610-2618) ------------
+ * With polar_iterative on, one more contraction runs behind the solver's last iteration, with the final dipoles: F_i = -sum_{j != i}
+ * A_ij mu_j.  With E_ind,i = mu_i / alpha_i - E0_i, the induced field that iteration used (what mpmc_get_dipoles reports),
+ *   ef_induced_change_i = F_i - E_ind,i for polarizable atoms, 0 for the others,
+ *   polarization_energy = -1/2 sum mu . E0 - 1/2 sum mu . ef_induced_change;  energy and NU follow.
+ * Under Gauss-Seidel sweeps (polar_gs) the contraction runs (MPMC_K_DIPOLE_ITER, its reduce in MPMC_K_REDUCE).  Under Jacobi iterations the
+ * reference contracts the dipoles the last iteration read, so it subtracts from the induced field that very field, and under the direct
+ * solve ef_induced_change is never written: there its correction is zero to the last bit, no contraction runs here and the correction
+ * reported is exactly 0.  It is 0 too when iterator_failed is set (:3483-3488).
+ * mpmc_polar_palmo_info: the correction of the last evaluation with a dipole solve (already part of its polarization_energy) and the
+ * per-atom change, [n][3] in the caller's atom order. */
+int mpmc_set_polar_wolf(mpmc_ctx *ctx, int enabled, double polar_wolf_alpha);
+int mpmc_set_polar_palmo(mpmc_ctx *ctx, int enabled);
+int mpmc_polar_palmo_info(mpmc_ctx *ctx, double *energy_correction, double *ef_induced_change /*[n][3], may be NULL*/);
+
 /* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL */
 int mpmc_get_dipoles(mpmc_ctx *ctx, double *mu, double *ef_static, double *ef_induced /* each [n][3] */);
 /* pairs() tail: update_com + wrap_all (src/System.cpp:1347-1425).  Host-side O(N); needs mass in set_atoms.

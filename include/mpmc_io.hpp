@@ -123,8 +123,8 @@ inline std::string read_input(const std::string &path, System &s) {
 	static const std::map<std::string, uint64_t> unsupported = {
 	    {"rd_crystal", MPMC_FLAG_RD_CRYSTAL}, {"spectre", MPMC_FLAG_SPECTRE},
 	    {"gwp", MPMC_FLAG_GWP}, {"sg", MPMC_FLAG_USE_SG}, {"polarvdw", MPMC_FLAG_POLARVDW}, {"cdvdw", MPMC_FLAG_POLARVDW},
-	    {"polar_ewald_full", MPMC_FLAG_POLAR_EWALD_FULL}, {"polar_wolf", MPMC_FLAG_POLAR_WOLF}, {"polar_wolf_full", MPMC_FLAG_POLAR_WOLF},
-	    {"polar_palmo", MPMC_FLAG_POLAR_PALMO}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED}, {"polar_sor", MPMC_FLAG_POLAR_SOR},
+	    {"polar_ewald_full", MPMC_FLAG_POLAR_EWALD_FULL}, {"polar_wolf_full", MPMC_FLAG_POLAR_WOLF},
+	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED}, {"polar_sor", MPMC_FLAG_POLAR_SOR},
 	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"waldmanhagler", MPMC_FLAG_NON_LB_MIXING},
 	    {"halgren_mixing", MPMC_FLAG_NON_LB_MIXING}, {"c6_mixing", MPMC_FLAG_NON_LB_MIXING}, {"dreiding", MPMC_FLAG_OTHER_RD},
 	    {"lj_buffered_14_7", MPMC_FLAG_OTHER_RD}, {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
@@ -165,6 +165,9 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "damp_dispersion") { need(1); s.damp_dispersion = onoff(t[1]); }
 		else if (k == "extrapolate_disp_coeffs") { need(1); s.extrapolate_disp_coeffs = onoff(t[1]); }
 		else if (k == "schmidt_ff") { need(1); s.schmidt_ff = onoff(t[1]); }
+		else if (k == "polar_wolf") { need(1); s.polar_wolf = onoff(t[1]); }
+		else if (k == "polar_palmo") { need(1); s.polar_palmo = onoff(t[1]); }
+		else if (k == "polar_wolf_alpha" || k == "polar_wolf_damp") { need(1); s.polar_wolf_alpha = dval(1); } // (two names of one setting, SimulationControl.cpp:751-759)
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
 		else if (k == "polar_max_iter") { need(1); s.polar_max_iter = (int)dval(1); }

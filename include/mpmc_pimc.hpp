@@ -154,6 +154,7 @@ public:
 			if (s->atoms.size() != a.size()) throw 9000; // internal_error: images are not consistent (:1427)
 			if (uses_three_body(*s, 0)) throw 4004;     // unsupported_setting: the three-body term is not part of this driver (yet)
 			if (uses_disp_expansion(*s, 0)) throw 4004; // unsupported_setting: nor is the disp-expansion term
+			if (uses_polar_wolf_or_palmo(*s, 0)) throw 4004; // unsupported_setting: nor are polar_wolf / polar_palmo
 			s->temperature = cfg.temperature;
 		}
 		pi.systems = systems;

@@ -65,6 +65,11 @@ template <class T>
 auto uses_disp_expansion(const T &s, int) -> decltype(bool(s.using_disp_expansion)) { return s.using_disp_expansion; }
 template <class T>
 bool uses_disp_expansion(const T &, long) { return false; }
+// the same for the Wolf static field and the Palmo-Krimm correction
+template <class T>
+auto uses_polar_wolf_or_palmo(const T &s, int) -> decltype(bool(s.polar_wolf || s.polar_palmo)) { return s.polar_wolf || s.polar_palmo; }
+template <class T>
+bool uses_polar_wolf_or_palmo(const T &, long) { return false; }
 
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
@@ -91,6 +96,8 @@ public:
 	int midzuno_kihara_approx = 0;     // its c9 from c6, src/System.h:655
 	bool using_disp_expansion = false; // disp-expansion repulsion/dispersion in place of lj() (mpmc_set_disp_expansion), src/System.h:661
 	int damp_dispersion = 0, extrapolate_disp_coeffs = 0, schmidt_ff = 0; // its switches, src/System.h:649-656
+	int polar_wolf = 0, polar_palmo = 0; // Wolf static field (mpmc_set_polar_wolf), Palmo-Krimm correction (mpmc_set_polar_palmo), src/System.h:685-694
+	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
 	double ewald_alpha = 0.5, polar_ewald_alpha = 0.5;
@@ -284,6 +291,8 @@ private:
 	int three_body_mk_ = 0;
 	bool disp_on_ = false; // what the context's disp-expansion setting is (sync_state)
 	int disp_flags_ = 0;
+	int polar_wolf_on_ = 0, polar_palmo_on_ = 0; // what the context's Wolf-field / Palmo settings are (sync_state)
+	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
 	mpmc_result trial_result_{};
@@ -303,6 +312,8 @@ private:
 			capacity_ = n + n / 4 + 64;
 			check(mpmc_ctx_create(device, capacity_, &ctx_), "mpmc_ctx_create");
 			atoms_dirty_ = box_dirty_ = true;
+			polar_wolf_on_ = polar_palmo_on_ = 0; // (a new context starts with both off)
+			polar_wolf_alpha_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -369,6 +380,16 @@ private:
 			check(mpmc_set_disp_expansion(ctx_, using_disp_expansion ? 1 : 0, dflags, c6.data(), c8.data(), c10.data()), "mpmc_set_disp_expansion");
 			disp_on_ = using_disp_expansion;
 			disp_flags_ = dflags;
+		}
+		// the Wolf static field and the Palmo-Krimm correction: switches of the context that outlive atom lists, set when they change
+		if ((polar_wolf != 0) != (polar_wolf_on_ != 0) || (polar_wolf && polar_wolf_alpha != polar_wolf_alpha_)) {
+			check(mpmc_set_polar_wolf(ctx_, polar_wolf ? 1 : 0, polar_wolf_alpha), "mpmc_set_polar_wolf");
+			polar_wolf_on_ = polar_wolf ? 1 : 0;
+			polar_wolf_alpha_ = polar_wolf_alpha;
+		}
+		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
+			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");
+			polar_palmo_on_ = polar_palmo ? 1 : 0;
 		}
 	}
 

@@ -212,7 +212,7 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	                c->d_flag, c->d_counter, c->d_kvec, c->d_kw, c->d_sf, c->d_w_en, c->d_e_recip_part, c->d_part, c->d_e_static, c->d_mu[0], c->d_mu[1],
 	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_chol, c->d_chol_v, c->d_chol_info, c->d_chol_list, c->d_chol_status, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
 	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part,
-	                c->d_de_co, c->d_de_t10, c->d_de_part};
+	                c->d_de_co, c->d_de_t10, c->d_de_part, c->d_palmo_f, c->d_palmo_change};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (c->h_stage) (void)pinned_free(c->h_stage);
@@ -622,6 +622,9 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	f->tb_mk = c->tb_mk;
 	f->de_enabled = c->de_enabled; // (the disp-expansion setting likewise)
 	f->de_flags = c->de_flags;
+	f->pw_enabled = c->pw_enabled; // (so do the Wolf static field and the Palmo-Krimm correction)
+	f->pw_alpha = c->pw_alpha;
+	f->palmo_enabled = c->palmo_enabled;
 	std::swap(*c, *f);
 	mpmc_ctx_destroy(f); // now owns the old, smaller buffers
 	return MPMC_OK;
@@ -738,6 +741,29 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->de_have = c->de_dirty = c->de_lrc_valid = false; // so do the disp-expansion coefficients (mpmc_set_disp_expansion again)
 	c->h_de.clear();
 	c->h_de_raw.clear();
+	return MPMC_OK;
+}
+
+// ---- `polar_wolf` / `polar_palmo` ------------------------------------------------------------------------------------------------------
+extern "C" int mpmc_set_polar_wolf(mpmc_ctx *c, int enabled, double polar_wolf_alpha) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_wolf: an evaluation or a trial move is open");
+	if (enabled && (!std::isfinite(polar_wolf_alpha) || polar_wolf_alpha < 0.0 || polar_wolf_alpha > 1.0)) // SimulationControl.cpp:2652-2660
+		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_wolf: polar_wolf_alpha must be in [0, 1]");
+	const bool on = enabled != 0;
+	if (on != c->pw_enabled || (on && polar_wolf_alpha != c->pw_alpha)) {
+		c->cache_valid = false; // (the accepted totals and the resident real-space field belong to the other static field)
+		c->e_real_valid = false;
+	}
+	c->pw_enabled = on;
+	c->pw_alpha = on ? polar_wolf_alpha : 0.0;
+	return MPMC_OK;
+}
+extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_palmo: an evaluation or a trial move is open");
+	if ((enabled != 0) != c->palmo_enabled) c->cache_valid = false; // (the accepted totals carry the correction)
+	c->palmo_enabled = enabled != 0;
 	return MPMC_OK;
 }
 

@@ -307,6 +307,15 @@ struct mpmc_ctx {
 	double *d_de_t10 = nullptr; // [max_pad]
 	double *d_de_part = nullptr; // [kDispBlocks] per-workgroup partials
 
+	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip): kept across mpmc_set_atoms, mpmc_set_box,
+	// mpmc_set_options and capacity growth
+	bool pw_enabled = false;
+	double pw_alpha = 0.0;
+	bool palmo_enabled = false;
+	bool palmo_ran = false;          // the pending / last evaluation did the extra contraction (Gauss-Seidel sweeps that did not fail)
+	double palmo_correction = 0.0;   // of the last evaluation with a dipole solve (wait_and_fill)
+	double *d_palmo_f = nullptr, *d_palmo_change = nullptr; // [max_pad][3]: -(A_off mu) of the final dipoles; ef_induced_change
+
 	// profiling
 	bool prof = false;
 	std::vector<EvPair> ev_free, ev_used;
@@ -478,6 +487,8 @@ int enqueue(mpmc_ctx *c, unsigned mask);         // one evaluation (the pieces i
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options
 inline bool direct_solve(const mpmc_ctx *c) { return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative; } // `polar_iterative off`
+// `polar_wolf` replaces the static field whenever polar_ewald is off (thole_field :3289-3294: polar_ewald wins)
+inline bool wolf_field_on(const mpmc_ctx *c) { return c->pw_enabled && c->opts.polarization && !c->opts.rd_only && !c->opts.polar_ewald; }
 void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Feynman-Hibbs fields of the pair parameters (evaluate.cpp)
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);

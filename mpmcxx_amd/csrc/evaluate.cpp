@@ -106,6 +106,8 @@ static int ensure_polar_buffers(mpmc_ctx *c) {
 		if ((rc = dev_alloc(c, &c->d_e_real, 3 * np)) != MPMC_OK) return rc;
 		if ((rc = dev_alloc(c, &c->d_e_real_trial, 3 * np)) != MPMC_OK) return rc;
 		if ((rc = dev_alloc(c, &c->d_gs_ul, 6 * np)) != MPMC_OK) return rc; // Gauss-Seidel sweeps: fields of the tiles above / below
+		if ((rc = dev_alloc(c, &c->d_palmo_f, 3 * np)) != MPMC_OK) return rc;
+		if ((rc = dev_alloc(c, &c->d_palmo_change, 3 * np)) != MPMC_OK) return rc;
 		// (dev_alloc zero-fills on the context's stream; nothing in this library touches the null stream, which is unordered against
 		// our non-blocking streams)
 	}
@@ -346,6 +348,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	c->run_mask = mask;
 	c->have_polar = false;
 	c->direct_ran = false;
+	c->palmo_ran = false;
 	c->iters = 0;
 	c->failed = 0;
 
@@ -446,7 +449,8 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		fp.polar_damp = o.polar_damp;
 		fp.rd_lrc = o.rd_lrc;
 		fp.do_es = ((mask & RUN_PAIR_ES) || (mask & RUN_FIELD)) ? 1 : 0;
-		fp.do_field = (mask & RUN_FIELD) ? (o.polar_ewald ? 1 : 2) : 0;
+		// (`polar_wolf`: the field is k_wolf_field's, below; the sweep keeps its energies and the tensor store)
+		fp.do_field = ((mask & RUN_FIELD) && !wolf_field_on(c)) ? (o.polar_ewald ? 1 : 2) : 0;
 		fp.do_thole = compact ? 1 : 0;
 		ext_params(c, fp, (o.wolf && (mask & RUN_WOLF)) != 0);
 		fp.thole_far_x = kTholeFarX;
@@ -542,6 +546,8 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	if (mask & RUN_FIELD) {
 		ProfScope p(c, MPMC_K_FIELD);
 		c->mu_cur = 0;
+		if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
+			launch_wolf_field(st, at, c->box, wolf_field_params(c->pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
 		launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
 		                      c->d_mu[0], c->d_e_real);
 		c->e_real_valid = (mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
@@ -685,6 +691,24 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 				launch_polar_energy_and_pairs(st, at, c->d_mu[c->mu_cur], c->d_e_static, want_rrms ? c->d_rrms : nullptr, c->d_block_part, c->d_block_cnt,
 				                              c->n_tile_pairs, c->d_scal, c->d_cnt);
 			else launch_polar_energy(st, at, c->d_mu[c->mu_cur], c->d_e_static, want_rrms ? c->d_rrms : nullptr, c->d_scal);
+		}
+		// `polar_palmo` (:3517-3519, palmo_contraction :3602-3627): one more contraction with the final dipoles.  Under Jacobi the reference
+		// contracts the dipoles the last iteration read (mu is overwritten with new_mu only afterwards, :3526-3536), so it subtracts from the
+		// induced field that very field: zero to the bit, and nothing runs here.  Under Gauss-Seidel sweeps the dipoles are the swept ones:
+		// F = -(A_off mu) through the matrix-free Jacobi contraction (Gauss-Seidel contexts store nothing), against the induced field the
+		// last sweep used.  A failed iteration leaves the correction at 0 (:3483-3488).
+		if (c->palmo_enabled && o.polar_gs && !c->failed) {
+			double *mu = c->d_mu[c->mu_cur];
+			{
+				ProfScope p(c, MPMC_K_DIPOLE_ITER);
+				launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift,
+				                          c->n_tile_pairs, nullptr, c->d_part, o.polar_damp, nullptr);
+			}
+			ProfScope p(c, MPMC_K_REDUCE);
+			// (the slots summed by the update kernel: d_palmo_f = F; its new dipoles go to the spare vector and are dropped, rrms untouched)
+			launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, c->d_mu[1 - c->mu_cur], c->d_palmo_f, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
+			launch_palmo_reduce(st, at, mu, c->d_palmo_f, c->d_e_induced, c->d_palmo_change, c->d_scal);
+			c->palmo_ran = true;
 		}
 		c->have_polar = true;
 	}
@@ -873,6 +897,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	out->es_self = (c->run_mask & RUN_RECIP) ? c->h_static[2] : 0.0;
 	out->coulombic_energy = (out->es_real + out->es_recip) + out->es_self; // coulombic() :1412
 	out->polarization_energy = s[S_POLAR];
+	if (c->run_mask & RUN_SOLVE) c->palmo_correction = c->palmo_ran ? s[S_PALMO] : 0.0;
 	out->dipole_rrms = s[S_RRMS];
 	out->three_body_energy = (c->run_mask & RUN_THREE_BODY) ? s[S_THREE_BODY] : 0.0;
 	out->energy = out->rd_energy + out->coulombic_energy + out->polarization_energy + out->vdw_energy + out->three_body_energy; // :136
@@ -1040,6 +1065,21 @@ extern "C" int mpmc_polar_direct_info(mpmc_ctx *c, mpmc_direct_info *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_direct_info: an evaluation is in flight");
 	*out = c->direct;
+	return MPMC_OK;
+}
+
+// the Palmo-Krimm correction of the last evaluation with a dipole solve and its per-atom ef_induced_change (zeros where no contraction ran)
+extern "C" int mpmc_polar_palmo_info(mpmc_ctx *c, double *energy_correction, double *ef_induced_change) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_palmo_info: an evaluation is in flight");
+	if (energy_correction) *energy_correction = c->palmo_correction;
+	if (ef_induced_change) {
+		if (c->palmo_ran && c->d_palmo_change) {
+			HIP_TRY(c, hipSetDevice(c->device));
+			return fetch_atoms3(c, c->d_palmo_change, ef_induced_change);
+		}
+		std::fill(ef_induced_change, ef_induced_change + 3 * (size_t)c->n, 0.0);
+	}
 	return MPMC_OK;
 }
 

@@ -43,6 +43,7 @@ enum : int {
 	S_POLAR, S_RRMS,                             // polarization
 	S_THREE_BODY,                                // Axilrod-Teller (kernels_three_body.hip)
 	S_DISP, S_DISP_LRC_PAIR, S_DISP_LRC_SELF,    // disp-expansion pair sum and its two long-range corrections (kernels_disp.hip)
+	S_PALMO,                                     // Palmo-Krimm correction, already part of S_POLAR (kernels_wolf_field.hip)
 	S_COUNT = 16
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
@@ -308,6 +309,24 @@ void launch_disp_expansion(hipStream_t st, const AtomsDev &at, const double4 *co
 // kernels (marked and cleared again inside)
 void launch_disp_expansion_delta(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const Box &bx, const DispParams &dp,
                                  const int *mv_slot, const double4 *mv_new, int m, int *moved_idx, double *part, double *out);
+
+// ---- `polar_wolf`: the Wolf static field, and the reduce of `polar_palmo` (kernels_wolf_field.hip) --------------------------------------
+struct WolfFieldParams {
+	double a;           // polar_wolf_alpha
+	double c_gauss;     // 2 a / sqrt(pi)
+	double cutoff_term; // a > 0: erfc(a R) / R^2 + 2 a / sqrt(pi) exp(-a^2 R^2) / R;  a = 0: 1 / R^2
+};
+WolfFieldParams wolf_field_params(double polar_wolf_alpha, double cutoff); // (host; follows every change of the cutoff: made per launch)
+// the whole field into the real-space slots fpart[nt][n_pad][3] that launch_field_finalize adds up (polar_ewald = 0); cls: this
+// evaluation's tile-pair classes
+void launch_wolf_field(hipStream_t st, const AtomsDev &at, const Box &bx, const WolfFieldParams &wp, const int2 *tile_pairs, const int *cls,
+                       int n_tile_pairs, double *fpart);
+// trial moves: e_real_trial = e_real + (field of the pairs with a moved atom, new minus old geometry); dk_part: scratch [n_tiles][m][3];
+// moved_idx: the all -1 slot map of the delta kernels (marked and cleared again inside)
+void launch_wolf_field_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const WolfFieldParams &wp, const int *mv_slot, const double4 *mv_new, int m,
+                             int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part);
+// change = f_new - e_induced for polarizable atoms, 0 for the others; scal[S_PALMO] = -1/2 sum mu . change, added to scal[S_POLAR]
+void launch_palmo_reduce(hipStream_t st, const AtomsDev &at, const double *mu, const double *f_new, const double *e_induced, double *change, double *scal);
 
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);

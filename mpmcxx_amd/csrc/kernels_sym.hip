@@ -409,8 +409,10 @@ static void launch_fused_o(hipStream_t st, const AtomsDev &at, const Box &bx, co
 		launch_fused_t<ORTHO, false, 0, true>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);
 	else if (!fp.do_es)
 		launch_fused_t<ORTHO, false, 0, false>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);
-	else if (fp.do_field == 0)
-		launch_fused_t<ORTHO, true, 0, false>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);
+	else if (fp.do_field == 0) {
+		if (thole) launch_fused_t<ORTHO, true, 0, true>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list); // (`polar_wolf`: the field is k_wolf_field's)
+		else launch_fused_t<ORTHO, true, 0, false>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);
+	}
 	else if (fp.do_field == 1) {
 		if (thole) launch_fused_t<ORTHO, true, 1, true>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);
 		else launch_fused_t<ORTHO, true, 1, false>(st, at, bx, fp, tp, cls, ntp, bpart, bcnt, fpart, ab, tp_list);

@@ -164,8 +164,12 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		const AtomsDev at = atoms_view(c);
 		{
 			ProfScope p(c, MPMC_K_FIELD);
-			launch_delta_field(st, at, c->box, c->polar_ewald_alpha, o.polar_ewald, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
-			                   c->d_e_real_trial, c->d_dk_part);
+			if (wolf_field_on(c)) // (`polar_wolf`: the same O(m N) difference of thole_field_wolf's pair sum)
+				launch_wolf_field_delta(st, at, c->box, wolf_field_params(c->pw_alpha, c->box.cutoff), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
+				                        c->d_e_real_trial, c->d_dk_part);
+			else
+				launch_delta_field(st, at, c->box, c->polar_ewald_alpha, o.polar_ewald, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
+				                   c->d_e_real_trial, c->d_dk_part);
 			// from here on the resident positions are the TRIAL ones (the old ones wait in d_mv_new: reject swaps them back)
 			launch_swap_positions(st, c->d_xyzq, c->d_mv_slot, c->d_mv_new, m);
 			if (o.polar_ewald) {

@@ -141,6 +141,10 @@ def lib():
     L.mpmc_memory_usage.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "mpmc_polar_direct_info") or not os.environ.get("MPMC_ENERGY_LIB"):
         L.mpmc_polar_direct_info.argtypes = [vp, C.POINTER(DirectInfo)]
+    if hasattr(L, "mpmc_set_polar_wolf") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the Wolf static field and the Palmo-Krimm correction)
+        L.mpmc_set_polar_wolf.argtypes = [vp, C.c_int, C.c_double]
+        L.mpmc_set_polar_palmo.argtypes = [vp, C.c_int]
+        L.mpmc_polar_palmo_info.argtypes = [vp, dp, dp]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -318,6 +322,13 @@ class System:
         self._opts = make_options(options)
         self._check(self._L.mpmc_set_options(self._h, C.byref(self._opts)))
         self.options = dict(options)
+        # `polar_wolf` / `polar_palmo` are switches of their own in the library and follow the options here (only when some options named them:
+        # a library of before this term, named by MPMC_ENERGY_LIB, is never asked)
+        if "polar_wolf" in options or "polar_palmo" in options or getattr(self, "_polar_wolf_set", False):
+            self._polar_wolf_set = True
+            alpha = options.get("polar_wolf_alpha")
+            self.set_polar_wolf(bool(options.get("polar_wolf")), 0.0 if alpha is None else float(alpha))
+            self.set_polar_palmo(bool(options.get("polar_palmo")))
 
     def set_atoms(self, atoms: Dict[str, np.ndarray]):
         f = lambda k: np.ascontiguousarray(atoms[k], dtype=np.float64)
@@ -352,6 +363,23 @@ class System:
         a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (c6, c8, c10)]
         flags = (DISP_DAMP if damp else 0) | (DISP_EXTRAPOLATE_C10 if extrapolate_c10 else 0) | (DISP_SCHMIDT if schmidt else 0)
         self._check(self._L.mpmc_set_disp_expansion(self._h, int(bool(enabled)), flags, _dp(a[0]), _dp(a[1]), _dp(a[2])))
+
+    def set_polar_wolf(self, enabled: bool, polar_wolf_alpha: float = 0.0):
+        """`polar_wolf`: the static field of the dipole solve as a Wolf sum with damping parameter polar_wolf_alpha in [0, 1]
+        (mpmc_set_polar_wolf); it applies whenever polar_ewald is off."""
+        self._check(self._L.mpmc_set_polar_wolf(self._h, int(bool(enabled)), float(polar_wolf_alpha)))
+
+    def set_polar_palmo(self, enabled: bool):
+        """`polar_palmo`: the Palmo-Krimm correction to the polarization energy (mpmc_set_polar_palmo)"""
+        self._check(self._L.mpmc_set_polar_palmo(self._h, int(bool(enabled))))
+
+    def palmo_info(self):
+        """(correction, ef_induced_change[n][3]) of the last evaluation with a dipole solve (mpmc_polar_palmo_info); the correction is
+        already part of polarization_energy, and exactly 0 under Jacobi iterations and under the direct solve."""
+        v = C.c_double(0.0)
+        d = np.zeros((self.n, 3))
+        self._check(self._L.mpmc_polar_palmo_info(self._h, C.byref(v), _dp(d)))
+        return v.value, d
 
     def set_axilrod_teller(self, enabled: bool, c6: Optional[np.ndarray] = None, c9: Optional[np.ndarray] = None,
                            midzuno_kihara_approx: bool = False):

@@ -329,6 +329,8 @@ def fixture(name: str):
     if name in DIRECT_FIXTURES:  # the same boxes with the dipoles by matrix inversion (the reference's default, `polar_iterative off`)
         rows, basis, o = fixture(name[:-len("_direct")])
         return rows, basis, dict(o, polar_iterative="off")
+    if name in WOLF_FIXTURES:
+        return _wolf_fixture(name)
     if name in THREE_BODY_FIXTURES:
         return _three_body_fixture(name)
     if name in DISP_FIXTURES:
@@ -515,6 +517,111 @@ def keep_direct_golden(golden_dir: str) -> None:
                 os.remove(os.path.join(golden_dir, name + ext))
 
 
+# ---- `polar_wolf` / `polar_palmo` (reference src/System.Energy.cpp:3337-3396, 3602-3627) ------------------------------------------------------
+# NAME = BASE_pw_VARIANT: the box BASE with polar_ewald off and the Wolf static field (polar_wolf_alpha 0.13), solved as VARIANT says
+WOLF_VARIANTS = {
+    "jac": {},                                                                            # Jacobi, 10 iterations
+    "gs": {"polar_gs": "on", "polar_max_iter": 4},                                        # Gauss-Seidel, 4 sweeps
+    "gsp": {"polar_gs": "on", "polar_max_iter": 4, "polar_palmo": "on"},                  # ... + Palmo-Krimm
+    "gspg": {"polar_gs": "on", "polar_max_iter": 4, "polar_palmo": "on", "polar_gamma": 1.03},
+    "direct": {"polar_iterative": "off"},                                                 # matrix inversion
+    "gspp": {"polar_gs": "on", "polar_palmo": "on", "polar_precision": 1e-7, "polar_max_iter": None},  # sweeps until converged
+    "jacp": {"polar_palmo": "on"},                                                        # Jacobi + Palmo-Krimm: the correction is zero to the bit
+    "directp": {"polar_iterative": "off", "polar_palmo": "on"},                           # likewise under matrix inversion
+}
+WOLF_BASES = ["ion216_polar", "water64_polar", "ion216_framework", "ion216_triclinic"]
+WOLF_FIXTURES = [f"{b}_pw_{v}" for b in WOLF_BASES for v in ("jac", "gs", "gsp", "gspg", "direct", "gspp")] + [
+    "ion216_polar_pw_jacp", "ion216_polar_pw_directp",
+    "ion216_polar_pw0_jac",    # polar_wolf_alpha 0: the undamped branch (:3379-3382)
+    "ion216_polar_pw0_gsp",
+    "ion216_polar_pwewald_gsp",  # polar_ewald on as well: Ewald wins (:3289-3294), Palmo-Krimm on an Ewald field
+    "ion216_frozen_pw_gsp",
+    "ion1000_gs_pw_gsp",       # 16 tiles: the blocked sweep, then the contraction
+    "ion4000_pw1_gsp",         # polar_wolf_alpha 1 at a cutoff of 32 A: a R = 32, erfc and the Gaussian underflow for most pairs
+]
+WOLF_SAMPLE_EVERY = 16  # boxes of more than 216 atoms keep the per-atom results of every 16th atom
+
+
+def _wolf_fixture(name: str):
+    base, variant = name.rsplit("_", 1)
+    o_extra = dict(WOLF_VARIANTS[variant])
+    if base == "ion4000_pw1":
+        rows, basis, o = lattice_box(4000, 64.0, 17), cubic(64.0), dict(POLAR_OPTS)
+        kind = "pw1"
+    else:
+        box, kind = base.rsplit("_", 1)
+        rows, basis, o = fixture(box)
+        o = dict(o)
+    o["polar_gs"] = "off"  # (ion1000_gs brings its own; the variant decides)
+    o["polar_max_iter"] = 10
+    o["polar_ewald"] = "on" if kind == "pwewald" else "off"
+    o["polar_wolf"] = "on"
+    o["polar_wolf_alpha"] = {"pw": 0.13, "pwewald": 0.13, "pw0": 0.0, "pw1": 1.0}[kind]
+    for k, v in o_extra.items():
+        if v is None:
+            o.pop(k, None)
+        else:
+            o[k] = v
+    return rows, basis, o
+
+
+WOLF_GOLDEN = ("polar_wolf.json", "polar_wolf_atoms.npz")  # under tests/golden/: every fixture's scalars; the per-atom arrays, each once
+
+
+def keep_wolf_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <WOLF_FIXTURES>`: the per-fixture files are folded into WOLF_GOLDEN and removed, the box text
+    too (the tests regenerate it with `materialize`, which writes the same bytes the reference read).  polar_wolf.json holds every
+    fixture's scalars and cell; polar_wolf_atoms.npz holds ef_static, mu and ef_induced as float64 -- of every atom for boxes of up to
+    216 atoms, of every WOLF_SAMPLE_EVERY-th atom for larger ones -- with nothing lost (the harness prints %.17g) and each distinct
+    array stored once: the variants of one box share its static field, and Palmo-Krimm leaves the dipoles alone.  A fixture's "arrays"
+    entry names the key of each of its arrays; an ef_induced of zeros (the direct path never writes it) is left out."""
+    import json
+
+    import numpy as np
+
+    scalars, arrays, by_bytes = {}, {}, {}
+    for name in (names or WOLF_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        n = res["natoms"]
+        every = WOLF_SAMPLE_EVERY if n > 216 else 1
+        out = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+        out["sample_every"] = every
+        out["arrays"] = {}
+        for k in ("ef_static", "mu", "ef_induced"):
+            a = np.asarray(res[k], dtype=np.float64).reshape(-1, 3)
+            a = a[::every] if a.shape[0] == n else a  # (a file that an earlier pass has already cut down to the sample)
+            if k == "ef_induced" and not a.any():
+                continue
+            key = by_bytes.setdefault(a.tobytes(), f"{name}.{k}")
+            arrays.setdefault(key, a)
+            out["arrays"][k] = key
+        scalars[name] = out
+    with open(os.path.join(golden_dir, WOLF_GOLDEN[0]), "w") as f:
+        json.dump(scalars, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    np.savez_compressed(os.path.join(golden_dir, WOLF_GOLDEN[1]), **arrays)
+    for name in (names or WOLF_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def wolf_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    """one fixture of WOLF_GOLDEN as make_golden wrote it: scalars, `sample_atoms`, and ef_static / mu / ef_induced as [k, 3] arrays"""
+    import json
+
+    import numpy as np
+
+    with open(os.path.join(golden_dir, WOLF_GOLDEN[0])) as f:
+        g = json.load(f)[name]
+    with np.load(os.path.join(golden_dir, WOLF_GOLDEN[1])) as z:
+        for k, key in g.pop("arrays").items():
+            g[k] = z[key]
+    g["sample_atoms"] = list(range(0, g["natoms"], g.pop("sample_every")))
+    return g
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -553,6 +660,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-direct-golden"]:
         keep_direct_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-wolf-golden"]:
+        keep_wolf_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)
