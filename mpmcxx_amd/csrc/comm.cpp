@@ -426,7 +426,7 @@ static void destroy_auto_comms() {
 // Test hook: a context configured with "virtual_device" = v >= 0 counts as living on device -(1 + v): a one-GPU box then drives the
 // thread-per-device path for real (worker hand-off, per-thread evaluation, ordered combine) -- tools/host_tsan.sh, tests/test_gpu_comm.py --
 // with a host copy in RCCL's place (RCCL admits one rank per physical device).
-static int device_key(const mpmc_ctx *c) { return c->tune.virtual_device >= 0 ? -(1 + c->tune.virtual_device) : c->device; }
+static int device_key(const mpmc_ctx *c) { return c->kept.tune.virtual_device >= 0 ? -(1 + c->kept.tune.virtual_device) : c->device; }
 static void group_beads(mpmc_ctx **beads, int n_beads, std::vector<int> &devs, std::vector<int> &dev_of, std::vector<int> &slot_of,
                         std::vector<std::vector<int>> &members) {
 	dev_of.assign(n_beads, 0);

@@ -111,13 +111,18 @@ static double bisect_threshold(double rc, Pred pred) {
 static std::atomic<int> g_rot_ok[64];
 static int rot_selftest(mpmc_ctx *c) {
 	if (c->device < 64 && g_rot_ok[c->device].load(std::memory_order_acquire)) return MPMC_OK;
-	int *d = nullptr, h[64];
-	HIP_TRY(c, hipMalloc((void **)&d, 64 * sizeof(int)));
-	launch_rot_selftest(c->stream, d);
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	(void)hipFree(d);
+	DevBuf<int> d; // scratch
+	int h[64], rc = d.reserve(c, 64);
+	if (rc != MPMC_OK) return rc;
+	rc = [&] {
+		launch_rot_selftest(c->stream, d);
+		HIP_TRY(c, hipGetLastError());
+		HIP_TRY(c, hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream));
+		return (int)MPMC_OK;
+	}();
+	d.release(c); // on every way out: the context's byte count never keeps the scratch
+	if (rc != MPMC_OK) return rc;
 	for (int l = 0; l < 64; l++)
 		if (h[l] != ((l + 1) & 63)) {
 			c->err = "lane-rotation self-test failed (v_mov_b32_dpp wave_rol:1): not a gfx950 device?";
@@ -151,29 +156,29 @@ extern "C" int mpmc_ctx_create(int device, int max_atoms, mpmc_ctx **out) {
 	auto A = [&](int r) { if (rc == MPMC_OK) rc = r; };
 	{
 		std::lock_guard<std::mutex> lk(g_tuning_mu);
-		c->tune = g_tuning_default;
+		c->kept.tune = g_tuning_default;
 	}
 	if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-	    (!c->tune.lazy_side_stream && hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) ||
+	    (!c->kept.tune.lazy_side_stream && hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) ||
 	    hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
 	    hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
 		delete c;
 		return fail(nullptr, MPMC_ERR_HIP, "mpmc_ctx_create: hipStreamCreate failed");
 	}
-	c->two_streams = (c->tune.stream_mode != 0);
+	c->two_streams = (c->kept.tune.stream_mode != 0);
 	const size_t P = (size_t)c->max_pad;
-	A(dev_alloc(c, &c->d_atoms_blob, P * kAtomRecordBytes)); // every per-atom array, one block (layout: atom_block_layout)
+	A(c->d_atoms_blob.reserve(c, P * kAtomRecordBytes)); // every per-atom array, one block (layout: atom_block_layout)
 	if (rc == MPMC_OK)
 		atom_block_layout(c->d_atoms_blob, P, [c](double4 *xyzq, double2 *lj, int2 *mf, double *al, double *ep, double *imm, int32_t *perm, int32_t *slot) {
 			c->d_xyzq = xyzq, c->d_lj = lj, c->d_mf = mf, c->d_alpha = al, c->d_eps = ep, c->d_inv_molmass = imm, c->d_perm = perm, c->d_slot_of = slot;
 		});
-	A(dev_alloc(c, &c->d_tile_bounds, 12 * (P / kTile)));
-	A(dev_alloc(c, &c->d_scal, (size_t)S_COUNT + (size_t)C_COUNT)); // scalars and counts share one buffer: one clear, one read-back
+	A(c->d_tile_bounds.reserve(c, 12 * (P / kTile)));
+	A(c->d_scal.reserve(c, (size_t)S_COUNT + (size_t)C_COUNT)); // scalars and counts share one buffer: one clear, one read-back
 	if (rc == MPMC_OK) c->d_cnt = reinterpret_cast<long long *>(c->d_scal + S_COUNT);
-	A(dev_alloc(c, &c->d_flag, (size_t)4)); // [0]: Gauss-Seidel's per-sweep flag; [1..3]: iteration control of the precision-terminated Jacobi solve
-	A(dev_alloc(c, &c->d_counter, (size_t)1));
-	A(dev_alloc(c, &c->d_atom_part, kAtomTermScratch));
-	A(dev_alloc(c, &c->d_erf_tab, (size_t)kErfTableDouble2));
+	A(c->d_flag.reserve(c, 4)); // [0]: Gauss-Seidel's per-sweep flag; [1..3]: iteration control of the precision-terminated Jacobi solve
+	A(c->d_counter.reserve(c, 1));
+	A(c->d_atom_part.reserve(c, kAtomTermScratch));
+	A(c->d_erf_tab.reserve(c, kErfTableDouble2));
 	if (rc == MPMC_OK) { // the erfc table of the pair sweep: 24 KB, once per context
 		std::vector<double2> tab(kErfTableDouble2);
 		erfc_table_device_layout(tab.data());
@@ -182,12 +187,12 @@ extern "C" int mpmc_ctx_create(int device, int max_atoms, mpmc_ctx **out) {
 			rc = MPMC_ERR_HIP;
 	}
 	static_assert(sizeof(long long) == sizeof(double), "scalars and counts share one buffer");
-	if (rc == MPMC_OK && pinned_alloc(&c->h_scal, (S_COUNT + C_COUNT + 1) * sizeof(double)) != hipSuccess) rc = MPMC_ERR_HIP;
+	A(c->h_scal.reserve(c, S_COUNT + C_COUNT + 1));
 	if (rc == MPMC_OK) {
 		c->h_cnt = reinterpret_cast<long long *>(c->h_scal + S_COUNT);
 		std::memset(c->h_scal, 0, (S_COUNT + C_COUNT + 1) * sizeof(double)); // (the launch-number slot the waits poll starts at 0: a recycled pinned block may hold an old context's 1.0)
 	}
-	if (rc == MPMC_OK && pinned_alloc(&c->h_flag, 4 * sizeof(int)) != hipSuccess) rc = MPMC_ERR_HIP;
+	A(c->h_flag.reserve(c, 4));
 	if (rc == MPMC_OK) rc = rot_selftest(c);
 	if (rc != MPMC_OK) {
 		g_create_error = "mpmc_ctx_create: device allocation failed: " + c->err;
@@ -208,26 +213,12 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
 	for (auto &e : c->ev_used) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
 	for (auto &e : c->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-	void *ptrs[] = {c->d_atoms_blob, c->d_atom_part, c->d_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_scal,
-	                c->d_flag, c->d_counter, c->d_kvec, c->d_kw, c->d_sf, c->d_w_en, c->d_e_recip_part, c->d_part, c->d_e_static, c->d_mu[0], c->d_mu[1],
-	                c->d_e_induced, c->d_rrms, c->d_arows, c->d_adense, c->d_chol, c->d_chol_v, c->d_chol_info, c->d_chol_list, c->d_chol_status, c->d_ab, c->d_cls, c->d_tp_shift, c->d_lvec, c->d_sf_part, c->d_tile_bounds, c->d_panels, c->d_seg, c->d_gpart, c->d_trace, c->d_mv_blob, c->d_moved_idx,
-	                c->d_sf_trial, c->d_delta_out, c->d_e_real, c->d_e_real_trial, c->d_dk_part, c->d_gs_ul, c->d_gs_blocks, c->d_erf_tab, c->d_sweep_blocks, c->d_generic_list, c->d_tb_au, c->d_tb_part,
-	                c->d_de_co, c->d_de_t10, c->d_de_part, c->d_palmo_f, c->d_palmo_change};
-	for (void *p : ptrs)
-		if (p) (void)hipFree(p);
-	if (c->h_stage) (void)pinned_free(c->h_stage);
-	if (c->h_xyzq) (void)pinned_free(c->h_xyzq);
 	if (c->ev_xyzq) (void)hipEventDestroy(c->ev_xyzq);
-	if (c->h_kstage) (void)pinned_free(c->h_kstage);
 	if (c->ev_kstage) (void)hipEventDestroy(c->ev_kstage);
-	if (c->static_cnt) (void)pinned_free(c->static_cnt);
 	if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
-	if (c->h_scal) (void)pinned_free(c->h_scal);
-	if (c->h_flag) (void)pinned_free(c->h_flag);
-	if (c->h_delta_out) (void)pinned_free(c->h_delta_out);
-	if (c->h_chol_info) (void)pinned_free(c->h_chol_info);
-	if (c->h_mv_blob) (void)pinned_free(c->h_mv_blob);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
+	// the buffers free themselves, behind the destruction of the streams: both were synchronised above, so nothing enqueued can still
+	// touch the memory, and freeing needs no stream
 	delete c;
 	return MPMC_OK;
 }
@@ -325,7 +316,7 @@ static void compute_spatial_order(mpmc_ctx *c) {
 	for (int i = 0; i < n; i++) c->perm[i] = i;
 	bool enable = c->box_set && n > 2 * kTile;
 	if (c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only) enable = false; // the sweep order IS the atom order (:3569)
-	if (c->tune.no_sort) enable = false;
+	if (c->kept.tune.no_sort) enable = false;
 	if (enable) {
 		// fractional coordinates counted from the smallest one in each dimension: with all atoms inside one period (the usual case) the
 		// periodic wrap is cut at the edge of the occupied range, so tiles are compact in the RAW coordinates too -- which is what lets
@@ -355,8 +346,8 @@ static void compute_spatial_order(mpmc_ctx *c) {
 		// The columns are walked in serpentine order, z up one and down the next, so that a tile that runs over the end of a column
 		// continues in the neighbouring one at the same z edge and stays compact.  Cells per dimension: 2 ceil(|b_d| / 2e) for the edge e of a
 		// cube of one tile's volume; used when every column holds at least two tiles (below that the bisection's cubes are better).
-		int grid_x = c->tune.sort_nx, grid_y = c->tune.sort_ny;
-		if ((grid_x <= 0 || grid_y <= 0) && c->tune.sort_grid != 0) {
+		int grid_x = c->kept.tune.sort_nx, grid_y = c->kept.tune.sort_ny;
+		if ((grid_x <= 0 || grid_y <= 0) && c->kept.tune.sort_grid != 0) {
 			const int T = (n + kTile - 1) / kTile;
 			const double e = std::cbrt(std::fabs(c->box.volume) * (double)kTile / (double)n);
 			double len[2];
@@ -445,11 +436,11 @@ static bool carry_spatial_order(mpmc_ctx *c, const double *new_pos, int n_new) {
 int mpmc::upload_atoms(mpmc_ctx *c) {
 	// (atoms_dirty_order: somebody asked for a NEW order since the list was carried -- a set_options that switches Gauss-Seidel sweeps on
 	// needs the identity order of System.Energy.cpp:3569, not the carried spatial one)
-	if (!c->order_carried || c->atoms_dirty_order || c->tune.no_order_carry || (int)c->perm.size() != c->n) {
+	if (!c->order_carried || c->atoms_dirty_order || c->kept.tune.no_order_carry || (int)c->perm.size() != c->n) {
 		compute_spatial_order(c);
-		c->n_uploads_sorted++;
+		c->kept.n_uploads_sorted++;
 	} else {
-		c->n_uploads_carried++;
+		c->kept.n_uploads_carried++;
 	}
 	c->order_carried = false;
 	c->atoms_dirty_order = false;
@@ -458,12 +449,13 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	// every one of them was a staged, blocking copy, and a stream synchronisation kept the vectors alive) -- an insertion or removal
 	// (uVT, Gibbs) pays for a sort and eight enqueues here, nothing else.
 	const size_t P = (size_t)c->max_pad;
-	if (!c->h_stage) {
-		HIP_TRY(c, pinned_alloc(&c->h_stage, P * kAtomRecordBytes));
-		HIP_TRY(c, pinned_alloc(&c->h_xyzq, P * sizeof(double4)));
-		HIP_TRY(c, hipEventCreateWithFlags(&c->ev_xyzq, hipEventDisableTiming));
-		HIP_TRY(c, hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming));
-		HIP_TRY(c, pinned_alloc(&c->static_cnt, 4 * sizeof(long long)));
+	if (!c->static_cnt) {
+		int rc;
+		if ((rc = c->h_stage.reserve(c, P * kAtomRecordBytes)) != MPMC_OK) return rc;
+		if ((rc = c->h_xyzq.reserve(c, P)) != MPMC_OK) return rc;
+		if (!c->ev_xyzq) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_xyzq, hipEventDisableTiming));
+		if (!c->ev_stage) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming));
+		if ((rc = c->static_cnt.reserve(c, 4)) != MPMC_OK) return rc;
 		for (int k = 0; k < 4; k++) c->static_cnt[k] = 0;
 	}
 	if (c->stage_in_flight) { // (an upload per evaluation at most, and evaluations are waited for: normally long done)
@@ -499,7 +491,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 			int fl = 0;
 			if (c->h_frozen[i]) fl |= AF_FROZEN;
 			if (c->h_eps[i] == 0.0 || c->h_sigma[i] == 0.0) fl |= AF_NULL_RD;
-			if (c->h_disp[i]) fl |= c->de_enabled ? AF_DISP_RD : AF_HAS_DISP; // (disp-expansion: LJ mixing no longer matters, pair_math.h)
+			if (c->h_disp[i]) fl |= c->kept.de_enabled ? AF_DISP_RD : AF_HAS_DISP; // (disp-expansion: LJ mixing no longer matters, pair_math.h)
 			if (c->h_sigma[i] < 0.0) fl |= AF_NEG_SIGMA;
 			if (c->h_sigma[i] == 0.0) fl |= AF_ZERO_SIGMA;
 			if (c->h_q[i] == 0.0) fl |= AF_ZERO_Q;
@@ -531,13 +523,9 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 					if (special[I] || special[J]) c->h_generic.push_back(t);
 		c->n_generic = (int)c->h_generic.size();
 		if (c->n_generic > 0) {
-			if ((size_t)c->n_generic > c->cap_generic) {
-				dev_free(c, &c->d_generic_list, c->cap_generic);
-				c->cap_generic = 0;
-				const int rc_a = dev_alloc(c, &c->d_generic_list, (size_t)c->n_tile_pairs);
-				if (rc_a != MPMC_OK) return rc_a;
-				c->cap_generic = (size_t)c->n_tile_pairs;
-			}
+			// (room for every tile pair at once: the list changes with every upload, and no later one can then outgrow it)
+			const int rc_a = c->d_generic_list.reserve(c, (size_t)c->n_generic, (size_t)c->n_tile_pairs);
+			if (rc_a != MPMC_OK) return rc_a;
 			HIP_TRY(c, hipMemcpyAsync(c->d_generic_list, c->h_generic.data(), (size_t)c->n_generic * sizeof(int), hipMemcpyHostToDevice, c->stream));
 			HIP_TRY(c, hipStreamSynchronize(c->stream)); // pageable source that the next upload clears: wait, as the tile-pair and block tables do
 		}
@@ -612,19 +600,7 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 		mpmc_ctx_destroy(f);
 		return rc;
 	}
-	f->prof = c->prof;
-	f->tim = c->tim;
-	f->tune = c->tune;
-	f->n_poll_hits = c->n_poll_hits, f->n_poll_timeouts = c->n_poll_timeouts, f->n_stream_syncs = c->n_stream_syncs, f->n_poll_yields = c->n_poll_yields;
-	f->n_uploads_carried = c->n_uploads_carried; // (diagnostics survive the growth; the order itself does not: the new context sorts)
-	f->n_uploads_sorted = c->n_uploads_sorted;
-	f->tb_enabled = c->tb_enabled; // (the three-body setting survives; its coefficients go with the atom list that is being replaced)
-	f->tb_mk = c->tb_mk;
-	f->de_enabled = c->de_enabled; // (the disp-expansion setting likewise)
-	f->de_flags = c->de_flags;
-	f->pw_enabled = c->pw_enabled; // (so do the Wolf static field and the Palmo-Krimm correction)
-	f->pw_alpha = c->pw_alpha;
-	f->palmo_enabled = c->palmo_enabled;
+	f->kept = c->kept; // (the switched-on terms survive, their coefficients go with the atom list that is being replaced; the new context sorts)
 	std::swap(*c, *f);
 	mpmc_ctx_destroy(f); // now owns the old, smaller buffers
 	return MPMC_OK;
@@ -690,20 +666,11 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	// upper-triangular tile-pair schedule of the pair kernel
 	const int nt = c->n_tiles;
 	const size_t ntp = (size_t)nt * (nt + 1) / 2;
-	if (ntp > c->cap_tile_pairs) {
-		dev_free(c, &c->d_tile_pairs, c->cap_tile_pairs);
-		dev_free(c, &c->d_block_part, 2 * c->cap_tile_pairs);
-		dev_free(c, &c->d_block_cnt, 4 * c->cap_tile_pairs);
-		dev_free(c, &c->d_cls, c->cap_tile_pairs);
-		dev_free(c, &c->d_tp_shift, c->cap_tile_pairs);
-		c->cap_tile_pairs = 0;
-		if ((rc = dev_alloc(c, &c->d_tile_pairs, ntp)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_block_part, 2 * ntp)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_block_cnt, 4 * ntp)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_cls, ntp)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_tp_shift, ntp)) != MPMC_OK) return rc;
-		c->cap_tile_pairs = ntp;
-	}
+	if ((rc = c->d_tile_pairs.reserve(c, ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_block_part.reserve(c, 2 * ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_block_cnt.reserve(c, 4 * ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_cls.reserve(c, ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_tp_shift.reserve(c, ntp)) != MPMC_OK) return rc;
 	std::vector<int2> tp;
 	tp.reserve(ntp);
 	for (int I = 0; I < nt; I++)
@@ -716,13 +683,8 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 		const int nb = pair_sweep_blocks(nt, nullptr);
 		std::vector<int2> blocks((size_t)nb);
 		pair_sweep_blocks(nt, blocks.data());
-		if (c->tune.sweep_order == 1) std::reverse(blocks.begin(), blocks.end()); // j-tiles descending (measurement)
-		if ((size_t)nb > c->cap_sweep_blocks) {
-			dev_free(c, &c->d_sweep_blocks, c->cap_sweep_blocks);
-			c->cap_sweep_blocks = 0;
-			if ((rc = dev_alloc(c, &c->d_sweep_blocks, (size_t)nb)) != MPMC_OK) return rc;
-			c->cap_sweep_blocks = (size_t)nb;
-		}
+		if (c->kept.tune.sweep_order == 1) std::reverse(blocks.begin(), blocks.end()); // j-tiles descending (measurement)
+		if ((rc = c->d_sweep_blocks.reserve(c, (size_t)nb)) != MPMC_OK) return rc;
 		HIP_TRY(c, hipMemcpyAsync(c->d_sweep_blocks, blocks.data(), (size_t)nb * sizeof(int2), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(c, hipStreamSynchronize(c->stream)); // `blocks` dies here
 		c->n_sweep_blocks = nb;
@@ -751,19 +713,19 @@ extern "C" int mpmc_set_polar_wolf(mpmc_ctx *c, int enabled, double polar_wolf_a
 	if (enabled && (!std::isfinite(polar_wolf_alpha) || polar_wolf_alpha < 0.0 || polar_wolf_alpha > 1.0)) // SimulationControl.cpp:2652-2660
 		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_wolf: polar_wolf_alpha must be in [0, 1]");
 	const bool on = enabled != 0;
-	if (on != c->pw_enabled || (on && polar_wolf_alpha != c->pw_alpha)) {
+	if (on != c->kept.pw_enabled || (on && polar_wolf_alpha != c->kept.pw_alpha)) {
 		c->cache_valid = false; // (the accepted totals and the resident real-space field belong to the other static field)
 		c->e_real_valid = false;
 	}
-	c->pw_enabled = on;
-	c->pw_alpha = on ? polar_wolf_alpha : 0.0;
+	c->kept.pw_enabled = on;
+	c->kept.pw_alpha = on ? polar_wolf_alpha : 0.0;
 	return MPMC_OK;
 }
 extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 	if (!c) return MPMC_ERR_ARG;
 	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_palmo: an evaluation or a trial move is open");
-	if ((enabled != 0) != c->palmo_enabled) c->cache_valid = false; // (the accepted totals carry the correction)
-	c->palmo_enabled = enabled != 0;
+	if ((enabled != 0) != c->kept.palmo_enabled) c->cache_valid = false; // (the accepted totals carry the correction)
+	c->kept.palmo_enabled = enabled != 0;
 	return MPMC_OK;
 }
 
@@ -787,8 +749,8 @@ extern "C" int mpmc_set_axilrod_teller(mpmc_ctx *c, int enabled, int mk, const d
 	if (!c) return MPMC_ERR_ARG;
 	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: an evaluation or a trial move is open");
 	if (!enabled) {
-		if (c->tb_enabled) c->cache_valid = false; // (the accepted totals carry the term)
-		c->tb_enabled = c->tb_mk = c->tb_have = c->tb_dirty = false;
+		if (c->kept.tb_enabled) c->cache_valid = false; // (the accepted totals carry the term)
+		c->kept.tb_enabled = c->kept.tb_mk = c->tb_have = c->tb_dirty = false;
 		c->h_tb_au.clear();
 		return MPMC_OK;
 	}
@@ -800,8 +762,8 @@ extern "C" int mpmc_set_axilrod_teller(mpmc_ctx *c, int enabled, int mk, const d
 	if (three_body_tile_triples(c->n_tiles) > 0x7fffffffLL)
 		return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: more tile triples than one launch can index");
 	three_body_coefficients(c->n, c->h_alpha.data(), mk, c6, c9, c->h_tb_au);
-	c->tb_enabled = c->tb_have = c->tb_dirty = true;
-	c->tb_mk = mk != 0;
+	c->kept.tb_enabled = c->tb_have = c->tb_dirty = true;
+	c->kept.tb_mk = mk != 0;
 	c->cache_valid = false; // (the accepted totals of trial moves lack the term until the next mpmc_energy)
 	return MPMC_OK;
 }
@@ -830,8 +792,8 @@ static void disp_coefficients(int n, const double *alpha, const double *r0, int 
 
 DispParams mpmc::disp_params(const mpmc_ctx *c) {
 	DispParams dp;
-	dp.damp = (c->de_flags & MPMC_DISP_DAMP) ? 1 : 0;
-	dp.schmidt = (c->de_flags & MPMC_DISP_SCHMIDT) ? 1 : 0;
+	dp.damp = (c->kept.de_flags & MPMC_DISP_DAMP) ? 1 : 0;
+	dp.schmidt = (c->kept.de_flags & MPMC_DISP_SCHMIDT) ? 1 : 0;
 	return dp;
 }
 
@@ -844,7 +806,7 @@ static void disp_lrc(mpmc_ctx *c) {
 		const double rc = c->box.cutoff, V = c->box.volume;
 		long double S[3][2] = {{0, 0}, {0, 0}, {0, 0}}, Q[3][2] = {{0, 0}, {0, 0}, {0, 0}}; // [coefficient][all, frozen]
 		double self = 0.0;
-		const bool ex = (c->de_flags & MPMC_DISP_EXTRAPOLATE_C10) != 0;
+		const bool ex = (c->kept.de_flags & MPMC_DISP_EXTRAPOLATE_C10) != 0;
 		for (int i = 0; i < c->n; i++) {
 			const double *d = &c->h_de[5 * (size_t)i];
 			const bool fr = c->h_frozen[i] != 0;
@@ -875,9 +837,9 @@ extern "C" int mpmc_set_disp_expansion(mpmc_ctx *c, int enabled, int flags, cons
 	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: an evaluation or a trial move is open");
 	if (flags & ~(MPMC_DISP_DAMP | MPMC_DISP_EXTRAPOLATE_C10 | MPMC_DISP_SCHMIDT)) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: unknown flag bits");
 	if (!enabled) {
-		if (c->de_enabled) c->cache_valid = false, c->atoms_dirty = true; // (the accepted totals carry the term; the atoms' flags change back)
-		c->de_enabled = c->de_have = c->de_dirty = c->de_lrc_valid = false;
-		c->de_flags = 0;
+		if (c->kept.de_enabled) c->cache_valid = false, c->atoms_dirty = true; // (the accepted totals carry the term; the atoms' flags change back)
+		c->kept.de_enabled = c->de_have = c->de_dirty = c->de_lrc_valid = false;
+		c->kept.de_flags = 0;
 		c->h_de.clear();
 		c->h_de_raw.clear();
 		return MPMC_OK;
@@ -890,24 +852,22 @@ extern "C" int mpmc_set_disp_expansion(mpmc_ctx *c, int enabled, int flags, cons
 			if (!std::isfinite(x) || x < 0.0) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_set_disp_expansion: coefficients must be finite and >= 0");
 	}
 	disp_coefficients(c->n, c->h_eps.data(), c->h_sigma.data(), flags, c6, c8, c10, c->h_de, c->h_de_raw);
-	if (!c->de_enabled) c->atoms_dirty = true; // (the atoms' dispersion flag becomes AF_DISP_RD: upload_atoms)
-	c->de_enabled = c->de_have = c->de_dirty = true;
+	if (!c->kept.de_enabled) c->atoms_dirty = true; // (the atoms' dispersion flag becomes AF_DISP_RD: upload_atoms)
+	c->kept.de_enabled = c->de_have = c->de_dirty = true;
 	c->de_lrc_valid = false;
-	c->de_flags = flags;
+	c->kept.de_flags = flags;
 	c->cache_valid = false; // (the accepted totals of trial moves lack the term until the next mpmc_energy)
 	return MPMC_OK;
 }
 
 int mpmc::disp_ready(mpmc_ctx *c) {
-	if (!c->de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the disp-expansion term is off (mpmc_set_disp_expansion)");
+	if (!c->kept.de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the disp-expansion term is off (mpmc_set_disp_expansion)");
 	if (!c->de_have)
 		return fail(c, MPMC_ERR_ARG, "the disp-expansion term is on but has no coefficients for this atom list (mpmc_set_disp_expansion after mpmc_set_atoms)");
 	int rc;
-	if (!c->d_de_co) {
-		if ((rc = dev_alloc(c, &c->d_de_co, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_de_t10, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_de_part, (size_t)kDispBlocks)) != MPMC_OK) return rc;
-	}
+	if ((rc = c->d_de_co.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_de_t10.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_de_part.reserve(c, (size_t)kDispBlocks)) != MPMC_OK) return rc;
 	if (c->de_dirty) { // slot order, like every other per-atom array (upload_atoms)
 		std::vector<double4> co((size_t)c->n_pad, make_double4(0.0, 0.0, 0.0, 0.0));
 		std::vector<double> t10((size_t)c->n_pad, 0.0);
@@ -927,14 +887,12 @@ int mpmc::disp_ready(mpmc_ctx *c) {
 }
 
 int mpmc::three_body_ready(mpmc_ctx *c) {
-	if (!c->tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the Axilrod-Teller term is off (mpmc_set_axilrod_teller)");
+	if (!c->kept.tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "the Axilrod-Teller term is off (mpmc_set_axilrod_teller)");
 	if (!c->tb_have)
 		return fail(c, MPMC_ERR_ARG, "the Axilrod-Teller term is on but has no coefficients for this atom list (mpmc_set_axilrod_teller after mpmc_set_atoms)");
 	int rc;
-	if (!c->d_tb_au) {
-		if ((rc = dev_alloc(c, &c->d_tb_au, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_tb_part, (size_t)kThreeBodyBlocks)) != MPMC_OK) return rc;
-	}
+	if ((rc = c->d_tb_au.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_tb_part.reserve(c, (size_t)kThreeBodyBlocks)) != MPMC_OK) return rc;
 	if (c->tb_dirty) { // slot order, like every other per-atom array (upload_atoms)
 		std::vector<double2> au((size_t)c->n_pad, make_double2(0.0, 1.0));
 		for (int k = 0; k < c->n; k++) {
@@ -1039,7 +997,7 @@ extern "C" int mpmc_set_positions_device(mpmc_ctx *c, const double *pos_device) 
 // ---- measurement -----------------------------------------------------------------------------------------
 extern "C" int mpmc_set_profiling(mpmc_ctx *c, int enabled) {
 	if (!c) return MPMC_ERR_ARG;
-	c->prof = enabled != 0;
+	c->kept.prof = enabled != 0;
 	return MPMC_OK;
 }
 extern "C" int mpmc_get_timings(mpmc_ctx *c, mpmc_timings *out, int reset) {
@@ -1047,8 +1005,8 @@ extern "C" int mpmc_get_timings(mpmc_ctx *c, mpmc_timings *out, int reset) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	prof_harvest(c);
-	*out = c->tim;
-	if (reset) std::memset(&c->tim, 0, sizeof(c->tim));
+	*out = c->kept.tim;
+	if (reset) std::memset(&c->kept.tim, 0, sizeof(c->kept.tim));
 	return MPMC_OK;
 }
 extern "C" int mpmc_synchronize(mpmc_ctx *c) {
@@ -1090,7 +1048,7 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	for (int k = 0; k < 12; k++) out[k] = 0;
 	const int nt = c->n_tiles;
-	const bool uni = !(c->tune.no_uniform || c->tune.no_classes);
+	const bool uni = !(c->kept.tune.no_uniform || c->kept.tune.no_classes);
 	auto real = [&](int T) { return (int64_t)std::max(0, std::min(kTile, c->n - T * kTile)); };
 	size_t t = 0;
 	for (int I = 0; I < nt; I++)
@@ -1125,7 +1083,7 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 	if (!key) return MPMC_ERR_ARG;
 	std::unique_lock<std::mutex> tuning_lk(g_tuning_mu, std::defer_lock);
 	if (!c) tuning_lk.lock();
-	mpmc_tuning &t = c ? c->tune : g_tuning_default;
+	mpmc_tuning &t = c ? c->kept.tune : g_tuning_default;
 	const std::string k(key);
 	const int v = (int)value;
 	const bool on = (value != 0.0);
@@ -1208,18 +1166,18 @@ extern "C" int mpmc_debug_last_pair_kernel(mpmc_ctx *c) { return c ? (c->last_pa
 // budget (the wait then synchronised the stream), stream synchronisations, yields taken inside long polls (poll_posted, context.h)
 extern "C" int mpmc_debug_wait_counters(mpmc_ctx *c, long long *out4) {
 	if (!c || !out4) return -1;
-	out4[0] = c->n_poll_hits;
-	out4[1] = c->n_poll_timeouts;
-	out4[2] = c->n_stream_syncs;
-	out4[3] = c->n_poll_yields;
+	out4[0] = c->kept.n_poll_hits;
+	out4[1] = c->kept.n_poll_timeouts;
+	out4[2] = c->kept.n_stream_syncs;
+	out4[3] = c->kept.n_poll_yields;
 	return 0;
 }
 
 // diagnostics only (tests assert that the order was really carried): uploads of the atom list that kept the order / that sorted
 extern "C" int mpmc_debug_upload_counts(mpmc_ctx *c, long long *out2) {
 	if (!c || !out2) return -1;
-	out2[0] = c->n_uploads_carried;
-	out2[1] = c->n_uploads_sorted;
+	out2[0] = c->kept.n_uploads_carried;
+	out2[1] = c->kept.n_uploads_sorted;
 	return 0;
 }
 
@@ -1248,6 +1206,6 @@ extern "C" int mpmc_debug_panel_table(mpmc_ctx *c, int *out4, int max_entries) {
 extern "C" int mpmc_memory_usage(mpmc_ctx *c, int64_t *total, int64_t *tensor) {
 	if (!c) return MPMC_ERR_ARG;
 	if (total) *total = c->bytes_total;
-	if (tensor) *tensor = (c->solver_used == MPMC_SOLVER_COMPACT) ? (int64_t)(c->cap_ab * sizeof(double2)) : 0;
+	if (tensor) *tensor = (c->solver_used == MPMC_SOLVER_COMPACT) ? (int64_t)(c->d_ab.cap * sizeof(double2)) : 0;
 	return MPMC_OK;
 }

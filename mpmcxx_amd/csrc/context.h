@@ -53,6 +53,30 @@ inline hipError_t pinned_free(void *p) {
 	return hipHostFree(p);
 }
 
+// A grow-only buffer that owns its memory: device memory that starts from zeros and is counted in the context's bytes_total (DevBuf), or
+// pinned host memory, neither filled nor counted (PinnedBuf).  Move-only.  The destructor frees without a context: a buffer dies with
+// the context that owns it, and there is nothing left to account to.
+struct mpmc_ctx;
+template <class T, bool kPinned = false>
+struct DevBuf {
+	T *p = nullptr;
+	size_t cap = 0; // elements (what bytes_total counts for p; the allocation itself is never shorter than one element)
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept {
+		std::swap(p, o.p), std::swap(cap, o.cap);
+		return *this;
+	}
+	~DevBuf() { release(nullptr); } // (members of a context: it dies with them; a local buffer calls release(c) itself before it goes)
+	operator T *() const { return p; }
+	void release(mpmc_ctx *c); // frees; given a context, takes the bytes out of its count
+	// Room for `need` elements: nothing to do when need <= cap; otherwise the old buffer goes (with its contents) and a fresh one of
+	// max(need, grow_to) elements takes its place.  MPMC_OK, or the error code with c->err set and the buffer left empty.
+	int reserve(mpmc_ctx *c, size_t need, size_t grow_to = 0);
+};
+template <class T>
+using PinnedBuf = DevBuf<T, true>;
+
 // Measurement / A-B switches (mpmc_debug_configure; the library reads no environment variable for any of them).  The defaults are the
 // production path; none of them changes a result beyond the last bits (tests/test_gpu_round3_fixes.py holds every one to the reference).
 struct mpmc_tuning {
@@ -91,8 +115,26 @@ struct mpmc_tuning {
 	long long direct_budget_mb = -1;   // "direct_budget_mb": direct dipole solve: largest factor it will allocate (-1: what the device has free)
 };
 
-struct mpmc_ctx {
+// What a context keeps across mpmc_set_atoms AND across a growth of its capacity (grow_capacity hands `kept` to the fresh context in one
+// assignment).  Everything else of mpmc_ctx is rebuilt by the fresh context: the spatial order, the per-atom coefficients, every buffer.
+struct mpmc_kept {
 	mpmc_tuning tune;
+	bool prof = false; // profiling (mpmc_set_profiling) and what it has measured so far
+	mpmc_timings tim{};
+	// how the host waits ended (mpmc_debug_wait_counters): polls that saw the device's post, polls that ran out of their budget (the
+	// wait then fell back to a stream synchronisation), plain stream synchronisations, and yields taken inside long polls
+	long long n_poll_hits = 0, n_poll_timeouts = 0, n_stream_syncs = 0, n_poll_yields = 0;
+	long long n_uploads_carried = 0, n_uploads_sorted = 0; // (diagnostics: mpmc_debug_upload_counts)
+	bool tb_enabled = false, tb_mk = false; // Axilrod-Teller term switched on; Midzuno-Kihara c9 (mpmc_set_axilrod_teller)
+	bool de_enabled = false;                // disp-expansion term switched on (mpmc_set_disp_expansion); the atoms' dispersion flag is AF_DISP_RD then
+	int de_flags = 0;                       // MPMC_DISP_*
+	bool pw_enabled = false;                // `polar_wolf` (mpmc_set_polar_wolf), kept across mpmc_set_box and mpmc_set_options too
+	double pw_alpha = 0.0;
+	bool palmo_enabled = false;             // `polar_palmo` (mpmc_set_polar_palmo), likewise
+};
+
+struct mpmc_ctx {
+	mpmc_kept kept;
 	int device = 0;
 	hipStream_t stream = nullptr;
 	// second stream for work that is independent of the main chain inside ONE evaluation (reciprocal space next to the
@@ -120,34 +162,32 @@ struct mpmc_ctx {
 	// device atom arrays
 	// the per-atom arrays below are pieces of ONE device block laid out like the pinned staging block of upload_atoms
 	// ([xyzq][lj][mf][alpha][eps][inv_molmass][perm][slot_of], each max_pad long): an upload of the atoms is one copy
-	char *d_atoms_blob = nullptr;
+	DevBuf<char> d_atoms_blob;
 	double4 *d_xyzq = nullptr;
 	double2 *d_lj = nullptr;
 	int2 *d_mf = nullptr;
 	double *d_alpha = nullptr, *d_eps = nullptr, *d_inv_molmass = nullptr;
 
 	// pair kernel
-	int2 *d_tile_pairs = nullptr;
-	double *d_block_part = nullptr; // [ntp][2]
-	int *d_block_cnt = nullptr;     // [ntp][4] (2 used by the pair kernel, 4 by the static-count kernel)
-	int *d_cls = nullptr;           // tile-pair classes (CLS_*), recomputed every evaluation
-	double *d_tile_bounds = nullptr; // [n_tiles][12]: wrapped fractional lo/hi, raw Cartesian lo/hi
-	double4 *d_tp_shift = nullptr;   // [n_tile_pairs] lattice vector components of the common image index (CLS_UNIFORM_X/Y/Z)
-	int4 *d_panels = nullptr;        // work table of the panel form of the Jacobi contraction (k_build_panels), rebuilt every evaluation
-	int *d_seg = nullptr;            // [n_tiles + 1] first entry of every j-tile's segment of that table
-	double *d_gpart = nullptr;       // [entries][3][64] j-side partial sums, one slot per entry of the table
-	size_t cap_panels = 0, cap_seg = 0;
-	long long *d_trace = nullptr;    // measurement only (tune.trace_panel): [entries][4] start / end ticks, HW_ID, XCC_ID of every workgroup of the LAST panel launch
+	// (the five per-tile-pair arrays are sized together, mpmc_set_atoms)
+	DevBuf<int2> d_tile_pairs;
+	DevBuf<double> d_block_part;    // [ntp][2]
+	DevBuf<int> d_block_cnt;        // [ntp][4] (2 used by the pair kernel, 4 by the static-count kernel)
+	DevBuf<int> d_cls;              // tile-pair classes (CLS_*), recomputed every evaluation
+	DevBuf<double> d_tile_bounds;   // [n_tiles][12]: wrapped fractional lo/hi, raw Cartesian lo/hi
+	DevBuf<double4> d_tp_shift;     // [n_tile_pairs] lattice vector components of the common image index (CLS_UNIFORM_X/Y/Z)
+	DevBuf<int4> d_panels;          // work table of the panel form of the Jacobi contraction (k_build_panels), rebuilt every evaluation
+	DevBuf<int> d_seg;              // [n_tiles + 1] first entry of every j-tile's segment of that table
+	DevBuf<double> d_gpart;         // [entries][3][64] j-side partial sums, one slot per entry of the table
+	DevBuf<long long> d_trace;      // measurement only (tune.trace_panel): [entries][4] start / end ticks, HW_ID, XCC_ID of every workgroup of the LAST panel launch
 	int n_panel_entries = 0, seg_tiles = -1; // entries of the table / the tile count its layout was made for
 	bool panels_built = false;       // this evaluation's classes carry CLS_GROUPED bits and d_panels is valid
 	// the fast pair sweep (kernels_pair.hip): its erfc table, its work table { J, I0 } (depends on the tile count only) and the list of
 	// tile pairs it leaves to k_pair_fused (a tile with a kAtomFlagsMixing atom -- sigma < 0 or dispersion coefficients: rebuilt with every upload)
-	double2 *d_erf_tab = nullptr;
-	int2 *d_sweep_blocks = nullptr;
-	size_t cap_sweep_blocks = 0;
+	DevBuf<double2> d_erf_tab;
+	DevBuf<int2> d_sweep_blocks;
 	int n_sweep_blocks = 0, sweep_tiles = -1;
-	int *d_generic_list = nullptr;
-	size_t cap_generic = 0;
+	DevBuf<int> d_generic_list;
 	int n_generic = 0;
 	std::vector<int> h_generic;
 	int inflight_hint = 1; // evaluations the caller keeps in flight together with this one (mpmc_hint_in_flight; the PI loops set their bead count)
@@ -155,7 +195,7 @@ struct mpmc_ctx {
 	FusedParams last_fp{};            // the pair pass's parameters in the last evaluation (mpmc_debug_time_pair replays it)
 	bool last_fp_valid = false;
 	int debug_panel_replicas = 1;     // mpmc_debug_configure "panel_replicas": grid repetitions of mpmc_debug_time_panel's launches
-	double4 *h_xyzq = nullptr;       // PINNED host mirror of d_xyzq (slot order, max_pad entries): position updates copy from it asynchronously;
+	PinnedBuf<double4> h_xyzq;       // PINNED host mirror of d_xyzq (slot order, max_pad entries): position updates copy from it asynchronously;
 	hipEvent_t ev_xyzq = nullptr;    // marks the last copy out of it done -- whoever is about to write the mirror waits for that copy only
 	bool xyzq_in_flight = false;     // (mirror_guard), not for the evaluations queued behind it
 	std::vector<double> h_pos_sorted; // positions at the time of the last spatial sort
@@ -165,21 +205,18 @@ struct mpmc_ctx {
 	bool order_sorted = false;  // perm is a spatial sort of the current atom list (not the identity of small / Gauss-Seidel systems)
 	bool order_carried = false; // set_atoms has already brought perm / slot_of up to date: upload_atoms does not sort
 	bool atoms_dirty_order = false; // a NEW sort was asked for (cell, options, drift) and is pending: nothing is carried across it
-	long long n_uploads_carried = 0, n_uploads_sorted = 0; // (diagnostics: mpmc_debug_upload_counts)
 	int edits_since_sort = 0;   // atoms inserted + removed since the last real sort
 	double sort_origin_f[3] = {0, 0, 0}; // fractional coordinate at which the spatial sort cuts the periodic wrap
 	hipStream_t sync_stream = nullptr;  // stream that carries this context's final copies (null: its own)
-	size_t cap_tile_pairs = 0;
 	std::vector<double> molmass_tmp; // (scratch of upload_atoms)
-	long long *static_cnt = nullptr; // pinned [4]: n_intra, n_rd_excluded, n_es_excluded, n_frozen (position independent; copied back behind every upload of the atoms)
+	PinnedBuf<long long> static_cnt; // pinned [4]: n_intra, n_rd_excluded, n_es_excluded, n_frozen (position independent; copied back behind every upload of the atoms)
 	// upload_atoms stages every per-atom array in ONE persistent pinned block (eight truly asynchronous copies, no synchronisation);
 	// ev_stage marks the copies done, the next upload waits for it before it refills the block
-	char *h_kstage = nullptr; // the same for the k-vector tables of build_k_tables ([kvec][kw][lvec][w_en], each cap_kstage long: 16-byte types first)
-	size_t cap_kstage = 0;
+	PinnedBuf<char> h_kstage; // the same for the k-vector tables of build_k_tables ([kvec][kw][lvec][w_en], each K long: 16-byte types first)
 	hipEvent_t ev_kstage = nullptr;
 	bool kstage_in_flight = false;
 	int lvec_kmax = -1;       // the integer l-vectors on the device belong to this kmax (they depend on nothing else)
-	char *h_stage = nullptr;
+	PinnedBuf<char> h_stage;
 	hipEvent_t ev_stage = nullptr;
 	bool stage_in_flight = false;
 	// the position-independent terms (LRC, Ewald self) ride along with the next general evaluation when they are stale: static_gen
@@ -190,52 +227,45 @@ struct mpmc_ctx {
 	// only -- computed once (k_atom_terms) whenever one of those changed, kept on the host, added when a result is assembled
 	bool static_dirty = true;
 	double h_static[3] = {0, 0, 0}; // lrc_pair, lrc_self, es_self
-	int *d_counter = nullptr;       // ticket counter of the single-launch small-system kernels (zero between launches)
+	DevBuf<int> d_counter;          // ticket counter of the single-launch small-system kernels (zero between launches)
 	bool scal_clean = false;        // d_scal is all zeros (the post kernel of the last evaluation left it so): no clear needed in front of this one
 	int poll_budget_us = 1000;      // ... for at most this long before the wait falls back to hipStreamSynchronize
 	bool spin_on_post = false;      // the pending evaluation ends in k_post_results and is short: wait_and_fill polls the launch number first
 	bool last_was_single = false;   // the pending evaluation wrote h_scal from the device: nothing to copy back
 	double single_seq = 0;          // launch number the single-launch kernel posts behind its results (host polls h_scal[S_COUNT + C_COUNT])
 	// scalars
-	double *d_atom_part = nullptr;   // scratch of launch_atom_terms (per-block partial sums)
-	double *d_scal = nullptr;
-	long long *d_cnt = nullptr;
-	double *h_scal = nullptr; // pinned
-	long long *h_cnt = nullptr;
-	int *d_flag = nullptr;
-	int *h_flag = nullptr; // pinned
+	DevBuf<double> d_atom_part;   // scratch of launch_atom_terms (per-block partial sums)
+	DevBuf<double> d_scal;
+	long long *d_cnt = nullptr;   // (the counts' part of d_scal)
+	PinnedBuf<double> h_scal;
+	long long *h_cnt = nullptr;   // (the counts' part of h_scal)
+	DevBuf<int> d_flag;
+	PinnedBuf<int> h_flag;
 
 	// reciprocal tables
-	int K = 0, cap_K = 0; // cap_K: capacity of the k tables (d_kvec, d_kw, d_lvec, d_w_en)
-	int cap_sf = 0;       // capacity of d_sf, which trades places with d_sf_trial when a trial move is accepted
-	double4 *d_kvec = nullptr, *d_kw = nullptr, *d_sf = nullptr;
-	int4 *d_lvec = nullptr;       // integer l-vectors of the k table
-	double4 *d_sf_part = nullptr; // [n_tiles][K] per-tile structure-factor partials (factorised phases)
-	size_t cap_sf_part = 0;
-	double *d_w_en = nullptr;
+	int K = 0;
+	DevBuf<double4> d_kvec, d_kw; // the k tables, with d_lvec and d_w_en (build_k_tables sizes the four together)
+	DevBuf<double4> d_sf;         // structure factors; trades places with d_sf_trial when a trial move is accepted
+	DevBuf<int4> d_lvec;          // integer l-vectors of the k table
+	DevBuf<double4> d_sf_part;    // [n_tiles][K] per-tile structure-factor partials (factorised phases)
+	DevBuf<double> d_w_en;
 
 	// polarization work
-	double *d_e_recip_part = nullptr, *d_part = nullptr, *d_e_static = nullptr, *d_mu[2] = {nullptr, nullptr}, *d_e_induced = nullptr,
-	       *d_rrms = nullptr;
-	size_t cap_part = 0;
-	double2 *d_gs_blocks = nullptr; // Gauss-Seidel sweeps: the in-tile 3 x 3 blocks (k_gs_blocks), cap_gs_blocks double2 elements
-	size_t cap_gs_blocks = 0;
-	double *d_gs_ul = nullptr; // Gauss-Seidel sweeps (kernels_gs.hip): [2][max_pad][3] induced-field parts from the tiles above / below
+	DevBuf<double> d_e_recip_part, d_part, d_e_static, d_mu[2], d_e_induced, d_rrms;
+	DevBuf<double2> d_gs_blocks; // Gauss-Seidel sweeps: the in-tile 3 x 3 blocks (k_gs_blocks)
+	DevBuf<double> d_gs_ul; // Gauss-Seidel sweeps (kernels_gs.hip): [2][max_pad][3] induced-field parts from the tiles above / below
 	int mu_cur = 0;
 	// dense A rows scratch
-	double *d_arows = nullptr;
-	double *d_adense = nullptr; // solver DENSE: the (3 n_pad)^2 matrix of thole_amatrix without its diagonal blocks
-	size_t cap_adense = 0;
-	size_t cap_arows = 0;
+	DevBuf<double> d_arows;
+	DevBuf<double> d_adense; // solver DENSE: the (3 n_pad)^2 matrix of thole_amatrix without its diagonal blocks
 	// compact Thole tensor store: (a,b) per unordered pair, tile-pair major, 64*64 double2 per tile pair
-	double2 *d_ab = nullptr;
-	size_t cap_ab = 0; // in double2 elements
+	DevBuf<double2> d_ab;
 	int solver_used = MPMC_SOLVER_MATRIX_FREE;
 	// direct dipole solve (`polar_iterative off`, kernels_chol.hip): the factor (np x np doubles, lower triangle), the slot list of the
 	// polarizable atoms, two vectors of np doubles, { status } on the device and { status, max |r|, max |E0| } on the device / pinned
-	double *d_chol = nullptr, *d_chol_v = nullptr, *d_chol_info = nullptr, *h_chol_info = nullptr;
-	int *d_chol_list = nullptr, *d_chol_status = nullptr;
-	size_t cap_chol = 0, cap_chol_v = 0, cap_chol_list = 0;
+	DevBuf<double> d_chol, d_chol_v, d_chol_info;
+	PinnedBuf<double> h_chol_info;
+	DevBuf<int> d_chol_list, d_chol_status;
 	bool direct_ran = false;       // the pending / last evaluation solved the dipoles directly
 	mpmc_direct_info direct{};     // of the last such evaluation (filled by wait_and_fill)
 
@@ -261,41 +291,38 @@ struct mpmc_ctx {
 	mpmc_result trial_keep{}; // accepted totals while a full-evaluation trial is in flight
 	int trial_first = 0, trial_count = 0;
 	std::vector<double> trial_new, trial_old;
-	int *d_mv_slot = nullptr, *d_mv_orig = nullptr, *d_moved_idx = nullptr; // d_mv_slot/d_mv_orig/d_mv_new live in ONE allocation (d_mv_blob)
-	double4 *d_mv_new = nullptr, *d_sf_trial = nullptr;
+	int *d_mv_slot = nullptr, *d_mv_orig = nullptr; // d_mv_slot/d_mv_orig/d_mv_new live in ONE allocation (d_mv_blob)
+	double4 *d_mv_new = nullptr;
+	DevBuf<int> d_moved_idx;
+	DevBuf<double4> d_sf_trial;
 	// polarizable boxes: the real-space static field of the accepted configuration (k_field_finalize) and of the trial one
 	// (e_real + delta of the pairs with a moved atom); they trade places on accept.  dk_part: scratch of k_delta_field.
-	double *d_e_real = nullptr, *d_e_real_trial = nullptr, *d_dk_part = nullptr;
-	size_t cap_dk_part = 0;
+	DevBuf<double> d_e_real, d_e_real_trial, d_dk_part;
 	bool e_real_valid = false;     // d_e_real describes the accepted configuration
 	bool trial_polar_delta = false; // the open trial took the incremental polarizable path (positions swapped on the device)
 	// the tensor store between trial moves: a trial rebuilds only the tile pairs of the tiles its moved atoms live in; after a REJECTED
 	// trial those tiles hold the rejected geometry's tensors and are rebuilt by the next trial (or by any full evaluation)
 	std::vector<int> store_dirty_tiles, trial_tiles;
 	int touch_n = -1, touch[8] = {0}; // what enqueue(RUN_STORE) passes to the store-only sweep (-1: all tile pairs)
-	unsigned char *d_mv_blob = nullptr, *h_mv_blob = nullptr; // device / pinned host staging of a trial's moved-atom list
-	int cap_sf_trial = 0;
-	double *d_delta_out = nullptr, *h_delta_out = nullptr; // h: pinned [10] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8])
+	DevBuf<unsigned char> d_mv_blob; // device / pinned host staging of a trial's moved-atom list
+	PinnedBuf<unsigned char> h_mv_blob;
+	DevBuf<double> d_delta_out;
+	PinnedBuf<double> h_delta_out; // [10] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8])
 	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
-	long long *d_delta_cnt = nullptr, *h_delta_cnt = nullptr;
-
-	// how the host waits ended (mpmc_debug_wait_counters): polls that saw the device's post, polls that ran out of their budget (the
-	// wait then fell back to a stream synchronisation), plain stream synchronisations, and yields taken inside long polls
-	long long n_poll_hits = 0, n_poll_timeouts = 0, n_stream_syncs = 0, n_poll_yields = 0;
+	long long *d_delta_cnt = nullptr, *h_delta_cnt = nullptr; // (the counts' part of d_delta_out / h_delta_out)
 
 	// Axilrod-Teller three-body term (mpmc_set_axilrod_teller, kernels_three_body.hip)
-	bool tb_enabled = false, tb_mk = false; // switched on; Midzuno-Kihara c9 (kept across mpmc_set_atoms and capacity growth)
+	// (switched on: kept.tb_enabled, kept.tb_mk)
 	bool tb_have = false;                   // coefficients set since the last mpmc_set_atoms
 	bool tb_dirty = false;                  // d_tb_au is older than h_tb_au or than the spatial order
 	std::vector<double> h_tb_au;            // [n][2] (a, u) per atom in original order (three_body_coefficients)
-	double2 *d_tb_au = nullptr;             // [max_pad] the same in slot order, padding (0, 1)
-	double *d_tb_part = nullptr;            // [kThreeBodyBlocks] per-workgroup partials
+	DevBuf<double2> d_tb_au;                // [max_pad] the same in slot order, padding (0, 1)
+	DevBuf<double> d_tb_part;               // [kThreeBodyBlocks] per-workgroup partials
 
 	// dispersion-expansion term (mpmc_set_disp_expansion, kernels_disp.hip): replaces the LJ sums of rd_energy
-	bool de_enabled = false;   // switched on (kept across mpmc_set_atoms and capacity growth); the atoms' dispersion flag is AF_DISP_RD then
-	int de_flags = 0;          // MPMC_DISP_* (kept likewise)
+	// (switched on: kept.de_enabled, kept.de_flags)
 	bool de_have = false;      // coefficients set since the last mpmc_set_atoms
 	bool de_dirty = false;     // d_de_co / d_de_t10 are older than h_de or than the spatial order
 	std::vector<double> h_de;  // [n][5] (alpha, r0, sqrt c6, sqrt c8, t10) per atom in original order (disp_coefficients)
@@ -303,25 +330,19 @@ struct mpmc_ctx {
 	bool de_lrc_valid = false; // de_lrc holds the two long-range corrections of the volume / cutoff / rd_lrc below
 	double de_lrc[2] = {0, 0}, de_lrc_volume = 0, de_lrc_cutoff = 0;
 	int de_lrc_rd_lrc = 0;
-	double4 *d_de_co = nullptr; // [max_pad] (alpha, r0, sqrt c6, sqrt c8) in slot order, padding zeros
-	double *d_de_t10 = nullptr; // [max_pad]
-	double *d_de_part = nullptr; // [kDispBlocks] per-workgroup partials
+	DevBuf<double4> d_de_co;   // [max_pad] (alpha, r0, sqrt c6, sqrt c8) in slot order, padding zeros
+	DevBuf<double> d_de_t10;   // [max_pad]
+	DevBuf<double> d_de_part;  // [kDispBlocks] per-workgroup partials
 
-	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip): kept across mpmc_set_atoms, mpmc_set_box,
-	// mpmc_set_options and capacity growth
-	bool pw_enabled = false;
-	double pw_alpha = 0.0;
-	bool palmo_enabled = false;
+	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip; switched on: kept.pw_enabled, kept.pw_alpha,
+	// kept.palmo_enabled)
 	bool palmo_ran = false;          // the pending / last evaluation did the extra contraction (Gauss-Seidel sweeps that did not fail)
 	double palmo_correction = 0.0;   // of the last evaluation with a dipole solve (wait_and_fill)
-	double *d_palmo_f = nullptr, *d_palmo_change = nullptr; // [max_pad][3]: -(A_off mu) of the final dipoles; ef_induced_change
+	DevBuf<double> d_palmo_f, d_palmo_change; // [max_pad][3]: -(A_off mu) of the final dipoles; ef_induced_change
 
-	// profiling
-	bool prof = false;
-	std::vector<EvPair> ev_free, ev_used;
-	mpmc_timings tim{};
+	std::vector<EvPair> ev_free, ev_used; // profiling (kept.prof): event pairs to reuse / recorded and not yet harvested into kept.tim
 
-	int64_t bytes_total = 0;
+	int64_t bytes_total = 0; // device memory held by this context's DevBuf members (mpmc_memory_usage)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -334,11 +355,38 @@ struct mpmc_ctx {
 		}                                                                                                         \
 	} while (0)
 
+template <class T, bool kPinned>
+inline void DevBuf<T, kPinned>::release(mpmc_ctx *c) {
+	if (p) (void)(kPinned ? pinned_free(p) : hipFree(p));
+	if (p && c && !kPinned) c->bytes_total -= (int64_t)(cap * sizeof(T));
+	p = nullptr, cap = 0;
+}
+template <class T, bool kPinned>
+inline int DevBuf<T, kPinned>::reserve(mpmc_ctx *c, size_t need, size_t grow_to) {
+	if (need <= cap) return MPMC_OK;
+	release(c);
+	const size_t count = std::max(need, grow_to), bytes = std::max<size_t>(count, 1) * sizeof(T);
+	hipError_t e = kPinned ? pinned_alloc(&p, bytes) : hipMalloc((void **)&p, bytes);
+	if (e != hipSuccess) p = nullptr;
+	// Every device buffer starts from zeros: what a kernel finds in a slot it has not written yet must not depend on what an earlier process
+	// left in that memory.  The fill is WAITED for -- buffers are also allocated in the middle of an evaluation, after the side stream
+	// was forked, and the first writer may be a side-stream kernel that is not ordered behind a fill on the main stream (seen: structure
+	// factors zeroed under the reciprocal-space kernels).  Allocations happen once per context, the wait costs nothing in steady state.
+	// (The fill is on the context's stream; nothing in this library touches the null stream, which is unordered against our non-blocking ones.)
+	if (e == hipSuccess && !kPinned && (e = hipMemsetAsync(p, 0, bytes, c->stream)) == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) {
+		release(nullptr);
+		c->err = std::string(kPinned ? "pinned host" : "device") + " allocation of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e);
+		return MPMC_ERR_HIP;
+	}
+	cap = count;
+	if (!kPinned) c->bytes_total += (int64_t)(count * sizeof(T));
+	return MPMC_OK;
+}
+
 namespace mpmc { // internal helpers: mangled names, nothing here can collide with a symbol of the host program
 
 constexpr size_t kAtomRecordBytes = sizeof(double4) + sizeof(double2) + sizeof(int2) + 3 * sizeof(double) + 2 * sizeof(int32_t); // per atom, all arrays of the block
-template <typename T>
-inline int dev_alloc(mpmc_ctx *c, T **p, size_t count);
 // carve the per-atom arrays out of a block of P records (device block and pinned staging block share the layout)
 template <typename F>
 inline void atom_block_layout(char *base, size_t P, F &&set) {
@@ -349,19 +397,6 @@ inline void atom_block_layout(char *base, size_t P, F &&set) {
 	int32_t *perm = reinterpret_cast<int32_t *>(imm + P), *slot = perm + P;
 	set(xyzq, lj, mf, al, ep, imm, perm, slot);
 }
-template <typename T>
-inline int dev_alloc(mpmc_ctx *c, T **p, size_t count) {
-	const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-	HIP_TRY(c, hipMalloc((void **)p, bytes));
-	// Every buffer starts from zeros: what a kernel finds in a slot it has not written yet must not depend on what an earlier process
-	// left in that memory.  The fill is WAITED for -- buffers are also allocated in the middle of an evaluation, after the side stream
-	// was forked, and the first writer may be a side-stream kernel that is not ordered behind a fill on the main stream (seen: structure
-	// factors zeroed under the reciprocal-space kernels).  Allocations happen once per context, the wait costs nothing in steady state.
-	HIP_TRY(c, hipMemsetAsync(*p, 0, bytes, c->stream));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	c->bytes_total += (int64_t)(count * sizeof(T));
-	return MPMC_OK;
-}
 // before the slot-ordered mirror is written: the last asynchronous copy out of it must have read it
 inline int mirror_guard(mpmc_ctx *c) {
 	if (c->xyzq_in_flight) {
@@ -369,14 +404,6 @@ inline int mirror_guard(mpmc_ctx *c) {
 		c->xyzq_in_flight = false;
 	}
 	return MPMC_OK;
-}
-template <typename T>
-inline void dev_free(mpmc_ctx *c, T **p, size_t count) {
-	if (*p) {
-		(void)hipFree(*p);
-		c->bytes_total -= (int64_t)(count * sizeof(T));
-		*p = nullptr;
-	}
 }
 
 inline int fail(mpmc_ctx *c, int code, const std::string &msg) {
@@ -396,17 +423,17 @@ inline bool poll_posted(mpmc_ctx *c, Pred seen, std::chrono::microseconds budget
 	for (int spins = 0;; ++spins) {
 		if (seen()) {
 			std::atomic_thread_fence(std::memory_order_acquire);
-			c->n_poll_hits++;
+			c->kept.n_poll_hits++;
 			return true;
 		}
 		if ((spins & 255) == 255) {
 			const auto dt = std::chrono::steady_clock::now() - t0;
 			if (dt > budget) {
-				c->n_poll_timeouts++;
+				c->kept.n_poll_timeouts++;
 				return false;
 			}
 			if (dt > std::chrono::microseconds(50)) {
-				c->n_poll_yields++;
+				c->kept.n_poll_yields++;
 				std::this_thread::yield();
 			}
 		}
@@ -416,7 +443,7 @@ inline bool poll_posted(mpmc_ctx *c, Pred seen, std::chrono::microseconds budget
 // ---- profiling ------------------------------------------------------------------------------------------
 inline void prof_begin(mpmc_ctx *c, int cls, int &cur, hipStream_t st) {
 	cur = -1;
-	if (!c->prof) return;
+	if (!c->kept.prof) return;
 	EvPair e;
 	if (!c->ev_free.empty()) {
 		e = c->ev_free.back();
@@ -436,8 +463,8 @@ inline void prof_harvest(mpmc_ctx *c) { // stream must be idle
 	for (auto &e : c->ev_used) {
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
-			c->tim.ms[e.cls] += ms;
-			c->tim.launches[e.cls] += 1;
+			c->kept.tim.ms[e.cls] += ms;
+			c->kept.tim.launches[e.cls] += 1;
 		}
 		c->ev_free.push_back(e);
 	}
@@ -488,7 +515,7 @@ int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles 
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options
 inline bool direct_solve(const mpmc_ctx *c) { return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative; } // `polar_iterative off`
 // `polar_wolf` replaces the static field whenever polar_ewald is off (thole_field :3289-3294: polar_ewald wins)
-inline bool wolf_field_on(const mpmc_ctx *c) { return c->pw_enabled && c->opts.polarization && !c->opts.rd_only && !c->opts.polar_ewald; }
+inline bool wolf_field_on(const mpmc_ctx *c) { return c->kept.pw_enabled && c->opts.polarization && !c->opts.rd_only && !c->opts.polar_ewald; }
 void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Feynman-Hibbs fields of the pair parameters (evaluate.cpp)
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);

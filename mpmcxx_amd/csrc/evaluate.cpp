@@ -12,68 +12,47 @@ static int build_k_tables(mpmc_ctx *c) {
 	// the set of l-vectors depends on kmax alone: count it, make room (device tables and ONE persistent pinned staging block), fill the
 	// staging block in place and copy asynchronously -- a volume move rebuilds these tables every time, and four blocking copies from
 	// pageable vectors plus a stream synchronisation cost more than the reciprocal-space kernels they feed
-	int K = 0;
-	int l[3];
-	for (l[0] = 0; l[0] <= kmax; l[0]++)
-		for (l[1] = (!l[0] ? 0 : -kmax); l[1] <= kmax; l[1]++)
-			for (l[2] = ((!l[0] && !l[1]) ? 1 : -kmax); l[2] <= kmax; l[2]++)
-				if (l[0] * l[0] + l[1] * l[1] + l[2] * l[2] <= kmax * kmax) K++;
-	if (K > c->cap_K) {
-		dev_free(c, &c->d_kvec, (size_t)c->cap_K);
-		dev_free(c, &c->d_kw, (size_t)c->cap_K);
-		dev_free(c, &c->d_lvec, (size_t)c->cap_K);
-		dev_free(c, &c->d_w_en, (size_t)c->cap_K);
-		c->cap_K = 0;
-		c->lvec_kmax = -1;
-		int rc;
-		if ((rc = dev_alloc(c, &c->d_kvec, (size_t)K)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_kw, (size_t)K)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_lvec, (size_t)K)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_w_en, (size_t)K)) != MPMC_OK) return rc;
-		c->cap_K = K;
-	}
-	if (K > c->cap_sf) { // the structure factors swap buffers with the trial ones on accept: sized on their own
-		dev_free(c, &c->d_sf, (size_t)c->cap_sf);
-		c->cap_sf = 0;
-		int rc = dev_alloc(c, &c->d_sf, (size_t)K);
-		if (rc != MPMC_OK) return rc;
-		c->cap_sf = K;
-	}
+	auto each_lvec = [kmax](auto &&visit) { // the hemisphere of integer l-vectors inside the sphere of radius kmax, in the reference's order
+		int l[3];
+		for (l[0] = 0; l[0] <= kmax; l[0]++)
+			for (l[1] = (!l[0] ? 0 : -kmax); l[1] <= kmax; l[1]++)
+				for (l[2] = ((!l[0] && !l[1]) ? 1 : -kmax); l[2] <= kmax; l[2]++)
+					if (l[0] * l[0] + l[1] * l[1] + l[2] * l[2] <= kmax * kmax) visit(l);
+	};
+	int K = 0, rc;
+	each_lvec([&K](const int *) { K++; });
+	if ((size_t)K > c->d_lvec.cap) c->lvec_kmax = -1; // (a fresh d_lvec holds zeros)
+	if ((rc = c->d_kvec.reserve(c, (size_t)K)) != MPMC_OK) return rc;
+	if ((rc = c->d_kw.reserve(c, (size_t)K)) != MPMC_OK) return rc;
+	if ((rc = c->d_lvec.reserve(c, (size_t)K)) != MPMC_OK) return rc;
+	if ((rc = c->d_w_en.reserve(c, (size_t)K)) != MPMC_OK) return rc;
+	if ((rc = c->d_sf.reserve(c, (size_t)K)) != MPMC_OK) return rc;
 	if (K > 0) {
 		if (c->kstage_in_flight) { // (one rebuild per evaluation at most, and evaluations are waited for: normally long done)
 			HIP_TRY(c, hipEventSynchronize(c->ev_kstage));
 			c->kstage_in_flight = false;
 		}
-		if ((size_t)K > c->cap_kstage) {
-			if (c->h_kstage) HIP_TRY(c, pinned_free(c->h_kstage));
-			c->h_kstage = nullptr;
-			c->cap_kstage = 0;
-			HIP_TRY(c, pinned_alloc(&c->h_kstage, (size_t)K * (2 * sizeof(double4) + sizeof(double) + sizeof(int4))));
-			c->cap_kstage = (size_t)K;
-			if (!c->ev_kstage) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_kstage, hipEventDisableTiming));
-		}
+		if ((rc = c->h_kstage.reserve(c, (size_t)K * (2 * sizeof(double4) + sizeof(double) + sizeof(int4)))) != MPMC_OK) return rc;
+		if (!c->ev_kstage) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_kstage, hipEventDisableTiming));
 		// (the 16-byte types first: behind an odd number of doubles an int4 array would be misaligned -- found by tools/host_asan.sh)
-		double4 *kvec = reinterpret_cast<double4 *>(c->h_kstage), *kw = kvec + c->cap_kstage;
-		int4 *lvec = reinterpret_cast<int4 *>(kw + c->cap_kstage);
-		double *wen = reinterpret_cast<double *>(lvec + c->cap_kstage);
+		double4 *kvec = reinterpret_cast<double4 *>(c->h_kstage.p), *kw = kvec + K;
+		int4 *lvec = reinterpret_cast<int4 *>(kw + K);
+		double *wen = reinterpret_cast<double *>(lvec + K);
 		int n = 0;
-		for (l[0] = 0; l[0] <= kmax; l[0]++)
-			for (l[1] = (!l[0] ? 0 : -kmax); l[1] <= kmax; l[1]++)
-				for (l[2] = ((!l[0] && !l[1]) ? 1 : -kmax); l[2] <= kmax; l[2]++) {
-					if (l[0] * l[0] + l[1] * l[1] + l[2] * l[2] > kmax * kmax) continue;
-					double k[3];
-					for (int p = 0; p < 3; p++) {
-						k[p] = 0;
-						for (int q = 0; q < 3; q++) k[p] += 2.0 * kPi * c->box.r[3 * p + q] * l[q];
-					}
-					const double k2 = k[0] * k[0] + k[1] * k[1] + k[2] * k[2];
-					kvec[n] = make_double4(k[0], k[1], k[2], k2);
-					lvec[n] = make_int4(l[0], l[1], l[2], 0);
-					wen[n] = std::exp(-k2 / (4.0 * alpha * alpha)) / k2;
-					const double g = std::exp(-k2 / (4.0 * ea * ea));
-					kw[n] = make_double4(k[0] / k2 * g, k[1] / k2 * g, k[2] / k2 * g, 0.0);
-					n++;
-				}
+		each_lvec([&](const int *l) {
+			double k[3];
+			for (int p = 0; p < 3; p++) {
+				k[p] = 0;
+				for (int q = 0; q < 3; q++) k[p] += 2.0 * kPi * c->box.r[3 * p + q] * l[q];
+			}
+			const double k2 = k[0] * k[0] + k[1] * k[1] + k[2] * k[2];
+			kvec[n] = make_double4(k[0], k[1], k[2], k2);
+			lvec[n] = make_int4(l[0], l[1], l[2], 0);
+			wen[n] = std::exp(-k2 / (4.0 * alpha * alpha)) / k2;
+			const double g = std::exp(-k2 / (4.0 * ea * ea));
+			kw[n] = make_double4(k[0] / k2 * g, k[1] / k2 * g, k[2] / k2 * g, 0.0);
+			n++;
+		});
 		HIP_TRY(c, hipMemcpyAsync(c->d_kvec, kvec, K * sizeof(double4), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(c->d_kw, kw, K * sizeof(double4), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(c->d_w_en, wen, K * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -96,32 +75,22 @@ constexpr int kSingleLaunchTiles = 32; // <= 2048 atoms (528 tile pairs): LJ-onl
 static int ensure_polar_buffers(mpmc_ctx *c) {
 	const size_t np = (size_t)c->max_pad;
 	int rc;
-	if (!c->d_e_static) {
-		if ((rc = dev_alloc(c, &c->d_e_static, 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_mu[0], 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_mu[1], 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_e_induced, 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_rrms, np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_e_recip_part, recip_slices_capacity(np))) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_e_real, 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_e_real_trial, 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_gs_ul, 6 * np)) != MPMC_OK) return rc; // Gauss-Seidel sweeps: fields of the tiles above / below
-		if ((rc = dev_alloc(c, &c->d_palmo_f, 3 * np)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_palmo_change, 3 * np)) != MPMC_OK) return rc;
-		// (dev_alloc zero-fills on the context's stream; nothing in this library touches the null stream, which is unordered against
-		// our non-blocking streams)
-	}
+	if ((rc = c->d_e_static.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_mu[0].reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_mu[1].reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_e_induced.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_rrms.reserve(c, np)) != MPMC_OK) return rc;
+	if ((rc = c->d_e_recip_part.reserve(c, recip_slices_capacity(np))) != MPMC_OK) return rc;
+	if ((rc = c->d_e_real.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_e_real_trial.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_gs_ul.reserve(c, 6 * np)) != MPMC_OK) return rc; // Gauss-Seidel sweeps: fields of the tiles above / below
+	if ((rc = c->d_palmo_f.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_palmo_change.reserve(c, 3 * np)) != MPMC_OK) return rc;
 	// per-atom partial slots: one per source tile (symmetric kernels) -- also covers the n_split <= n_tiles slots of the matrix-free
 	// row kernel -- and never fewer than the kDenseChunks row chunks the dense matrix-vector product writes (small systems have fewer
 	// tiles than that: the dense solver used to write past the end of this buffer, into the matrix that was allocated right behind it)
 	const size_t need = (size_t)std::max(c->n_tiles, kDenseChunks) * c->n_pad * 3;
-	if (need > c->cap_part) {
-		dev_free(c, &c->d_part, c->cap_part);
-		c->cap_part = 0;
-		if ((rc = dev_alloc(c, &c->d_part, need)) != MPMC_OK) return rc;
-		c->cap_part = need;
-	}
-	return MPMC_OK;
+	return c->d_part.reserve(c, need);
 }
 
 // decide how the dipole iteration runs and (COMPACT) make room for the tensor store
@@ -134,31 +103,21 @@ static int resolve_solver(mpmc_ctx *c) {
 	}
 	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
 	if (want == MPMC_SOLVER_AUTO) {
-		const size_t budget_mb = (size_t)c->tune.tensor_budget_mb;
+		const size_t budget_mb = (size_t)c->kept.tune.tensor_budget_mb;
 		want = (need * sizeof(double2) <= budget_mb * (size_t)1048576) ? MPMC_SOLVER_COMPACT : MPMC_SOLVER_MATRIX_FREE;
 		// building the store costs about as much as three iterations save (0.10 ms against 0.03 ms per iteration at 10 000 atoms)
 		if (c->opts.polar_precision == 0.0 && c->opts.polar_max_iter <= 3) want = MPMC_SOLVER_MATRIX_FREE;
 	}
 	if (want == MPMC_SOLVER_DENSE) { // the reference's layout, on request only: (3 n_pad)^2 doubles
-		const size_t nd = (size_t)3 * c->n_pad * (size_t)3 * c->n_pad;
-		if (nd > c->cap_adense) {
-			dev_free(c, &c->d_adense, c->cap_adense);
-			c->cap_adense = 0;
-			int rc = dev_alloc(c, &c->d_adense, nd);
-			if (rc != MPMC_OK) return rc;
-			c->cap_adense = nd;
-		}
+		const int rc = c->d_adense.reserve(c, (size_t)3 * c->n_pad * (size_t)3 * c->n_pad);
+		if (rc != MPMC_OK) return rc;
 	}
-	if (want == MPMC_SOLVER_COMPACT && need > c->cap_ab) {
-		dev_free(c, &c->d_ab, c->cap_ab);
-		c->cap_ab = 0;
-		int rc = dev_alloc(c, &c->d_ab, need);
+	if (want == MPMC_SOLVER_COMPACT) {
+		const int rc = c->d_ab.reserve(c, need);
 		if (rc != MPMC_OK) {
 			if (c->opts.solver == MPMC_SOLVER_COMPACT) return rc; // explicitly requested: report
 			(void)hipGetLastError();
 			want = MPMC_SOLVER_MATRIX_FREE; // AUTO: fall back to recomputing the tensors (still the HIP path)
-		} else {
-			c->cap_ab = need;
 		}
 	}
 	c->solver_used = want;
@@ -219,11 +178,14 @@ RecipDev mpmc::recip_view(const mpmc_ctx *c) {
 	r.kvec = c->d_kvec;
 	r.w_en = c->d_w_en;
 	r.kw = c->d_kw;
-	r.lvec = c->tune.no_recip_tab ? nullptr : c->d_lvec;
+	r.lvec = c->kept.tune.no_recip_tab ? nullptr : c->d_lvec;
 	r.sf = c->d_sf;
 	r.K = c->K;
 	return r;
 }
+
+// the tile pairs' common-image lattice vectors, or null when the tile-pair-wide images are switched off (the kernels then take every image per pair)
+static inline const double4 *shift_view(const mpmc_ctx *c) { return (c->kept.tune.no_uniform || c->kept.tune.no_classes) ? nullptr : c->d_tp_shift.p; }
 
 // the Wolf / Feynman-Hibbs fields of the pair parameters (pair sweep and per-move delta kernels)
 void mpmc::ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on) {
@@ -243,9 +205,9 @@ void mpmc::ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on) {
 // two waves per tile pair in the fast pair sweep (half-length workgroups): by default for the LAST quarter of the work table only -- a lone
 // launch drains on units half as long, an ensemble (whose other kernels fill the drain anyway) pays the halved form's overhead on a quarter of
 // the work.  The rule is a function of the table alone (never of the call): an evaluation gives the same bits alone and inside an ensemble.
-static inline int sweep_split_mode(const mpmc_ctx *c) { return c->tune.pair_split < 0 ? 2 : (c->tune.pair_split != 0 ? 1 : 0); }
+static inline int sweep_split_mode(const mpmc_ctx *c) { return c->kept.tune.pair_split < 0 ? 2 : (c->kept.tune.pair_split != 0 ? 1 : 0); }
 static inline int sweep_split_tail(const mpmc_ctx *c) {
-	const int permille = c->tune.pair_split_tail >= 0 ? c->tune.pair_split_tail : kSweepSplitTailPermille;
+	const int permille = c->kept.tune.pair_split_tail >= 0 ? c->kept.tune.pair_split_tail : kSweepSplitTailPermille;
 	return (int)((long long)c->n_sweep_blocks * permille / 1000);
 }
 
@@ -258,16 +220,14 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 	const int np = chol_padded(n_pol);
 	const size_t elems = (size_t)np * (size_t)np, bytes = elems * sizeof(double);
 	int rc;
-	if (!c->d_chol_status) {
-		if ((rc = dev_alloc(c, &c->d_chol_status, (size_t)4)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_chol_info, (size_t)4)) != MPMC_OK) return rc;
-		HIP_TRY(c, pinned_alloc(&c->h_chol_info, 4 * sizeof(double)));
-	}
+	if ((rc = c->d_chol_status.reserve(c, 4)) != MPMC_OK) return rc;
+	if ((rc = c->d_chol_info.reserve(c, 4)) != MPMC_OK) return rc;
+	if ((rc = c->h_chol_info.reserve(c, 4)) != MPMC_OK) return rc;
 	{ // size guard: the factor must fit what the device has free (or the budget of the tuning switch)
 		size_t free_b = 0, total_b = 0;
 		HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-		size_t avail = free_b + c->cap_chol * sizeof(double);
-		if (c->tune.direct_budget_mb >= 0) avail = std::min(avail, (size_t)c->tune.direct_budget_mb * (size_t)1048576);
+		size_t avail = free_b + c->d_chol.cap * sizeof(double);
+		if (c->kept.tune.direct_budget_mb >= 0) avail = std::min(avail, (size_t)c->kept.tune.direct_budget_mb * (size_t)1048576);
 		if (bytes > avail) {
 			char buf[256];
 			std::snprintf(buf, sizeof buf, "direct dipole solve: the factor of %d unknowns needs %.1f MB (%d x %d doubles), %.1f MB are available", 3 * n_pol,
@@ -275,28 +235,14 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 			return fail(c, MPMC_ERR_MEMORY, buf);
 		}
 	}
-	if (elems > c->cap_chol) {
-		dev_free(c, &c->d_chol, c->cap_chol);
-		c->cap_chol = 0;
-		if (dev_alloc(c, &c->d_chol, elems) != MPMC_OK) {
-			(void)hipGetLastError();
-			c->d_chol = nullptr;
-			return fail(c, MPMC_ERR_MEMORY, "direct dipole solve: cannot allocate the factor (" + std::to_string(bytes) + " bytes): " + c->err);
-		}
-		c->cap_chol = elems;
+	if (c->d_chol.reserve(c, elems) != MPMC_OK) {
+		(void)hipGetLastError();
+		return fail(c, MPMC_ERR_MEMORY, "direct dipole solve: cannot allocate the factor (" + std::to_string(bytes) + " bytes): " + c->err);
 	}
-	if ((size_t)2 * np > c->cap_chol_v) {
-		dev_free(c, &c->d_chol_v, c->cap_chol_v);
-		c->cap_chol_v = 0;
-		if ((rc = dev_alloc(c, &c->d_chol_v, (size_t)2 * np + 1)) != MPMC_OK) return rc;
-		c->cap_chol_v = (size_t)2 * np + 1;
-	}
-	if ((size_t)n_pol > c->cap_chol_list) {
-		dev_free(c, &c->d_chol_list, c->cap_chol_list);
-		c->cap_chol_list = 0;
-		if ((rc = dev_alloc(c, &c->d_chol_list, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		c->cap_chol_list = (size_t)c->max_pad;
-	}
+	// (v0 = [0, np) and v1 = [np, 2 np); the one element more is a spare that no kernel addresses, kept so that the bytes held stay what they were)
+	if ((rc = c->d_chol_v.reserve(c, (size_t)2 * np, (size_t)2 * np + 1)) != MPMC_OK) return rc;
+	// (room for every slot of the context: the number of polarizable atoms changes with the atom list and can then never outgrow it)
+	if ((rc = c->d_chol_list.reserve(c, (size_t)n_pol, (size_t)c->max_pad)) != MPMC_OK) return rc;
 	c->mu_cur = 0;
 	double *mu = c->d_mu[0], *v0 = c->d_chol_v, *v1 = c->d_chol_v + np;
 	HIP_TRY(c, hipMemsetAsync(c->d_chol_status, 0, sizeof(int), st));
@@ -316,7 +262,7 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 	}
 	{ // the residual from an independent product: one matrix-free contraction, -(A_off mu) into d_e_induced (d_mu[1] is scratch)
 		ProfScope p(c, MPMC_K_REDUCE);
-		launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift,
+		launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, shift_view(c),
 		                          c->n_tile_pairs, nullptr, c->d_part, c->opts.polar_damp, nullptr);
 		launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, c->d_mu[1], c->d_e_induced, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
 		launch_chol_finish(st, at, mu, c->d_e_static, c->d_e_induced, c->d_chol_status, c->d_chol_info);
@@ -324,7 +270,7 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipMemcpyAsync(c->h_chol_info, c->d_chol_info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
 	c->direct.n_unknowns = 3 * (int64_t)n_pol;
-	c->direct.factor_bytes = (int64_t)(c->cap_chol * sizeof(double));
+	c->direct.factor_bytes = (int64_t)(c->d_chol.cap * sizeof(double));
 	c->direct_ran = true;
 	return MPMC_OK;
 }
@@ -354,7 +300,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 
 	c->last_was_single = false;
 	c->spin_on_post = false;
-	if (c->tune.single_launch && mask == (RUN_PAIR | RUN_ATOMTERMS) && !o.feynman_hibbs && c->n_tiles <= kSingleLaunchTiles && !c->prof && !static_ride) {
+	if (c->kept.tune.single_launch && mask == (RUN_PAIR | RUN_ATOMTERMS) && !o.feynman_hibbs && c->n_tiles <= kSingleLaunchTiles && !c->kept.prof && !static_ride) {
 		// small LJ box (BASELINE configs[1]): the whole evaluation is one launch -- pair sweep without classes, the block that finishes last
 		// folds the partials into the pinned result vector; the LRC terms are the cached position-independent ones
 		FusedParams fp{};
@@ -396,8 +342,8 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	// evaluation at a time the fork is worth 1.5 %.  The choice of streams does not touch the arithmetic.)
 	// Only for evaluations with a dipole solve: there the side work is 5 % of the evaluation; a 10 000-atom LJ + Ewald evaluation (sweep 95 us,
 	// reciprocal space 25 us) loses 4 % in flight without the overlap (9365 against 9600-9960 evaluations/s).
-	c->two_streams = (c->tune.stream_mode == 1) ||
-	                 (c->tune.stream_mode < 0 && c->n_tile_pairs > kOneStreamMaxPairs &&
+	c->two_streams = (c->kept.tune.stream_mode == 1) ||
+	                 (c->kept.tune.stream_mode < 0 && c->n_tile_pairs > kOneStreamMaxPairs &&
 	                  !((mask & RUN_SOLVE) && c->inflight_hint >= kOneStreamMinInflight));
 	const bool side_fork = c->two_streams && (need_sf || need_intra);
 	bool panel_side = false; // the panel table of the Jacobi contraction is being built on the side stream
@@ -413,12 +359,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 			ProfScope p(c, MPMC_K_RECIP, s2);
 			if (need_sf) {
 				const size_t need_part = (size_t)c->n_tiles * (size_t)c->K;
-				if (rcp.lvec && o.ewald_kmax <= kRecipTabMaxK && need_part > c->cap_sf_part) {
-					dev_free(c, &c->d_sf_part, c->cap_sf_part);
-					c->cap_sf_part = 0;
-					if ((side_rc = dev_alloc(c, &c->d_sf_part, need_part)) != MPMC_OK) return;
-					c->cap_sf_part = need_part;
-				}
+				if (rcp.lvec && o.ewald_kmax <= kRecipTabMaxK && (side_rc = c->d_sf_part.reserve(c, need_part)) != MPMC_OK) return;
 				launch_recip_sf(s2, at, c->box, rcp, o.ewald_kmax, c->d_sf_part);
 			}
 			if (mask & RUN_RECIP) launch_recip_energy(s2, rcp, c->box, c->d_scal); // (the LRC and self terms are cached: prepare())
@@ -428,7 +369,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 			launch_field_recip(s2, at, c->box, rcp, o.ewald_kmax, c->d_e_recip_part);
 		}
 	};
-	const bool side_deferred = side_work && side_fork && (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) != 0 && c->tune.side_after_sweep;
+	const bool side_deferred = side_work && side_fork && (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) != 0 && c->kept.tune.side_after_sweep;
 	if (side_work && !side_deferred) {
 		enqueue_side_work(side_fork ? fork_side(c) : st);
 		if (side_rc != MPMC_OK) return side_rc;
@@ -439,9 +380,9 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		// tile-pair classes from this configuration's tile bounding boxes
 		{
 			ProfScope pc(c, MPMC_K_CLASSES);
-			if (c->tune.no_classes) HIP_TRY(c, hipMemsetAsync(c->d_cls, 0, (size_t)c->n_tile_pairs * sizeof(int), st));
+			if (c->kept.tune.no_classes) HIP_TRY(c, hipMemsetAsync(c->d_cls, 0, (size_t)c->n_tile_pairs * sizeof(int), st));
 			else launch_tile_classes(st, at, c->box, c->d_tile_pairs, c->n_tile_pairs, (o.polarization && !o.rd_only) ? o.polar_damp : 0.0,
-			                         c->d_tile_bounds, c->d_cls, c->tune.no_uniform ? nullptr : c->d_tp_shift, c->sort_origin_f, kTholeFarX);
+			                         c->d_tile_bounds, c->d_cls, c->kept.tune.no_uniform ? nullptr : c->d_tp_shift, c->sort_origin_f, kTholeFarX);
 		}
 		FusedParams fp;
 		fp.ewald_alpha = c->ewald_alpha;
@@ -454,42 +395,27 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		fp.do_thole = compact ? 1 : 0;
 		ext_params(c, fp, (o.wolf && (mask & RUN_WOLF)) != 0);
 		fp.thole_far_x = kTholeFarX;
-		fp.pair_waves = c->tune.pair_waves ? c->tune.pair_waves : (c->n_tile_pairs <= kPairSplitMax ? 4 : 1);
+		fp.pair_waves = c->kept.tune.pair_waves ? c->kept.tune.pair_waves : (c->n_tile_pairs <= kPairSplitMax ? 4 : 1);
 		fp.store_only = ((mask & RUN_STORE) && !(mask & (RUN_PAIR | RUN_FIELD))) ? 1 : 0;
 		fp.touch_n = fp.store_only ? c->touch_n : -1;
 		for (int k = 0; k < 8; k++) fp.touch[k] = c->touch[k];
 		if (!fp.store_only && compact) c->store_dirty_tiles.clear(); // a full sweep rebuilds every stored tile pair
 		// panels of the Jacobi contraction: two tile pairs of equal class behind one j-tile per workgroup (compact solver)
 		c->panels_built = false;
-		if (compact && c->tune.use_panels && !c->tune.no_classes && !c->tune.no_uniform && c->n_tiles >= 3) {
+		if (compact && c->kept.tune.use_panels && !c->kept.tune.no_classes && !c->kept.tune.no_uniform && c->n_tiles >= 3) {
 			if (c->seg_tiles != c->n_tiles) { // the table's layout depends on the tile count only
 				std::vector<int> seg((size_t)c->n_tiles + 1, 0);
 				for (int J = 0; J < c->n_tiles; J++) seg[J + 1] = seg[J] + panel_segment_entries(J);
-				if ((size_t)c->n_tiles + 1 > c->cap_seg) {
-					dev_free(c, &c->d_seg, c->cap_seg);
-					c->cap_seg = 0;
-					if ((rc = dev_alloc(c, &c->d_seg, (size_t)c->n_tiles + 1)) != MPMC_OK) return rc;
-					c->cap_seg = (size_t)c->n_tiles + 1;
-				}
+				if ((rc = c->d_seg.reserve(c, seg.size())) != MPMC_OK) return rc;
 				HIP_TRY(c, hipMemcpyAsync(c->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, st));
 				HIP_TRY(c, hipStreamSynchronize(st)); // `seg` dies here
 				c->n_panel_entries = seg[c->n_tiles];
 				c->seg_tiles = c->n_tiles;
 			}
 			const size_t need = (size_t)c->n_panel_entries;
-			if (need > c->cap_panels) {
-				dev_free(c, &c->d_panels, c->cap_panels);
-				dev_free(c, &c->d_gpart, c->cap_panels * kTile * 3);
-				c->cap_panels = 0;
-				if ((rc = dev_alloc(c, &c->d_panels, need)) != MPMC_OK) return rc;
-				if ((rc = dev_alloc(c, &c->d_gpart, need * kTile * 3)) != MPMC_OK) return rc;
-				c->cap_panels = need;
-				if (c->tune.trace_panel) {
-					if (c->d_trace) (void)hipFree(c->d_trace);
-					c->d_trace = nullptr;
-					if ((rc = dev_alloc(c, &c->d_trace, need * 4)) != MPMC_OK) return rc;
-				}
-			}
+			if ((rc = c->d_panels.reserve(c, need)) != MPMC_OK) return rc;
+			if ((rc = c->d_gpart.reserve(c, need * kTile * 3)) != MPMC_OK) return rc;
+			if (c->kept.tune.trace_panel && (rc = c->d_trace.reserve(c, need * 4)) != MPMC_OK) return rc;
 			// the table is needed by the first Jacobi launch only: it is made beside the pair sweep (side stream, joined after the sweep)
 			panel_side = c->two_streams;
 			if (!panel_side) {
@@ -508,14 +434,14 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		// and, by default, where the table has more than kSweepMinPairs tile pairs (below that the 64 dependent steps of its one wave per
 		// tile pair are a latency chain: four waves per tile pair in k_pair_fused); the tile pairs with a special atom, which it skips,
 		// go through k_pair_fused on their list
-		const bool sweep = c->tune.pair_kernel != 1 && c->d_sweep_blocks && (c->tune.pair_kernel == 2 || c->n_tile_pairs > kSweepMinPairs) &&
+		const bool sweep = c->kept.tune.pair_kernel != 1 && c->d_sweep_blocks && (c->kept.tune.pair_kernel == 2 || c->n_tile_pairs > kSweepMinPairs) &&
 		                   pair_sweep_covers(c->box, fp, c->ewald_alpha);
 		c->last_pair_was_sweep = sweep;
 		if (sweep) {
 			launch_pair_sweep(st, at, c->box, fp, c->n_molecules != c->n, c->d_sweep_blocks, c->n_sweep_blocks, c->d_cls,
-			                  (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift, c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->tune.fast_geometry,
-			                  (side_deferred || panel_side) ? c->tune.sweep_lds_pad : 0);
+			                  shift_view(c), c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
+			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->kept.tune.fast_geometry,
+			                  (side_deferred || panel_side) ? c->kept.tune.sweep_lds_pad : 0);
 			if (c->n_generic > 0)
 				launch_pair_fused(st, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_generic, c->d_block_part, c->d_block_cnt, c->d_part,
 				                  compact ? c->d_ab : nullptr, c->d_generic_list);
@@ -547,7 +473,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		ProfScope p(c, MPMC_K_FIELD);
 		c->mu_cur = 0;
 		if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
-			launch_wolf_field(st, at, c->box, wolf_field_params(c->pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
+			launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
 		launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
 		                      c->d_mu[0], c->d_e_real);
 		c->e_real_valid = (mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
@@ -569,7 +495,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		const int want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
 		const double allowed = by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
 		const bool dense = (c->solver_used == MPMC_SOLVER_DENSE) && !o.polar_gs;
-		const bool dense_sym = dense && c->tune.dense_symmetric;
+		const bool dense_sym = dense && c->kept.tune.dense_symmetric;
 		const int iter_slots = (dense && !dense_sym) ? kDenseChunks : c->n_tiles;
 		if (dense) { // thole_amatrix into device memory, once per evaluation (the positions changed)
 			ProfScope p(c, MPMC_K_TENSOR);
@@ -589,13 +515,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 			c->h_flag[2] = c->h_flag[3] = 0; // (nothing of an earlier solve can still be in flight: every evaluation is waited for)
 		}
 		if (o.polar_gs) { // the in-tile blocks of the sweeps: positions and polarizabilities only, once per evaluation
-			const size_t need = gs_block_store_elements(c->n_tiles);
-			if (need > c->cap_gs_blocks) {
-				dev_free(c, &c->d_gs_blocks, c->cap_gs_blocks);
-				c->cap_gs_blocks = 0;
-				if ((rc = dev_alloc(c, &c->d_gs_blocks, need)) != MPMC_OK) return rc;
-				c->cap_gs_blocks = need;
-			}
+			if ((rc = c->d_gs_blocks.reserve(c, gs_block_store_elements(c->n_tiles))) != MPMC_OK) return rc;
 			ProfScope p(c, MPMC_K_TENSOR);
 			launch_gs_blocks(st, at, c->box, o.polar_damp, c->d_gs_blocks);
 		}
@@ -615,7 +535,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 				{
 					ProfScope p(c, MPMC_K_DIPOLE_ITER);
 					launch_gs_sweep(st, at, c->box, o.polar_damp, c->d_e_static, mu, c->d_e_induced, c->d_part, c->d_tile_pairs, c->d_cls,
-					                (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift, c->n_tile_pairs, c->d_gs_ul, c->d_gs_ul + 3 * (size_t)c->max_pad, c->d_gs_blocks);
+					                shift_view(c), c->n_tile_pairs, c->d_gs_ul, c->d_gs_ul + 3 * (size_t)c->max_pad, c->d_gs_blocks);
 				}
 				if (want_rrms) {
 					ProfScope p(c, MPMC_K_REDUCE);
@@ -641,12 +561,12 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 					                         c->n_panel_entries, c->d_ab, c->d_part, c->d_gpart, converged, c->d_trace);
 				else
 					launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
-					                          (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift, c->n_tile_pairs, c->d_ab, c->d_part, o.polar_damp,
+					                          shift_view(c), c->n_tile_pairs, c->d_ab, c->d_part, o.polar_damp,
 					                          converged);
 			} else { // matrix-free: the same symmetric tile-pair walk with nothing stored (null store => damped tensors rebuilt)
 				ProfScope p(c, MPMC_K_DIPOLE_ITER);
 				launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
-				                          (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift, c->n_tile_pairs, nullptr, c->d_part, o.polar_damp,
+				                          shift_view(c), c->n_tile_pairs, nullptr, c->d_part, o.polar_damp,
 				                          converged);
 			}
 			{
@@ -669,7 +589,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 					if (seen) {
 						done_at = hf[1];
 					} else {
-						c->n_stream_syncs++;
+						c->kept.n_stream_syncs++;
 						HIP_TRY(c, hipMemcpyAsync(c->h_flag, ctl + 1, sizeof(int), hipMemcpyDeviceToHost, st));
 						HIP_TRY(c, hipStreamSynchronize(st));
 						done_at = *c->h_flag;
@@ -697,11 +617,11 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		// induced field that very field: zero to the bit, and nothing runs here.  Under Gauss-Seidel sweeps the dipoles are the swept ones:
 		// F = -(A_off mu) through the matrix-free Jacobi contraction (Gauss-Seidel contexts store nothing), against the induced field the
 		// last sweep used.  A failed iteration leaves the correction at 0 (:3483-3488).
-		if (c->palmo_enabled && o.polar_gs && !c->failed) {
+		if (c->kept.palmo_enabled && o.polar_gs && !c->failed) {
 			double *mu = c->d_mu[c->mu_cur];
 			{
 				ProfScope p(c, MPMC_K_DIPOLE_ITER);
-				launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift,
+				launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, shift_view(c),
 				                          c->n_tile_pairs, nullptr, c->d_part, o.polar_damp, nullptr);
 			}
 			ProfScope p(c, MPMC_K_REDUCE);
@@ -734,7 +654,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 	// harvest needs an idle stream), are waited for the ordinary way
 	// (round 4: long evaluations are polled for as well, with a budget of a few of their own durations -- one evaluation at a time the
 	// posted launch number is seen ~10 us before hipStreamSynchronize returns; an ensemble's first wait outlasts the budget and synchronises)
-	c->spin_on_post = c->ev_used.empty() && (c->tune.poll_long || c->n_tile_pairs <= kOneStreamMaxPairs);
+	c->spin_on_post = c->ev_used.empty() && (c->kept.tune.poll_long || c->n_tile_pairs <= kOneStreamMaxPairs);
 	c->poll_budget_us = (c->n_tile_pairs <= kOneStreamMaxPairs) ? 1000 : 4000;
 	c->pending = true;
 	return MPMC_OK;
@@ -792,9 +712,9 @@ extern "C" int mpmc_debug_time_pair(mpmc_ctx *c, int reps, double *ms_per_launch
 	auto launch = [&] {
 		if (c->last_pair_was_sweep) {
 			launch_pair_sweep(c->stream, at, c->box, fp, c->n_molecules != c->n, c->d_sweep_blocks, c->n_sweep_blocks, c->d_cls,
-			                  (c->tune.no_uniform || c->tune.no_classes) ? nullptr : c->d_tp_shift, c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->tune.fast_geometry,
-			                  c->two_streams ? c->tune.sweep_lds_pad : 0, timed ? c->debug_panel_replicas : 1);
+			                  shift_view(c), c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
+			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->kept.tune.fast_geometry,
+			                  c->two_streams ? c->kept.tune.sweep_lds_pad : 0, timed ? c->debug_panel_replicas : 1);
 			if (c->n_generic > 0)
 				launch_pair_fused(c->stream, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_generic, c->d_block_part, c->d_block_cnt, c->d_part,
 				                  compact ? c->d_ab : nullptr, c->d_generic_list);
@@ -834,8 +754,8 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->static_ride_gen = 0;
 		return fail(c, MPMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 	};
-	hipError_t werr = c->tune.fail_next_wait ? hipErrorUnknown : hipSetDevice(c->device);
-	c->tune.fail_next_wait = 0;
+	hipError_t werr = c->kept.tune.fail_next_wait ? hipErrorUnknown : hipSetDevice(c->device);
+	c->kept.tune.fail_next_wait = 0;
 	if (werr != hipSuccess) return abandon(werr, "mpmc_energy_wait: hipSetDevice");
 	bool seen = false;
 	if (c->last_was_single || c->spin_on_post) {
@@ -846,10 +766,10 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		seen = poll_posted(c, [&] { return *flag == want; }, std::chrono::microseconds(c->last_was_single ? 200 : c->poll_budget_us));
 	}
 	if (!seen) {
-		c->n_stream_syncs++;
+		c->kept.n_stream_syncs++;
 		werr = hipStreamSynchronize(c->sync_stream ? c->sync_stream : c->stream);
 		if (werr != hipSuccess) return abandon(werr, "mpmc_energy_wait: hipStreamSynchronize");
-	} else if (c->tune.poll_retire && c->n_tile_pairs > kOneStreamMaxPairs) {
+	} else if (c->kept.tune.poll_retire && c->n_tile_pairs > kOneStreamMaxPairs) {
 		// the results are in, but the runtime has not been told: a stream that is never synchronised keeps its finished commands, and
 		// the next asynchronous copy on it pays for the backlog (measured with positions handed over in host memory: 900 against 966
 		// evaluations/s).  A query is enough to let it retire them.  Long evaluations only: the query costs a few microseconds, which is
@@ -926,8 +846,8 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 		m |= c->opts.wolf ? RUN_WOLF : RUN_RECIP; // coulombic() :1404-1413: Wolf replaces real + reciprocal + self
 		if (c->opts.polarization) m |= RUN_FIELD | RUN_SOLVE;
 	}
-	if (c->tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
-	if (c->de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
+	if (c->kept.tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
+	if (c->kept.de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
 	return m;
 }
 
@@ -1001,7 +921,7 @@ extern "C" int mpmc_polar(mpmc_ctx *c, double *out) {
 }
 extern "C" int mpmc_axilrod_teller(mpmc_ctx *c, double *out) {
 	if (!c) return MPMC_ERR_ARG;
-	if (!c->tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_axilrod_teller: the term is off (mpmc_set_axilrod_teller)");
+	if (!c->kept.tb_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_axilrod_teller: the term is off (mpmc_set_axilrod_teller)");
 	mpmc_result r;
 	int rc = run_piece(c, RUN_THREE_BODY, &r);
 	if (rc == MPMC_OK && out) *out = r.three_body_energy;
@@ -1009,7 +929,7 @@ extern "C" int mpmc_axilrod_teller(mpmc_ctx *c, double *out) {
 }
 extern "C" int mpmc_disp_expansion(mpmc_ctx *c, double *out) {
 	if (!c) return MPMC_ERR_ARG;
-	if (!c->de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_disp_expansion: the term is off (mpmc_set_disp_expansion)");
+	if (!c->kept.de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_disp_expansion: the term is off (mpmc_set_disp_expansion)");
 	mpmc_result r;
 	int rc = run_piece(c, RUN_DISP, &r);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
@@ -1044,12 +964,7 @@ extern "C" int mpmc_thole_amatrix(mpmc_ctx *c, int row0, int nrows, double *a) {
 	if (rc != MPMC_OK) return rc;
 	if (row0 % 3 || nrows % 3 || row0 + nrows > 3 * c->n) return fail(c, MPMC_ERR_ARG, "mpmc_thole_amatrix: rows must cover whole atoms (multiples of 3) inside 3N");
 	const size_t need = (size_t)nrows * 3 * c->n;
-	if (need > c->cap_arows) {
-		dev_free(c, &c->d_arows, c->cap_arows);
-		c->cap_arows = 0;
-		if ((rc = dev_alloc(c, &c->d_arows, need)) != MPMC_OK) return rc;
-		c->cap_arows = need;
-	}
+	if ((rc = c->d_arows.reserve(c, need)) != MPMC_OK) return rc;
 	{
 		ProfScope p(c, MPMC_K_TENSOR);
 		launch_amatrix_rows(c->stream, atoms_view(c), c->d_slot_of, c->box, c->opts.polar_damp, row0, nrows, c->d_arows);

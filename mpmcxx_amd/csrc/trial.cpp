@@ -12,27 +12,21 @@ using namespace mpmc;
 constexpr size_t kMvBlobBytes = MPMC_TRIAL_MAX_ATOMS * (2 * sizeof(int) + sizeof(double4));
 static int ensure_trial_buffers(mpmc_ctx *c) {
 	int rc;
-	if (!c->d_mv_blob) {
-		if ((rc = dev_alloc(c, &c->d_mv_blob, kMvBlobBytes)) != MPMC_OK) return rc;
-		c->d_mv_new = reinterpret_cast<double4 *>(c->d_mv_blob); // 32-byte records first (alignment), then the two int lists
+	if (!c->h_mv_blob) { // (the last step of the first use)
+		if ((rc = c->d_mv_blob.reserve(c, kMvBlobBytes)) != MPMC_OK) return rc;
+		c->d_mv_new = reinterpret_cast<double4 *>(c->d_mv_blob.p); // 32-byte records first (alignment), then the two int lists
 		c->d_mv_slot = reinterpret_cast<int *>(c->d_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		c->d_mv_orig = c->d_mv_slot + MPMC_TRIAL_MAX_ATOMS;
-		if ((rc = dev_alloc(c, &c->d_moved_idx, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = dev_alloc(c, &c->d_delta_out, (size_t)9)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body and disp-expansion deltas
+		if ((rc = c->d_moved_idx.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+		if ((rc = c->d_delta_out.reserve(c, 9)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body and disp-expansion deltas
 		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + 5);
 		HIP_TRY(c, hipMemsetAsync(c->d_moved_idx, 0xff, (size_t)c->max_pad * sizeof(int), c->stream)); // all -1; on our stream (ordered before the first delta kernel)
-		HIP_TRY(c, pinned_alloc(&c->h_delta_out, 10 * sizeof(double)));
+		if ((rc = c->h_delta_out.reserve(c, 10)) != MPMC_OK) return rc;
 		c->h_delta_out[8] = c->h_delta_out[9] = 0.0;
 		c->h_delta_cnt = reinterpret_cast<long long *>(c->h_delta_out + 5);
-		HIP_TRY(c, pinned_alloc(&c->h_mv_blob, kMvBlobBytes));
+		if ((rc = c->h_mv_blob.reserve(c, kMvBlobBytes)) != MPMC_OK) return rc;
 	}
-	if (c->K > c->cap_sf_trial) {
-		dev_free(c, &c->d_sf_trial, (size_t)c->cap_sf_trial);
-		c->cap_sf_trial = 0;
-		if ((rc = dev_alloc(c, &c->d_sf_trial, (size_t)std::max(c->K, 1))) != MPMC_OK) return rc;
-		c->cap_sf_trial = std::max(c->K, 1);
-	}
-	return MPMC_OK;
+	return c->d_sf_trial.reserve(c, (size_t)c->K);
 }
 
 extern "C" int mpmc_trial_begin(mpmc_ctx *c, int first, int count, const double *new_pos) {
@@ -70,7 +64,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	const bool polar = o.polarization && !o.rd_only;
 	const int m = c->trial_count;
 	c->trial_polar_delta = false;
-	const bool no_polar_delta = c->tune.no_polar_delta;
+	const bool no_polar_delta = c->kept.tune.no_polar_delta;
 	// (Wolf electrostatics and the Feynman-Hibbs corrections are per-pair terms like the others: the delta kernels carry them; a
 	// polarizable box under Wolf keeps the full evaluation -- its static field is the Ewald one, outside the reference's own combinations;
 	// so does a box whose dipoles are solved directly, polar_iterative off: the matrix is rebuilt and factored again anyway)
@@ -92,9 +86,9 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	hipStream_t st = c->stream;
 	// short moves of non-polarizable boxes travel in the kernel arguments: no staging copy (a trial is launch-bound on the host: every
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
-	const bool no_inline = c->tune.no_inline_move;
+	const bool no_inline = c->kept.tune.no_inline_move;
 	// (the three-body and disp-expansion deltas read the moved atoms from the device lists: a box with either term always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->tb_enabled && !c->de_enabled;
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled;
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -108,7 +102,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 			for (int d = 0; d < 4; d++) c->mv_inline.nw[t][d] = 0.0;
 		}
 	} else { // one pinned staging record, one host-to-device copy
-		double4 *nw = reinterpret_cast<double4 *>(c->h_mv_blob);
+		double4 *nw = reinterpret_cast<double4 *>(c->h_mv_blob.p);
 		int *slots = reinterpret_cast<int *>(c->h_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		int *origs = slots + MPMC_TRIAL_MAX_ATOMS;
 		for (int t = 0; t < m; t++) {
@@ -120,7 +114,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		HIP_TRY(c, hipMemcpyAsync(c->d_mv_blob, c->h_mv_blob, kMvBlobBytes, hipMemcpyHostToDevice, st));
 	}
 	const int do_es = o.rd_only ? 0 : 1;
-	if (c->tb_enabled) {
+	if (c->kept.tb_enabled) {
 		// Axilrod-Teller: the change of the triples with a moved atom, O(m N^2), with the accepted positions still resident; its sum lands in
 		// the spare slot 7 of the delta result block, which k_delta_finish copies out in front of the launch number it posts
 		if ((rc = three_body_ready(c)) != MPMC_OK) return rc;
@@ -128,7 +122,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		launch_three_body_delta(st, atoms_view(c), c->d_tb_au, c->box, kThreeBodyScale, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_tb_part,
 		                        c->d_delta_out + 7);
 	}
-	if (c->de_enabled) {
+	if (c->kept.de_enabled) {
 		// disp-expansion: the change of the pairs with a moved atom, O(m N), old positions still resident; into slot 8 of the delta result
 		// block, which k_delta_finish copies out behind the launch number's slot (h_delta_out[9]).  It replaces the LJ delta of launch_delta.
 		if ((rc = disp_ready(c)) != MPMC_OK) return rc;
@@ -154,18 +148,13 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		// atoms) -- then the tensor store is rebuilt for the trial geometry (store-only sweep of the near tile pairs) and the dipoles are
 		// solved from alpha E0 exactly as in a full evaluation (thole_iterative restarts every call, :3547-3560).  What is saved: the
 		// energy / erfc / field arithmetic of the N^2/2 pair sweep and the O(K N) structure factors.
-		const size_t need = (size_t)c->n_tiles * (size_t)m * 3;
-		if (need > c->cap_dk_part) {
-			dev_free(c, &c->d_dk_part, c->cap_dk_part);
-			c->cap_dk_part = 0;
-			if ((rc = dev_alloc(c, &c->d_dk_part, (size_t)c->n_tiles * MPMC_TRIAL_MAX_ATOMS * 3)) != MPMC_OK) return rc;
-			c->cap_dk_part = (size_t)c->n_tiles * MPMC_TRIAL_MAX_ATOMS * 3;
-		}
+		// (room for the longest move at this tile count: a longer move of the same box does not allocate again)
+		if ((rc = c->d_dk_part.reserve(c, (size_t)c->n_tiles * (size_t)m * 3, (size_t)c->n_tiles * MPMC_TRIAL_MAX_ATOMS * 3)) != MPMC_OK) return rc;
 		const AtomsDev at = atoms_view(c);
 		{
 			ProfScope p(c, MPMC_K_FIELD);
 			if (wolf_field_on(c)) // (`polar_wolf`: the same O(m N) difference of thole_field_wolf's pair sum)
-				launch_wolf_field_delta(st, at, c->box, wolf_field_params(c->pw_alpha, c->box.cutoff), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
+				launch_wolf_field_delta(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
 				                        c->d_e_real_trial, c->d_dk_part);
 			else
 				launch_delta_field(st, at, c->box, c->polar_ewald_alpha, o.polar_ewald, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_e_real,
@@ -238,7 +227,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 			seen = poll_posted(c, [&] { return *flag == want; }, std::chrono::microseconds(1000));
 		}
 		if (!seen) {
-			c->n_stream_syncs++;
+			c->kept.n_stream_syncs++;
 			HIP_TRY(c, hipStreamSynchronize(c->stream));
 		}
 		prof_harvest(c);
@@ -246,7 +235,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	const int do_es = c->opts.rd_only ? 0 : 1;
 	const mpmc_result &a = c->last_full;
 	mpmc_result r = a;
-	r.lj_pairs = a.lj_pairs + (c->de_enabled ? c->h_delta_out[9] : c->h_delta_out[0]); // (with the disp-expansion term lj_pairs holds its pair sum)
+	r.lj_pairs = a.lj_pairs + (c->kept.de_enabled ? c->h_delta_out[9] : c->h_delta_out[0]); // (with the disp-expansion term lj_pairs holds its pair sum)
 	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
@@ -261,7 +250,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		r.polar_iterations = solved.polar_iterations;
 		r.iterator_failed = solved.iterator_failed;
 	}
-	if (c->tb_enabled) r.three_body_energy = a.three_body_energy + c->h_delta_out[7];
+	if (c->kept.tb_enabled) r.three_body_energy = a.three_body_energy + c->h_delta_out[7];
 	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
 	r.NU = r.N * r.energy;
 	c->trial_res = r;
@@ -295,8 +284,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 			else launch_commit_positions(c->stream, c->d_xyzq, c->d_mv_slot, c->d_mv_new, m);
 		}
 		HIP_TRY(c, hipGetLastError());
-		std::swap(c->d_sf, c->d_sf_trial); // the trial structure factors become the accepted ones
-		std::swap(c->cap_sf, c->cap_sf_trial); // (d_sf has its own capacity: cap_K sizes the k tables, which do not move)
+		std::swap(c->d_sf, c->d_sf_trial); // the trial structure factors become the accepted ones (each buffer with its own capacity)
 		// (no wait: whatever comes next on this context is enqueued behind the commit on the same stream, and the host mirrors below are
 		// the host's own -- the stream synchronisation that stood here cost 13 us of a 41 us accepted move)
 		for (int t = 0; t < 3 * m; t++) c->h_pos[3 * (size_t)c->trial_first + t] = c->trial_new[t];
