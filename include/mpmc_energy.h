@@ -201,6 +201,26 @@ int mpmc_energy_wait(mpmc_ctx *ctx, mpmc_result *out);
  * themselves. */
 int mpmc_hint_in_flight(mpmc_ctx *ctx, int n_evaluations);
 
+/* ---- polarization energy from half the Jacobi iterations; dipoles on demand ------------------------------------------------------------
+ * A Jacobi solve with a fixed iteration count n = polar_max_iter (1 <= n <= 64) that starts from mu_0 = alpha E0 -- polar_iterative on,
+ * polar_precision 0, polar_gamma 1, no polar_rrms, no polar_gs (`polar_palmo` acts under polar_gs only and changes nothing here); any solver -- takes its polarization energy from the
+ * first ceil(n/2) iterations: with d_0 = mu_0 and d_k = mu_k - mu_(k-1) = (-alpha T)^k alpha E0 (T symmetric, alpha diagonal),
+ *   E0 . mu_n = sum_{k=0..n} m_k,   m_2a = sum_i d_a,i . d_a,i / alpha_i,   m_2a+1 = sum_i d_a,i . d_a+1,i / alpha_i,
+ * exact in exact arithmetic (polarization_energy differs from -1/2 sum mu_n . E0 in the last digits).  Every evaluation of such a context
+ * computes its energy this way, so mpmc_energy and a bead of mpmc_pi_potential_local return the same bits.
+ * The other n - ceil(n/2) iterations only produce mu_n, ef_induced and nothing an mpmc_result holds:
+ *   - mpmc_energy, mpmc_energy_async, the component entry points and the trial moves run them at once, as before (eager);
+ *   - mpmc_pi_potential_local, mpmc_pi_potential_local_host and mpmc_pi_allreduce leave them undone (on demand), and so do mpmc_energy /
+ *     mpmc_energy_async of a context after mpmc_set_dipoles_on_demand(ctx, 1).  The setting survives like mpmc_set_polar_wolf's.
+ * mpmc_get_dipoles (and the measurement entries that read the solve's state) first runs what is left, with the same kernels on the same
+ * tables, and waits: mu, ef_induced and polar_iterations (= n in both modes) are bit-identical to an eager evaluation's.  The undone
+ * iterations can no longer be run once their inputs are overwritten -- mpmc_set_atoms (capacity growth included), mpmc_update_positions,
+ * mpmc_set_positions_device, a new cell or new options, a trial move, a measurement switch, or the next evaluation of any kind:
+ * mpmc_get_dipoles then fails with MPMC_ERR_ARG and says so in mpmc_last_error; it never returns the dipoles of the half-way iteration.
+ * Evaluate again (or switch to eager) to get them.  Contexts outside the conditions above behave exactly as before.
+ * The debug key dipoles_on_demand = 0 (mpmc_debug_configure) makes every path eager, for A/B measurements. */
+int mpmc_set_dipoles_on_demand(mpmc_ctx *ctx, int enabled);
+
 /* ---- trial moves: the device-side counterpart of the reference's per-pair cache ----------------------------------------
  * The reference re-evaluates only the pairs whose displacement changed (Pair::recalculate_energy, src/System.cpp:1211-1224,
  * src/System.Energy.cpp:925,1484).  After a full mpmc_energy() of the accepted configuration:
@@ -320,7 +340,8 @@ int mpmc_set_polar_wolf(mpmc_ctx *ctx, int enabled, double polar_wolf_alpha);
 int mpmc_set_polar_palmo(mpmc_ctx *ctx, int enabled);
 int mpmc_polar_palmo_info(mpmc_ctx *ctx, double *energy_correction, double *ef_induced_change /*[n][3], may be NULL*/);
 
-/* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL */
+/* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL.  After an on-demand evaluation
+ * (mpmc_set_dipoles_on_demand above) the remaining Jacobi iterations run here first; MPMC_ERR_ARG when they no longer can. */
 int mpmc_get_dipoles(mpmc_ctx *ctx, double *mu, double *ef_static, double *ef_induced /* each [n][3] */);
 /* pairs() tail: update_com + wrap_all (src/System.cpp:1347-1425).  Host-side O(N); needs mass in set_atoms.
  * com / wrapped_com: [n_molecules][3]; wrapped_pos: [n][3]; any may be NULL. */

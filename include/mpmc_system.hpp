@@ -96,6 +96,7 @@ public:
 	int midzuno_kihara_approx = 0;     // its c9 from c6, src/System.h:655
 	bool using_disp_expansion = false; // disp-expansion repulsion/dispersion in place of lj() (mpmc_set_disp_expansion), src/System.h:661
 	int damp_dispersion = 0, extrapolate_disp_coeffs = 0, schmidt_ff = 0; // its switches, src/System.h:649-656
+	int dipoles_on_demand = 0; // energy() / energy_async() stop at the Jacobi iterations the energy needs; fetch_dipoles() runs the rest (mpmc_set_dipoles_on_demand)
 	int polar_wolf = 0, polar_palmo = 0; // Wolf static field (mpmc_set_polar_wolf), Palmo-Krimm correction (mpmc_set_polar_palmo), src/System.h:685-694
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
@@ -292,6 +293,7 @@ private:
 	bool disp_on_ = false; // what the context's disp-expansion setting is (sync_state)
 	int disp_flags_ = 0;
 	int polar_wolf_on_ = 0, polar_palmo_on_ = 0; // what the context's Wolf-field / Palmo settings are (sync_state)
+	int on_demand_on_ = 0;                       // ... and its dipoles-on-demand switch
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
@@ -312,7 +314,7 @@ private:
 			capacity_ = n + n / 4 + 64;
 			check(mpmc_ctx_create(device, capacity_, &ctx_), "mpmc_ctx_create");
 			atoms_dirty_ = box_dirty_ = true;
-			polar_wolf_on_ = polar_palmo_on_ = 0; // (a new context starts with both off)
+			polar_wolf_on_ = polar_palmo_on_ = on_demand_on_ = 0; // (a new context starts with all of them off)
 			polar_wolf_alpha_ = 0;
 		}
 		if (box_dirty_) {
@@ -390,6 +392,10 @@ private:
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");
 			polar_palmo_on_ = polar_palmo ? 1 : 0;
+		}
+		if ((dipoles_on_demand != 0) != (on_demand_on_ != 0)) {
+			check(mpmc_set_dipoles_on_demand(ctx_, dipoles_on_demand ? 1 : 0), "mpmc_set_dipoles_on_demand");
+			on_demand_on_ = dipoles_on_demand ? 1 : 0;
 		}
 	}
 

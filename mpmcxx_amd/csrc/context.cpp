@@ -241,6 +241,7 @@ extern "C" int mpmc_set_box(mpmc_ctx *c, const double basis[9], const double *re
 	if (volume > 0) vol = volume;
 	if (cutoff > 0) cut = cutoff;
 	if (!(vol > 0) || !(cut > 0)) return fail(c, MPMC_ERR_BOX, "mpmc_set_box: invalid volume / cutoff");
+	drop_pending_dipoles(c); // (an open on-demand solve belongs to the old cell)
 	std::memcpy(c->box.b, basis, sizeof(R));
 	std::memcpy(c->box.r, R, sizeof(R));
 	c->box.volume = vol;
@@ -295,6 +296,7 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 		const bool was = c->opts_set && atom_order(c->opts);
 		if (was != (bool)atom_order(*o)) c->atoms_dirty = c->atoms_dirty_order = true;
 	}
+	drop_pending_dipoles(c); // (... and to the old options)
 	c->opts = *o;
 	c->opts_set = true;
 	c->k_dirty = true;
@@ -609,10 +611,12 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const double *charge, const double *polarizability, const double *epsilon,
                               const double *sigma, const int32_t *mol_id, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
 	if (!c || n <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !mol_id || !frozen) return MPMC_ERR_ARG;
+	const bool solve_open = c->polar_pending != mpmc_ctx::PEND_NONE;
 	if (n > c->max_atoms) { // insertions (uVT / Gibbs callers) outgrew the capacity hint given at creation
 		const int rc_grow = grow_capacity(c, n);
 		if (rc_grow != MPMC_OK) return rc_grow;
 	}
+	if (solve_open) c->polar_pending = mpmc_ctx::PEND_DROPPED; // (an open on-demand solve belongs to the old atom list, and to the old buffers)
 	for (int i = 0; i < n; i++) {
 		if (!std::isfinite(pos[3 * i]) || !std::isfinite(pos[3 * i + 1]) || !std::isfinite(pos[3 * i + 2]))
 			return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_set_atoms: non-finite position");
@@ -922,6 +926,7 @@ extern "C" int mpmc_update_positions(mpmc_ctx *c, int first, int count, const do
 		c->h_pos[3 * i + 2] = pos[3 * t + 2];
 	}
 	c->cache_valid = false; // the accepted totals no longer describe the resident configuration
+	drop_pending_dipoles(c); // (... nor can an open on-demand solve be finished on them)
 	if (c->atoms_dirty) return MPMC_OK; // a full (re-sorted) upload is pending anyway
 	if (count > 256) { // bulk update (typically: all positions handed over in host memory for every evaluation)
 		// The atoms keep their slots -- the spatial order only matters for speed, the tile classes are recomputed from the actual
@@ -972,6 +977,7 @@ extern "C" int mpmc_set_positions_device(mpmc_ctx *c, const double *pos_device) 
 	if (c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: a trial move is open (accept or reject it first)");
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: an evaluation is in flight (mpmc_energy_wait first)");
 	c->cache_valid = false; // the accepted totals / structure factors no longer describe the resident configuration
+	drop_pending_dipoles(c);
 	HIP_TRY(c, hipSetDevice(c->device));
 	if (c->atoms_dirty) { // need the slot order first
 		int rc = upload_atoms(c);
@@ -1078,7 +1084,7 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 // any of this.  Keys (value 1 = on, 0 = off unless said otherwise):
 //   side_stream -1 | 0 | 1     pair_kernel 0 | 1 | 2     pair_waves 0 | 1 | 4     panels     uniform_images     tile_classes
 //   single_launch     recip_table     spatial_sort     order_carry     polar_delta     inline_move     trace_panel     tensor_budget_mb N
-//   direct_budget_mb N (-1: free device memory)
+//   direct_budget_mb N (-1: free device memory)     dipoles_on_demand (0: every evaluation runs all its Jacobi iterations at once)
 extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) {
 	if (!key) return MPMC_ERR_ARG;
 	std::unique_lock<std::mutex> tuning_lk(g_tuning_mu, std::defer_lock);
@@ -1139,6 +1145,7 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 	else if (k == "polar_delta") t.no_polar_delta = !on;
 	else if (k == "inline_move") t.no_inline_move = !on;
 	else if (k == "trace_panel") t.trace_panel = on;
+	else if (k == "dipoles_on_demand") t.dipoles_on_demand = on;
 	else if (k == "virtual_device") {
 		if (!c || v < -1 || v > 63) return MPMC_ERR_ARG;
 		t.virtual_device = v;
@@ -1155,6 +1162,8 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 		if (value < 0) return MPMC_ERR_ARG;
 		t.tensor_budget_mb = (long long)value;
 	} else return MPMC_ERR_ARG;
+	// an open on-demand solve was enqueued under the old switches (the keys that only steer a measurement or a wait leave it alone)
+	if (c && k != "panel_replicas" && k != "fail_next_wait" && k != "virtual_device" && k != "trace_panel") drop_pending_dipoles(c);
 	return MPMC_OK;
 }
 // the last evaluated trial move: 1 = a full evaluation of the trial configuration, 0 = per-move delta energies, -1 = none

@@ -111,6 +111,7 @@ struct mpmc_tuning {
 	int virtual_device = -1;     // "virtual_device" = v >= 0 (test hook): mpmc_pi_allreduce treats this context as living on a device of its own (csrc/comm.cpp group_beads)
 	int fail_next_wait = 0;      // "fail_next_wait" = 1: the next wait of this context fails as if the runtime had refused it (test of the recovery path)
 	bool trace_panel = false;    // "trace_panel" = 1: per-workgroup time stamps of the panel kernel (tools/panel_trace.py)
+	bool dipoles_on_demand = true; // "dipoles_on_demand" = 0: every evaluation runs all its Jacobi iterations at once (A/B against the on-demand path-integral loop)
 	long long tensor_budget_mb = 4096; // "tensor_budget_mb": AUTO solver: largest tensor store it will allocate
 	long long direct_budget_mb = -1;   // "direct_budget_mb": direct dipole solve: largest factor it will allocate (-1: what the device has free)
 };
@@ -131,6 +132,7 @@ struct mpmc_kept {
 	bool pw_enabled = false;                // `polar_wolf` (mpmc_set_polar_wolf), kept across mpmc_set_box and mpmc_set_options too
 	double pw_alpha = 0.0;
 	bool palmo_enabled = false;             // `polar_palmo` (mpmc_set_polar_palmo), likewise
+	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 };
 
 struct mpmc_ctx {
@@ -255,6 +257,13 @@ struct mpmc_ctx {
 	DevBuf<double2> d_gs_blocks; // Gauss-Seidel sweeps: the in-tile 3 x 3 blocks (k_gs_blocks)
 	DevBuf<double> d_gs_ul; // Gauss-Seidel sweeps (kernels_gs.hip): [2][max_pad][3] induced-field parts from the tiles above / below
 	int mu_cur = 0;
+	// Fixed-count Jacobi solves (polar_moments_apply): d_k = mu_k - mu_(k-1) of the first ceil(n/2) iterations, slot 0 = mu_0; the energy
+	// is the sum of their moments (k_polar_moments).  [ceil(n/2) + 1][3 n_pad]
+	DevBuf<double> d_dk_ring;
+	// dipoles on demand: the last evaluation stopped after pend_done of pend_target iterations; finish_pending_dipoles runs the rest
+	enum { PEND_NONE = 0, PEND_OPEN = 1, PEND_DROPPED = 2 };
+	int polar_pending = PEND_NONE; // PEND_DROPPED: the inputs of the open solve were overwritten before anybody asked for the dipoles
+	int pend_done = 0, pend_target = 0;
 	// dense A rows scratch
 	DevBuf<double> d_arows;
 	DevBuf<double> d_adense; // solver DENSE: the (3 n_pad)^2 matrix of thole_amatrix without its diagonal blocks
@@ -510,9 +519,28 @@ int three_body_ready(mpmc_ctx *c); // the term is on and its coefficients are on
 int disp_ready(mpmc_ctx *c);       // the same for the disp-expansion term, and its long-range corrections for the current box (context.cpp)
 DispParams disp_params(const mpmc_ctx *c);
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
-int enqueue(mpmc_ctx *c, unsigned mask);         // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp)
+// one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp); on_demand: where the energy comes from the moments of the
+// first half of the iterations, stop there and leave the rest to finish_pending_dipoles
+int enqueue(mpmc_ctx *c, unsigned mask, bool on_demand = false);
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options
+// The polarization energy of a Jacobi solve with a fixed iteration count n and mu_0 = alpha E0 is -1/2 sum_k m_k over the moments of the
+// first ceil(n/2) dipole differences: not for polar_gamma != 1, precision-terminated or rrms-reporting solves,
+// Gauss-Seidel sweeps (the only place where `polar_palmo` acts) or the direct solve.
+inline bool polar_moments_apply(const mpmc_ctx *c) {
+	const mpmc_options &o = c->opts;
+	return o.polarization && !o.rd_only && o.polar_iterative && o.polar_max_iter >= 1 && o.polar_max_iter <= kMomentsMaxIter && o.polar_gamma == 1.0 && o.polar_precision == 0.0 && !o.polar_rrms &&
+	       !o.polar_gs; // (`polar_palmo` acts under Gauss-Seidel sweeps only: under Jacobi its correction is zero and nothing runs)
+}
+inline int moments_half(int n) { return (n + 1) / 2; } // iterations whose differences the moments of n iterations need
+inline int reserve_dk_ring(mpmc_ctx *c) { return c->d_dk_ring.reserve(c, (size_t)(moments_half(c->opts.polar_max_iter) + 1) * 3 * (size_t)c->max_pad); }
+// Every reader of the dipoles, the induced field or anything else the remaining iterations write calls this first: runs what an on-demand
+// evaluation left undone and waits for it (nothing to do otherwise); MPMC_ERR_ARG when the open solve's inputs are gone (evaluate.cpp)
+int finish_pending_dipoles(mpmc_ctx *c);
+// whoever is about to overwrite positions, cell, options, tensor store or dipole vectors: the open solve can no longer be finished
+inline void drop_pending_dipoles(mpmc_ctx *c) {
+	if (c->polar_pending == mpmc_ctx::PEND_OPEN) c->polar_pending = mpmc_ctx::PEND_DROPPED;
+}
 inline bool direct_solve(const mpmc_ctx *c) { return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative; } // `polar_iterative off`
 // `polar_wolf` replaces the static field whenever polar_ewald is off (thole_field :3289-3294: polar_ewald wins)
 inline bool wolf_field_on(const mpmc_ctx *c) { return c->kept.pw_enabled && c->opts.polarization && !c->opts.rd_only && !c->opts.polar_ewald; }

@@ -86,6 +86,7 @@ static int ensure_polar_buffers(mpmc_ctx *c) {
 	if ((rc = c->d_gs_ul.reserve(c, 6 * np)) != MPMC_OK) return rc; // Gauss-Seidel sweeps: fields of the tiles above / below
 	if ((rc = c->d_palmo_f.reserve(c, 3 * np)) != MPMC_OK) return rc;
 	if ((rc = c->d_palmo_change.reserve(c, 3 * np)) != MPMC_OK) return rc;
+	if (polar_moments_apply(c) && (rc = reserve_dk_ring(c)) != MPMC_OK) return rc;
 	// per-atom partial slots: one per source tile (symmetric kernels) -- also covers the n_split <= n_tiles slots of the matrix-free
 	// row kernel -- and never fewer than the kDenseChunks row chunks the dense matrix-vector product writes (small systems have fewer
 	// tiles than that: the dense solver used to write past the end of this buffer, into the matrix that was allocated right behind it)
@@ -277,9 +278,80 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 
 // which pieces of energy() to run
 
-int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
+// One Jacobi iteration on the main stream: the contraction of the solver in use, then new_mu = alpha (E0 + F) into the other dipole
+// vector.  Shared by the solve inside an evaluation and by finish_pending_dipoles, which runs the iterations an on-demand evaluation
+// left undone: same kernels, same tables, same order.  dk (may be null): this iteration's slot of the ring of dipole differences.
+struct JacobiPlan {
+	bool dense, dense_sym, compact;
+	int iter_slots;
+};
+static JacobiPlan jacobi_plan(const mpmc_ctx *c) {
+	JacobiPlan jp;
+	jp.dense = (c->solver_used == MPMC_SOLVER_DENSE) && !c->opts.polar_gs;
+	jp.dense_sym = jp.dense && c->kept.tune.dense_symmetric;
+	jp.compact = c->solver_used == MPMC_SOLVER_COMPACT;
+	jp.iter_slots = (jp.dense && !jp.dense_sym) ? kDenseChunks : c->n_tiles;
+	return jp;
+}
+static void enqueue_jacobi_iteration(mpmc_ctx *c, const AtomsDev &at, const JacobiPlan &jp, int it, int want_rrms, double allowed, int *ctl, int *host_flag,
+                                     double *dk) {
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	const int *converged = ctl ? ctl + 1 : nullptr;
+	if (jp.dense) {
+		ProfScope p(c, MPMC_K_DIPOLE_ITER);
+		if (jp.dense_sym) launch_dense_symv(st, c->d_adense, c->n_pad, c->d_mu[c->mu_cur], c->d_tile_pairs, c->n_tile_pairs, c->d_part);
+		else launch_dense_matvec(st, c->d_adense, c->n_pad, c->d_mu[c->mu_cur], kDenseChunks, c->d_part);
+	} else if (jp.compact) {
+		ProfScope p(c, MPMC_K_DIPOLE_ITER);
+		if (c->panels_built) // every tile pair through the panel table: two per wave where classes allow
+			launch_dipole_iter_panel(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_tp_shift, c->d_panels,
+			                         c->n_panel_entries, c->d_ab, c->d_part, c->d_gpart, converged, c->d_trace);
+		else
+			launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
+			                          shift_view(c), c->n_tile_pairs, c->d_ab, c->d_part, o.polar_damp,
+			                          converged);
+	} else { // matrix-free: the same symmetric tile-pair walk with nothing stored (null store => damped tensors rebuilt)
+		ProfScope p(c, MPMC_K_DIPOLE_ITER);
+		launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
+		                          shift_view(c), c->n_tile_pairs, nullptr, c->d_part, o.polar_damp,
+		                          converged);
+	}
+	{
+		ProfScope p(c, MPMC_K_REDUCE);
+		if (jp.compact && c->panels_built && !jp.dense)
+			launch_dipole_update_panel(st, at, c->d_e_static, c->d_part, c->d_gpart, c->d_seg, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur],
+			                           c->d_e_induced, want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk);
+		else
+			launch_dipole_update(st, at, c->d_e_static, c->d_part, jp.iter_slots, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur], c->d_e_induced,
+			                     want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk);
+	}
+	c->mu_cur = 1 - c->mu_cur;
+}
+
+// The iterations an on-demand evaluation left undone, from mu_half on: dipoles, induced field and iteration count come out as an eager
+// evaluation leaves them.  Enqueued behind whatever the stream still carries and waited for.
+int mpmc::finish_pending_dipoles(mpmc_ctx *c) {
+	if (c->polar_pending == mpmc_ctx::PEND_NONE) return MPMC_OK;
+	if (c->polar_pending == mpmc_ctx::PEND_DROPPED)
+		return fail(c, MPMC_ERR_ARG, "the dipoles of the last evaluation were left to be computed on demand, and its positions, cell, options or buffers "
+		                             "have been overwritten since: evaluate again (or mpmc_set_dipoles_on_demand(ctx, 0))");
+	HIP_TRY(c, hipSetDevice(c->device));
+	const AtomsDev at = atoms_view(c);
+	const JacobiPlan jp = jacobi_plan(c);
+	for (int it = c->pend_done + 1; it <= c->pend_target; it++) enqueue_jacobi_iteration(c, at, jp, it, 0, 0.0, nullptr, nullptr, nullptr);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	c->polar_pending = mpmc_ctx::PEND_NONE;
+	c->pend_done = c->pend_target;
+	if (!c->pending) prof_harvest(c);
+	return MPMC_OK;
+}
+
+int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	// one evaluation per context at a time: a second enqueue would overwrite the scalar block and the result slots under the first
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "an evaluation of this context is still in flight (mpmc_energy_wait first)");
+	drop_pending_dipoles(c); // (its tables, slots and dipole vectors are this evaluation's from here on)
 	// stale position-independent terms ride along with this evaluation (an insertion / removal makes them stale every time)
 	int rc = prepare(c, true);
 	if (rc != MPMC_OK) return rc;
@@ -475,7 +547,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
 			launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
 		launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
-		                      c->d_mu[0], c->d_e_real);
+		                      c->d_mu[0], c->d_e_real, polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 		c->e_real_valid = (mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
 	}
 
@@ -490,13 +562,20 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 			else launch_polar_energy(st, at, c->d_mu[c->mu_cur], c->d_e_static, nullptr, c->d_scal);
 		}
 		c->have_polar = true;
+		c->polar_pending = mpmc_ctx::PEND_NONE;
 	} else if (mask & RUN_SOLVE) {
 		const bool by_precision = (o.polar_precision != 0.0);
 		const int want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
 		const double allowed = by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
-		const bool dense = (c->solver_used == MPMC_SOLVER_DENSE) && !o.polar_gs;
-		const bool dense_sym = dense && c->kept.tune.dense_symmetric;
-		const int iter_slots = (dense && !dense_sym) ? kDenseChunks : c->n_tiles;
+		const JacobiPlan jp = jacobi_plan(c);
+		const bool dense = jp.dense, dense_sym = jp.dense_sym;
+		// fixed-count solves from alpha E0: the energy is the moment sum of the first `half` dipole differences, whether or not the other
+		// iterations run now (on demand: they wait for somebody who reads the dipoles) -- alone or as a bead, an evaluation gives the same bits
+		const bool moments = polar_moments_apply(c);
+		const int half = moments_half(o.polar_max_iter);
+		const bool lazy = moments && on_demand && c->kept.tune.dipoles_on_demand && half < o.polar_max_iter;
+		const int last_it = lazy ? half : o.polar_max_iter;
+		const size_t dk_stride = 3 * (size_t)at.n_pad;
 		if (dense) { // thole_amatrix into device memory, once per evaluation (the positions changed)
 			ProfScope p(c, MPMC_K_TENSOR);
 			launch_dense_build(st, at, c->box, o.polar_damp, c->d_adense, dense_sym);
@@ -505,7 +584,6 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 		// enqueues kCheckEvery iterations at a time and reads the verdict once per batch -- the iterations enqueued behind the one that
 		// converged return at once and leave the dipoles alone.  (Gauss-Seidel sweeps and the dense solver still ask after every iteration.)
 		int *ctl = (by_precision && !o.polar_gs) ? c->d_flag + 1 : nullptr;
-		const int *converged = ctl ? ctl + 1 : nullptr;
 		const int check_every = dense ? 1 : kCheckEvery;
 		const int mu_start = c->mu_cur;
 		int done_at = 0;
@@ -550,35 +628,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 				}
 				continue;
 			}
-			if (dense) {
-				ProfScope p(c, MPMC_K_DIPOLE_ITER);
-				if (dense_sym) launch_dense_symv(st, c->d_adense, c->n_pad, c->d_mu[c->mu_cur], c->d_tile_pairs, c->n_tile_pairs, c->d_part);
-				else launch_dense_matvec(st, c->d_adense, c->n_pad, c->d_mu[c->mu_cur], kDenseChunks, c->d_part);
-			} else if (compact) {
-				ProfScope p(c, MPMC_K_DIPOLE_ITER);
-				if (c->panels_built) // every tile pair through the panel table: two per wave where classes allow
-					launch_dipole_iter_panel(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_tp_shift, c->d_panels,
-					                         c->n_panel_entries, c->d_ab, c->d_part, c->d_gpart, converged, c->d_trace);
-				else
-					launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
-					                          shift_view(c), c->n_tile_pairs, c->d_ab, c->d_part, o.polar_damp,
-					                          converged);
-			} else { // matrix-free: the same symmetric tile-pair walk with nothing stored (null store => damped tensors rebuilt)
-				ProfScope p(c, MPMC_K_DIPOLE_ITER);
-				launch_dipole_iter_hybrid(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->d_cls,
-				                          shift_view(c), c->n_tile_pairs, nullptr, c->d_part, o.polar_damp,
-				                          converged);
-			}
-			{
-				ProfScope p(c, MPMC_K_REDUCE);
-				if (compact && c->panels_built && !dense)
-					launch_dipole_update_panel(st, at, c->d_e_static, c->d_part, c->d_gpart, c->d_seg, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur],
-					                           c->d_e_induced, want_rrms, c->d_rrms, allowed, ctl, host_flag, it);
-				else
-					launch_dipole_update(st, at, c->d_e_static, c->d_part, iter_slots, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur], c->d_e_induced,
-					                     want_rrms, c->d_rrms, allowed, ctl, host_flag, it);
-			}
-			c->mu_cur = 1 - c->mu_cur;
+			enqueue_jacobi_iteration(c, at, jp, it, want_rrms, allowed, ctl, host_flag, (moments && it <= half) ? c->d_dk_ring + (size_t)it * dk_stride : nullptr);
 			if (by_precision) {
 				if (it % check_every == 0 || it + 1 >= kMaxIterationCount) { // the verdict of this batch
 					HIP_TRY(c, hipGetLastError());
@@ -597,15 +647,23 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask) {
 					keep = (done_at == 0);
 				}
 			} else {
-				keep = (it != o.polar_max_iter);
+				keep = (it != last_it);
 			}
 		}
 		if (done_at > 0) { // the iterations enqueued behind the converged one did nothing: the result is where iteration done_at left it
 			it = done_at;
 			c->mu_cur = (mu_start + done_at) & 1;
 		}
-		c->iters = it;
-		{
+		c->iters = lazy ? o.polar_max_iter : it; // (what the solve comes to once its dipoles are asked for)
+		c->polar_pending = lazy ? mpmc_ctx::PEND_OPEN : mpmc_ctx::PEND_NONE;
+		c->pend_done = it, c->pend_target = o.polar_max_iter;
+		if (moments) {
+			ProfScope p(c, MPMC_K_REDUCE);
+			if (reduce_in_tail)
+				launch_polar_moments_and_pairs(st, at, c->d_dk_ring, c->d_e_static, o.polar_max_iter, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal,
+				                               c->d_cnt);
+			else launch_polar_moments(st, at, c->d_dk_ring, c->d_e_static, o.polar_max_iter, c->d_scal);
+		} else {
 			ProfScope p(c, MPMC_K_REDUCE);
 			if (reduce_in_tail)
 				launch_polar_energy_and_pairs(st, at, c->d_mu[c->mu_cur], c->d_e_static, want_rrms ? c->d_rrms : nullptr, c->d_block_part, c->d_block_cnt,
@@ -672,6 +730,10 @@ extern "C" int mpmc_debug_time_panel(mpmc_ctx *c, int reps, double *ms_per_launc
 	if (!c->have_polar || !c->panels_built || c->solver_used != MPMC_SOLVER_COMPACT)
 		return fail(c, MPMC_ERR_ARG, "mpmc_debug_time_panel: the last evaluation did not run the panel kernel");
 	HIP_TRY(c, hipSetDevice(c->device));
+	{ // (the launches below overwrite the partial slots an open on-demand solve would still read)
+		const int rc_f = finish_pending_dipoles(c);
+		if (rc_f != MPMC_OK) return rc_f;
+	}
 	const AtomsDev at = atoms_view(c);
 	hipEvent_t e0, e1;
 	HIP_TRY(c, hipEventCreate(&e0));
@@ -705,6 +767,10 @@ extern "C" int mpmc_debug_time_pair(mpmc_ctx *c, int reps, double *ms_per_launch
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_debug_time_pair: an evaluation is in flight");
 	if (!c->cache_valid || !c->last_fp_valid) return fail(c, MPMC_ERR_ARG, "mpmc_debug_time_pair: no complete evaluation has run");
 	HIP_TRY(c, hipSetDevice(c->device));
+	{ // (the sweep rewrites the slots and the store an open on-demand solve would still read)
+		const int rc_f = finish_pending_dipoles(c);
+		if (rc_f != MPMC_OK) return rc_f;
+	}
 	const AtomsDev at = atoms_view(c);
 	const FusedParams &fp = c->last_fp;
 	const bool compact = c->solver_used == MPMC_SOLVER_COMPACT && fp.do_thole;
@@ -752,6 +818,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->pending = false;
 		c->scal_clean = false;
 		c->static_ride_gen = 0;
+		drop_pending_dipoles(c);
 		return fail(c, MPMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 	};
 	hipError_t werr = c->kept.tune.fail_next_wait ? hipErrorUnknown : hipSetDevice(c->device);
@@ -853,7 +920,12 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 
 extern "C" int mpmc_energy_async(mpmc_ctx *c) {
 	if (!c) return MPMC_ERR_ARG;
-	return enqueue(c, full_mask(c));
+	return enqueue(c, full_mask(c), c->kept.on_demand);
+}
+extern "C" int mpmc_set_dipoles_on_demand(mpmc_ctx *c, int enabled) {
+	if (!c) return MPMC_ERR_ARG;
+	c->kept.on_demand = enabled != 0; // (from the next evaluation on; an open solve stays open)
+	return MPMC_OK;
 }
 extern "C" int mpmc_hint_in_flight(mpmc_ctx *c, int n) {
 	if (!c || n < 1) return MPMC_ERR_ARG;
@@ -867,7 +939,7 @@ extern "C" int mpmc_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 extern "C" int mpmc_energy(mpmc_ctx *c, mpmc_result *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	c->inflight_hint = 1; // (a synchronous call: nothing else of this caller is in flight)
-	int rc = enqueue(c, full_mask(c));
+	int rc = enqueue(c, full_mask(c), c->kept.on_demand);
 	if (rc != MPMC_OK) return rc;
 	return wait_and_fill(c, out);
 }
@@ -1002,8 +1074,9 @@ extern "C" int mpmc_get_dipoles(mpmc_ctx *c, double *mu, double *ef_static, doub
 	if (!c) return MPMC_ERR_ARG;
 	if (!c->d_e_static) return fail(c, MPMC_ERR_ARG, "mpmc_get_dipoles: no polarization evaluation has run");
 	HIP_TRY(c, hipSetDevice(c->device));
+	int rc = finish_pending_dipoles(c); // an on-demand evaluation's remaining iterations; an error when its inputs are gone
+	if (rc != MPMC_OK) return rc;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	int rc = MPMC_OK;
 	if (mu && rc == MPMC_OK) rc = fetch_atoms3(c, c->d_mu[c->mu_cur], mu);
 	if (ef_static && rc == MPMC_OK) rc = fetch_atoms3(c, c->d_e_static, ef_static);
 	if (ef_induced && rc == MPMC_OK) rc = fetch_atoms3(c, c->d_e_induced, ef_induced);

@@ -90,14 +90,16 @@ void launch_field_recip(hipStream_t st, const AtomsDev &at, const Box &bx, const
 // E0 = recip*(8 pi/V) + sum_s part ; mu0 = gamma * alpha * E0
 void launch_field_finalize(hipStream_t st, const AtomsDev &at, const Box &bx, int polar_ewald, const double *e_recip,
                            const double *part, int n_split, double gamma, double *e_static, double *mu,
-                           double *e_real_out = nullptr /*the real-space part alone (sum of the slots): what a trial move updates incrementally*/);
+                           double *e_real_out = nullptr /*the real-space part alone (sum of the slots): what a trial move updates incrementally*/,
+                           double *mu_copy = nullptr /*a second copy of mu0: slot 0 of the ring of dipole differences*/);
 
 // new_mu = alpha (E0 + F) ; optionally rrms per atom.  Precision-terminated solves pass ctl = { broke, converged-at, ticket } (device
 // ints, zeroed at the start of the solve) and the iteration number: are_we_done_yet runs on the device, the kernels of iterations
 // enqueued after convergence return at once (see iteration_verdict in kernels.hip)
 void launch_dipole_update(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, int n_split,
                           const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom,
-                          double allowed_sqerr, int *ctl, int *host_flag /*pinned {closed iteration, converged-at}, may be null*/, int it);
+                          double allowed_sqerr, int *ctl, int *host_flag /*pinned {closed iteration, converged-at}, may be null*/, int it,
+                          double *dk = nullptr /*new_mu - mu_old per component: this iteration's slot of the ring of dipole differences*/);
 // iterator failure: mu = alpha * E0
 void launch_dipole_reset(hipStream_t st, const AtomsDev &at, const double *e_static, double *mu);
 // end of an evaluation: the scalar block [S_COUNT doubles][C_COUNT int64] goes to pinned host memory, the launch number behind it (a host
@@ -105,6 +107,14 @@ void launch_dipole_reset(hipStream_t st, const AtomsDev &at, const double *e_sta
 void launch_post_results(hipStream_t st, double *scal, double *out_host, double seq);
 void launch_polar_energy(hipStream_t st, const AtomsDev &at, const double *mu, const double *e_static, const double *rrms_atom,
                          double *scal);
+// The same energy of a Jacobi solve of n iterations from mu_0 = alpha E0, without mu_n: -1/2 sum_{k=0..n} m_k with
+// m_2a = <d_a, d_a>_{1/alpha} and m_2a+1 = <d_a, d_a+1>_{1/alpha} over the ring dk[ceil(n/2) + 1][3 n_pad] (d_0 = mu_0, d_k = mu_k -
+// mu_k-1); for a = 0, d_0 / alpha is E0 itself.  One block, fixed order; S_RRMS = 0 (such a solve reports none).
+constexpr int kMomentsMaxIter = 64;                         // longer fixed-count solves keep -1/2 E0 . mu_n (the ring would outgrow its use)
+constexpr int kMomentsMaxHalf = (kMomentsMaxIter + 1) / 2;
+void launch_polar_moments(hipStream_t st, const AtomsDev &at, const double *dk, const double *e_static, int n_iter, double *scal);
+void launch_polar_moments_and_pairs(hipStream_t st, const AtomsDev &at, const double *dk, const double *e_static, int n_iter,
+                                    const double *block_part, const int *block_cnt, int nb, double *scal, long long *cnt);
 
 // dense thole_amatrix rows (parity / DENSE solver)
 // rows and columns are ORIGINAL atom indices; slot_of maps them to the device order
@@ -217,7 +227,7 @@ void launch_dipole_iter_panel(hipStream_t st, const AtomsDev &at, const Box &bx,
 // new_mu = alpha (E0 + F) from the panel kernel's slots, one workgroup per tile (the launch that follows every panel contraction)
 void launch_dipole_update_panel(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, const double *gpart, const int *seg,
                                 const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr,
-                                int *ctl, int *host_flag, int it);
+                                int *ctl, int *host_flag, int it, double *dk = nullptr /*as launch_dipole_update*/);
 // lane-rotation primitive self-test: out[l] = lane whose value lane l received (must be (l+1)&63)
 void launch_rot_selftest(hipStream_t st, int *out);
 

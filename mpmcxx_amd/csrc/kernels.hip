@@ -440,7 +440,8 @@ __device__ __forceinline__ void slot_sum_64(const double *__restrict__ part, int
 
 __global__ __launch_bounds__(512) void k_field_finalize(AtomsDev at, Box bx, int polar_ewald, const double *__restrict__ e_recip_part,
                                                         const double *__restrict__ part, int n_split, double gamma,
-                                                        double *__restrict__ e_static, double *__restrict__ mu, double *__restrict__ e_real_out, int n_kslices) {
+                                                        double *__restrict__ e_static, double *__restrict__ mu, double *__restrict__ e_real_out, int n_kslices,
+                                                        double *__restrict__ mu_copy) {
 	__shared__ double sh[kSlotGroups][kTile][3];
 	__shared__ double shk[kSlotGroups][kTile][3];
 	const int a = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -462,7 +463,9 @@ __global__ __launch_bounds__(512) void k_field_finalize(AtomsDev at, Box bx, int
 	const double al = at.alpha[i];
 	for (int p = 0; p < 3; ++p) {
 		e_static[3 * (size_t)i + p] = e[p];
-		mu[3 * (size_t)i + p] = (al * e[p]) * gamma; // init_dipoles :3553-3556
+		const double m0 = (al * e[p]) * gamma; // init_dipoles :3553-3556
+		mu[3 * (size_t)i + p] = m0;
+		if (mu_copy) mu_copy[3 * (size_t)i + p] = m0;
 	}
 }
 
@@ -544,9 +547,9 @@ void launch_field_recip(hipStream_t st, const AtomsDev &at, const Box &bx, const
 }
 
 void launch_field_finalize(hipStream_t st, const AtomsDev &at, const Box &bx, int polar_ewald, const double *e_recip_part, const double *part,
-                           int n_split, double gamma, double *e_static, double *mu, double *e_real_out) {
+                           int n_split, double gamma, double *e_static, double *mu, double *e_real_out, double *mu_copy) {
 	hipLaunchKernelGGL(k_field_finalize, dim3(at.n_pad / kTile), dim3(kTile * kSlotGroups), 0, st, at, bx, polar_ewald, e_recip_part, part, n_split,
-	                   gamma, e_static, mu, e_real_out, recip_ksplit(at.n_pad));
+	                   gamma, e_static, mu, e_real_out, recip_ksplit(at.n_pad), mu_copy);
 }
 
 // are_we_done_yet (:3215-3239) on the device.  ctl = { "some atom broke the tolerance in this iteration", iteration at which the solve
@@ -578,7 +581,8 @@ __device__ __forceinline__ void iteration_verdict(int *__restrict__ ctl, int *__
 __device__ __forceinline__ void dipole_update_block(const AtomsDev &at, const double *__restrict__ e_static, const double *__restrict__ part,
                                                     int n_split, const double *__restrict__ mu_old, double *__restrict__ mu_new,
                                                     double *__restrict__ e_induced, int want_rrms, double *__restrict__ rrms_atom,
-                                                    double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it) {
+                                                    double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it,
+                                                    double *__restrict__ dk) {
 	__shared__ double sh[kSlotGroups][kTile][3];
 	if (ctl && ctl[1] != 0) return; // converged in an earlier iteration (block-uniform)
 	const int a = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -604,6 +608,7 @@ __device__ __forceinline__ void dipole_update_block(const AtomsDev &at, const do
 		if (d * d > allowed_sqerr) broke = true;
 		mu_new[3 * (size_t)i + p] = nm[p];
 		e_induced[3 * (size_t)i + p] = f[p];
+		if (dk) dk[3 * (size_t)i + p] = d;
 	}
 	if (want_rrms) {
 		double r = sqrt(acc / nn);
@@ -615,8 +620,9 @@ __device__ __forceinline__ void dipole_update_block(const AtomsDev &at, const do
 __global__ __launch_bounds__(512) void k_dipole_update(AtomsDev at, const double *__restrict__ e_static, const double *__restrict__ part,
                                                        int n_split, const double *__restrict__ mu_old, double *__restrict__ mu_new,
                                                        double *__restrict__ e_induced, int want_rrms, double *__restrict__ rrms_atom,
-                                                       double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it) {
-	dipole_update_block(at, e_static, part, n_split, mu_old, mu_new, e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it);
+                                                       double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it,
+                                                       double *__restrict__ dk) {
+	dipole_update_block(at, e_static, part, n_split, mu_old, mu_new, e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
 }
 
 __global__ __launch_bounds__(256) void k_dipole_reset(AtomsDev at, const double *__restrict__ e_static, double *__restrict__ mu) {
@@ -651,6 +657,119 @@ __global__ __launch_bounds__(256) void k_polar_energy(AtomsDev at, const double 
 	polar_energy_block(at, mu, e_static, rrms_atom, scal);
 }
 
+// The polarization energy of n Jacobi iterations from mu_0 = alpha E0 without mu_n.  With d_0 = mu_0, d_k = mu_k -
+// mu_k-1 = (-alpha T)^k alpha E0, T symmetric and alpha diagonal: E0 . d_(a+b) = sum_i d_a,i . d_b,i / alpha_i, hence
+// E0 . mu_n = sum_{k=0..n} m_k with m_2a = <d_a, d_a>_{1/alpha}, m_2a+1 = <d_a, d_a+1>_{1/alpha}.  One pass over the atoms per a (both of
+// its moments), the weight of a = 0 being E0 itself (d_0 / alpha); atoms with alpha = 0 carry no dipole and are skipped.  The moments are
+// added in ascending k by one thread.  The ring holds ceil(n/2) + 1 vectors of 3 n_pad doubles.
+constexpr int kMomentsMax = 2 * (kMomentsMaxHalf + 1);
+// Up to kMomentsOnePassHalf + 1 ring vectors (n <= 10, the usual counts) in ONE pass over the atoms: every vector is loaded once and all
+// moments accumulate side by side in registers -- the block is a latency chain on one CU, and a pass per a cost 24 us each at 10 000 atoms.
+// Per moment the additions are those of the pass-per-a form below, in the same order: the two forms give the same bits.
+constexpr int kMomentsOnePassHalf = 5;
+template <int H>
+__device__ __forceinline__ void polar_moments_one_pass(const AtomsDev &at, const double *__restrict__ dk, const double *__restrict__ e_static,
+                                                       double *__restrict__ sh, double *__restrict__ s_m) {
+	const size_t stride = 3 * (size_t)at.n_pad;
+	double acc[2 * H + 1] = {};
+#pragma unroll 2
+	for (int i = threadIdx.x; i < at.n; i += 256) {
+		const size_t b = 3 * (size_t)i;
+		const double al = at.alpha[i];
+		double d[H + 1][3], w[3];
+#pragma unroll
+		for (int a = 0; a <= H; ++a) {
+			const double *__restrict__ q = dk + (size_t)a * stride + b;
+			d[a][0] = q[0], d[a][1] = q[1], d[a][2] = q[2];
+		}
+		w[0] = e_static[b], w[1] = e_static[b + 1], w[2] = e_static[b + 2];
+		const double inv = (al != 0.0) ? 1.0 / al : 0.0;
+#pragma unroll
+		for (int a = 0; a <= H; ++a) {
+			if (a > 0) w[0] = d[a][0] * inv, w[1] = d[a][1] * inv, w[2] = d[a][2] * inv;
+			acc[2 * a] += ((w[0] * d[a][0]) + w[1] * d[a][1]) + w[2] * d[a][2];
+			if (a < H) acc[2 * a + 1] += ((w[0] * d[a + 1][0]) + w[1] * d[a + 1][1]) + w[2] * d[a + 1][2];
+		}
+	}
+#pragma unroll
+	for (int k = 0; k <= 2 * H; ++k) {
+		const double v = block_sum_256(acc[k], sh);
+		if (threadIdx.x == 0) s_m[k] = v;
+	}
+}
+__device__ __forceinline__ void polar_moments_block(const AtomsDev &at, const double *__restrict__ dk, const double *__restrict__ e_static, int n_iter,
+                                                    double *__restrict__ scal) {
+	__shared__ double sh[4];
+	__shared__ double s_m[kMomentsMax];
+	const size_t stride = 3 * (size_t)at.n_pad;
+	const int half = (n_iter + 1) / 2;
+	switch (half <= kMomentsOnePassHalf ? half : 0) { // (block-uniform)
+	case 1: polar_moments_one_pass<1>(at, dk, e_static, sh, s_m); break;
+	case 2: polar_moments_one_pass<2>(at, dk, e_static, sh, s_m); break;
+	case 3: polar_moments_one_pass<3>(at, dk, e_static, sh, s_m); break;
+	case 4: polar_moments_one_pass<4>(at, dk, e_static, sh, s_m); break;
+	case 5: polar_moments_one_pass<5>(at, dk, e_static, sh, s_m); break;
+	default: break;
+	}
+	for (int a = 0; a <= (half <= kMomentsOnePassHalf ? -1 : half); ++a) { // longer solves: one pass per a
+		const double *__restrict__ da = dk + (size_t)a * stride;
+		const bool odd = 2 * a + 1 <= n_iter; // m_2a+1 belongs to the sum (block-uniform)
+		const double *__restrict__ db = odd ? da + stride : da;
+		double m0 = 0, m1 = 0;
+		// (no branch inside the loops: an atom with alpha = 0 has d = 0 in every slot and the weight 0, so it adds +0.0; unrolled, the loads of
+		// four atoms are in flight together -- the block is a latency chain on one CU; one division per atom)
+		if (a == 0) {
+#pragma unroll 4
+			for (int i = threadIdx.x; i < at.n; i += 256) {
+				const size_t b = 3 * (size_t)i;
+				const double w0 = e_static[b], w1 = e_static[b + 1], w2 = e_static[b + 2];
+				m0 += ((w0 * da[b]) + w1 * da[b + 1]) + w2 * da[b + 2];
+				m1 += ((w0 * db[b]) + w1 * db[b + 1]) + w2 * db[b + 2];
+			}
+		} else {
+#pragma unroll 4
+			for (int i = threadIdx.x; i < at.n; i += 256) {
+				const size_t b = 3 * (size_t)i;
+				const double al = at.alpha[i];
+				const double inv = (al != 0.0) ? 1.0 / al : 0.0;
+				const double w0 = da[b] * inv, w1 = da[b + 1] * inv, w2 = da[b + 2] * inv;
+				m0 += ((w0 * da[b]) + w1 * da[b + 1]) + w2 * da[b + 2];
+				m1 += ((w0 * db[b]) + w1 * db[b + 1]) + w2 * db[b + 2];
+			}
+		}
+		m0 = block_sum_256(m0, sh);
+		m1 = block_sum_256(m1, sh);
+		if (threadIdx.x == 0) {
+			s_m[2 * a] = m0;
+			s_m[2 * a + 1] = odd ? m1 : 0.0;
+		}
+	}
+	if (threadIdx.x == 0) {
+		double u = 0;
+		for (int k = 0; k <= n_iter; ++k) u += s_m[k];
+		scal[S_POLAR] = -0.5 * u; // :2618
+		scal[S_RRMS] = 0.0;
+	}
+}
+__global__ __launch_bounds__(256) void k_polar_moments(AtomsDev at, const double *__restrict__ dk, const double *__restrict__ e_static, int n_iter,
+                                                       double *__restrict__ scal) {
+	polar_moments_block(at, dk, e_static, n_iter, scal);
+}
+// (with the fold of the pair sweep's partials as the second block, as k_polar_energy_and_pairs)
+__global__ __launch_bounds__(256) void k_polar_moments_and_pairs(AtomsDev at, const double *__restrict__ dk, const double *__restrict__ e_static, int n_iter,
+                                                                 const double *__restrict__ block_part, const int *__restrict__ block_cnt, int nb,
+                                                                 double *__restrict__ scal, long long *__restrict__ cnt) {
+	if (blockIdx.x == 0) polar_moments_block(at, dk, e_static, n_iter, scal);
+	else reduce_pairs_block(block_part, block_cnt, nb, scal, cnt);
+}
+void launch_polar_moments(hipStream_t st, const AtomsDev &at, const double *dk, const double *e_static, int n_iter, double *scal) {
+	hipLaunchKernelGGL(k_polar_moments, dim3(1), dim3(256), 0, st, at, dk, e_static, n_iter, scal);
+}
+void launch_polar_moments_and_pairs(hipStream_t st, const AtomsDev &at, const double *dk, const double *e_static, int n_iter, const double *block_part,
+                                    const int *block_cnt, int nb, double *scal, long long *cnt) {
+	hipLaunchKernelGGL(k_polar_moments_and_pairs, dim3(2), dim3(256), 0, st, at, dk, e_static, n_iter, block_part, block_cnt, nb, scal, cnt);
+}
+
 // the tail of a polarizable evaluation in ONE launch: block 0 the polarization energy, block 1 the fold of the pair sweep's partials (both
 // single-block, fixed-order sums; the fold used to run on the side stream, whose fork and join each cost the main stream a barrier packet)
 __global__ __launch_bounds__(256) void k_polar_energy_and_pairs(AtomsDev at, const double *__restrict__ mu, const double *__restrict__ e_static,
@@ -662,9 +781,10 @@ __global__ __launch_bounds__(256) void k_polar_energy_and_pairs(AtomsDev at, con
 }
 
 void launch_dipole_update(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, int n_split, const double *mu_old,
-                          double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr, int *ctl, int *host_flag, int it) {
+                          double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr, int *ctl, int *host_flag, int it,
+                          double *dk) {
 	hipLaunchKernelGGL(k_dipole_update, dim3(at.n_pad / kTile), dim3(kTile * kSlotGroups), 0, st, at, e_static, part, n_split, mu_old, mu_new,
-	                   e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it);
+	                   e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
 }
 void launch_dipole_reset(hipStream_t st, const AtomsDev &at, const double *e_static, double *mu) {
 	hipLaunchKernelGGL(k_dipole_reset, dim3((at.n_pad + 255) / 256), dim3(256), 0, st, at, e_static, mu);

@@ -440,7 +440,7 @@ constexpr int kUpdRounds = 2; // rounds of the wave's groups per trip
 struct PanelUpdate {
 	const double *e_static;
 	const int *seg;
-	double *mu_new, *e_induced /*may be null*/, *rrms_atom;
+	double *mu_new, *e_induced /*may be null*/, *rrms_atom, *dk /*may be null: new_mu - mu_old*/;
 	double allowed_sqerr;
 	int *ctl, *host_flag;
 	int nt, it, want_rrms;
@@ -524,6 +524,7 @@ __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const Pane
 		if (d * d > u.allowed_sqerr) broke = true;
 		u.mu_new[3 * (size_t)i + p] = nm[p];
 		if (u.e_induced) u.e_induced[3 * (size_t)i + p] = fo[p];
+		if (u.dk) u.dk[3 * (size_t)i + p] = d;
 	}
 	if (u.want_rrms) {
 		double r = sqrt(acc / nn);
@@ -620,8 +621,9 @@ void launch_dipole_iter_panel(hipStream_t st, const AtomsDev &at, const Box &bx,
 
 void launch_dipole_update_panel(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, const double *gpart, const int *seg,
                                 const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr,
-                                int *ctl, int *host_flag, int it) {
+                                int *ctl, int *host_flag, int it, double *dk) {
 	PanelUpdate u{};
+	u.dk = dk;
 	u.e_static = e_static, u.seg = seg, u.mu_new = mu_new, u.e_induced = e_induced, u.rrms_atom = rrms_atom, u.allowed_sqerr = allowed_sqerr;
 	u.ctl = ctl, u.host_flag = host_flag, u.nt = at.n_pad / kTile, u.it = it, u.want_rrms = want_rrms;
 	hipLaunchKernelGGL(k_dipole_update_panel, dim3(at.n_pad / kTile), dim3(kTile * kUpdWaves), 0, st, at, part, gpart, mu_old, u);

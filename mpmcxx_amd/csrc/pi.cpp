@@ -10,6 +10,8 @@ using namespace mpmc;
 // independent evaluation on its own context and streams; all of them are enqueued before the first wait, so one bead's pair sweep
 // fills the launch ramps and tails of another bead's dipole iterations (a lockstep form that shared launches between the beads was
 // measured in round 1 -- 650 against 737 evaluations/s -- and removed in round 3).
+// The loop reads four scalars per bead and never the dipoles: a fixed-count Jacobi solve stops at the iterations its energy needs, and the
+// rest runs when somebody asks for the dipoles (finish_pending_dipoles).
 // An error in the middle of the loop must not leave evaluations in flight that nobody waits for: the caller's next step would write a
 // bead's buffers under a running evaluation.  Beads [first, last) are waited for, their results dropped; the first error stays the answer.
 static void pi_drain(mpmc_ctx **beads, int first, int last) {
@@ -48,7 +50,7 @@ extern "C" int mpmc_pi_potential_local(mpmc_ctx **beads, int n_local, double sum
 	if (!beads || n_local < 0 || !sums4) return MPMC_ERR_ARG;
 	for (int b = 0; b < n_local; b++) {
 		if (beads[b]) beads[b]->inflight_hint = n_local;
-		int rc = beads[b] ? enqueue(beads[b], full_mask(beads[b])) : MPMC_ERR_ARG;
+		int rc = beads[b] ? enqueue(beads[b], full_mask(beads[b]), /*dipoles on demand*/ true) : MPMC_ERR_ARG;
 		if (rc != MPMC_OK) {
 			pi_drain(beads, 0, b);
 			return rc;
@@ -69,7 +71,7 @@ extern "C" int mpmc_pi_potential_local_host(mpmc_ctx **beads, int n_local, const
 		int rc = (c && pos[b]) ? mpmc_update_positions(c, 0, c->n, pos[b]) : MPMC_ERR_ARG;
 		if (rc == MPMC_OK) {
 			c->inflight_hint = n_local;
-			rc = enqueue(c, full_mask(c));
+			rc = enqueue(c, full_mask(c), /*dipoles on demand*/ true);
 		}
 		if (rc != MPMC_OK) {
 			pi_drain(beads, 0, b);

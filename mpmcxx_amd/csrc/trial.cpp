@@ -74,12 +74,13 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		c->trial_keep = c->last_full;
 		int rc = mpmc_update_positions(c, c->trial_first, m, c->trial_new.data());
 		if (rc != MPMC_OK) return rc;
-		if ((rc = mpmc_energy_async(c)) != MPMC_OK) return rc;
+		if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) return rc; // (eager: an accepted trial's dipoles are its caller's at once)
 		c->trial_was_full = true;
 		c->trial_last_kind = 1;
 		c->trial_enqueued = true;
 		return MPMC_OK;
 	}
+	drop_pending_dipoles(c); // (the delta path swaps positions and rewrites the field and the store under an open on-demand solve)
 	int rc = prepare(c);
 	if (rc != MPMC_OK) return rc;
 	if ((rc = ensure_trial_buffers(c)) != MPMC_OK) return rc;
@@ -167,7 +168,9 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 				launch_field_recip(st, at, c->box, rt, o.ewald_kmax, c->d_e_recip_part);
 			}
 			c->mu_cur = 0;
-			launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_e_real_trial, 1, o.polar_gamma, c->d_e_static, c->d_mu[0]);
+			if (polar_moments_apply(c) && (rc = reserve_dk_ring(c)) != MPMC_OK) return rc;
+			launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_e_real_trial, 1, o.polar_gamma, c->d_e_static, c->d_mu[0], nullptr,
+			                      polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 		}
 		HIP_TRY(c, hipGetLastError());
 		c->trial_polar_delta = true;

@@ -167,6 +167,8 @@ def lib():
     L.mpmc_pi_gather_beads.argtypes = [vp, dp, C.c_int, C.c_int, dp]
     if hasattr(L, "mpmc_hint_in_flight") or not os.environ.get("MPMC_ENERGY_LIB"):
         L.mpmc_hint_in_flight.argtypes = [vp, C.c_int]
+    if hasattr(L, "mpmc_set_dipoles_on_demand") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an older build under the A/B override lacks it)
+        L.mpmc_set_dipoles_on_demand.argtypes = [vp, C.c_int]
     L.mpmc_pi_allreduce.argtypes = [C.POINTER(vp), C.c_int, dp, C.POINTER(Result), C.POINTER(C.c_int)]
     if hasattr(L, "mpmc_pi_allreduce_info") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an older build under the A/B override lacks the ABI-5 entry)
         L.mpmc_pi_allreduce_info.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -368,6 +370,11 @@ class System:
         """`polar_wolf`: the static field of the dipole solve as a Wolf sum with damping parameter polar_wolf_alpha in [0, 1]
         (mpmc_set_polar_wolf); it applies whenever polar_ewald is off."""
         self._check(self._L.mpmc_set_polar_wolf(self._h, int(bool(enabled)), float(polar_wolf_alpha)))
+
+    def set_dipoles_on_demand(self, enabled: bool):
+        """energy() / energy_async() of a fixed-count Jacobi solve stop at the iterations the energy needs; dipoles() runs the rest
+        (mpmc_set_dipoles_on_demand; the pi_* loops always work this way)"""
+        self._check(self._L.mpmc_set_dipoles_on_demand(self._h, int(bool(enabled))))
 
     def set_polar_palmo(self, enabled: bool):
         """`polar_palmo`: the Palmo-Krimm correction to the polarization energy (mpmc_set_polar_palmo)"""
