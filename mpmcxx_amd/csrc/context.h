@@ -305,7 +305,7 @@ struct mpmc_ctx {
 	DevBuf<int> d_moved_idx;
 	DevBuf<double4> d_sf_trial;
 	// polarizable boxes: the real-space static field of the accepted configuration (k_field_finalize) and of the trial one
-	// (e_real + delta of the pairs with a moved atom); they trade places on accept.  dk_part: scratch of k_delta_field.
+	// (e_real + delta of the pairs with a moved atom); they trade places on accept.  dk_part: scratch of k_field_delta.
 	DevBuf<double> d_e_real, d_e_real_trial, d_dk_part;
 	bool e_real_valid = false;     // d_e_real describes the accepted configuration
 	bool trial_polar_delta = false; // the open trial took the incremental polarizable path (positions swapped on the device)

@@ -1,5 +1,5 @@
-// device_math.h -- device-only helpers shared by the HIP translation units (wave reductions, SGPR-constant Horner
-// steps, exp, erfc).  Included after kernels.h; compiled with -ffp-contract=off like everything else.
+// device_math.h -- device-only helpers shared by the HIP translation units (the fixed-order wave and block reductions, SGPR-constant
+// Horner steps, exp, erfc).  Included after kernels.h; compiled with -ffp-contract=off like everything else.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,16 +9,39 @@
 
 namespace mpmc {
 
+// ---- reductions: the ONE place that fixes the order of every sum over lanes and waves (bit-reproducibility, see kernels.hip) ----------
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-	return v;
+	return v; // valid in lane 0
 }
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
 	return v;
 }
+// sum over a 256-thread block; result valid in thread 0.  `sh` must hold 4 doubles.
+__device__ __forceinline__ double block_sum_256(double v, double *sh) {
+	v = wave_sum(v);
+	__syncthreads();
+	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+	__syncthreads();
+	return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+// sum of one count per thread of a 256-thread block.  `shc` must hold 256 entries.
+__device__ __forceinline__ long long block_count_256(long long v, long long *shc) {
+	__syncthreads();
+	shc[threadIdx.x] = v;
+	__syncthreads();
+	for (int off = 128; off > 0; off >>= 1) {
+		if (threadIdx.x < off) shc[threadIdx.x] += shc[threadIdx.x + off];
+		__syncthreads();
+	}
+	return shc[0];
+}
+
+// tile pair (I <= J) of nt tiles -> its index in the row-major upper-triangle tile-pair table
+__device__ __forceinline__ int tp_index(int I, int J, int nt) { return I * nt - (I * (I - 1)) / 2 + (J - I); }
 
 // lane l receives the value held by lane (l+1) & 63: two v_mov_b32_dpp wave_rol:1 (verified once per device at context creation,
 // launch_rot_selftest)

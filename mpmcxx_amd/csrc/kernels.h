@@ -5,10 +5,23 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "pair_math.h"
 
 namespace mpmc {
+
+// run-time flags -> template arguments: f receives std::true_type / std::false_type per flag, e.g.
+//   with_flags(bx.ortho, damped, [&](auto O, auto D) { hipLaunchKernelGGL((k<O.value, D.value>), ...); });
+template <class F>
+inline void with_flag(bool a, F &&f) {
+	if (a) f(std::true_type{});
+	else f(std::false_type{});
+}
+template <class F>
+inline void with_flags(bool a, bool b, F &&f) {
+	with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { f(A, B); }); });
+}
 
 constexpr int kTile = 64; // one wavefront owns 64 i-atoms; j-atoms are staged in LDS 64 at a time
 constexpr int kKSplit = 8; // k-vector range split of the reciprocal field kernel: at least this many slices, ...

@@ -7,30 +7,9 @@
 //
 // Compiled with -ffp-contract=off (see pair_math.h).
 #include "kernels.h"
+#include "device_math.h"
 
 namespace mpmc {
-
-// ------------------------------------------------------------------------------------------------------
-// reductions
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-	return v; // valid in lane 0
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-	return v;
-}
-// sum over a 256-thread block; result valid in thread 0.  `sh` must hold 4 doubles.
-__device__ __forceinline__ double block_sum_256(double v, double *sh) {
-	v = wave_sum(v);
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // ------------------------------------------------------------------------------------------------------
 // fixed-order final reduction of the per-tile-pair partials of k_pair_fused: {lj, es_real} and {n_lj, n_es}
@@ -54,15 +33,11 @@ __device__ __forceinline__ void reduce_pairs_block(const double *__restrict__ bl
 		scal[S_LJ] = s0;
 		scal[S_ES_REAL] = s1;
 	}
-	for (int k = 0; k < 2; ++k) {
-		__syncthreads();
-		shc[threadIdx.x] = k ? c1 : c0;
-		__syncthreads();
-		for (int off = 128; off > 0; off >>= 1) {
-			if (threadIdx.x < off) shc[threadIdx.x] += shc[threadIdx.x + off];
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) cnt[k ? C_ES_IN : C_LJ_IN] = shc[0];
+	c0 = block_count_256(c0, shc);
+	c1 = block_count_256(c1, shc);
+	if (threadIdx.x == 0) {
+		cnt[C_LJ_IN] = c0;
+		cnt[C_ES_IN] = c1;
 	}
 }
 __global__ __launch_bounds__(256) void k_reduce_pairs(const double *__restrict__ block_part, const int *__restrict__ block_cnt, int nb,
@@ -108,14 +83,8 @@ __global__ __launch_bounds__(256) void k_reduce_counts4(const int *__restrict__ 
 	for (int b = threadIdx.x; b < nb; b += 256) // (one block over all tile pairs: unrolled, the loads overlap)
 		for (int k = 0; k < 4; ++k) c[k] += block_cnt[4 * (size_t)b + k];
 	for (int k = 0; k < 4; ++k) {
-		__syncthreads();
-		shc[threadIdx.x] = c[k];
-		__syncthreads();
-		for (int off = 128; off > 0; off >>= 1) {
-			if (threadIdx.x < off) shc[threadIdx.x] += shc[threadIdx.x + off];
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) cnt4[k] = shc[0];
+		const long long tot = block_count_256(c[k], shc);
+		if (threadIdx.x == 0) cnt4[k] = tot;
 	}
 }
 void launch_static_counts(hipStream_t st, const AtomsDev &at, const int2 *tile_pairs, int n_tile_pairs, int *block_cnt, long long *cnt4) {

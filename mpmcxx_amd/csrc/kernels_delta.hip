@@ -7,8 +7,11 @@
 // in its old and in its new geometry, with exactly the per-pair arithmetic of k_pair_fused -- plus the change of the
 // structure factors:   E_trial = E_accepted + sum_{pairs with a moved atom} (u_new - u_old) + (E_recip[S + dS] - E_recip[S]).
 // Cost O(m N) + O(K m) instead of O(N^2) + O(K N).
+// The moved-atom map (k_mark_moved), the delta-field kernel and its finish (k_field_delta, k_field_delta_finish) and their launch sequence
+// live in trial_kernels.h, shared with the other trial-move terms; the block reductions in device_math.h.  Here: the pair arithmetic.
 #include "kernels.h"
 #include "device_math.h"
+#include "trial_kernels.h"
 
 namespace mpmc {
 
@@ -237,16 +240,9 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 			const double4 sf = sf_trial[k];
 			e += rc.w_en[k] * (sf.x * sf.x + sf.y * sf.y);
 		}
-	auto bsum = [&](double v) {
-		v = wave_sum(v);
-		__syncthreads();
-		if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-		__syncthreads();
-		return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-	};
-	s0 = bsum(s0);
-	s1 = bsum(s1);
-	e = bsum(e);
+	s0 = block_sum_256(s0, sh);
+	s1 = block_sum_256(s1, sh);
+	e = block_sum_256(e, sh);
 	if (threadIdx.x == 0) {
 		out[0] = s0;
 		out[1] = s1;
@@ -254,16 +250,11 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 		out[3] = e * (4.0 * kPi / bx.volume);
 		out[4] = (double)0;
 	}
-	long long tot[2] = {0, 0};
-	for (int k = 0; k < 2; ++k) {
-		__syncthreads();
-		shc[threadIdx.x] = k ? c1 : c0;
-		__syncthreads();
-		for (int off = 128; off > 0; off >>= 1) {
-			if (threadIdx.x < off) shc[threadIdx.x] += shc[threadIdx.x + off];
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) dcnt[k] = tot[k] = shc[0];
+	c0 = block_count_256(c0, shc);
+	c1 = block_count_256(c1, shc);
+	if (threadIdx.x == 0) {
+		dcnt[0] = c0;
+		dcnt[1] = c1;
 	}
 	// the result goes to the caller's pinned block from here (no copy-back command, no stream synchronisation: the host polls the launch
 	// number, which is stored last, behind a system-scope fence)
@@ -274,8 +265,8 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 		host_out[3] = e * (4.0 * kPi / bx.volume);
 		host_out[4] = 0.0;
 		long long *hc = reinterpret_cast<long long *>(host_out + 5);
-		hc[0] = tot[0];
-		hc[1] = tot[1];
+		hc[0] = c0;
+		hc[1] = c1;
 		host_out[7] = out[7]; // (the three-body delta of contexts with the term, kernels_three_body.hip; 0 for every other context)
 		host_out[9] = out[8]; // (the disp-expansion delta likewise, kernels_disp.hip; behind the launch number's slot 8, which stays where it was)
 		__threadfence_system();
@@ -283,119 +274,48 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 	}
 }
 
-// set / clear the moved-atom index map
-__global__ void k_mark_moved(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m, int set) {
-	const int k = blockIdx.x * blockDim.x + threadIdx.x;
-	if (k < m) moved_idx[mv_slot[k]] = set ? k : -1;
-}
-
-// ---- polarizable boxes: change of the REAL-SPACE static field ---------------------------------------------------------------------
-// thole_field's real part (real_term :2900-2940 with polar_ewald, thole_field_nopbc :3300-3333 without) is a pair sum: a trial move of
-// m atoms changes, for every atom j, only the terms with a moved partner.  Thread = atom j, loop over the moved atoms k, each pair in
-// its new and in its old geometry with the arithmetic of k_pair_fused:
-//   E_j += q_k [F(r_j - r_k')  - F(r_j - r_k)],      E_k += q_j [F(r_k' - r_j) - F(r_k - r_j)]   (F odd: the pair is evaluated once)
+// ---- polarizable boxes: change of the REAL-SPACE static field (k_field_delta, trial_kernels.h) -----------------------------------------
+// thole_field's real part (real_term :2900-2940 with polar_ewald, thole_field_nopbc :3300-3333 without), with the arithmetic of k_pair_fused.
 // FIELD 1: F(d) = fac(|d|) d with fac = (2 a/sqrt(pi) e^{-a^2 r^2} r +- erfc/erf(a r)) / r^3 inside the cutoff (es_excluded pairs take
-// the erf form); FIELD 2: fac = 1/r^3 for inter-molecular pairs inside the cutoff.  The moved atoms' own changes are reduced per wave and
-// land in dk_part[tile][k][3]; k_delta_field_finish adds them up over the tiles.
-template <bool ORTHO, int FIELD>
-__device__ __forceinline__ void field_pair(const Box &bx, double ap, const double4 &pi, const double4 &pj, const PairFlags &f, double sg,
-                                           double (&ei)[3], double (&ej)[3]) {
-	double ox, oy, oz;
-	const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
-	if (ri2 == 0.0) return;
-	double fac;
-	if (FIELD == 1) {
-		if (!(ri2 <= bx.t_es) || (pi.w == 0.0 && pj.w == 0.0)) return; // real_term :2916-2917
-		const double ir = fast_rsqrt_1(ri2), r = ri2 * ir;
-		double ga;
-		const double ec = erfc_and_gauss(ap * r, ga);
-		const double g = (2.0 * kOneOverSqrtPi * ap) * (ga * r);
-		fac = (f.es_excluded ? (g - (1.0 - ec)) : (g + ec)) * (ir * ir * ir);
-	} else {
-		if (f.intra || !(ri2 <= bx.t_lj)) return; // thole_field_nopbc :3311-3326
-		const double ir = fast_rsqrt_1(ri2);
-		fac = ir * ir * ir;
-	}
-	const double fj = sg * fac * pj.w, fi = sg * fac * pi.w;
-	ei[0] = fma(fj, ox, ei[0]);
-	ei[1] = fma(fj, oy, ei[1]);
-	ei[2] = fma(fj, oz, ei[2]);
-	ej[0] = fma(-fi, ox, ej[0]);
-	ej[1] = fma(-fi, oy, ej[1]);
-	ej[2] = fma(-fi, oz, ej[2]);
-}
-
-template <bool ORTHO, int FIELD>
-__global__ __launch_bounds__(64) void k_delta_field(AtomsDev at, Box bx, double ap, const int *__restrict__ mv_slot, const double4 *__restrict__ mv_new,
-                                                    int m, const int *__restrict__ moved_idx, const double *__restrict__ e_real,
-                                                    double *__restrict__ e_real_trial, double *__restrict__ dk_part /*[n_tiles][m][3]*/) {
-	const int j = blockIdx.x * kTile + threadIdx.x;
-	const double4 pj_old = at.xyzq[j];
-	const int2 mj = at.mf[j];
-	int kj = -1;
-	if (moved_idx) kj = moved_idx[j];
-	else
-		for (int k = 0; k < m; ++k)
-			if (mv_slot[k] == j) kj = k;
-	const double4 pj_new = (kj >= 0) ? mv_new[kj] : pj_old;
-	const bool j_real = !(mj.y & AF_PAD);
-	double ej[3] = {0, 0, 0};
-	for (int k = 0; k < m; ++k) {
-		double ek[3] = {0, 0, 0};
-		if (j_real && !(kj >= 0 && kj <= k)) { // moved-moved pairs once (from the higher list index), never an atom with itself
-			const int si = mv_slot[k];
-			const int2 mi = at.mf[si];
-			const PairFlags f = pair_flags(mi.x, mi.y, mj.x, mj.y);
-			if (!f.frozen) {
-				field_pair<ORTHO, FIELD>(bx, ap, mv_new[k], pj_new, f, 1.0, ek, ej);
-				field_pair<ORTHO, FIELD>(bx, ap, at.xyzq[si], pj_old, f, -1.0, ek, ej);
-			}
+// the erf form); FIELD 2: fac = 1/r^3 for inter-molecular pairs inside the cutoff.
+template <int FIELD>
+struct EwaldField {
+	double ap; // polar_ewald_alpha
+	template <bool ORTHO>
+	__device__ __forceinline__ void add(const Box &bx, const double4 &pi, const double4 &pj, const PairFlags &f, double sg, double (&ei)[3],
+	                                    double (&ej)[3]) const {
+		double ox, oy, oz;
+		const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
+		if (ri2 == 0.0) return;
+		double fac;
+		if (FIELD == 1) {
+			if (!(ri2 <= bx.t_es) || (pi.w == 0.0 && pj.w == 0.0)) return; // real_term :2916-2917
+			const double ir = fast_rsqrt_1(ri2), r = ri2 * ir;
+			double ga;
+			const double ec = erfc_and_gauss(ap * r, ga);
+			const double g = (2.0 * kOneOverSqrtPi * ap) * (ga * r);
+			fac = (f.es_excluded ? (g - (1.0 - ec)) : (g + ec)) * (ir * ir * ir);
+		} else {
+			if (f.intra || !(ri2 <= bx.t_lj)) return; // thole_field_nopbc :3311-3326
+			const double ir = fast_rsqrt_1(ri2);
+			fac = ir * ir * ir;
 		}
-		for (int d = 0; d < 3; ++d) ek[d] = wave_sum(ek[d]);
-		if (threadIdx.x == 0) {
-			double *o = dk_part + ((size_t)blockIdx.x * m + k) * 3;
-			o[0] = ek[0];
-			o[1] = ek[1];
-			o[2] = ek[2];
-		}
+		const double fj = sg * fac * pj.w, fi = sg * fac * pi.w;
+		ei[0] = fma(fj, ox, ei[0]);
+		ei[1] = fma(fj, oy, ei[1]);
+		ei[2] = fma(fj, oz, ei[2]);
+		ej[0] = fma(-fi, ox, ej[0]);
+		ej[1] = fma(-fi, oy, ej[1]);
+		ej[2] = fma(-fi, oz, ej[2]);
 	}
-	for (int d = 0; d < 3; ++d) e_real_trial[3 * (size_t)j + d] = e_real[3 * (size_t)j + d] + ej[d];
-}
-// the moved atoms' own share: e_real_trial[slot_k] += sum over tiles of dk_part[tile][k]  (one thread per moved atom, tiles in order)
-__global__ __launch_bounds__(64) void k_delta_field_finish(const int *__restrict__ mv_slot, int m, int n_tiles, const double *__restrict__ dk_part,
-                                                           double *__restrict__ e_real_trial) {
-	const int k = blockIdx.x * 64 + threadIdx.x;
-	if (k >= m) return;
-	double s[3] = {0, 0, 0};
-	for (int t = 0; t < n_tiles; ++t) {
-		const double *q = dk_part + ((size_t)t * m + k) * 3;
-		s[0] += q[0];
-		s[1] += q[1];
-		s[2] += q[2];
-	}
-	double *o = e_real_trial + 3 * (size_t)mv_slot[k];
-	o[0] += s[0];
-	o[1] += s[1];
-	o[2] += s[2];
-}
+};
 
 void launch_delta_field(hipStream_t st, const AtomsDev &at, const Box &bx, double polar_ewald_alpha, int polar_ewald, const int *mv_slot,
                         const double4 *mv_new, int m, int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part) {
-	const int nt = at.n_pad / kTile;
-	const bool use_map = (m > 8);
-	if (use_map) hipLaunchKernelGGL(k_mark_moved, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m, 1);
-	else moved_idx = nullptr;
-#define MPMC_DF(O, F) hipLaunchKernelGGL((k_delta_field<O, F>), dim3(nt), dim3(kTile), 0, st, at, bx, polar_ewald_alpha, mv_slot, mv_new, m, moved_idx, e_real, e_real_trial, dk_part)
-	if (bx.ortho) {
-		if (polar_ewald) MPMC_DF(true, 1);
-		else MPMC_DF(true, 2);
-	} else {
-		if (polar_ewald) MPMC_DF(false, 1);
-		else MPMC_DF(false, 2);
-	}
-#undef MPMC_DF
-	hipLaunchKernelGGL(k_delta_field_finish, dim3((m + 63) / 64), dim3(64), 0, st, mv_slot, m, nt, dk_part, e_real_trial);
-	if (use_map) hipLaunchKernelGGL(k_mark_moved, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m, 0);
+	with_flags(bx.ortho, polar_ewald != 0, [&](auto O, auto E) { // short lists are scanned in the kernel, long ones go through the map
+		launch_field_delta<O.value>(st, at, bx, EwaldField<E.value ? 1 : 2>{polar_ewald_alpha}, m > 8, mv_slot, mv_new, m, moved_idx, e_real, e_real_trial,
+		                            dk_part);
+	});
 }
 
 // swap: the resident positions of the moved atoms become the trial ones, the old ones are kept in mv_new's place (a second call undoes it)
@@ -442,14 +362,14 @@ void launch_delta(hipStream_t st, const AtomsDev &at, const int *slot_of, const 
 		return;
 	}
 	const bool use_map = (m > 8); // short lists are scanned in the kernels; long ones go through the slot -> list-index map
-	if (use_map) hipLaunchKernelGGL(k_mark_moved, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m, 1);
+	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 1);
 	else moved_idx = nullptr;
 	const MvDev mv{mv_slot, orig_of_mv, mv_new};
 	MPMC_DELTA_OE(MvDev, mv, moved_idx)
 #undef MPMC_DELTA_OE
 #undef MPMC_DELTA
 	hipLaunchKernelGGL(k_delta_finish, dim3(1), dim3(256), 0, st, block_part, block_cnt, nt, rc, sf_trial, bx, do_ewald, out4, dcnt2, host_out, seq);
-	if (use_map) hipLaunchKernelGGL(k_mark_moved, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m, 0);
+	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 0);
 }
 // accept, the move in the kernel arguments
 __global__ void k_commit_positions_arg(double4 *__restrict__ xyzq, MvArg mv, int m) {

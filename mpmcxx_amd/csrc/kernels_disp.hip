@@ -10,12 +10,13 @@
 //
 // k_disp_expansion: all tile pairs I <= J of the 64-atom tiles, one wave per tile pair, lanes own the i-atoms, the j-tile in LDS read at
 // wave-uniform addresses; equal tiles keep i < j.  Workgroups take tile pairs in a fixed stride and leave one fp64 partial each;
-// k_disp_sum adds them in a fixed order, so a repeated evaluation is bit-identical.
+// k_sum_partials (trial_kernels.h) adds them in a fixed order, unscaled, so a repeated evaluation is bit-identical.
 //
 // k_disp_expansion_delta: the change under a trial move of m atoms (slots mv_slot, new positions mv_new; old positions resident).  One wave
 // per (moved atom t, tile J), lanes own j; a pair of two moved atoms belongs to the one earlier in the move list: O(m N).
 #include "kernels.h"
 #include "device_math.h"
+#include "trial_kernels.h"
 
 namespace mpmc {
 
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(64) void k_disp_expansion(const double4 *__restrict
 	if (l == 0) part[blockIdx.x] = acc;
 }
 
-// moved_idx[slot] = index of the slot in the moved list, -1 for every other slot (set by k_disp_mark)
+// moved_idx[slot] = index of the slot in the moved list, -1 for every other slot (k_mark_moved, trial_kernels.h)
 template <bool ORTHO, bool DAMP>
 __global__ __launch_bounds__(64) void k_disp_expansion_delta(const double4 *__restrict__ xyzq, const int2 *__restrict__ mf, const double4 *__restrict__ co,
                                                              const double *__restrict__ t10, int n, int n_tiles, Box bx, DispParams dp,
@@ -129,61 +130,28 @@ __global__ __launch_bounds__(64) void k_disp_expansion_delta(const double4 *__re
 	if (l == 0) part[blockIdx.x] = acc;
 }
 
-__global__ void k_disp_mark(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m) {
-	const int k = blockIdx.x * blockDim.x + threadIdx.x;
-	if (k < m) moved_idx[mv_slot[k]] = k;
-}
-
-// out[0] = the partials summed in a fixed order; with_lrc: out[1], out[2] = the two long-range corrections; clears the moved-atom map
-// behind a delta launch (mv_slot may be null)
-__global__ __launch_bounds__(256) void k_disp_sum(const double *__restrict__ part, int nparts, double *__restrict__ out, int with_lrc, double lrc_pair,
-                                                  double lrc_self, int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m) {
-	__shared__ double sh[4];
-	double s = 0.0;
-	for (int b = threadIdx.x; b < nparts; b += 256) s += part[b];
-	s = wave_sum(s);
-	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		out[0] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-		if (with_lrc) out[1] = lrc_pair, out[2] = lrc_self;
-	}
-	if (mv_slot)
-		for (int k = threadIdx.x; k < m; k += 256) moved_idx[mv_slot[k]] = -1;
-}
-
 int disp_grid(long long work_items) { return (int)std::min<long long>(work_items, kDispBlocks); }
 
 void launch_disp_expansion(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const int2 *tile_pairs, int n_tile_pairs,
                            const Box &bx, const DispParams &dp, double lrc_pair, double lrc_self, double *part, double *out) {
 	const int grid = disp_grid(n_tile_pairs);
-#define MPMC_DISP_FULL(O, D) hipLaunchKernelGGL((k_disp_expansion<O, D>), dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, co, t10, tile_pairs, at.n, n_tile_pairs, bx, dp, part)
-	if (bx.ortho) {
-		if (dp.damp) MPMC_DISP_FULL(true, true);
-		else MPMC_DISP_FULL(true, false);
-	} else {
-		if (dp.damp) MPMC_DISP_FULL(false, true);
-		else MPMC_DISP_FULL(false, false);
-	}
-#undef MPMC_DISP_FULL
-	hipLaunchKernelGGL(k_disp_sum, dim3(1), dim3(256), 0, st, part, grid, out, 1, lrc_pair, lrc_self, nullptr, nullptr, 0);
+	with_flags(bx.ortho, dp.damp != 0, [&](auto O, auto D) {
+		hipLaunchKernelGGL((k_disp_expansion<O.value, D.value>), dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, co, t10, tile_pairs, at.n, n_tile_pairs, bx, dp,
+		                   part);
+	});
+	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 0, 1.0, 1, lrc_pair, lrc_self, nullptr, nullptr, 0); // (+ the corrections)
 }
 
 void launch_disp_expansion_delta(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const Box &bx, const DispParams &dp,
                                  const int *mv_slot, const double4 *mv_new, int m, int *moved_idx, double *part, double *out) {
 	const int nt = at.n_pad / kTile;
 	const int grid = disp_grid((long long)m * nt);
-	hipLaunchKernelGGL(k_disp_mark, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m);
-#define MPMC_DISP_DELTA(O, D) hipLaunchKernelGGL((k_disp_expansion_delta<O, D>), dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, co, t10, at.n, nt, bx, dp, mv_slot, mv_new, m, moved_idx, part)
-	if (bx.ortho) {
-		if (dp.damp) MPMC_DISP_DELTA(true, true);
-		else MPMC_DISP_DELTA(true, false);
-	} else {
-		if (dp.damp) MPMC_DISP_DELTA(false, true);
-		else MPMC_DISP_DELTA(false, false);
-	}
-#undef MPMC_DISP_DELTA
-	hipLaunchKernelGGL(k_disp_sum, dim3(1), dim3(256), 0, st, part, grid, out, 0, 0.0, 0.0, moved_idx, mv_slot, m);
+	launch_mark_moved(st, moved_idx, mv_slot, m, 1);
+	with_flags(bx.ortho, dp.damp != 0, [&](auto O, auto D) {
+		hipLaunchKernelGGL((k_disp_expansion_delta<O.value, D.value>), dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, co, t10, at.n, nt, bx, dp, mv_slot, mv_new,
+		                   m, moved_idx, part);
+	});
+	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 0, 1.0, 0, 0.0, 0.0, moved_idx, mv_slot, m); // (clears the map)
 }
 
 } // namespace mpmc

@@ -34,8 +34,6 @@ constexpr int kSweepWaves = 4;
 constexpr int kSpecialAtom = AF_FROZEN | AF_NULL_RD | AF_HAS_DISP | AF_NEG_SIGMA | AF_ZERO_SIGMA | AF_ZERO_Q; // (what pair_flags / lj_mix look at)
 constexpr int kUnmaskable = kAtomFlagsMixing; // (pair_math.h) these change the MIXING (lj_mix), not just the masks: the generic kernel keeps them
 
-__device__ __forceinline__ int sweep_tp_index(int I, int J, int nt) { return I * nt - (I * (I - 1)) / 2 + (J - I); }
-
 typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr double kSweepEsScale = 0.5, kSweepFieldScale = 0.125; // the walk works with Y = 2 / r: its Coulomb sum carries 2 / r, its field sums 8 / r^3
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(64 * kSweepWaves) void k_pair_sweep(AtomsDev at, Bo
 	if (!split && I > J) return; // (a j-tile's last workgroup may have fewer tile pairs than waves; with pp.split every wave stays for the barriers)
 	const bool have_tp = (I <= J);
 	const int nt = pp.nt;
-	const int tp = have_tp ? sweep_tp_index(I, J, nt) : 0;
+	const int tp = have_tp ? tp_index(I, J, nt) : 0;
 	const int i = (have_tp ? I : J) * kTile + lane;
 	const double4 pi = at.xyzq[i];
 	const double2 li = at.lj[i];

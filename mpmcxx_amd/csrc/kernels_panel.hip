@@ -52,8 +52,6 @@ constexpr int kPanelWaves = MPMC_PANEL_WAVES;
 #endif
 constexpr double kFarSumScale = 0.125; // the far-field walk works with 2 / r (pan_step): its sums carry 8 / r^3
 
-__device__ __forceinline__ int tp_index(int I, int J, int nt) { return I * nt - (I * (I - 1)) / 2 + (J - I); }
-
 // One WAVE per j-tile J.  Its off-diagonal tile pairs (I < J, J) are taken 64 at a time: lane = one tile pair, key = its class
 // (far << 3 | uniform mask).  Within a class the members pair up by rank (ballot + popcount): ranks (0,1), (2,3), ...; an odd one out
 // is carried to the next chunk of 64 as that class's pending member.  At the end the pending members of equal kind (stored / far)

@@ -467,11 +467,8 @@ __global__ __launch_bounds__(256) void k_intra_terms(AtomsDev at, const int *__r
 			acc += qq * (1.0 - erfc_and_gauss(alpha * (r2 * ir), g)) * ir; // erf = 1 - erfc
 		}
 	}
-	acc = wave_sum(acc);
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-	__syncthreads();
-	if (threadIdx.x == 0) scal[S_ES_INTRA] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+	acc = block_sum_256(acc, sh);
+	if (threadIdx.x == 0) scal[S_ES_INTRA] = acc;
 }
 void launch_intra_terms(hipStream_t st, const AtomsDev &at, const int *slot_of, double ewald_alpha, double *scal) {
 	hipLaunchKernelGGL(k_intra_terms, dim3(1), dim3(256), 0, st, at, slot_of, ewald_alpha, scal);

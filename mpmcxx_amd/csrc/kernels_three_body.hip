@@ -14,8 +14,8 @@
 // k_three_body walks unordered triples of the 64-atom tiles of the spatial order, I <= J <= K, one wave per tile triple: lanes own k, the
 // (i, k) vector and r^2 stay in registers across the j loop, the (i, j) row of the j-tile (vector, r^2, a_i a_j, u_i + u_j, molecule) is
 // computed once per i into LDS and read at a wave-uniform address, the (j, k) vector is recomputed per triple.  Equal tiles keep i < j < k.
-// Workgroups take tile triples in a fixed stride and leave one fp64 partial each; k_three_body_sum adds them in a fixed order, so repeated
-// evaluations are bit-identical.
+// Workgroups take tile triples in a fixed stride and leave one fp64 partial each; k_sum_partials (trial_kernels.h) adds them in a fixed order,
+// so repeated evaluations are bit-identical.
 //
 // k_three_body_delta: the change of E3 under a trial move of m atoms (slots mv_slot, new positions mv_new).  A triple with a moved atom is
 // owned by its lowest-slot moved atom a, which pairs with every pair {b, c} of atoms that are neither a nor a moved atom of lower slot;
@@ -23,6 +23,7 @@
 // the b-tile in LDS, the (a, c) vectors in registers, (b, c) recomputed: O(m N^2).
 #include "kernels.h"
 #include "device_math.h"
+#include "trial_kernels.h"
 
 namespace mpmc {
 
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(64) void k_three_body(const double4 *__restrict__ x
 	if (l == 0) part[blockIdx.x] = acc;
 }
 
-// trial moves.  moved_idx[slot] = index of the slot in the moved list, -1 for every other slot (set by k_three_body_mark)
+// trial moves.  moved_idx[slot] = index of the slot in the moved list, -1 for every other slot (k_mark_moved, trial_kernels.h)
 template <bool ORTHO>
 __global__ __launch_bounds__(64) void k_three_body_delta(const double4 *__restrict__ xyzq, const int2 *__restrict__ mf, const double2 *__restrict__ au,
                                                          int n, int n_tile_pairs, Box bx, const int *__restrict__ mv_slot,
@@ -182,34 +183,14 @@ __global__ __launch_bounds__(64) void k_three_body_delta(const double4 *__restri
 	if (l == 0) part[blockIdx.x] = acc;
 }
 
-__global__ void k_three_body_mark(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m) {
-	const int k = blockIdx.x * blockDim.x + threadIdx.x;
-	if (k < m) moved_idx[mv_slot[k]] = k;
-}
-
-// out[0] = scale * (sum of the partials in a fixed order); clears the moved-atom map behind a delta launch (mv_slot may be null)
-__global__ __launch_bounds__(256) void k_three_body_sum(const double *__restrict__ part, int nparts, double scale, double *__restrict__ out,
-                                                        int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m) {
-	__shared__ double sh[4];
-	double s = 0.0;
-	for (int b = threadIdx.x; b < nparts; b += 256) s += part[b];
-	s = wave_sum(s);
-	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-	__syncthreads();
-	if (threadIdx.x == 0) out[0] = (((sh[0] + sh[1]) + sh[2]) + sh[3]) * scale;
-	if (mv_slot)
-		for (int k = threadIdx.x; k < m; k += 256) moved_idx[mv_slot[k]] = -1;
-}
-
 long long three_body_tile_triples(int n_tiles) { return (long long)n_tiles * (n_tiles + 1) * (n_tiles + 2) / 6; }
 int three_body_grid(long long work_items) { return (int)std::min<long long>(work_items, kThreeBodyBlocks); }
 
 void launch_three_body(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, double *part, double *out) {
 	const int nt3 = (int)three_body_tile_triples(at.n_pad / kTile); // (mpmc_set_axilrod_teller refuses boxes beyond INT_MAX tile triples)
 	const int grid = three_body_grid(nt3);
-	if (bx.ortho) hipLaunchKernelGGL(k_three_body<true>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, nt3, bx, part);
-	else hipLaunchKernelGGL(k_three_body<false>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, nt3, bx, part);
-	hipLaunchKernelGGL(k_three_body_sum, dim3(1), dim3(256), 0, st, part, grid, scale, out, nullptr, nullptr, 0);
+	with_flag(bx.ortho, [&](auto O) { hipLaunchKernelGGL(k_three_body<O.value>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, nt3, bx, part); });
+	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 1, scale, 0, 0.0, 0.0, nullptr, nullptr, 0);
 }
 
 void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, const int *mv_slot, const double4 *mv_new,
@@ -217,12 +198,11 @@ void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *
 	const int nt = at.n_pad / kTile;
 	const int ntp = nt * (nt + 1) / 2;
 	const int grid = three_body_grid(ntp);
-	hipLaunchKernelGGL(k_three_body_mark, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m);
-	if (bx.ortho)
-		hipLaunchKernelGGL(k_three_body_delta<true>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, ntp, bx, mv_slot, mv_new, m, moved_idx, part);
-	else
-		hipLaunchKernelGGL(k_three_body_delta<false>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, ntp, bx, mv_slot, mv_new, m, moved_idx, part);
-	hipLaunchKernelGGL(k_three_body_sum, dim3(1), dim3(256), 0, st, part, grid, scale, out, moved_idx, mv_slot, m);
+	launch_mark_moved(st, moved_idx, mv_slot, m, 1);
+	with_flag(bx.ortho, [&](auto O) {
+		hipLaunchKernelGGL(k_three_body_delta<O.value>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, ntp, bx, mv_slot, mv_new, m, moved_idx, part);
+	});
+	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 1, scale, 0, 0.0, 0.0, moved_idx, mv_slot, m); // (clears the map)
 }
 
 } // namespace mpmc

@@ -15,13 +15,14 @@
 // accumulated in registers without atomics and in a fixed order -- a repeated evaluation gives the same bits.  The sums land in the
 // real-space field slots [source tile][atom][3] that k_field_finalize adds up; tile pairs wholly beyond the cutoff publish zeros.
 //
-// k_wolf_field_delta: the change of that field under a trial move of m atoms, O(m N): thread = atom j, loop over the moved atoms, each
-// pair in its new and in its old geometry (the layout of k_delta_field, kernels_delta.hip).
+// Trial moves: the change of that field under a move of m atoms, O(m N), is k_field_delta (trial_kernels.h: thread = atom j, loop over
+// the moved atoms, each pair in its new and in its old geometry) with the pair arithmetic WolfField below.
 //
 // k_palmo_reduce: ef_induced_change = F - E_ind per polarizable atom, with F = -sum A_ij mu_j from one more contraction of the final
 // dipoles and E_ind the induced field the last sweep used; the correction -1/2 sum mu . ef_induced_change goes on top of S_POLAR.
 #include "kernels.h"
 #include "device_math.h"
+#include "trial_kernels.h"
 
 namespace mpmc {
 
@@ -110,106 +111,37 @@ __global__ __launch_bounds__(64) void k_wolf_field(AtomsDev at, Box bx, WolfFiel
 void launch_wolf_field(hipStream_t st, const AtomsDev &at, const Box &bx, const WolfFieldParams &wp, const int2 *tile_pairs, const int *cls,
                        int n_tile_pairs, double *fpart) {
 	if (n_tile_pairs <= 0) return;
-#define MPMC_WF(O, D) hipLaunchKernelGGL((k_wolf_field<O, D>), dim3(n_tile_pairs), dim3(kTile), 0, st, at, bx, wp, tile_pairs, cls, fpart)
-	if (bx.ortho) {
-		if (wp.a != 0.0) MPMC_WF(true, true);
-		else MPMC_WF(true, false);
-	} else {
-		if (wp.a != 0.0) MPMC_WF(false, true);
-		else MPMC_WF(false, false);
-	}
-#undef MPMC_WF
+	with_flags(bx.ortho, wp.a != 0.0, [&](auto O, auto D) {
+		hipLaunchKernelGGL((k_wolf_field<O.value, D.value>), dim3(n_tile_pairs), dim3(kTile), 0, st, at, bx, wp, tile_pairs, cls, fpart);
+	});
 }
 
 // ---- trial moves -------------------------------------------------------------------------------------------------------------------
-template <bool ORTHO, bool DAMPED>
-__device__ __forceinline__ void wolf_field_pair(const Box &bx, const WolfFieldParams &wp, const double4 &pi, const double4 &pj, const PairFlags &f, double sg,
-                                                double (&ei)[3], double (&ej)[3]) {
-	double ox, oy, oz;
-	const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
-	if (ri2 == 0.0 || f.intra || !(ri2 <= bx.t_lj)) return; // :3361-3368
-	const double fac = wolf_fac<DAMPED>(wp, ri2);
-	const double fj = sg * fac * pj.w, fi = sg * fac * pi.w;
-	ei[0] = fma(fj, ox, ei[0]);
-	ei[1] = fma(fj, oy, ei[1]);
-	ei[2] = fma(fj, oz, ei[2]);
-	ej[0] = fma(-fi, ox, ej[0]);
-	ej[1] = fma(-fi, oy, ej[1]);
-	ej[2] = fma(-fi, oz, ej[2]);
-}
-
-// moved_idx[slot] = index of the slot in the move list, -1 for every other slot (k_wolf_mark sets and clears it)
-template <bool ORTHO, bool DAMPED>
-__global__ __launch_bounds__(64) void k_wolf_field_delta(AtomsDev at, Box bx, WolfFieldParams wp, const int *__restrict__ mv_slot,
-                                                         const double4 *__restrict__ mv_new, int m, const int *__restrict__ moved_idx,
-                                                         const double *__restrict__ e_real, double *__restrict__ e_real_trial,
-                                                         double *__restrict__ dk_part /*[n_tiles][m][3]*/) {
-	const int j = blockIdx.x * kTile + threadIdx.x; // (j < n_pad: the grid is n_pad / 64 workgroups)
-	const double4 pj_old = at.xyzq[j];
-	const int2 mj = at.mf[j];
-	const int kj = moved_idx[j];
-	const double4 pj_new = (kj >= 0) ? mv_new[kj] : pj_old;
-	const bool j_real = !(mj.y & AF_PAD);
-	double ej[3] = {0, 0, 0};
-	for (int k = 0; k < m; ++k) {
-		double ek[3] = {0, 0, 0};
-		if (j_real && !(kj >= 0 && kj <= k)) { // moved-moved pairs once (from the higher list index), never an atom with itself
-			const int si = mv_slot[k];
-			const int2 mi = at.mf[si];
-			const PairFlags f = pair_flags(mi.x, mi.y, mj.x, mj.y);
-			if (!f.frozen) {
-				wolf_field_pair<ORTHO, DAMPED>(bx, wp, mv_new[k], pj_new, f, 1.0, ek, ej);
-				wolf_field_pair<ORTHO, DAMPED>(bx, wp, at.xyzq[si], pj_old, f, -1.0, ek, ej);
-			}
-		}
-		for (int d = 0; d < 3; ++d) ek[d] = wave_sum(ek[d]);
-		if (threadIdx.x == 0) {
-			double *o = dk_part + ((size_t)blockIdx.x * m + k) * 3;
-			o[0] = ek[0];
-			o[1] = ek[1];
-			o[2] = ek[2];
-		}
+template <bool DAMPED>
+struct WolfField {
+	WolfFieldParams wp;
+	template <bool ORTHO>
+	__device__ __forceinline__ void add(const Box &bx, const double4 &pi, const double4 &pj, const PairFlags &f, double sg, double (&ei)[3],
+	                                    double (&ej)[3]) const {
+		double ox, oy, oz;
+		const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
+		if (ri2 == 0.0 || f.intra || !(ri2 <= bx.t_lj)) return; // :3361-3368
+		const double fac = wolf_fac<DAMPED>(wp, ri2);
+		const double fj = sg * fac * pj.w, fi = sg * fac * pi.w;
+		ei[0] = fma(fj, ox, ei[0]);
+		ei[1] = fma(fj, oy, ei[1]);
+		ei[2] = fma(fj, oz, ei[2]);
+		ej[0] = fma(-fi, ox, ej[0]);
+		ej[1] = fma(-fi, oy, ej[1]);
+		ej[2] = fma(-fi, oz, ej[2]);
 	}
-	for (int d = 0; d < 3; ++d) e_real_trial[3 * (size_t)j + d] = e_real[3 * (size_t)j + d] + ej[d];
-}
-__global__ void k_wolf_mark(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m, int set) {
-	const int k = blockIdx.x * blockDim.x + threadIdx.x;
-	if (k < m) moved_idx[mv_slot[k]] = set ? k : -1;
-}
-// the moved atoms' own share: e_real_trial[slot_k] += sum over the tiles of dk_part[tile][k], tiles in order
-__global__ __launch_bounds__(64) void k_wolf_field_delta_finish(const int *__restrict__ mv_slot, int m, int n_tiles, const double *__restrict__ dk_part,
-                                                                double *__restrict__ e_real_trial) {
-	const int k = blockIdx.x * 64 + threadIdx.x;
-	if (k >= m) return;
-	double s[3] = {0, 0, 0};
-	for (int t = 0; t < n_tiles; ++t) {
-		const double *q = dk_part + ((size_t)t * m + k) * 3;
-		s[0] += q[0];
-		s[1] += q[1];
-		s[2] += q[2];
-	}
-	double *o = e_real_trial + 3 * (size_t)mv_slot[k];
-	o[0] += s[0];
-	o[1] += s[1];
-	o[2] += s[2];
-}
+};
 
 void launch_wolf_field_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const WolfFieldParams &wp, const int *mv_slot, const double4 *mv_new, int m,
                              int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part) {
-	const int nt = at.n_pad / kTile;
-	const dim3 mg((m + 63) / 64), mb(64);
-	hipLaunchKernelGGL(k_wolf_mark, mg, mb, 0, st, moved_idx, mv_slot, m, 1);
-#define MPMC_WD(O, D) hipLaunchKernelGGL((k_wolf_field_delta<O, D>), dim3(nt), dim3(kTile), 0, st, at, bx, wp, mv_slot, mv_new, m, moved_idx, e_real, e_real_trial, dk_part)
-	if (bx.ortho) {
-		if (wp.a != 0.0) MPMC_WD(true, true);
-		else MPMC_WD(true, false);
-	} else {
-		if (wp.a != 0.0) MPMC_WD(false, true);
-		else MPMC_WD(false, false);
-	}
-#undef MPMC_WD
-	hipLaunchKernelGGL(k_wolf_field_delta_finish, mg, mb, 0, st, mv_slot, m, nt, dk_part, e_real_trial);
-	hipLaunchKernelGGL(k_wolf_mark, mg, mb, 0, st, moved_idx, mv_slot, m, 0);
+	with_flags(bx.ortho, wp.a != 0.0, [&](auto O, auto D) { // (always through the map, whatever the length of the list)
+		launch_field_delta<O.value>(st, at, bx, WolfField<D.value>{wp}, true, mv_slot, mv_new, m, moved_idx, e_real, e_real_trial, dk_part);
+	});
 }
 
 // ---- Palmo-Krimm ---------------------------------------------------------------------------------------------------------------------
@@ -228,11 +160,9 @@ __global__ __launch_bounds__(256) void k_palmo_reduce(AtomsDev at, const double 
 		}
 		if (live) u += ((mu[b] * c[0]) + mu[b + 1] * c[1]) + mu[b + 2] * c[2]; // :2615
 	}
-	u = wave_sum(u);
-	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = u;
-	__syncthreads();
+	u = block_sum_256(u, sh);
 	if (threadIdx.x == 0) {
-		const double corr = -0.5 * (((sh[0] + sh[1]) + sh[2]) + sh[3]);
+		const double corr = -0.5 * u;
 		scal[S_PALMO] = corr;
 		scal[S_POLAR] += corr;
 	}

@@ -1,0 +1,111 @@
+// trial_kernels.h -- the scaffold the trial-move ("delta") terms share: the moved-atom map, the real-space delta-field kernel with its
+// finish, the launch sequence around them, and the fixed-order sum of per-workgroup partials.  Included after kernels.h by the HIP
+// translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, kernels_disp.hip); the kernels
+// are static, one copy per code object.  A new trial-move term brings its pair arithmetic and calls these.
+#pragma once
+
+#include "kernels.h"
+#include "device_math.h"
+
+namespace mpmc {
+
+// moved_idx[slot] = index of the slot in the move list (set) or -1 as for every other slot (clear)
+static __global__ void k_mark_moved(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m, int set) {
+	const int k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k < m) moved_idx[mv_slot[k]] = set ? k : -1;
+}
+inline void launch_mark_moved(hipStream_t st, int *moved_idx, const int *mv_slot, int m, int set) {
+	hipLaunchKernelGGL(k_mark_moved, dim3((m + 63) / 64), dim3(64), 0, st, moved_idx, mv_slot, m, set);
+}
+
+// ---- polarizable boxes: change of a REAL-SPACE static field that is a pair sum --------------------------------------------------------
+// A trial move of m atoms changes, for every atom j, only the terms with a moved partner.  Thread = atom j, loop over the moved atoms k,
+// each pair in its new and in its old geometry:
+//   E_j += q_k [F(r_j - r_k')  - F(r_j - r_k)],      E_k += q_j [F(r_k' - r_j) - F(r_k - r_j)]   (F odd: the pair is evaluated once)
+// PairField (by value, with its parameters) adds sg times one pair's contribution to both atoms: pf.add<ORTHO>(bx, pi, pj, flags, sg, ei, ej).
+// The moved atoms' own changes are reduced per wave and land in dk_part[tile][k][3]; k_field_delta_finish adds them up over the tiles.
+// moved_idx: the slot -> list-index map, or null: the (short) list is scanned instead.
+template <bool ORTHO, class PairField>
+__global__ __launch_bounds__(64) void k_field_delta(AtomsDev at, Box bx, PairField pf, const int *__restrict__ mv_slot, const double4 *__restrict__ mv_new,
+                                                    int m, const int *__restrict__ moved_idx, const double *__restrict__ e_real,
+                                                    double *__restrict__ e_real_trial, double *__restrict__ dk_part /*[n_tiles][m][3]*/) {
+	const int j = blockIdx.x * kTile + threadIdx.x; // (j < n_pad: the grid is n_pad / 64 workgroups)
+	const double4 pj_old = at.xyzq[j];
+	const int2 mj = at.mf[j];
+	int kj = -1;
+	if (moved_idx) kj = moved_idx[j];
+	else
+		for (int k = 0; k < m; ++k)
+			if (mv_slot[k] == j) kj = k;
+	const double4 pj_new = (kj >= 0) ? mv_new[kj] : pj_old;
+	const bool j_real = !(mj.y & AF_PAD);
+	double ej[3] = {0, 0, 0};
+	for (int k = 0; k < m; ++k) {
+		double ek[3] = {0, 0, 0};
+		if (j_real && !(kj >= 0 && kj <= k)) { // moved-moved pairs once (from the higher list index), never an atom with itself
+			const int si = mv_slot[k];
+			const int2 mi = at.mf[si];
+			const PairFlags f = pair_flags(mi.x, mi.y, mj.x, mj.y);
+			if (!f.frozen) {
+				pf.template add<ORTHO>(bx, mv_new[k], pj_new, f, 1.0, ek, ej);
+				pf.template add<ORTHO>(bx, at.xyzq[si], pj_old, f, -1.0, ek, ej);
+			}
+		}
+		for (int d = 0; d < 3; ++d) ek[d] = wave_sum(ek[d]);
+		if (threadIdx.x == 0) {
+			double *o = dk_part + ((size_t)blockIdx.x * m + k) * 3;
+			o[0] = ek[0];
+			o[1] = ek[1];
+			o[2] = ek[2];
+		}
+	}
+	for (int d = 0; d < 3; ++d) e_real_trial[3 * (size_t)j + d] = e_real[3 * (size_t)j + d] + ej[d];
+}
+// the moved atoms' own share: e_real_trial[slot_k] += sum over tiles of dk_part[tile][k]  (one thread per moved atom, tiles in order)
+static __global__ __launch_bounds__(64) void k_field_delta_finish(const int *__restrict__ mv_slot, int m, int n_tiles, const double *__restrict__ dk_part,
+                                                                  double *__restrict__ e_real_trial) {
+	const int k = blockIdx.x * 64 + threadIdx.x;
+	if (k >= m) return;
+	double s[3] = {0, 0, 0};
+	for (int t = 0; t < n_tiles; ++t) {
+		const double *q = dk_part + ((size_t)t * m + k) * 3;
+		s[0] += q[0];
+		s[1] += q[1];
+		s[2] += q[2];
+	}
+	double *o = e_real_trial + 3 * (size_t)mv_slot[k];
+	o[0] += s[0];
+	o[1] += s[1];
+	o[2] += s[2];
+}
+// mark -> field delta -> finish -> clear; without use_map (short lists) the two map launches drop out and the kernel scans the list
+template <bool ORTHO, class PairField>
+inline void launch_field_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const PairField &pf, bool use_map, const int *mv_slot,
+                               const double4 *mv_new, int m, int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part) {
+	const int nt = at.n_pad / kTile;
+	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 1);
+	hipLaunchKernelGGL((k_field_delta<ORTHO, PairField>), dim3(nt), dim3(kTile), 0, st, at, bx, pf, mv_slot, mv_new, m, use_map ? moved_idx : nullptr, e_real,
+	                   e_real_trial, dk_part);
+	hipLaunchKernelGGL(k_field_delta_finish, dim3((m + 63) / 64), dim3(64), 0, st, mv_slot, m, nt, dk_part, e_real_trial);
+	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 0);
+}
+
+// ---- out[0] = the per-workgroup partials summed in a fixed order (times `scale` when `scaled`; an unscaled sum is not multiplied at all);
+// n_extra: out[1], out[2] = extra1, extra2 (values the host keeps and the result block carries); mv_slot non-null: clears the moved-atom
+// map behind a delta launch ---------------------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__ part, int nparts, double *__restrict__ out, int scaled, double scale,
+                                                             int n_extra, double extra1, double extra2, int *__restrict__ moved_idx,
+                                                             const int *__restrict__ mv_slot, int m) {
+	__shared__ double sh[4];
+	double s = 0.0;
+	for (int b = threadIdx.x; b < nparts; b += 256) s += part[b];
+	s = block_sum_256(s, sh);
+	if (threadIdx.x == 0) {
+		out[0] = scaled ? s * scale : s;
+		if (n_extra) out[1] = extra1, out[2] = extra2;
+	}
+	if (mv_slot)
+		for (int k = threadIdx.x; k < m; k += 256) moved_idx[mv_slot[k]] = -1;
+}
+
+} // namespace mpmc

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Monte Carlo trial-move rate: single-molecule displacements through mpmc_trial_* versus full evaluations.
-usage: python tools/trial_bench.py [natoms] [n_trials]   (non-polarizable LJ + Ewald box of the bench generator)"""
+usage: python tools/trial_bench.py [natoms] [n_trials] [--polar]   (LJ + Ewald box of the bench generator, non-polarizable unless --polar:
+then the trials take the delta field and a dipole solve each, so ask for fewer of them)"""
 import os
 import sys
 import tempfile
@@ -14,11 +15,13 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import bench  # noqa: E402
 from mpmcxx_amd import energy  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
-trials = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
+args = [a for a in sys.argv[1:] if a != "--polar"]
+n = int(args[0]) if len(args) > 0 else 10000
+trials = int(args[1]) if len(args) > 1 else 2000
 atoms, basis, opts = bench.build_case(n, tempfile.mkdtemp())
 opts = dict(opts)
-opts.update(polarization=0, polar_iterative=0)
+if "--polar" not in sys.argv:
+    opts.update(polarization=0, polar_iterative=0)
 S = energy.System(atoms, basis, opts)
 e = S.energy()
 t0 = time.perf_counter()
