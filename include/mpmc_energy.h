@@ -136,7 +136,7 @@ typedef struct mpmc_result {
 
 /* accumulated device time of the kernels of one context, measured with HIP events on the context's stream
  * (only while profiling is enabled with mpmc_set_profiling).  Index with MPMC_K_*. */
-#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel; the disp-expansion sum / trial difference too */
+#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel; the disp-expansion and rd_crystal sums / trial differences too */
 #define MPMC_K_RECIP 1       /* structure factors + reciprocal energy + atom terms  */
 #define MPMC_K_FIELD 2       /* static field (recip + real, or nopbc)               */
 #define MPMC_K_TENSOR 3      /* dense thole_amatrix rows (mpmc_thole_amatrix)        */
@@ -273,8 +273,37 @@ int mpmc_axilrod_teller(mpmc_ctx *ctx, double *out); /* System::axilrod_teller()
 int mpmc_set_disp_expansion(mpmc_ctx *ctx, int enabled, int flags, const double *c6, const double *c8, const double *c10);
 int mpmc_disp_expansion(mpmc_ctx *ctx, double *out); /* System::disp_expansion() (rd_energy of the term), component entry like mpmc_lj */
 
+/* ---- `rd_crystal on`: the lattice-summed Lennard-Jones of System::lj (src/System.Energy.cpp:916-963, 1017-1022, 1152-1208) ----------------
+ * With o = order and cut = 2 * cutoff * (o - 0.5) every unordered pair that is not frozen and whose minimum-image distance passes
+ * rimg - 1e-12 < cut contributes the sum over the images n in [-(o-1), o-1]^3 at a = B n + (pos_i - pos_j), RAW positions as handed to
+ * mpmc_set_atoms / mpmc_update_positions (not wrapped, not minimum image), of the terms with |a| <= cut:
+ *   4 eps_ij (t12 - S6),  S6 = sum (|sigma_ij| / |a|)^6,  S12 likewise,  t12 = 0 for an attractive-only pair
+ * (+ lj_fh_corr of the two sums at 1 / rimg under feynman_hibbs).  rd_excluded pairs (same molecule, null sigma / epsilon) are NOT skipped:
+ * they only lose the image n = 0.  Every atom with sigma or epsilon != 0 adds 4 eps_i (t12 - t6) of half its own images n != 0 inside cut
+ * (crystal_self); lrc_pair and lrc_self are taken at cut instead of the box cutoff.
+ *   lj_pairs = the pair sum, rd_energy = ((lj_pairs + lrc_pair) + crystal_self) + lrc_self;  mpmc_lj returns this rd_energy.
+ * The counts keep their meaning (box cutoff, !rd_excluded); electrostatics and polarization are untouched.  The image table, cut, the
+ * corrections and crystal_self follow every mpmc_set_box.  The setting has the lifetime of mpmc_set_polar_wolf's: it survives
+ * mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates, accepted trials and capacity growth; enabled = 0 (order ignored)
+ * restores the plain term.  order < 1 or > MPMC_RD_CRYSTAL_MAX_ORDER is refused with MPMC_ERR_INVALID_SETTING (SimulationControl.cpp:
+ * 1688-1692).  Cost O(N^2 (2o-1)^3) per evaluation, O(m N (2o-1)^3) per trial move of m <= MPMC_TRIAL_MAX_ATOMS atoms; time is counted in
+ * MPMC_K_PAIR.  System::disp_expansion ignores rd_crystal: a context with mpmc_set_disp_expansion on returns the disp-expansion result
+ * unchanged, bit for bit, whatever this setting is.  MPMC_FLAG_RD_CRYSTAL in unsupported_flags is still refused: this call alone
+ * switches the term on.  cavity_autoreject stays refused. */
+#define MPMC_RD_CRYSTAL_MAX_ORDER 8 /* (2 * 8 - 1)^3 = 3375 images */
+/* (a struct tag, not a typedef: the entry point below carries the same name) */
+struct mpmc_rd_crystal_info {
+	int32_t order;          /* of the last evaluation (complete, component or trial) with the term on; 0: none has run */
+	int32_t n_images;       /* (2 order - 1)^3, the size of the image table                                             */
+	double cutoff;          /* 2 * box cutoff * (order - 0.5)                                                           */
+	int64_t n_image_terms;  /* image terms that passed |a| <= cutoff, over all contributing pairs                       */
+	double crystal_self;    /* sum of rd_crystal_self over the atoms                                                    */
+};
+int mpmc_set_rd_crystal(mpmc_ctx *ctx, int enabled, int order);
+int mpmc_rd_crystal_info(mpmc_ctx *ctx, struct mpmc_rd_crystal_info *out);
+
 /* ---- public component entry points of the reference (src/System.h:346-402), for parity tests ----------- */
-int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj()                   */
+int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj() (rd_crystal: its lattice sum) */
 int mpmc_coulombic(mpmc_ctx *ctx, double *out);           /* System::coulombic()            */
 int mpmc_coulombic_real(mpmc_ctx *ctx, double *out);      /* System::coulombic_real()       */
 int mpmc_coulombic_reciprocal(mpmc_ctx *ctx, double *out);/* System::coulombic_reciprocal() */

@@ -168,6 +168,11 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "polar_wolf") { need(1); s.polar_wolf = onoff(t[1]); }
 		else if (k == "polar_palmo") { need(1); s.polar_palmo = onoff(t[1]); }
 		else if (k == "polar_wolf_alpha" || k == "polar_wolf_damp") { need(1); s.polar_wolf_alpha = dval(1); } // (two names of one setting, SimulationControl.cpp:751-759)
+		else if (k == "rd_crystal") { // (the flag as for every keyword of the table above: the facade clears it when it hands the term to mpmc_set_rd_crystal)
+			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_RD_CRYSTAL;
+			s.rd_crystal = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
+		}
+		else if (k == "rd_crystal_order") { need(1); s.rd_crystal_order = (int)dval(1); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
 		else if (k == "polar_max_iter") { need(1); s.polar_max_iter = (int)dval(1); }

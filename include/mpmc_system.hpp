@@ -98,6 +98,7 @@ public:
 	int damp_dispersion = 0, extrapolate_disp_coeffs = 0, schmidt_ff = 0; // its switches, src/System.h:649-656
 	int dipoles_on_demand = 0; // energy() / energy_async() stop at the Jacobi iterations the energy needs; fetch_dipoles() runs the rest (mpmc_set_dipoles_on_demand)
 	int polar_wolf = 0, polar_palmo = 0; // Wolf static field (mpmc_set_polar_wolf), Palmo-Krimm correction (mpmc_set_polar_palmo), src/System.h:685-694
+	int rd_crystal = 0, rd_crystal_order = 0; // lattice-summed Lennard-Jones (mpmc_set_rd_crystal), src/System.h:632-633
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
@@ -294,6 +295,7 @@ private:
 	int disp_flags_ = 0;
 	int polar_wolf_on_ = 0, polar_palmo_on_ = 0; // what the context's Wolf-field / Palmo settings are (sync_state)
 	int on_demand_on_ = 0;                       // ... and its dipoles-on-demand switch
+	int rd_crystal_on_ = 0, rd_crystal_order_ = 0; // ... and its rd_crystal setting
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
@@ -316,6 +318,7 @@ private:
 			atoms_dirty_ = box_dirty_ = true;
 			polar_wolf_on_ = polar_palmo_on_ = on_demand_on_ = 0; // (a new context starts with all of them off)
 			polar_wolf_alpha_ = 0;
+			rd_crystal_on_ = rd_crystal_order_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -343,7 +346,9 @@ private:
 		o.polar_damp = polar_damp;
 		o.ewald_alpha = ewald_alpha;
 		o.polar_ewald_alpha = polar_ewald_alpha;
-		o.unsupported_flags = unsupported_flags; // (polar_iterative off is the library's direct dipole solve: no flag)
+		// (polar_iterative off is the library's direct dipole solve: no flag; `rd_crystal on` goes to mpmc_set_rd_crystal below: the reader's
+		// flag for the keyword is cleared here, a caller's flag without the field is still refused)
+		o.unsupported_flags = rd_crystal ? (unsupported_flags & ~(uint64_t)MPMC_FLAG_RD_CRYSTAL) : unsupported_flags;
 		check(mpmc_set_options(ctx_, &o), "mpmc_set_options");
 		if (atoms_dirty_) {
 			std::vector<double> pos(3 * (size_t)n), q(n), al(n), ep(n), sg(n), ms(n);
@@ -388,6 +393,11 @@ private:
 			check(mpmc_set_polar_wolf(ctx_, polar_wolf ? 1 : 0, polar_wolf_alpha), "mpmc_set_polar_wolf");
 			polar_wolf_on_ = polar_wolf ? 1 : 0;
 			polar_wolf_alpha_ = polar_wolf_alpha;
+		}
+		if ((rd_crystal != 0) != (rd_crystal_on_ != 0) || (rd_crystal && rd_crystal_order != rd_crystal_order_)) {
+			check(mpmc_set_rd_crystal(ctx_, rd_crystal ? 1 : 0, rd_crystal_order), "mpmc_set_rd_crystal");
+			rd_crystal_on_ = rd_crystal ? 1 : 0;
+			rd_crystal_order_ = rd_crystal_order;
 		}
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");

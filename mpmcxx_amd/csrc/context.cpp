@@ -733,6 +733,82 @@ extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 	return MPMC_OK;
 }
 
+// ---- `rd_crystal` (System::lj :916-963, rd_crystal_self :1152-1208) ----------------------------------------------------------------------
+extern "C" int mpmc_set_rd_crystal(mpmc_ctx *c, int enabled, int order) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_crystal: an evaluation or a trial move is open");
+	if (enabled && order < 1) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_crystal: rd_crystal_order must be at least 1"); // SimulationControl.cpp:1688-1692
+	if (enabled && order > MPMC_RD_CRYSTAL_MAX_ORDER)
+		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_crystal: rd_crystal_order above MPMC_RD_CRYSTAL_MAX_ORDER");
+	const bool on = enabled != 0;
+	if (on != c->kept.rc_enabled || (on && order != c->kept.rc_order)) {
+		c->cache_valid = false;  // (the accepted totals carry the other LJ term)
+		c->static_dirty = true;  // (the long-range corrections are taken at the other cutoff: lrc_box)
+		c->static_gen++;
+	}
+	c->kept.rc_enabled = on;
+	c->kept.rc_order = on ? order : 0;
+	return MPMC_OK;
+}
+extern "C" int mpmc_rd_crystal_info(mpmc_ctx *c, struct mpmc_rd_crystal_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	*out = c->rc_info;
+	return MPMC_OK;
+}
+
+// The image table S(n) in the reference's loop and association order, the cutoff with its two squared-distance thresholds, and
+// crystal_self: sum over the atoms with sigma or epsilon != 0 of 4 eps_i (t12 - t6), t6 = |sigma_i|^6 sum_{n != 0, |S(n)| <= cut} 0.5 /
+// |S(n)|^6 (the reference forms pow(|sigma_i| / |S(n)|, 6) per image: the same to a few ulp), t12 = 0 for sigma_i < 0.
+int mpmc::crystal_ready(mpmc_ctx *c) {
+	const int order = c->kept.rc_order;
+	int rc;
+	if ((rc = c->d_rc_part.reserve(c, (size_t)2 * kCrystalBlocks)) != MPMC_OK) return rc;
+	if (c->rc_gen == c->static_gen && c->rc_table_order == order) return MPMC_OK;
+	const int w = 2 * order - 1, n_img = w * w * w;
+	const double cut = 2.0 * c->box.cutoff * ((double)order - 0.5);
+	std::vector<double4> sh((size_t)n_img);
+	const double *b = c->box.b; // b[3 q + p] = basis[q][p]
+	double h6 = 0.0, h12 = 0.0;
+	int k = 0, centre = 0;
+	for (int i0 = -(order - 1); i0 <= order - 1; i0++)
+		for (int i1 = -(order - 1); i1 <= order - 1; i1++)
+			for (int i2 = -(order - 1); i2 <= order - 1; i2++, k++) {
+				double a[3];
+				for (int p = 0; p < 3; p++) a[p] = ((0.0 + b[p] * i0) + b[3 + p] * i1) + b[6 + p] * i2;
+				sh[k] = make_double4(a[0], a[1], a[2], 0.0);
+				if (!i0 && !i1 && !i2) {
+					centre = k;
+					continue;
+				}
+				const double r = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+				if (r > cut) continue;
+				const double ir = 1.0 / r, ir6 = std::pow(ir, 6);
+				h6 += 0.5 * ir6;
+				h12 += 0.5 * (ir6 * ir6);
+			}
+	double self = 0.0;
+	for (int i = 0; i < c->n; i++) {
+		const double sg = c->h_sigma[i], ep = c->h_eps[i];
+		if (sg == 0.0 && ep == 0.0) continue;
+		const double s = std::fabs(sg), s2 = s * s, s6 = s2 * s2 * s2;
+		const double t6 = s6 * h6, t12 = (sg < 0.0) ? 0.0 : (s6 * s6) * h12;
+		self += 4.0 * ep * (t12 - t6);
+	}
+	if ((rc = c->d_rc_shift.reserve(c, (size_t)n_img)) != MPMC_OK) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->d_rc_shift, sh.data(), sh.size() * sizeof(double4), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream)); // (`sh` dies here; once per change of the cell, the atom list or the order)
+	c->rc_par = CrystalParams{};
+	c->rc_par.n_img = n_img;
+	c->rc_par.centre = centre;
+	c->rc_par.t_pair = bisect_threshold(cut, [cut](double t) { return std::sqrt(t) - kSmallDR < cut; });
+	c->rc_par.t_img = bisect_threshold(cut, [cut](double t) { return !(std::sqrt(t) > cut); });
+	c->rc_cut = cut;
+	c->rc_self = self;
+	c->rc_gen = c->static_gen;
+	c->rc_table_order = order;
+	return MPMC_OK;
+}
+
 // ---- Axilrod-Teller coefficients (System::axilrod_teller, src/System.Energy.cpp:1685-1709) ------------------------------------------------
 // Per atom a_i = 6.7483345 alpha_i and u_i = a_i^3 / c9_i, so that c9_abc = 3 a_a a_b a_c / (u_a + u_b + u_c) times the unit factor
 // (kThreeBodyScale).  The reference gives 0 for a triple with alpha = 0 (explicitly) or c9 = 0 (1 / (c9 / a^3) is infinite); such an atom
@@ -840,6 +916,8 @@ extern "C" int mpmc_set_disp_expansion(mpmc_ctx *c, int enabled, int flags, cons
 	if (!c) return MPMC_ERR_ARG;
 	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: an evaluation or a trial move is open");
 	if (flags & ~(MPMC_DISP_DAMP | MPMC_DISP_EXTRAPOLATE_C10 | MPMC_DISP_SCHMIDT)) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: unknown flag bits");
+	// (a context with rd_crystal set takes its long-range corrections at the crystal cutoff only while this term is off: lrc_box)
+	if ((enabled != 0) != c->kept.de_enabled && c->kept.rc_enabled) c->static_dirty = true, c->static_gen++;
 	if (!enabled) {
 		if (c->kept.de_enabled) c->cache_valid = false, c->atoms_dirty = true; // (the accepted totals carry the term; the atoms' flags change back)
 		c->kept.de_enabled = c->de_have = c->de_dirty = c->de_lrc_valid = false;

@@ -132,6 +132,8 @@ struct mpmc_kept {
 	bool pw_enabled = false;                // `polar_wolf` (mpmc_set_polar_wolf), kept across mpmc_set_box and mpmc_set_options too
 	double pw_alpha = 0.0;
 	bool palmo_enabled = false;             // `polar_palmo` (mpmc_set_polar_palmo), likewise
+	bool rc_enabled = false;                // `rd_crystal` (mpmc_set_rd_crystal), kept across mpmc_set_box and mpmc_set_options too
+	int rc_order = 0;                       // rd_crystal_order
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 };
 
@@ -316,7 +318,8 @@ struct mpmc_ctx {
 	DevBuf<unsigned char> d_mv_blob; // device / pinned host staging of a trial's moved-atom list
 	PinnedBuf<unsigned char> h_mv_blob;
 	DevBuf<double> d_delta_out;
-	PinnedBuf<double> h_delta_out; // [10] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8])
+	PinnedBuf<double> h_delta_out; // [12] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8]),
+	                               // rd_crystal delta and the change of its image-term count (d_delta_out[9], [10])
 	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
@@ -342,6 +345,19 @@ struct mpmc_ctx {
 	DevBuf<double4> d_de_co;   // [max_pad] (alpha, r0, sqrt c6, sqrt c8) in slot order, padding zeros
 	DevBuf<double> d_de_t10;   // [max_pad]
 	DevBuf<double> d_de_part;  // [kDispBlocks] per-workgroup partials
+
+	// `rd_crystal` (mpmc_set_rd_crystal, kernels_crystal.hip; switched on: kept.rc_enabled, kept.rc_order): the lattice sum replaces the LJ
+	// sum of rd_energy.  The image table, the cutoff with its thresholds and crystal_self follow the cell and the atom parameters: they
+	// belong to the value of static_gen they were made at (crystal_ready, context.cpp); the two long-range corrections are h_static's,
+	// taken at the crystal cutoff (lrc_box).
+	unsigned rc_gen = 0;                    // static_gen of the table below (0: none)
+	int rc_table_order = 0;                 // the order it was made for
+	CrystalParams rc_par{};                 // n_img, centre, thresholds (the Feynman-Hibbs fields are filled per launch)
+	double rc_cut = 0, rc_self = 0;         // 2 cutoff (order - 0.5); sum of rd_crystal_self
+	DevBuf<double4> d_rc_shift;             // [n_img] lattice vectors of the images, reference order
+	DevBuf<double> d_rc_part;               // [2 kCrystalBlocks] per-workgroup partials: energies, image-term counts
+	struct mpmc_rd_crystal_info rc_info{};         // of the last evaluation with the term (mpmc_rd_crystal_info)
+	int64_t rc_terms_accepted = 0, rc_terms_trial = 0; // image terms of the accepted configuration (with last_full) / of the evaluated trial
 
 	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip; switched on: kept.pw_enabled, kept.pw_alpha,
 	// kept.palmo_enabled)
@@ -510,7 +526,8 @@ enum : unsigned {
 	RUN_PAIR = 1, RUN_PAIR_ES = 2, RUN_RECIP = 4, RUN_ATOMTERMS = 8, RUN_FIELD = 16, RUN_SOLVE = 32, RUN_WOLF = 64,
 	RUN_STORE = 128, // tile classes + the Thole tensor store alone (no energies, no field): trial moves of polarizable boxes
 	RUN_THREE_BODY = 256, // the Axilrod-Teller sum (contexts with the term switched on)
-	RUN_DISP = 512        // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
+	RUN_DISP = 512,       // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
+	RUN_CRYSTAL = 1024    // the rd_crystal lattice sum (contexts with the term switched on and disp-expansion off: it replaces the LJ sum)
 };
 // 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
 // applied once to the sum of the per-triple terms
@@ -518,6 +535,10 @@ constexpr double kThreeBodyScale = 3.0 * (0.0032539449 / (3.166811429 * 0.000001
 int three_body_ready(mpmc_ctx *c); // the term is on and its coefficients are on the device in the current slot order (context.cpp)
 int disp_ready(mpmc_ctx *c);       // the same for the disp-expansion term, and its long-range corrections for the current box (context.cpp)
 DispParams disp_params(const mpmc_ctx *c);
+inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled; } // (disp_expansion() ignores rd_crystal)
+int crystal_ready(mpmc_ctx *c);    // the image table, cutoff, thresholds and crystal_self of the current cell and atoms are in place (context.cpp)
+CrystalParams crystal_params(const mpmc_ctx *c); // rc_par with this evaluation's Feynman-Hibbs constants (evaluate.cpp)
+Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see it: rd_crystal puts its own cutoff in (evaluate.cpp)
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
 // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp); on_demand: where the energy comes from the moments of the
 // first half of the iterations, stop there and leave the rest to finish_pending_dipoles

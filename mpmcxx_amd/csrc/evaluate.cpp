@@ -149,7 +149,7 @@ int mpmc::prepare(mpmc_ctx *c, bool defer_static) {
 	// kernel behind its clear of the scalar block and wait_and_fill adopts the three values); everybody else gets them here and now.
 	if (c->static_dirty && !defer_static) {
 		c->scal_clean = false; // (the kernel writes its slots of the scalar block: the next evaluation clears the block first)
-		launch_atom_terms(c->stream, atoms_view(c), c->box, c->ewald_alpha, c->opts.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
+		launch_atom_terms(c->stream, atoms_view(c), lrc_box(c), c->ewald_alpha, c->opts.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
 		HIP_TRY(c, hipGetLastError());
 		double tmp[S_COUNT];
 		HIP_TRY(c, hipMemcpyAsync(tmp, c->d_scal, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
@@ -160,6 +160,23 @@ int mpmc::prepare(mpmc_ctx *c, bool defer_static) {
 		c->static_dirty = false;
 	}
 	return MPMC_OK;
+}
+
+// lj_lrc_corr / lj_lrc_self take the cutoff lj() hands them (:916-919, 931, 1028): under rd_crystal 2 cutoff (order - 0.5).  Only the cutoff
+// and the volume of this box are read by the atom-terms kernels.
+Box mpmc::lrc_box(const mpmc_ctx *c) {
+	Box b = c->box;
+	if (crystal_on(c)) b.cutoff = 2.0 * c->box.cutoff * ((double)c->kept.rc_order - 0.5);
+	return b;
+}
+CrystalParams mpmc::crystal_params(const mpmc_ctx *c) {
+	CrystalParams cp = c->rc_par;
+	FusedParams fp{};
+	ext_params(c, fp, false);
+	cp.fh_order = fp.fh_order;
+	cp.fh_c2 = fp.fh_c2;
+	cp.fh_c4 = fp.fh_c4;
+	return cp;
 }
 
 AtomsDev mpmc::atoms_view(const mpmc_ctx *c) {
@@ -357,6 +374,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if (rc != MPMC_OK) return rc;
 	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
 	const bool static_ride = c->static_dirty;
 	c->static_ride_gen = 0;
 	const AtomsDev at = atoms_view(c);
@@ -390,7 +408,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if (!c->scal_clean) HIP_TRY(c, hipMemsetAsync(c->d_scal, 0, (S_COUNT + C_COUNT) * sizeof(double), st));
 	c->scal_clean = false;
 	if (static_ride) { // first thing on the main stream: its slots are nobody else's (S_LRC_PAIR, S_LRC_SELF, S_ES_SELF)
-		launch_atom_terms(st, at, c->box, c->ewald_alpha, o.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
+		launch_atom_terms(st, at, lrc_box(c), c->ewald_alpha, o.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
 		HIP_TRY(c, hipGetLastError());
 		c->static_ride_gen = c->static_gen;
 	}
@@ -701,6 +719,12 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 		launch_disp_expansion(st, at, c->d_de_co, c->d_de_t10, c->d_tile_pairs, c->n_tile_pairs, c->box, disp_params(c), c->de_lrc[0], c->de_lrc[1],
 		                      c->d_de_part, c->d_scal + S_DISP);
 	}
+	// ---- rd_crystal, System::lj (:916-963): the lattice sum and its image-term count into their two slots ---------------------------------
+	if (mask & RUN_CRYSTAL) {
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL,
+		               c->d_scal + S_CRYSTAL_TERMS);
+	}
 	HIP_TRY(c, hipGetLastError());
 	// results to the pinned block by a kernel of ours (a blit and a stream synchronisation cost more than the whole reciprocal space of a
 	// small box): copy, zero the device block for the next evaluation, launch number last
@@ -879,6 +903,15 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		out->lrc_self = lrc ? c->h_static[1] : 0.0;
 	}
 	out->rd_energy = (out->lj_pairs + out->lrc_pair) + out->lrc_self;
+	if (c->run_mask & RUN_CRYSTAL) { // the lattice sum replaces the LJ sum of the pair kernels; crystal_self joins in lj()'s order (:1011-1028)
+		out->lj_pairs = s[S_CRYSTAL];
+		out->rd_energy = ((out->lj_pairs + out->lrc_pair) + c->rc_self) + out->lrc_self;
+		c->rc_info.order = c->rc_table_order;
+		c->rc_info.n_images = c->rc_par.n_img;
+		c->rc_info.cutoff = c->rc_cut;
+		c->rc_info.n_image_terms = (int64_t)s[S_CRYSTAL_TERMS];
+		c->rc_info.crystal_self = c->rc_self;
+	}
 	out->es_real = s[S_ES_REAL] - s[S_ES_INTRA];
 	out->es_recip = s[S_ES_RECIP];
 	out->es_self = (c->run_mask & RUN_RECIP) ? c->h_static[2] : 0.0;
@@ -902,6 +935,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	if (c->run_mask == full_mask(c)) { // a complete energy(): it re-bases the trial-move totals
 		c->last_full = *out;
 		c->cache_valid = true;
+		c->rc_terms_accepted = c->rc_info.n_image_terms;
 	}
 	return MPMC_OK;
 }
@@ -915,6 +949,7 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 	}
 	if (c->kept.tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
 	if (c->kept.de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
+	if (crystal_on(c)) m |= RUN_CRYSTAL;         // (in place of the LJ sum; disp_expansion() ignores rd_crystal)
 	return m;
 }
 
@@ -954,7 +989,8 @@ static int run_piece(mpmc_ctx *c, unsigned mask, mpmc_result *r) {
 }
 extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	mpmc_result r;
-	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS, &r);
+	if (!c) return MPMC_ERR_ARG;
+	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u), &r);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }

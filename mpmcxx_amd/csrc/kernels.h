@@ -57,6 +57,7 @@ enum : int {
 	S_THREE_BODY,                                // Axilrod-Teller (kernels_three_body.hip)
 	S_DISP, S_DISP_LRC_PAIR, S_DISP_LRC_SELF,    // disp-expansion pair sum and its two long-range corrections (kernels_disp.hip)
 	S_PALMO,                                     // Palmo-Krimm correction, already part of S_POLAR (kernels_wolf_field.hip)
+	S_CRYSTAL, S_CRYSTAL_TERMS,                  // rd_crystal pair sum and its image-term count (a double: exact) (kernels_crystal.hip)
 	S_COUNT = 16
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
@@ -333,7 +334,29 @@ void launch_disp_expansion(hipStream_t st, const AtomsDev &at, const double4 *co
 void launch_disp_expansion_delta(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const Box &bx, const DispParams &dp,
                                  const int *mv_slot, const double4 *mv_new, int m, int *moved_idx, double *part, double *out);
 
-// ---- `polar_wolf`: the Wolf static field, and the reduce of `polar_palmo` (kernels_wolf_field.hip) --------------------------------------
+// ---- `rd_crystal`: the lattice-summed Lennard-Jones of System::lj (kernels_crystal.hip) --------------------------------------------
+// shift[n] = the lattice vector S(n) = ((B[0] n0 + B[1] n1) + B[2] n2) of image n, n in [-(order-1), order-1]^3 in the reference's loop
+// order (context.cpp: crystal_ready builds it on the host with the cutoff and the two thresholds below, after every change of the cell).
+// Both launches leave kCrystalBlocks (or fewer) energy partials in part[0 ..] and as many image-term counts (as doubles: exact) in
+// part[kCrystalBlocks ..], and write the two fixed-order sums to out_e[0] and out_terms[0].
+constexpr int kCrystalBlocks = 16384;
+constexpr int kCrystalMinItems = 2048; // small tables split every tile pair's j range until about this many waves share the sum
+struct CrystalParams {
+	int n_img, centre;    // images in the table; index of n = (0, 0, 0), which rd_excluded pairs skip
+	double t_pair;        // ri2 <= t_pair  <=>  sqrt(ri2) - 1e-12 < cut   (the pair contributes, :934)
+	double t_img;         // r2 <= t_img    <=>  !(sqrt(r2) > cut)         (the image term is kept, :957)
+	int fh_order;         // Feynman-Hibbs: 0 off, 2 or 4, with the constants of FusedParams
+	double fh_c2, fh_c4;
+};
+int crystal_jsplit(int n_tile_pairs); // waves per tile pair of the sum (a function of the table alone: repeated evaluations agree to the bit)
+void launch_crystal(hipStream_t st, const AtomsDev &at, const Box &bx, const CrystalParams &cp, const double4 *shift, const int2 *tile_pairs,
+                    int n_tile_pairs, double *part /*[2 kCrystalBlocks]*/, double *out_e, double *out_terms);
+// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
+// kernels (marked and cleared again inside); out2 = { change of the pair sum, change of the image-term count }
+void launch_crystal_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const CrystalParams &cp, const double4 *shift, const int *mv_slot,
+                          const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
+
+// ---- `polar_wolf`: the Wolf static field, and the reduce of `polar_palmo` (kernels_wolf_field.hip)--------------------------------------
 struct WolfFieldParams {
 	double a;           // polar_wolf_alpha
 	double c_gauss;     // 2 a / sqrt(pi)

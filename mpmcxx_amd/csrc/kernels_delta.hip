@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
                                                       RecipDev rc, const double4 *__restrict__ sf_trial, Box bx, int do_es,
                                                       double *__restrict__ out /* dlj, des_real, (dintra at [2]), e_recip_trial at [3] */,
                                                       long long *__restrict__ dcnt,
-                                                      double *__restrict__ host_out /* pinned [10]: the same 5 doubles + 2 counts, three-body delta, launch number, disp-expansion delta */,
+                                                      double *__restrict__ host_out /* pinned [12]: the same 5 doubles + 2 counts, three-body delta, launch number, disp-expansion delta, rd_crystal delta and count */,
                                                       double seq) {
 	__shared__ double sh[4];
 	__shared__ long long shc[256];
@@ -269,6 +269,8 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 		hc[1] = c1;
 		host_out[7] = out[7]; // (the three-body delta of contexts with the term, kernels_three_body.hip; 0 for every other context)
 		host_out[9] = out[8]; // (the disp-expansion delta likewise, kernels_disp.hip; behind the launch number's slot 8, which stays where it was)
+		host_out[10] = out[9]; // (the rd_crystal delta and the change of its image-term count, kernels_crystal.hip)
+		host_out[11] = out[10];
 		__threadfence_system();
 		__hip_atomic_store(host_out + 8, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 	}

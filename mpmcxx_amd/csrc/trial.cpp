@@ -18,11 +18,12 @@ static int ensure_trial_buffers(mpmc_ctx *c) {
 		c->d_mv_slot = reinterpret_cast<int *>(c->d_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		c->d_mv_orig = c->d_mv_slot + MPMC_TRIAL_MAX_ATOMS;
 		if ((rc = c->d_moved_idx.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = c->d_delta_out.reserve(c, 9)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body and disp-expansion deltas
+		if ((rc = c->d_delta_out.reserve(c, 11)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body, disp-expansion and rd_crystal (2) deltas
+		HIP_TRY(c, hipMemsetAsync(c->d_delta_out, 0, 11 * sizeof(double), c->stream));
 		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + 5);
 		HIP_TRY(c, hipMemsetAsync(c->d_moved_idx, 0xff, (size_t)c->max_pad * sizeof(int), c->stream)); // all -1; on our stream (ordered before the first delta kernel)
-		if ((rc = c->h_delta_out.reserve(c, 10)) != MPMC_OK) return rc;
-		c->h_delta_out[8] = c->h_delta_out[9] = 0.0;
+		if ((rc = c->h_delta_out.reserve(c, 12)) != MPMC_OK) return rc;
+		c->h_delta_out[8] = c->h_delta_out[9] = c->h_delta_out[10] = c->h_delta_out[11] = 0.0;
 		c->h_delta_cnt = reinterpret_cast<long long *>(c->h_delta_out + 5);
 		if ((rc = c->h_mv_blob.reserve(c, kMvBlobBytes)) != MPMC_OK) return rc;
 	}
@@ -88,8 +89,8 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// short moves of non-polarizable boxes travel in the kernel arguments: no staging copy (a trial is launch-bound on the host: every
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->kept.tune.no_inline_move;
-	// (the three-body and disp-expansion deltas read the moved atoms from the device lists: a box with either term always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled;
+	// (the three-body, disp-expansion and rd_crystal deltas read the moved atoms from the device lists: a box with one of them always stages its move)
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c);
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -130,6 +131,14 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_disp_expansion_delta(st, atoms_view(c), c->d_de_co, c->d_de_t10, c->box, disp_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx,
 		                            c->d_de_part, c->d_delta_out + 8);
+	}
+	if (crystal_on(c)) {
+		// rd_crystal: the change of the lattice sums of the pairs with a moved atom, O(m N images), old positions still resident; into slots
+		// 9 and 10 of the delta result block (h_delta_out[10], [11]).  It replaces the LJ delta of launch_delta.
+		if ((rc = crystal_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_crystal_delta(st, atoms_view(c), c->box, crystal_params(c), c->d_rc_shift, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rc_part,
+		                     c->d_delta_out + 9);
 	}
 	{
 		FusedParams fp{};
@@ -206,10 +215,13 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		return MPMC_OK;
 	}
 	if (c->trial_was_full) {
+		const int64_t terms_keep = c->rc_terms_accepted;
 		int rc = mpmc_energy_wait(c, out);
 		if (rc != MPMC_OK) return rc;
 		c->trial_res = *out;
 		c->last_full = c->trial_keep; // still the ACCEPTED configuration's totals until mpmc_trial_accept
+		c->rc_terms_trial = c->rc_info.n_image_terms; // (rd_crystal: the same for the image-term count)
+		c->rc_terms_accepted = terms_keep;
 		c->trial_evaluated = true;
 		return MPMC_OK;
 	}
@@ -240,6 +252,12 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	mpmc_result r = a;
 	r.lj_pairs = a.lj_pairs + (c->kept.de_enabled ? c->h_delta_out[9] : c->h_delta_out[0]); // (with the disp-expansion term lj_pairs holds its pair sum)
 	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
+	if (crystal_on(c)) { // (lj_pairs holds the lattice sum; crystal_self and the corrections do not move with the atoms)
+		r.lj_pairs = a.lj_pairs + c->h_delta_out[10];
+		r.rd_energy = ((r.lj_pairs + r.lrc_pair) + c->rc_self) + r.lrc_self;
+		c->rc_terms_trial = c->rc_terms_accepted + (int64_t)c->h_delta_out[11];
+		c->rc_info.n_image_terms = c->rc_terms_trial;
+	}
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
 		r.es_real = a.es_real + (c->h_delta_out[1] - c->h_delta_out[2]);
@@ -302,6 +320,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 	}
 	c->last_full = c->trial_res;
 	c->cache_valid = true;
+	if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
 	c->trial_open = false;
 	c->trial_polar_delta = false;
 	return MPMC_OK;

@@ -74,6 +74,11 @@ class DirectInfo(C.Structure):
     _fields_ = [("n_unknowns", C.c_int64), ("status", C.c_int64), ("residual", C.c_double), ("factor_bytes", C.c_int64)]
 
 
+class RdCrystalInfo(C.Structure):
+    """mpmc_rd_crystal_info: the last evaluation of a context with `rd_crystal` on."""
+    _fields_ = [("order", C.c_int32), ("n_images", C.c_int32), ("cutoff", C.c_double), ("n_image_terms", C.c_int64), ("crystal_self", C.c_double)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -145,6 +150,9 @@ def lib():
         L.mpmc_set_polar_wolf.argtypes = [vp, C.c_int, C.c_double]
         L.mpmc_set_polar_palmo.argtypes = [vp, C.c_int]
         L.mpmc_polar_palmo_info.argtypes = [vp, dp, dp]
+    if hasattr(L, "mpmc_set_rd_crystal") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the lattice-summed Lennard-Jones)
+        L.mpmc_set_rd_crystal.argtypes = [vp, C.c_int, C.c_int]
+        L.mpmc_rd_crystal_info.argtypes = [vp, C.POINTER(RdCrystalInfo)]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -331,6 +339,10 @@ class System:
             alpha = options.get("polar_wolf_alpha")
             self.set_polar_wolf(bool(options.get("polar_wolf")), 0.0 if alpha is None else float(alpha))
             self.set_polar_palmo(bool(options.get("polar_palmo")))
+        # `rd_crystal` likewise (reference default of rd_crystal_order: 0, which it refuses with the term on)
+        if "rd_crystal" in options or getattr(self, "_rd_crystal_set", False):
+            self._rd_crystal_set = True
+            self.set_rd_crystal(bool(options.get("rd_crystal")), int(options.get("rd_crystal_order") or 0))
 
     def set_atoms(self, atoms: Dict[str, np.ndarray]):
         f = lambda k: np.ascontiguousarray(atoms[k], dtype=np.float64)
@@ -365,6 +377,17 @@ class System:
         a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (c6, c8, c10)]
         flags = (DISP_DAMP if damp else 0) | (DISP_EXTRAPOLATE_C10 if extrapolate_c10 else 0) | (DISP_SCHMIDT if schmidt else 0)
         self._check(self._L.mpmc_set_disp_expansion(self._h, int(bool(enabled)), flags, _dp(a[0]), _dp(a[1]), _dp(a[2])))
+
+    def set_rd_crystal(self, enabled: bool, order: int = 0):
+        """`rd_crystal`: Lennard-Jones summed over the (2 order - 1)^3 periodic images of the cell with the cutoff 2 * cutoff * (order - 0.5)
+        (mpmc_set_rd_crystal).  It replaces the LJ sum of rd_energy."""
+        self._check(self._L.mpmc_set_rd_crystal(self._h, int(bool(enabled)), int(order)))
+
+    def rd_crystal_info(self) -> Dict[str, object]:
+        """order, n_images, cutoff, n_image_terms and crystal_self of the last evaluation with the term on (mpmc_rd_crystal_info)"""
+        v = RdCrystalInfo()
+        self._check(self._L.mpmc_rd_crystal_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in RdCrystalInfo._fields_}
 
     def set_polar_wolf(self, enabled: bool, polar_wolf_alpha: float = 0.0):
         """`polar_wolf`: the static field of the dipole solve as a Wolf sum with damping parameter polar_wolf_alpha in [0, 1]

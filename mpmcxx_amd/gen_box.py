@@ -335,6 +335,8 @@ def fixture(name: str):
         return _three_body_fixture(name)
     if name in DISP_FIXTURES:
         return _disp_fixture(name)
+    if name in RD_CRYSTAL_FIXTURES:
+        return _rd_crystal_fixture(name)
     raise KeyError(name)
 
 
@@ -622,6 +624,72 @@ def wolf_golden(golden_dir: str, name: str) -> Dict[str, object]:
     return g
 
 
+# ---- `rd_crystal on` (reference src/System.Energy.cpp:916-963, 1017-1022, 1152-1208) ----------------------------------------------------------
+# NAME = BASE_rcO: the box BASE with the lattice-summed Lennard-Jones of order O.  Bases that exist only here:
+#   ar2_eq / ar2_gt / ar2_lt  two Ar atoms in a cubic 10 A cell at x = 0 and x = 5.0 / 5.000001 / 4.999999, rd_only: at x = 5.0 and order 2 one
+#                             image lies exactly at the cutoff 15 A (kept: the reference drops r > cutoff only)
+#   water64_shift             water64_polar with every molecule moved by a whole lattice vector (the term reads the raw positions)
+#   ion216_nolrc              ion216_polar with rd_lrc off
+#   ion4000_polar             63 tiles, Ewald + polarization (golden only: the tests of the large sizes regenerate it)
+RD_CRYSTAL_FIXTURES = [f"ar2_{t}_rc{o}" for t in ("eq", "gt", "lt") for o in (1, 2, 3)] + [
+    "lj64_rc2", "water64_polar_rc1", "water64_polar_rc2", "water64_polar_rc3", "water64_shift_rc1", "water64_shift_rc2",
+    "ion216_triclinic_rc2", "ion216_framework_rc2", "water64_fh2_rc2", "water64_fh4_rc2", "ion216_nolrc_rc2", "ion216_polar_rc1",
+    "ion1000_polar_rc2", "ion4000_polar_rc2"]
+RD_CRYSTAL_AR2_X = {"eq": 5.0, "gt": 5.000001, "lt": 4.999999}
+RD_CRYSTAL_GOLDEN = "rd_crystal.json"  # under tests/golden/: every fixture's scalars
+
+
+def _rd_crystal_fixture(name: str):
+    base, order = name.rsplit("_rc", 1)
+    if base.startswith("ar2_"):
+        x = RD_CRYSTAL_AR2_X[base[4:]]
+        rows = [AtomRow(1, "Ar", "Ar", "M", 1, 0.0, 0.0, 0.0, 39.948, 0.0, 0.0, 119.8, 3.405),
+                AtomRow(2, "Ar", "Ar", "M", 2, x, 0.0, 0.0, 39.948, 0.0, 0.0, 119.8, 3.405)]
+        basis, o = cubic(10.0), {"rd_only": "on"}
+    elif base == "water64_shift":
+        rows, basis, o = fixture("water64_polar")
+        L = basis[0][0]
+        for r in rows:  # molecule m by (m % 3 - 1, m // 3 % 3 - 1, m // 9 % 3 - 1) cells
+            m = r.mol_id
+            r.x += (m % 3 - 1) * L
+            r.y += (m // 3 % 3 - 1) * L
+            r.z += (m // 9 % 3 - 1) * L
+    elif base == "ion216_nolrc":
+        rows, basis, o = fixture("ion216_polar")
+        o = dict(o, rd_lrc="off")
+    elif base == "ion4000_polar":
+        rows, basis, o = lattice_box(4000, 64.0, 17), cubic(64.0), dict(POLAR_OPTS)
+    else:
+        rows, basis, o = fixture(base)
+    return rows, basis, dict(o, rd_crystal="on", rd_crystal_order=int(order))
+
+
+def keep_rd_crystal_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <RD_CRYSTAL_FIXTURES>`: the per-fixture files are folded into RD_CRYSTAL_GOLDEN (scalars and
+    cell only) and removed, the box text too (the tests regenerate it with `materialize`, which writes the same bytes the reference read)."""
+    import json
+
+    out = {}
+    for name in (names or RD_CRYSTAL_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        out[name] = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+    with open(os.path.join(golden_dir, RD_CRYSTAL_GOLDEN), "w") as f:
+        json.dump(out, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    for name in (names or RD_CRYSTAL_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def rd_crystal_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    import json
+
+    with open(os.path.join(golden_dir, RD_CRYSTAL_GOLDEN)) as f:
+        return json.load(f)[name]
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -663,6 +731,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-wolf-golden"]:
         keep_wolf_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-rd-crystal-golden"]:
+        keep_rd_crystal_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)
