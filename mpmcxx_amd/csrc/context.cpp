@@ -558,16 +558,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	// position-independent pair-flag counts (diagnostics of pair_exclusions), once per upload; they arrive in pinned memory in front of
 	// the evaluation that follows on this stream, and are read when that evaluation has been waited for
 	{
-		AtomsDev at;
-		at.xyzq = c->d_xyzq;
-		at.lj = c->d_lj;
-		at.mf = c->d_mf;
-		at.alpha = c->d_alpha;
-		at.eps = c->d_eps;
-		at.inv_molmass = c->d_inv_molmass;
-		at.n = c->n;
-		at.n_pad = c->n_pad;
-		launch_static_counts(c->stream, at, c->d_tile_pairs, c->n_tile_pairs, c->d_block_cnt, c->d_cnt);
+		launch_static_counts(c->stream, atoms_view(c), c->d_tile_pairs, c->n_tile_pairs, c->d_block_cnt, c->d_cnt);
 		c->scal_clean = false; // (d_cnt is part of the scalar block: the next evaluation clears it instead of trusting which kernel overwrites what)
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipMemcpyAsync(c->static_cnt, c->d_cnt, 4 * sizeof(long long), hipMemcpyDeviceToHost, c->stream));

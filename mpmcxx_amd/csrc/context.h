@@ -196,7 +196,7 @@ struct mpmc_ctx {
 	std::vector<int> h_generic;
 	int inflight_hint = 1; // evaluations the caller keeps in flight together with this one (mpmc_hint_in_flight; the PI loops set their bead count)
 	bool last_pair_was_sweep = false; // (diagnostics: which kernel the last evaluation's pair pass ran)
-	FusedParams last_fp{};            // the pair pass's parameters in the last evaluation (mpmc_debug_time_pair replays it)
+	FusedParams last_fp{};            // the pair pass's parameters in the last evaluation: a copy of its plan's (mpmc_debug_time_pair replays it)
 	bool last_fp_valid = false;
 	int debug_panel_replicas = 1;     // mpmc_debug_configure "panel_replicas": grid repetitions of mpmc_debug_time_panel's launches
 	PinnedBuf<double4> h_xyzq;       // PINNED host mirror of d_xyzq (slot order, max_pad entries): position updates copy from it asynchronously;
@@ -394,9 +394,10 @@ inline int DevBuf<T, kPinned>::reserve(mpmc_ctx *c, size_t need, size_t grow_to)
 	hipError_t e = kPinned ? pinned_alloc(&p, bytes) : hipMalloc((void **)&p, bytes);
 	if (e != hipSuccess) p = nullptr;
 	// Every device buffer starts from zeros: what a kernel finds in a slot it has not written yet must not depend on what an earlier process
-	// left in that memory.  The fill is WAITED for -- buffers are also allocated in the middle of an evaluation, after the side stream
-	// was forked, and the first writer may be a side-stream kernel that is not ordered behind a fill on the main stream (seen: structure
-	// factors zeroed under the reciprocal-space kernels).  Allocations happen once per context, the wait costs nothing in steady state.
+	// left in that memory.  The fill is WAITED for -- the first writer may be a side-stream kernel that is not ordered behind a fill on the
+	// main stream (seen when evaluations still allocated after the side stream was forked: structure factors zeroed under the
+	// reciprocal-space kernels; an evaluation now makes all its room before its first launch, make_room in evaluate.cpp, and the wait
+	// stays for every other caller).  Allocations happen once per context, the wait costs nothing in steady state.
 	// (The fill is on the context's stream; nothing in this library touches the null stream, which is unordered against our non-blocking ones.)
 	if (e == hipSuccess && !kPinned && (e = hipMemsetAsync(p, 0, bytes, c->stream)) == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e != hipSuccess) {
@@ -540,8 +541,8 @@ int crystal_ready(mpmc_ctx *c);    // the image table, cutoff, thresholds and cr
 CrystalParams crystal_params(const mpmc_ctx *c); // rc_par with this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see it: rd_crystal puts its own cutoff in (evaluate.cpp)
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
-// one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp); on_demand: where the energy comes from the moments of the
-// first half of the iterations, stop there and leave the rest to finish_pending_dipoles
+// one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp: a plan, the room it needs, then the stages); on_demand: where
+// the energy comes from the moments of the first half of the iterations, stop there and leave the rest to finish_pending_dipoles
 int enqueue(mpmc_ctx *c, unsigned mask, bool on_demand = false);
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options

@@ -94,37 +94,6 @@ static int ensure_polar_buffers(mpmc_ctx *c) {
 	return c->d_part.reserve(c, need);
 }
 
-// decide how the dipole iteration runs and (COMPACT) make room for the tensor store
-static int resolve_solver(mpmc_ctx *c) {
-	const size_t need = (size_t)c->n_tile_pairs * (kTile * kTile); // double2 elements, 16 B each
-	int want = c->opts.solver;
-	if (direct_solve(c)) { // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
-		c->solver_used = MPMC_SOLVER_MATRIX_FREE;
-		return MPMC_OK;
-	}
-	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
-	if (want == MPMC_SOLVER_AUTO) {
-		const size_t budget_mb = (size_t)c->kept.tune.tensor_budget_mb;
-		want = (need * sizeof(double2) <= budget_mb * (size_t)1048576) ? MPMC_SOLVER_COMPACT : MPMC_SOLVER_MATRIX_FREE;
-		// building the store costs about as much as three iterations save (0.10 ms against 0.03 ms per iteration at 10 000 atoms)
-		if (c->opts.polar_precision == 0.0 && c->opts.polar_max_iter <= 3) want = MPMC_SOLVER_MATRIX_FREE;
-	}
-	if (want == MPMC_SOLVER_DENSE) { // the reference's layout, on request only: (3 n_pad)^2 doubles
-		const int rc = c->d_adense.reserve(c, (size_t)3 * c->n_pad * (size_t)3 * c->n_pad);
-		if (rc != MPMC_OK) return rc;
-	}
-	if (want == MPMC_SOLVER_COMPACT) {
-		const int rc = c->d_ab.reserve(c, need);
-		if (rc != MPMC_OK) {
-			if (c->opts.solver == MPMC_SOLVER_COMPACT) return rc; // explicitly requested: report
-			(void)hipGetLastError();
-			want = MPMC_SOLVER_MATRIX_FREE; // AUTO: fall back to recomputing the tensors (still the HIP path)
-		}
-	}
-	c->solver_used = want;
-	return MPMC_OK;
-}
-
 // resolve alpha defaults, rebuild k tables when box/options changed
 int mpmc::prepare(mpmc_ctx *c, bool defer_static) {
 	if (!c->box_set) return fail(c, MPMC_ERR_BOX, "energy: no box set (mpmc_set_box)");
@@ -229,26 +198,211 @@ static inline int sweep_split_tail(const mpmc_ctx *c) {
 	return (int)((long long)c->n_sweep_blocks * permille / 1000);
 }
 
-// `polar_iterative off` (System::polar :2590-2607): A mu = E0 solved directly (kernels_chol.hip), behind the static field.  Leaves the
-// dipoles in d_mu[mu_cur], mu / alpha - E0 in d_e_induced and { status, max |r|, max |E0| } on their way to the pinned info block.
-static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
-	hipStream_t st = c->stream;
-	int n_pol = 0;
-	for (int i = 0; i < c->n; i++) n_pol += (c->h_alpha[i] != 0.0) ? 1 : 0;
-	const int np = chol_padded(n_pol);
+// ---- the plan of one evaluation ---------------------------------------------------------------------------------------------------------
+// Everything enqueue() decides, decided once and in one place, from the context's state alone: no HIP call, no allocation.  make_room()
+// may still take the tensor store out of it (AUTO, and the store does not fit); after that it is const, and the stages only read it.
+struct JacobiPlan {
+	bool dense, dense_sym, compact;
+	int iter_slots;
+};
+static JacobiPlan jacobi_plan(const mpmc_ctx *c, int solver) {
+	JacobiPlan jp;
+	jp.dense = (solver == MPMC_SOLVER_DENSE) && !c->opts.polar_gs;
+	jp.dense_sym = jp.dense && c->kept.tune.dense_symmetric;
+	jp.compact = solver == MPMC_SOLVER_COMPACT;
+	jp.iter_slots = (jp.dense && !jp.dense_sym) ? kDenseChunks : c->n_tiles;
+	return jp;
+}
+struct EvalPlan {
+	unsigned mask = 0;
+	bool single = false;      // small LJ box: the whole evaluation is one launch, and nothing below is filled in
+	bool static_ride = false; // stale position-independent terms ride along (an insertion / removal makes them stale every time)
+	// streams and side work
+	bool need_sf = false, need_intra = false, side_work = false;
+	bool sf_part = false;     // the structure factors go through the per-tile partials of the factorised phases (d_sf_part)
+	bool two_streams = false, side_fork = false, side_deferred = false;
+	// pair pass
+	bool pair_pass = false, sweep = false;
+	FusedParams fp{};         // (c->last_fp is a copy of it)
+	bool use_panels = false, panel_side = false; // the panel table is built in this evaluation / on the side stream
+	bool reduce_in_tail = false;
+	// dipole solve
+	int solver = MPMC_SOLVER_MATRIX_FREE;
+	bool compact = false;     // this evaluation fills and reads the tensor store
+	bool solve = false, direct = false, gs = false;
+	int n_pol = 0, chol_np = 0; // direct solve: polarizable atoms, padded order of the factor
+	JacobiPlan jp{};
+	bool by_precision = false, moments = false, lazy = false;
+	int want_rrms = 0, half = 0, last_it = 0, check_every = kCheckEvery;
+	double allowed = 0.0;
+	bool palmo = false;
+};
+
+static inline size_t store_elements(const mpmc_ctx *c) { return (size_t)c->n_tile_pairs * (kTile * kTile); } // double2 elements, 16 B each
+// how the dipole iteration runs (room for what it stores: reserve_solver_store)
+static int choose_solver(const mpmc_ctx *c) {
+	if (direct_solve(c)) return MPMC_SOLVER_MATRIX_FREE; // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
+	int want = c->opts.solver;
+	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
+	if (want == MPMC_SOLVER_AUTO) {
+		const size_t budget_mb = (size_t)c->kept.tune.tensor_budget_mb;
+		want = (store_elements(c) * sizeof(double2) <= budget_mb * (size_t)1048576) ? MPMC_SOLVER_COMPACT : MPMC_SOLVER_MATRIX_FREE;
+		// building the store costs about as much as three iterations save (0.10 ms against 0.03 ms per iteration at 10 000 atoms)
+		if (c->opts.polar_precision == 0.0 && c->opts.polar_max_iter <= 3) want = MPMC_SOLVER_MATRIX_FREE;
+	}
+	return want;
+}
+// what follows from the solver (twice when AUTO has to give up the store: plan_evaluation, reserve_solver_store)
+static void plan_solver(const mpmc_ctx *c, EvalPlan &p, int solver) {
+	p.solver = solver;
+	p.compact = (p.mask & RUN_SOLVE) && solver == MPMC_SOLVER_COMPACT;
+	p.fp.do_thole = p.compact ? 1 : 0;
+	// panels of the Jacobi contraction: two tile pairs of equal class behind one j-tile per workgroup (compact solver)
+	p.use_panels = p.pair_pass && p.compact && c->kept.tune.use_panels && !c->kept.tune.no_classes && !c->kept.tune.no_uniform && c->n_tiles >= 3;
+	// the table is needed by the first Jacobi launch only: it is made beside the pair sweep (side stream, joined after the sweep)
+	p.panel_side = p.use_panels && p.two_streams;
+	p.jp = jacobi_plan(c, solver);
+	p.check_every = p.jp.dense ? 1 : kCheckEvery;
+}
+
+static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand) {
+	const mpmc_options &o = c->opts;
+	const mpmc_tuning &t = c->kept.tune;
+	EvalPlan p;
+	p.mask = mask;
+	p.static_ride = c->static_dirty;
+	// small LJ box (BASELINE configs[1]): the whole evaluation is one launch -- pair sweep without classes, the block that finishes last
+	// folds the partials into the pinned result vector; the LRC terms are the cached position-independent ones
+	p.single = t.single_launch && mask == (RUN_PAIR | RUN_ATOMTERMS) && !o.feynman_hibbs && c->n_tiles <= kSingleLaunchTiles && !c->kept.prof && !p.static_ride;
+	if (p.single) return p;
+
+	// ---- reciprocal space + O(N) atom terms on the side stream, next to the pair sweep ------------------------------
+	p.need_sf = (mask & RUN_RECIP) || ((mask & RUN_FIELD) && o.polar_ewald);
+	// intramolecular charge-to-screen term of coulombic_real: position dependent but independent of the pair sweep; identically zero
+	// when every molecule is a single atom
+	p.need_intra = (mask & RUN_PAIR) && (mask & RUN_PAIR_ES) && !(o.wolf && (mask & RUN_WOLF)) && (c->n_molecules != c->n);
+	p.side_work = p.need_sf || p.need_intra;
+	p.sf_part = p.need_sf && recip_view(c).lvec && o.ewald_kmax <= kRecipTabMaxK;
+	// a fork/join costs ~20 us of dispatch latency: worth it next to reciprocal-space work, not for the O(N) atom terms alone -- and not
+	// for small tables at all (kOneStreamMaxPairs).  Decided here, once per evaluation: nothing is forked at this point.
+	// (round 4: ... and not when the caller keeps kOneStreamMinInflight or more evaluations in flight: other evaluations fill the device then,
+	// and the fork and join are pure cost -- 1018-1025 against 1006-1012 evaluations/s with 32 beads, 1021 against 1002 with 8; one
+	// evaluation at a time the fork is worth 1.5 %.  The choice of streams does not touch the arithmetic.)
+	// Only for evaluations with a dipole solve: there the side work is 5 % of the evaluation; a 10 000-atom LJ + Ewald evaluation (sweep 95 us,
+	// reciprocal space 25 us) loses 4 % in flight without the overlap (9365 against 9600-9960 evaluations/s).
+	p.two_streams = (t.stream_mode == 1) ||
+	                (t.stream_mode < 0 && c->n_tile_pairs > kOneStreamMaxPairs && !((mask & RUN_SOLVE) && c->inflight_hint >= kOneStreamMinInflight));
+	p.side_fork = p.two_streams && (p.need_sf || p.need_intra);
+	// (two streams: enqueued BEHIND the pair sweep -- the main stream's critical path (classes, sweep) reaches the device first; one
+	// evaluation at a time the host used to be ~15 us late with the sweep because nine API calls of side work stood in front of it)
+	p.side_deferred = p.side_work && p.side_fork && (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) != 0 && t.side_after_sweep;
+
+	// ---- pairwise pass: one symmetric sweep (energies + counts, static-field partials, Thole tensor store) ----------
+	p.pair_pass = (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) != 0;
+	if (p.pair_pass) {
+		FusedParams &fp = p.fp;
+		fp.ewald_alpha = c->ewald_alpha;
+		fp.polar_ewald_alpha = c->polar_ewald_alpha;
+		fp.polar_damp = o.polar_damp;
+		fp.rd_lrc = o.rd_lrc;
+		fp.do_es = ((mask & RUN_PAIR_ES) || (mask & RUN_FIELD)) ? 1 : 0;
+		// (`polar_wolf`: the field is k_wolf_field's, below; the sweep keeps its energies and the tensor store)
+		fp.do_field = ((mask & RUN_FIELD) && !wolf_field_on(c)) ? (o.polar_ewald ? 1 : 2) : 0;
+		ext_params(c, fp, (o.wolf && (mask & RUN_WOLF)) != 0);
+		fp.thole_far_x = kTholeFarX;
+		fp.pair_waves = t.pair_waves ? t.pair_waves : (c->n_tile_pairs <= kPairSplitMax ? 4 : 1);
+		fp.store_only = ((mask & RUN_STORE) && !(mask & (RUN_PAIR | RUN_FIELD))) ? 1 : 0;
+		fp.touch_n = fp.store_only ? c->touch_n : -1;
+		for (int k = 0; k < 8; k++) fp.touch[k] = c->touch[k];
+		// the fast sweep (kernels_pair.hip) where it applies -- Ewald electrostatics, alpha r_c inside its erfc table --
+		// and, by default, where the table has more than kSweepMinPairs tile pairs (below that the 64 dependent steps of its one wave per
+		// tile pair are a latency chain: four waves per tile pair in k_pair_fused); the tile pairs with a special atom, which it skips,
+		// go through k_pair_fused on their list
+		p.sweep = t.pair_kernel != 1 && c->d_sweep_blocks && (t.pair_kernel == 2 || c->n_tile_pairs > kSweepMinPairs) && pair_sweep_covers(c->box, fp, c->ewald_alpha);
+	}
+	// the scalar totals of the sweep are only read back at the very end.  Polarizable evaluations on two streams fold them in the launch
+	// that closes the evaluation (second block of the polarization-energy kernel: launch_polar_energy_and_pairs) -- rounds 2-3 forked the
+	// side stream for it, which put an event record in front of the static field and a join in front of the posted results (~10 us of
+	// barrier packets on the main stream, one evaluation at a time)
+	p.reduce_in_tail = (mask & RUN_PAIR) && (mask & RUN_SOLVE); // (on one stream too: one launch fewer)
+
+	// ---- thole_iterative, reference src/System.Energy.cpp:3450-3543 ------------------------------------------------
+	plan_solver(c, p, (mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) ? choose_solver(c) : c->solver_used);
+	p.solve = (mask & RUN_SOLVE) != 0;
+	p.direct = p.solve && direct_solve(c);
+	if (p.direct) {
+		for (int i = 0; i < c->n; i++) p.n_pol += (c->h_alpha[i] != 0.0) ? 1 : 0;
+		p.chol_np = chol_padded(p.n_pol);
+	} else if (p.solve) {
+		p.gs = o.polar_gs != 0;
+		p.by_precision = (o.polar_precision != 0.0);
+		p.want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
+		p.allowed = p.by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
+		// fixed-count solves from alpha E0: the energy is the moment sum of the first `half` dipole differences, whether or not the other
+		// iterations run now (on demand: they wait for somebody who reads the dipoles) -- alone or as a bead, an evaluation gives the same bits
+		p.moments = polar_moments_apply(c);
+		p.half = moments_half(o.polar_max_iter);
+		p.lazy = p.moments && on_demand && t.dipoles_on_demand && p.half < o.polar_max_iter;
+		p.last_it = p.lazy ? p.half : o.polar_max_iter;
+		p.palmo = c->kept.palmo_enabled && p.gs; // (and the iteration must not have failed: stage_palmo)
+	}
+	return p;
+}
+
+// ---- room: every allocation, table upload and size guard of the evaluation, before anything of it is enqueued -----------------------------
+// (a refusal here leaves nothing of the evaluation on the device, and no buffer is born after the side stream has been forked, where its
+// first writer would not be ordered behind its fill -- see DevBuf::reserve)
+// (COMPACT, DENSE) room for what the solver stores; AUTO falls back to recomputing the tensors when the store cannot be had
+static int reserve_solver_store(mpmc_ctx *c, EvalPlan &p) {
+	if (p.solver == MPMC_SOLVER_DENSE && !direct_solve(c)) { // the reference's layout, on request only: (3 n_pad)^2 doubles
+		const int rc = c->d_adense.reserve(c, (size_t)3 * c->n_pad * (size_t)3 * c->n_pad);
+		if (rc != MPMC_OK) return rc;
+	}
+	if (p.solver == MPMC_SOLVER_COMPACT) {
+		const int rc = c->d_ab.reserve(c, store_elements(c));
+		if (rc != MPMC_OK) {
+			if (c->opts.solver == MPMC_SOLVER_COMPACT) return rc; // explicitly requested: report
+			(void)hipGetLastError();
+			plan_solver(c, p, MPMC_SOLVER_MATRIX_FREE); // AUTO: fall back to recomputing the tensors (still the HIP path)
+		}
+	}
+	c->solver_used = p.solver;
+	return MPMC_OK;
+}
+// the panel table's segments (its layout depends on the tile count only), the table and its per-entry slots
+static int reserve_panels(mpmc_ctx *c) {
+	int rc;
+	if (c->seg_tiles != c->n_tiles) {
+		std::vector<int> seg((size_t)c->n_tiles + 1, 0);
+		for (int J = 0; J < c->n_tiles; J++) seg[J + 1] = seg[J] + panel_segment_entries(J);
+		if ((rc = c->d_seg.reserve(c, seg.size())) != MPMC_OK) return rc;
+		HIP_TRY(c, hipMemcpyAsync(c->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // `seg` dies here
+		c->n_panel_entries = seg[c->n_tiles];
+		c->seg_tiles = c->n_tiles;
+	}
+	const size_t need = (size_t)c->n_panel_entries;
+	if ((rc = c->d_panels.reserve(c, need)) != MPMC_OK) return rc;
+	if ((rc = c->d_gpart.reserve(c, need * kTile * 3)) != MPMC_OK) return rc;
+	if (c->kept.tune.trace_panel && (rc = c->d_trace.reserve(c, need * 4)) != MPMC_OK) return rc;
+	return MPMC_OK;
+}
+// `polar_iterative off`: the factor must fit what the device has free (or the budget of the tuning switch); then the factor and its vectors
+static int reserve_direct_solve(mpmc_ctx *c, const EvalPlan &p) {
+	const int np = p.chol_np;
 	const size_t elems = (size_t)np * (size_t)np, bytes = elems * sizeof(double);
 	int rc;
 	if ((rc = c->d_chol_status.reserve(c, 4)) != MPMC_OK) return rc;
 	if ((rc = c->d_chol_info.reserve(c, 4)) != MPMC_OK) return rc;
 	if ((rc = c->h_chol_info.reserve(c, 4)) != MPMC_OK) return rc;
-	{ // size guard: the factor must fit what the device has free (or the budget of the tuning switch)
+	{ // size guard
 		size_t free_b = 0, total_b = 0;
 		HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
 		size_t avail = free_b + c->d_chol.cap * sizeof(double);
 		if (c->kept.tune.direct_budget_mb >= 0) avail = std::min(avail, (size_t)c->kept.tune.direct_budget_mb * (size_t)1048576);
 		if (bytes > avail) {
 			char buf[256];
-			std::snprintf(buf, sizeof buf, "direct dipole solve: the factor of %d unknowns needs %.1f MB (%d x %d doubles), %.1f MB are available", 3 * n_pol,
+			std::snprintf(buf, sizeof buf, "direct dipole solve: the factor of %d unknowns needs %.1f MB (%d x %d doubles), %.1f MB are available", 3 * p.n_pol,
 			              (double)bytes / 1048576.0, np, np, (double)avail / 1048576.0);
 			return fail(c, MPMC_ERR_MEMORY, buf);
 		}
@@ -260,56 +414,26 @@ static int enqueue_direct_solve(mpmc_ctx *c, const AtomsDev &at) {
 	// (v0 = [0, np) and v1 = [np, 2 np); the one element more is a spare that no kernel addresses, kept so that the bytes held stay what they were)
 	if ((rc = c->d_chol_v.reserve(c, (size_t)2 * np, (size_t)2 * np + 1)) != MPMC_OK) return rc;
 	// (room for every slot of the context: the number of polarizable atoms changes with the atom list and can then never outgrow it)
-	if ((rc = c->d_chol_list.reserve(c, (size_t)n_pol, (size_t)c->max_pad)) != MPMC_OK) return rc;
-	c->mu_cur = 0;
-	double *mu = c->d_mu[0], *v0 = c->d_chol_v, *v1 = c->d_chol_v + np;
-	HIP_TRY(c, hipMemsetAsync(c->d_chol_status, 0, sizeof(int), st));
-	HIP_TRY(c, hipMemsetAsync(mu, 0, 3 * (size_t)at.n_pad * sizeof(double), st));
-	if (n_pol > 0) {
-		{
-			ProfScope p(c, MPMC_K_TENSOR);
-			launch_chol_build(st, at, c->box, c->opts.polar_damp, c->d_chol_list, n_pol, np, c->d_chol);
-		}
-		{
-			ProfScope p(c, MPMC_K_DIPOLE_ITER);
-			launch_chol_rhs(st, c->d_chol_list, n_pol, np, c->d_e_static, v0, c->d_chol_status);
-			launch_chol_factor(st, c->d_chol, np, c->d_chol_status);
-			launch_chol_solve(st, c->d_chol, np, v0, v1, c->d_chol_status);
-			launch_chol_scatter(st, c->d_chol_list, n_pol, v0, mu, c->d_chol_status);
-		}
+	return c->d_chol_list.reserve(c, (size_t)p.n_pol, (size_t)c->max_pad);
+}
+static int make_room(mpmc_ctx *c, EvalPlan &p) {
+	int rc;
+	if (p.mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) {
+		if ((rc = ensure_polar_buffers(c)) != MPMC_OK) return rc;
+		if ((rc = reserve_solver_store(c, p)) != MPMC_OK) return rc;
 	}
-	{ // the residual from an independent product: one matrix-free contraction, -(A_off mu) into d_e_induced (d_mu[1] is scratch)
-		ProfScope p(c, MPMC_K_REDUCE);
-		launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, shift_view(c),
-		                          c->n_tile_pairs, nullptr, c->d_part, c->opts.polar_damp, nullptr);
-		launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, c->d_mu[1], c->d_e_induced, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
-		launch_chol_finish(st, at, mu, c->d_e_static, c->d_e_induced, c->d_chol_status, c->d_chol_info);
-	}
-	HIP_TRY(c, hipGetLastError());
-	HIP_TRY(c, hipMemcpyAsync(c->h_chol_info, c->d_chol_info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-	c->direct.n_unknowns = 3 * (int64_t)n_pol;
-	c->direct.factor_bytes = (int64_t)(c->d_chol.cap * sizeof(double));
-	c->direct_ran = true;
+	if (p.sf_part && (rc = c->d_sf_part.reserve(c, (size_t)c->n_tiles * (size_t)c->K)) != MPMC_OK) return rc;
+	if (p.use_panels && (rc = reserve_panels(c)) != MPMC_OK) return rc;
+	if (p.direct && (rc = reserve_direct_solve(c, p)) != MPMC_OK) return rc;
+	// the in-tile blocks of the Gauss-Seidel sweeps
+	if (p.gs && (rc = c->d_gs_blocks.reserve(c, gs_block_store_elements(c->n_tiles))) != MPMC_OK) return rc;
 	return MPMC_OK;
 }
 
-// which pieces of energy() to run
-
+// ---- launches written once ------------------------------------------------------------------------------------------------------------------
 // One Jacobi iteration on the main stream: the contraction of the solver in use, then new_mu = alpha (E0 + F) into the other dipole
 // vector.  Shared by the solve inside an evaluation and by finish_pending_dipoles, which runs the iterations an on-demand evaluation
 // left undone: same kernels, same tables, same order.  dk (may be null): this iteration's slot of the ring of dipole differences.
-struct JacobiPlan {
-	bool dense, dense_sym, compact;
-	int iter_slots;
-};
-static JacobiPlan jacobi_plan(const mpmc_ctx *c) {
-	JacobiPlan jp;
-	jp.dense = (c->solver_used == MPMC_SOLVER_DENSE) && !c->opts.polar_gs;
-	jp.dense_sym = jp.dense && c->kept.tune.dense_symmetric;
-	jp.compact = c->solver_used == MPMC_SOLVER_COMPACT;
-	jp.iter_slots = (jp.dense && !jp.dense_sym) ? kDenseChunks : c->n_tiles;
-	return jp;
-}
 static void enqueue_jacobi_iteration(mpmc_ctx *c, const AtomsDev &at, const JacobiPlan &jp, int it, int want_rrms, double allowed, int *ctl, int *host_flag,
                                      double *dk) {
 	hipStream_t st = c->stream;
@@ -355,7 +479,7 @@ int mpmc::finish_pending_dipoles(mpmc_ctx *c) {
 		                             "have been overwritten since: evaluate again (or mpmc_set_dipoles_on_demand(ctx, 0))");
 	HIP_TRY(c, hipSetDevice(c->device));
 	const AtomsDev at = atoms_view(c);
-	const JacobiPlan jp = jacobi_plan(c);
+	const JacobiPlan jp = jacobi_plan(c, c->solver_used);
 	for (int it = c->pend_done + 1; it <= c->pend_target; it++) enqueue_jacobi_iteration(c, at, jp, it, 0, 0.0, nullptr, nullptr, nullptr);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -364,6 +488,375 @@ int mpmc::finish_pending_dipoles(mpmc_ctx *c) {
 	if (!c->pending) prof_harvest(c);
 	return MPMC_OK;
 }
+
+// The pair pass on the main stream: the fast sweep with k_pair_fused on its list of generic tile pairs, or k_pair_fused on the whole table
+// (c->last_pair_was_sweep says which).  Shared by the evaluation and by mpmc_debug_time_pair, which replays it.
+static void launch_pair_pass(mpmc_ctx *c, const AtomsDev &at, const FusedParams &fp, bool compact, int lds_pad, int replicas) {
+	hipStream_t st = c->stream;
+	if (c->last_pair_was_sweep) {
+		launch_pair_sweep(st, at, c->box, fp, c->n_molecules != c->n, c->d_sweep_blocks, c->n_sweep_blocks, c->d_cls,
+		                  shift_view(c), c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
+		                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->kept.tune.fast_geometry, lds_pad, replicas);
+		if (c->n_generic > 0)
+			launch_pair_fused(st, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_generic, c->d_block_part, c->d_block_cnt, c->d_part,
+			                  compact ? c->d_ab : nullptr, c->d_generic_list);
+	} else if (!(fp.store_only && !compact)) // (a store-only pass without a store to fill has nothing to do beyond the classes)
+		launch_pair_fused(st, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_part,
+		                  compact ? c->d_ab : nullptr);
+}
+
+// F = -(A_off mu) of the dipoles `mu` into `field`: one matrix-free Jacobi contraction (nothing stored), its slots summed by the update
+// kernel, whose new dipoles go to `spare` and are dropped (rrms untouched); `tail` launches what the caller reads the field with.  The sum
+// and the tail share one MPMC_K_REDUCE bracket; the contraction is inside it too, or in a MPMC_K_DIPOLE_ITER bracket of its own.
+template <class Tail>
+static void contract_into_field(mpmc_ctx *c, const AtomsDev &at, double *mu, double *spare, double *field, bool own_bracket, Tail &&tail) {
+	hipStream_t st = c->stream;
+	int cur;
+	prof_begin(c, own_bracket ? MPMC_K_DIPOLE_ITER : MPMC_K_REDUCE, cur, st);
+	launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, shift_view(c), c->n_tile_pairs, nullptr, c->d_part, c->opts.polar_damp, nullptr);
+	if (own_bracket) {
+		prof_end(c, cur, st);
+		prof_begin(c, MPMC_K_REDUCE, cur, st);
+	}
+	launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, spare, field, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
+	tail();
+	prof_end(c, cur, st);
+}
+
+// reciprocal space and the O(N) intramolecular term, on the stream they are given
+static void enqueue_side_work(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &rcp, hipStream_t s2) {
+	const mpmc_options &o = c->opts;
+	if (p.need_intra) {
+		ProfScope ps(c, MPMC_K_PAIR, s2);
+		launch_intra_terms(s2, at, c->d_slot_of, c->ewald_alpha, c->d_scal);
+	}
+	{
+		ProfScope ps(c, MPMC_K_RECIP, s2);
+		if (p.need_sf) launch_recip_sf(s2, at, c->box, rcp, o.ewald_kmax, c->d_sf_part);
+		if (p.mask & RUN_RECIP) launch_recip_energy(s2, rcp, c->box, c->d_scal); // (the LRC and self terms are cached: prepare())
+	}
+	if ((p.mask & RUN_FIELD) && o.polar_ewald) {
+		ProfScope ps(c, MPMC_K_FIELD, s2);
+		launch_field_recip(s2, at, c->box, rcp, o.ewald_kmax, c->d_e_recip_part);
+	}
+}
+
+// ---- the stages of one evaluation, in the order enqueue() runs them: each looks at the plan for whether it has anything to do, and none
+// returns anything but a HIP error (everything that can be refused was refused by make_room) ---------------------------------------------
+static int stage_single_launch(mpmc_ctx *c, const EvalPlan &, const AtomsDev &at, const RecipDev &) {
+	FusedParams fp{};
+	fp.rd_lrc = c->opts.rd_lrc;
+	c->single_seq += 1.0;
+	launch_pair_lj_single(c->stream, at, c->box, fp, c->d_tile_pairs, c->n_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_counter, c->h_scal,
+	                      c->single_seq);
+	HIP_TRY(c, hipGetLastError());
+	c->last_was_single = true;
+	c->pending = true;
+	return MPMC_OK;
+}
+
+static int stage_clear_and_static_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	hipStream_t st = c->stream;
+	// the scalar block: zeroed by the post kernel of the evaluation before this one; cleared here only when something else used it since
+	// (the static-terms pass, an upload of the atoms, an evaluation that failed half way)
+	if (!c->scal_clean) HIP_TRY(c, hipMemsetAsync(c->d_scal, 0, (S_COUNT + C_COUNT) * sizeof(double), st));
+	c->scal_clean = false;
+	if (p.static_ride) { // first thing on the main stream: its slots are nobody else's (S_LRC_PAIR, S_LRC_SELF, S_ES_SELF)
+		launch_atom_terms(st, at, lrc_box(c), c->ewald_alpha, c->opts.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
+		HIP_TRY(c, hipGetLastError());
+		c->static_ride_gen = c->static_gen;
+	}
+	return MPMC_OK;
+}
+
+static int stage_side_work(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &rcp) {
+	c->two_streams = p.two_streams; // (fork_side takes it back when the side stream cannot be had)
+	if (p.side_work && !p.side_deferred) enqueue_side_work(c, p, at, rcp, p.side_fork ? fork_side(c) : c->stream);
+	return MPMC_OK;
+}
+
+// classes, panel table, pair launch, the side work that was left for behind it, join
+static int stage_pair_pass(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &rcp) {
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	if (p.pair_pass) {
+		// tile-pair classes from this configuration's tile bounding boxes
+		{
+			ProfScope pc(c, MPMC_K_CLASSES);
+			if (c->kept.tune.no_classes) HIP_TRY(c, hipMemsetAsync(c->d_cls, 0, (size_t)c->n_tile_pairs * sizeof(int), st));
+			else launch_tile_classes(st, at, c->box, c->d_tile_pairs, c->n_tile_pairs, (o.polarization && !o.rd_only) ? o.polar_damp : 0.0,
+			                         c->d_tile_bounds, c->d_cls, c->kept.tune.no_uniform ? nullptr : c->d_tp_shift, c->sort_origin_f, kTholeFarX);
+		}
+		if (!p.fp.store_only && p.compact) c->store_dirty_tiles.clear(); // a full sweep rebuilds every stored tile pair
+		c->panels_built = false;
+		if (p.use_panels) {
+			if (!p.panel_side) {
+				ProfScope pc(c, MPMC_K_CLASSES, st);
+				launch_build_panels(st, c->d_cls, c->n_tiles, c->d_seg, c->d_panels);
+			}
+			c->panels_built = true;
+		}
+		// the side stream starts behind the classes (what it reads of the main stream's work: positions, classes); its kernels are
+		// enqueued after the sweep's launch call
+		hipStream_t s_side = (p.side_deferred || p.panel_side) ? fork_side(c) : st;
+		c->last_fp = p.fp;
+		c->last_fp_valid = !p.fp.store_only;
+		ProfScope pp(c, MPMC_K_PAIR);
+		c->last_pair_was_sweep = p.sweep;
+		launch_pair_pass(c, at, p.fp, p.compact, (p.side_deferred || p.panel_side) ? c->kept.tune.sweep_lds_pad : 0, 1);
+		if (p.side_deferred) enqueue_side_work(c, p, at, rcp, s_side);
+		if (p.panel_side) {
+			ProfScope pc(c, MPMC_K_CLASSES, s_side);
+			launch_build_panels(s_side, c->d_cls, c->n_tiles, c->d_seg, c->d_panels);
+		}
+	}
+	if ((p.side_work && p.side_fork) || p.panel_side) join_side(c);
+	return MPMC_OK;
+}
+
+static int stage_pair_reduce(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &, const RecipDev &) {
+	if ((p.mask & RUN_PAIR) && !p.reduce_in_tail) {
+		ProfScope ps(c, MPMC_K_REDUCE);
+		launch_reduce_pairs(c->stream, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal, c->d_cnt);
+	}
+	return MPMC_OK;
+}
+
+static int stage_static_field(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!(p.mask & RUN_FIELD)) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	ProfScope ps(c, MPMC_K_FIELD);
+	c->mu_cur = 0;
+	if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
+		launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
+	launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
+	                      c->d_mu[0], c->d_e_real, polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
+	c->e_real_valid = (p.mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
+	return MPMC_OK;
+}
+
+// `polar_iterative off` (System::polar :2590-2607; thole_bmatrix + thole_bmatrix_dipoles :2596-2600): A mu = E0 solved directly
+// (kernels_chol.hip), behind the static field.  Leaves the dipoles in d_mu[mu_cur], mu / alpha - E0 in d_e_induced and { status, max |r|,
+// max |E0| } on their way to the pinned info block.
+static int stage_direct_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!p.direct) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const int n_pol = p.n_pol, np = p.chol_np;
+	c->mu_cur = 0;
+	double *mu = c->d_mu[0], *v0 = c->d_chol_v, *v1 = c->d_chol_v + np;
+	HIP_TRY(c, hipMemsetAsync(c->d_chol_status, 0, sizeof(int), st));
+	HIP_TRY(c, hipMemsetAsync(mu, 0, 3 * (size_t)at.n_pad * sizeof(double), st));
+	if (n_pol > 0) {
+		{
+			ProfScope ps(c, MPMC_K_TENSOR);
+			launch_chol_build(st, at, c->box, c->opts.polar_damp, c->d_chol_list, n_pol, np, c->d_chol);
+		}
+		{
+			ProfScope ps(c, MPMC_K_DIPOLE_ITER);
+			launch_chol_rhs(st, c->d_chol_list, n_pol, np, c->d_e_static, v0, c->d_chol_status);
+			launch_chol_factor(st, c->d_chol, np, c->d_chol_status);
+			launch_chol_solve(st, c->d_chol, np, v0, v1, c->d_chol_status);
+			launch_chol_scatter(st, c->d_chol_list, n_pol, v0, mu, c->d_chol_status);
+		}
+	}
+	// the residual from an independent product: one matrix-free contraction, -(A_off mu) into d_e_induced (d_mu[1] is scratch)
+	contract_into_field(c, at, mu, c->d_mu[1], c->d_e_induced, false,
+	                    [&] { launch_chol_finish(st, at, mu, c->d_e_static, c->d_e_induced, c->d_chol_status, c->d_chol_info); });
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipMemcpyAsync(c->h_chol_info, c->d_chol_info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+	c->direct.n_unknowns = 3 * (int64_t)n_pol;
+	c->direct.factor_bytes = (int64_t)(c->d_chol.cap * sizeof(double));
+	c->direct_ran = true;
+	c->polar_pending = mpmc_ctx::PEND_NONE;
+	return MPMC_OK;
+}
+
+// what an iterative solve leaves behind after `it` iterations
+static void close_solve(mpmc_ctx *c, const EvalPlan &p, int it) {
+	c->iters = p.lazy ? c->opts.polar_max_iter : it; // (what the solve comes to once its dipoles are asked for)
+	c->polar_pending = p.lazy ? mpmc_ctx::PEND_OPEN : mpmc_ctx::PEND_NONE;
+	c->pend_done = it, c->pend_target = c->opts.polar_max_iter;
+}
+
+// Gauss-Seidel sweeps: in place, in atom order; the host asks for the verdict of a precision-terminated solve after every sweep
+static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!p.solve || p.direct || !p.gs) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	{ // the in-tile blocks of the sweeps: positions and polarizabilities only, once per evaluation
+		ProfScope ps(c, MPMC_K_TENSOR);
+		launch_gs_blocks(st, at, c->box, o.polar_damp, c->d_gs_blocks);
+	}
+	int it = 0;
+	for (bool keep = true; keep;) {
+		it++;
+		if (it >= kMaxIterationCount && p.by_precision) { // divergence: mu = alpha E0, iterator_failed (:3483-3494)
+			launch_dipole_reset(st, at, c->d_e_static, c->d_mu[c->mu_cur]);
+			c->failed = 1;
+			break;
+		}
+		if (p.by_precision) HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), st));
+		// in-place sweep in atom order; old_mu is kept only when rrms / precision need it (:3503-3507)
+		double *mu = c->d_mu[c->mu_cur], *mu_old = c->d_mu[1 - c->mu_cur];
+		if (p.want_rrms) HIP_TRY(c, hipMemcpyAsync(mu_old, mu, 3 * (size_t)at.n_pad * sizeof(double), hipMemcpyDeviceToDevice, st));
+		{
+			ProfScope ps(c, MPMC_K_DIPOLE_ITER);
+			launch_gs_sweep(st, at, c->box, o.polar_damp, c->d_e_static, mu, c->d_e_induced, c->d_part, c->d_tile_pairs, c->d_cls,
+			                shift_view(c), c->n_tile_pairs, c->d_gs_ul, c->d_gs_ul + 3 * (size_t)c->max_pad, c->d_gs_blocks);
+		}
+		if (p.want_rrms) {
+			ProfScope ps(c, MPMC_K_REDUCE);
+			launch_gs_finish(st, at, mu_old, mu, p.want_rrms, c->d_rrms, p.allowed, c->d_flag);
+		}
+		if (p.by_precision) {
+			HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipStreamSynchronize(st));
+			keep = (*c->h_flag != 0);
+		} else {
+			keep = (it != o.polar_max_iter);
+		}
+	}
+	close_solve(c, p, it);
+	return MPMC_OK;
+}
+
+static int stage_jacobi_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!p.solve || p.direct || p.gs) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	const size_t dk_stride = 3 * (size_t)at.n_pad;
+	if (p.jp.dense) { // thole_amatrix into device memory, once per evaluation (the positions changed)
+		ProfScope ps(c, MPMC_K_TENSOR);
+		launch_dense_build(st, at, c->box, o.polar_damp, c->d_adense, p.jp.dense_sym);
+	}
+	// Precision-terminated Jacobi solves: are_we_done_yet (:3215-3239) runs on the device (ctl = {broke, converged-at, ticket}); the host
+	// enqueues kCheckEvery iterations at a time and reads the verdict once per batch -- the iterations enqueued behind the one that
+	// converged return at once and leave the dipoles alone.  (Gauss-Seidel sweeps and the dense solver still ask after every iteration.)
+	int *ctl = p.by_precision ? c->d_flag + 1 : nullptr;
+	const int mu_start = c->mu_cur;
+	int done_at = 0;
+	int *host_flag = ctl ? c->h_flag + 2 : nullptr; // pinned {last closed iteration, converged-at} the closing update block posts
+	if (ctl) {
+		HIP_TRY(c, hipMemsetAsync(ctl, 0, 3 * sizeof(int), st));
+		c->h_flag[2] = c->h_flag[3] = 0; // (nothing of an earlier solve can still be in flight: every evaluation is waited for)
+	}
+	int it = 0;
+	for (bool keep = true; keep;) {
+		it++;
+		if (it >= kMaxIterationCount && p.by_precision) { // divergence: mu = alpha E0, iterator_failed (:3483-3494)
+			launch_dipole_reset(st, at, c->d_e_static, c->d_mu[c->mu_cur]);
+			c->failed = 1;
+			break;
+		}
+		enqueue_jacobi_iteration(c, at, p.jp, it, p.want_rrms, p.allowed, ctl, host_flag, (p.moments && it <= p.half) ? c->d_dk_ring + (size_t)it * dk_stride : nullptr);
+		if (p.by_precision) {
+			if (it % p.check_every == 0 || it + 1 >= kMaxIterationCount) { // the verdict of this batch
+				HIP_TRY(c, hipGetLastError());
+				// spin on the pinned flag until iteration `it` is closed (or an earlier one converged); a stream synchronisation costs
+				// ~15 us, this ~2.  Past a generous budget fall back to the blocking read (correct either way).
+				volatile const int *hf = host_flag;
+				const bool seen = poll_posted(c, [&] { return hf[0] >= it || hf[1] != 0; }, std::chrono::microseconds(50000));
+				if (seen) {
+					done_at = hf[1];
+				} else {
+					c->kept.n_stream_syncs++;
+					HIP_TRY(c, hipMemcpyAsync(c->h_flag, ctl + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+					HIP_TRY(c, hipStreamSynchronize(st));
+					done_at = *c->h_flag;
+				}
+				keep = (done_at == 0);
+			}
+		} else {
+			keep = (it != p.last_it);
+		}
+	}
+	if (done_at > 0) { // the iterations enqueued behind the converged one did nothing: the result is where iteration done_at left it
+		it = done_at;
+		c->mu_cur = (mu_start + done_at) & 1;
+	}
+	close_solve(c, p, it);
+	return MPMC_OK;
+}
+
+// -1/2 mu . E0 (or the moment sum of a fixed-count Jacobi solve) into the scalar block; with the pair totals as the launch's second block
+// when this is the tail of the evaluation (plan: reduce_in_tail).  The one place that picks among the four kernels.
+static int stage_polar_energy(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!p.solve) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const double *mu = c->d_mu[c->mu_cur], *rrms = p.want_rrms ? c->d_rrms.p : nullptr;
+	ProfScope ps(c, MPMC_K_REDUCE);
+	if (p.moments && p.reduce_in_tail)
+		launch_polar_moments_and_pairs(st, at, c->d_dk_ring, c->d_e_static, c->opts.polar_max_iter, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal,
+		                               c->d_cnt);
+	else if (p.moments) launch_polar_moments(st, at, c->d_dk_ring, c->d_e_static, c->opts.polar_max_iter, c->d_scal);
+	else if (p.reduce_in_tail)
+		launch_polar_energy_and_pairs(st, at, mu, c->d_e_static, rrms, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal, c->d_cnt);
+	else launch_polar_energy(st, at, mu, c->d_e_static, rrms, c->d_scal);
+	c->have_polar = true;
+	return MPMC_OK;
+}
+
+// `polar_palmo` (:3517-3519, palmo_contraction :3602-3627): one more contraction with the final dipoles.  Under Jacobi the reference
+// contracts the dipoles the last iteration read (mu is overwritten with new_mu only afterwards, :3526-3536), so it subtracts from the
+// induced field that very field: zero to the bit, and nothing runs here.  Under Gauss-Seidel sweeps the dipoles are the swept ones:
+// F = -(A_off mu) through the matrix-free Jacobi contraction (Gauss-Seidel contexts store nothing), against the induced field the
+// last sweep used.  A failed iteration leaves the correction at 0 (:3483-3488).
+static int stage_palmo(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	if (!p.palmo || c->failed) return MPMC_OK;
+	double *mu = c->d_mu[c->mu_cur];
+	// (the slots summed by the update kernel: d_palmo_f = F; its new dipoles go to the spare vector and are dropped, rrms untouched)
+	contract_into_field(c, at, mu, c->d_mu[1 - c->mu_cur], c->d_palmo_f, true,
+	                    [&] { launch_palmo_reduce(c->stream, at, mu, c->d_palmo_f, c->d_e_induced, c->d_palmo_change, c->d_scal); });
+	c->palmo_ran = true;
+	return MPMC_OK;
+}
+
+// the terms added on top: each into its slots of the scalar block, in front of the post
+static int stage_added_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
+	hipStream_t st = c->stream;
+	// ---- Axilrod-Teller, System::axilrod_teller (:129-136): into its slot of the scalar block, in front of the post below ----------------
+	if (p.mask & RUN_THREE_BODY) {
+		ProfScope ps(c, MPMC_K_THREE_BODY);
+		launch_three_body(st, at, c->d_tb_au, c->box, kThreeBodyScale, c->d_tb_part, c->d_scal + S_THREE_BODY);
+	}
+	// ---- disp-expansion, System::disp_expansion (:121-122, 1939-2018): pair sum and the cached corrections into their three slots ----------
+	if (p.mask & RUN_DISP) {
+		ProfScope ps(c, MPMC_K_PAIR);
+		launch_disp_expansion(st, at, c->d_de_co, c->d_de_t10, c->d_tile_pairs, c->n_tile_pairs, c->box, disp_params(c), c->de_lrc[0], c->de_lrc[1],
+		                      c->d_de_part, c->d_scal + S_DISP);
+	}
+	// ---- rd_crystal, System::lj (:916-963): the lattice sum and its image-term count into their two slots ---------------------------------
+	if (p.mask & RUN_CRYSTAL) {
+		ProfScope ps(c, MPMC_K_PAIR);
+		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL,
+		               c->d_scal + S_CRYSTAL_TERMS);
+	}
+	HIP_TRY(c, hipGetLastError());
+	return MPMC_OK;
+}
+
+static int stage_post(mpmc_ctx *c, const EvalPlan &, const AtomsDev &, const RecipDev &) {
+	// results to the pinned block by a kernel of ours (a blit and a stream synchronisation cost more than the whole reciprocal space of a
+	// small box): copy, zero the device block for the next evaluation, launch number last
+	c->single_seq += 1.0;
+	launch_post_results(c->stream, c->d_scal, c->h_scal, c->single_seq);
+	HIP_TRY(c, hipGetLastError());
+	c->scal_clean = true;
+	// short evaluations are polled for (a few us against ~10-15 for the synchronisation); long ones, and profiled ones (the event
+	// harvest needs an idle stream), are waited for the ordinary way
+	// (round 4: long evaluations are polled for as well, with a budget of a few of their own durations -- one evaluation at a time the
+	// posted launch number is seen ~10 us before hipStreamSynchronize returns; an ensemble's first wait outlasts the budget and synchronises)
+	c->spin_on_post = c->ev_used.empty() && (c->kept.tune.poll_long || c->n_tile_pairs <= kOneStreamMaxPairs);
+	c->poll_budget_us = (c->n_tile_pairs <= kOneStreamMaxPairs) ? 1000 : 4000;
+	c->pending = true;
+	return MPMC_OK;
+}
+
+using Stage = int (*)(mpmc_ctx *, const EvalPlan &, const AtomsDev &, const RecipDev &);
+static constexpr Stage kStages[] = {stage_clear_and_static_terms, stage_side_work,         stage_pair_pass,    stage_pair_reduce, stage_static_field,
+                                    stage_direct_solve,           stage_gauss_seidel_solve, stage_jacobi_solve, stage_polar_energy, stage_palmo,
+                                    stage_added_terms,            stage_post};
 
 int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	// one evaluation per context at a time: a second enqueue would overwrite the scalar block and the result slots under the first
@@ -375,370 +868,20 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
-	const bool static_ride = c->static_dirty;
 	c->static_ride_gen = 0;
+	c->run_mask = mask;
+	c->have_polar = c->direct_ran = c->palmo_ran = false;
+	c->iters = c->failed = 0;
+	c->last_was_single = c->spin_on_post = false;
+
+	EvalPlan made = plan_evaluation(c, mask, on_demand);
+	if (!made.single && (rc = make_room(c, made)) != MPMC_OK) return rc; // (before anything of this evaluation is on a stream)
+	const EvalPlan &plan = made;
 	const AtomsDev at = atoms_view(c);
 	const RecipDev rcp = recip_view(c);
-	const mpmc_options &o = c->opts;
-	hipStream_t st = c->stream;
-	c->run_mask = mask;
-	c->have_polar = false;
-	c->direct_ran = false;
-	c->palmo_ran = false;
-	c->iters = 0;
-	c->failed = 0;
-
-	c->last_was_single = false;
-	c->spin_on_post = false;
-	if (c->kept.tune.single_launch && mask == (RUN_PAIR | RUN_ATOMTERMS) && !o.feynman_hibbs && c->n_tiles <= kSingleLaunchTiles && !c->kept.prof && !static_ride) {
-		// small LJ box (BASELINE configs[1]): the whole evaluation is one launch -- pair sweep without classes, the block that finishes last
-		// folds the partials into the pinned result vector; the LRC terms are the cached position-independent ones
-		FusedParams fp{};
-		fp.rd_lrc = o.rd_lrc;
-		c->single_seq += 1.0;
-		launch_pair_lj_single(st, at, c->box, fp, c->d_tile_pairs, c->n_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_counter, c->h_scal,
-		                      c->single_seq);
-		HIP_TRY(c, hipGetLastError());
-		c->last_was_single = true;
-		c->pending = true;
-		return MPMC_OK;
-	}
-	// the scalar block: zeroed by the post kernel of the evaluation before this one; cleared here only when something else used it since
-	// (the static-terms pass, an upload of the atoms, an evaluation that failed half way)
-	if (!c->scal_clean) HIP_TRY(c, hipMemsetAsync(c->d_scal, 0, (S_COUNT + C_COUNT) * sizeof(double), st));
-	c->scal_clean = false;
-	if (static_ride) { // first thing on the main stream: its slots are nobody else's (S_LRC_PAIR, S_LRC_SELF, S_ES_SELF)
-		launch_atom_terms(st, at, lrc_box(c), c->ewald_alpha, o.rd_lrc, /*self term*/ 1, c->d_atom_part, c->d_scal);
-		HIP_TRY(c, hipGetLastError());
-		c->static_ride_gen = c->static_gen;
-	}
-
-	if (mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) {
-		if ((rc = ensure_polar_buffers(c)) != MPMC_OK) return rc;
-		if ((rc = resolve_solver(c)) != MPMC_OK) return rc;
-	}
-	const bool compact = (mask & RUN_SOLVE) && c->solver_used == MPMC_SOLVER_COMPACT;
-
-	// ---- reciprocal space + O(N) atom terms on the side stream, next to the pair sweep ------------------------------
-	const bool need_sf = (mask & RUN_RECIP) || ((mask & RUN_FIELD) && o.polar_ewald);
-	// intramolecular charge-to-screen term of coulombic_real: position dependent but independent of the pair sweep; identically zero
-	// when every molecule is a single atom
-	const bool need_intra = (mask & RUN_PAIR) && (mask & RUN_PAIR_ES) && !(o.wolf && (mask & RUN_WOLF)) && (c->n_molecules != c->n);
-	const bool side_work = need_sf || need_intra;
-	// a fork/join costs ~20 us of dispatch latency: worth it next to reciprocal-space work, not for the O(N) atom terms alone -- and not
-	// for small tables at all (kOneStreamMaxPairs).  Decided here, once per evaluation: nothing is forked at this point.
-	// (round 4: ... and not when the caller keeps kOneStreamMinInflight or more evaluations in flight: other evaluations fill the device then,
-	// and the fork and join are pure cost -- 1018-1025 against 1006-1012 evaluations/s with 32 beads, 1021 against 1002 with 8; one
-	// evaluation at a time the fork is worth 1.5 %.  The choice of streams does not touch the arithmetic.)
-	// Only for evaluations with a dipole solve: there the side work is 5 % of the evaluation; a 10 000-atom LJ + Ewald evaluation (sweep 95 us,
-	// reciprocal space 25 us) loses 4 % in flight without the overlap (9365 against 9600-9960 evaluations/s).
-	c->two_streams = (c->kept.tune.stream_mode == 1) ||
-	                 (c->kept.tune.stream_mode < 0 && c->n_tile_pairs > kOneStreamMaxPairs &&
-	                  !((mask & RUN_SOLVE) && c->inflight_hint >= kOneStreamMinInflight));
-	const bool side_fork = c->two_streams && (need_sf || need_intra);
-	bool panel_side = false; // the panel table of the Jacobi contraction is being built on the side stream
-	// (two streams: enqueued BEHIND the pair sweep -- the main stream's critical path (classes, sweep) reaches the device first; one
-	// evaluation at a time the host used to be ~15 us late with the sweep because nine API calls of side work stood in front of it)
-	int side_rc = MPMC_OK;
-	auto enqueue_side_work = [&](hipStream_t s2) {
-		if (need_intra) {
-			ProfScope p(c, MPMC_K_PAIR, s2);
-			launch_intra_terms(s2, at, c->d_slot_of, c->ewald_alpha, c->d_scal);
-		}
-		{
-			ProfScope p(c, MPMC_K_RECIP, s2);
-			if (need_sf) {
-				const size_t need_part = (size_t)c->n_tiles * (size_t)c->K;
-				if (rcp.lvec && o.ewald_kmax <= kRecipTabMaxK && (side_rc = c->d_sf_part.reserve(c, need_part)) != MPMC_OK) return;
-				launch_recip_sf(s2, at, c->box, rcp, o.ewald_kmax, c->d_sf_part);
-			}
-			if (mask & RUN_RECIP) launch_recip_energy(s2, rcp, c->box, c->d_scal); // (the LRC and self terms are cached: prepare())
-		}
-		if ((mask & RUN_FIELD) && o.polar_ewald) {
-			ProfScope p(c, MPMC_K_FIELD, s2);
-			launch_field_recip(s2, at, c->box, rcp, o.ewald_kmax, c->d_e_recip_part);
-		}
-	};
-	const bool side_deferred = side_work && side_fork && (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) != 0 && c->kept.tune.side_after_sweep;
-	if (side_work && !side_deferred) {
-		enqueue_side_work(side_fork ? fork_side(c) : st);
-		if (side_rc != MPMC_OK) return side_rc;
-	}
-
-	// ---- pairwise pass: one symmetric sweep (energies + counts, static-field partials, Thole tensor store) ----------
-	if (mask & (RUN_PAIR | RUN_FIELD | RUN_STORE)) {
-		// tile-pair classes from this configuration's tile bounding boxes
-		{
-			ProfScope pc(c, MPMC_K_CLASSES);
-			if (c->kept.tune.no_classes) HIP_TRY(c, hipMemsetAsync(c->d_cls, 0, (size_t)c->n_tile_pairs * sizeof(int), st));
-			else launch_tile_classes(st, at, c->box, c->d_tile_pairs, c->n_tile_pairs, (o.polarization && !o.rd_only) ? o.polar_damp : 0.0,
-			                         c->d_tile_bounds, c->d_cls, c->kept.tune.no_uniform ? nullptr : c->d_tp_shift, c->sort_origin_f, kTholeFarX);
-		}
-		FusedParams fp;
-		fp.ewald_alpha = c->ewald_alpha;
-		fp.polar_ewald_alpha = c->polar_ewald_alpha;
-		fp.polar_damp = o.polar_damp;
-		fp.rd_lrc = o.rd_lrc;
-		fp.do_es = ((mask & RUN_PAIR_ES) || (mask & RUN_FIELD)) ? 1 : 0;
-		// (`polar_wolf`: the field is k_wolf_field's, below; the sweep keeps its energies and the tensor store)
-		fp.do_field = ((mask & RUN_FIELD) && !wolf_field_on(c)) ? (o.polar_ewald ? 1 : 2) : 0;
-		fp.do_thole = compact ? 1 : 0;
-		ext_params(c, fp, (o.wolf && (mask & RUN_WOLF)) != 0);
-		fp.thole_far_x = kTholeFarX;
-		fp.pair_waves = c->kept.tune.pair_waves ? c->kept.tune.pair_waves : (c->n_tile_pairs <= kPairSplitMax ? 4 : 1);
-		fp.store_only = ((mask & RUN_STORE) && !(mask & (RUN_PAIR | RUN_FIELD))) ? 1 : 0;
-		fp.touch_n = fp.store_only ? c->touch_n : -1;
-		for (int k = 0; k < 8; k++) fp.touch[k] = c->touch[k];
-		if (!fp.store_only && compact) c->store_dirty_tiles.clear(); // a full sweep rebuilds every stored tile pair
-		// panels of the Jacobi contraction: two tile pairs of equal class behind one j-tile per workgroup (compact solver)
-		c->panels_built = false;
-		if (compact && c->kept.tune.use_panels && !c->kept.tune.no_classes && !c->kept.tune.no_uniform && c->n_tiles >= 3) {
-			if (c->seg_tiles != c->n_tiles) { // the table's layout depends on the tile count only
-				std::vector<int> seg((size_t)c->n_tiles + 1, 0);
-				for (int J = 0; J < c->n_tiles; J++) seg[J + 1] = seg[J] + panel_segment_entries(J);
-				if ((rc = c->d_seg.reserve(c, seg.size())) != MPMC_OK) return rc;
-				HIP_TRY(c, hipMemcpyAsync(c->d_seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, st));
-				HIP_TRY(c, hipStreamSynchronize(st)); // `seg` dies here
-				c->n_panel_entries = seg[c->n_tiles];
-				c->seg_tiles = c->n_tiles;
-			}
-			const size_t need = (size_t)c->n_panel_entries;
-			if ((rc = c->d_panels.reserve(c, need)) != MPMC_OK) return rc;
-			if ((rc = c->d_gpart.reserve(c, need * kTile * 3)) != MPMC_OK) return rc;
-			if (c->kept.tune.trace_panel && (rc = c->d_trace.reserve(c, need * 4)) != MPMC_OK) return rc;
-			// the table is needed by the first Jacobi launch only: it is made beside the pair sweep (side stream, joined after the sweep)
-			panel_side = c->two_streams;
-			if (!panel_side) {
-				ProfScope pc(c, MPMC_K_CLASSES, st);
-				launch_build_panels(st, c->d_cls, c->n_tiles, c->d_seg, c->d_panels);
-			}
-			c->panels_built = true;
-		}
-		// the side stream starts behind the classes (what it reads of the main stream's work: positions, classes); its kernels are
-		// enqueued after the sweep's launch call
-		hipStream_t s_side = (side_deferred || panel_side) ? fork_side(c) : st;
-		c->last_fp = fp;
-		c->last_fp_valid = !fp.store_only;
-		ProfScope p(c, MPMC_K_PAIR);
-		// the fast sweep (kernels_pair.hip) where it applies -- Ewald electrostatics, alpha r_c inside its erfc table --
-		// and, by default, where the table has more than kSweepMinPairs tile pairs (below that the 64 dependent steps of its one wave per
-		// tile pair are a latency chain: four waves per tile pair in k_pair_fused); the tile pairs with a special atom, which it skips,
-		// go through k_pair_fused on their list
-		const bool sweep = c->kept.tune.pair_kernel != 1 && c->d_sweep_blocks && (c->kept.tune.pair_kernel == 2 || c->n_tile_pairs > kSweepMinPairs) &&
-		                   pair_sweep_covers(c->box, fp, c->ewald_alpha);
-		c->last_pair_was_sweep = sweep;
-		if (sweep) {
-			launch_pair_sweep(st, at, c->box, fp, c->n_molecules != c->n, c->d_sweep_blocks, c->n_sweep_blocks, c->d_cls,
-			                  shift_view(c), c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->kept.tune.fast_geometry,
-			                  (side_deferred || panel_side) ? c->kept.tune.sweep_lds_pad : 0);
-			if (c->n_generic > 0)
-				launch_pair_fused(st, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_generic, c->d_block_part, c->d_block_cnt, c->d_part,
-				                  compact ? c->d_ab : nullptr, c->d_generic_list);
-		} else if (!(fp.store_only && !compact)) // (a store-only pass without a store to fill has nothing to do beyond the classes)
-			launch_pair_fused(st, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr);
-		if (side_deferred) {
-			enqueue_side_work(s_side);
-			if (side_rc != MPMC_OK) return side_rc;
-		}
-		if (panel_side) {
-			ProfScope pc(c, MPMC_K_CLASSES, s_side);
-			launch_build_panels(s_side, c->d_cls, c->n_tiles, c->d_seg, c->d_panels);
-		}
-	}
-	if ((side_work && side_fork) || panel_side) join_side(c);
-	// the scalar totals of the sweep are only read back at the very end.  Polarizable evaluations on two streams fold them in the launch
-	// that closes the evaluation (second block of the polarization-energy kernel: launch_polar_energy_and_pairs) -- rounds 2-3 forked the
-	// side stream for it, which put an event record in front of the static field and a join in front of the posted results (~10 us of
-	// barrier packets on the main stream, one evaluation at a time)
-	const bool reduce_in_tail = (mask & RUN_PAIR) && (mask & RUN_SOLVE); // (on one stream too: one launch fewer)
-	if ((mask & RUN_PAIR) && !reduce_in_tail) {
-		ProfScope p(c, MPMC_K_REDUCE);
-		launch_reduce_pairs(st, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal, c->d_cnt);
-	}
-
-	// ---- static field ---------------------------------------------------------------------------------------
-	if (mask & RUN_FIELD) {
-		ProfScope p(c, MPMC_K_FIELD);
-		c->mu_cur = 0;
-		if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
-			launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
-		launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
-		                      c->d_mu[0], c->d_e_real, polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
-		c->e_real_valid = (mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
-	}
-
-	// ---- thole_iterative, reference src/System.Energy.cpp:3450-3543 ------------------------------------------------
-	if ((mask & RUN_SOLVE) && direct_solve(c)) { // thole_bmatrix + thole_bmatrix_dipoles (:2596-2600) as a direct solve of A mu = E0
-		if ((rc = enqueue_direct_solve(c, at)) != MPMC_OK) return rc;
-		{
-			ProfScope p(c, MPMC_K_REDUCE);
-			if (reduce_in_tail)
-				launch_polar_energy_and_pairs(st, at, c->d_mu[c->mu_cur], c->d_e_static, nullptr, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal,
-				                              c->d_cnt);
-			else launch_polar_energy(st, at, c->d_mu[c->mu_cur], c->d_e_static, nullptr, c->d_scal);
-		}
-		c->have_polar = true;
-		c->polar_pending = mpmc_ctx::PEND_NONE;
-	} else if (mask & RUN_SOLVE) {
-		const bool by_precision = (o.polar_precision != 0.0);
-		const int want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
-		const double allowed = by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
-		const JacobiPlan jp = jacobi_plan(c);
-		const bool dense = jp.dense, dense_sym = jp.dense_sym;
-		// fixed-count solves from alpha E0: the energy is the moment sum of the first `half` dipole differences, whether or not the other
-		// iterations run now (on demand: they wait for somebody who reads the dipoles) -- alone or as a bead, an evaluation gives the same bits
-		const bool moments = polar_moments_apply(c);
-		const int half = moments_half(o.polar_max_iter);
-		const bool lazy = moments && on_demand && c->kept.tune.dipoles_on_demand && half < o.polar_max_iter;
-		const int last_it = lazy ? half : o.polar_max_iter;
-		const size_t dk_stride = 3 * (size_t)at.n_pad;
-		if (dense) { // thole_amatrix into device memory, once per evaluation (the positions changed)
-			ProfScope p(c, MPMC_K_TENSOR);
-			launch_dense_build(st, at, c->box, o.polar_damp, c->d_adense, dense_sym);
-		}
-		// Precision-terminated Jacobi solves: are_we_done_yet (:3215-3239) runs on the device (ctl = {broke, converged-at, ticket}); the host
-		// enqueues kCheckEvery iterations at a time and reads the verdict once per batch -- the iterations enqueued behind the one that
-		// converged return at once and leave the dipoles alone.  (Gauss-Seidel sweeps and the dense solver still ask after every iteration.)
-		int *ctl = (by_precision && !o.polar_gs) ? c->d_flag + 1 : nullptr;
-		const int check_every = dense ? 1 : kCheckEvery;
-		const int mu_start = c->mu_cur;
-		int done_at = 0;
-		int *host_flag = ctl ? c->h_flag + 2 : nullptr; // pinned {last closed iteration, converged-at} the closing update block posts
-		if (ctl) {
-			HIP_TRY(c, hipMemsetAsync(ctl, 0, 3 * sizeof(int), st));
-			c->h_flag[2] = c->h_flag[3] = 0; // (nothing of an earlier solve can still be in flight: every evaluation is waited for)
-		}
-		if (o.polar_gs) { // the in-tile blocks of the sweeps: positions and polarizabilities only, once per evaluation
-			if ((rc = c->d_gs_blocks.reserve(c, gs_block_store_elements(c->n_tiles))) != MPMC_OK) return rc;
-			ProfScope p(c, MPMC_K_TENSOR);
-			launch_gs_blocks(st, at, c->box, o.polar_damp, c->d_gs_blocks);
-		}
-		int it = 0;
-		bool keep = true;
-		while (keep) {
-			it++;
-			if (it >= kMaxIterationCount && by_precision) { // divergence: mu = alpha E0, iterator_failed (:3483-3494)
-				launch_dipole_reset(st, at, c->d_e_static, c->d_mu[c->mu_cur]);
-				c->failed = 1;
-				break;
-			}
-			if (by_precision && o.polar_gs) HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), st));
-			if (o.polar_gs) { // in-place sweep in atom order; old_mu is kept only when rrms / precision need it (:3503-3507)
-				double *mu = c->d_mu[c->mu_cur], *mu_old = c->d_mu[1 - c->mu_cur];
-				if (want_rrms) HIP_TRY(c, hipMemcpyAsync(mu_old, mu, 3 * (size_t)at.n_pad * sizeof(double), hipMemcpyDeviceToDevice, st));
-				{
-					ProfScope p(c, MPMC_K_DIPOLE_ITER);
-					launch_gs_sweep(st, at, c->box, o.polar_damp, c->d_e_static, mu, c->d_e_induced, c->d_part, c->d_tile_pairs, c->d_cls,
-					                shift_view(c), c->n_tile_pairs, c->d_gs_ul, c->d_gs_ul + 3 * (size_t)c->max_pad, c->d_gs_blocks);
-				}
-				if (want_rrms) {
-					ProfScope p(c, MPMC_K_REDUCE);
-					launch_gs_finish(st, at, mu_old, mu, want_rrms, c->d_rrms, allowed, c->d_flag);
-				}
-				if (by_precision) {
-					HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-					HIP_TRY(c, hipStreamSynchronize(st));
-					keep = (*c->h_flag != 0);
-				} else {
-					keep = (it != o.polar_max_iter);
-				}
-				continue;
-			}
-			enqueue_jacobi_iteration(c, at, jp, it, want_rrms, allowed, ctl, host_flag, (moments && it <= half) ? c->d_dk_ring + (size_t)it * dk_stride : nullptr);
-			if (by_precision) {
-				if (it % check_every == 0 || it + 1 >= kMaxIterationCount) { // the verdict of this batch
-					HIP_TRY(c, hipGetLastError());
-					// spin on the pinned flag until iteration `it` is closed (or an earlier one converged); a stream synchronisation costs
-					// ~15 us, this ~2.  Past a generous budget fall back to the blocking read (correct either way).
-					volatile const int *hf = host_flag;
-					const bool seen = poll_posted(c, [&] { return hf[0] >= it || hf[1] != 0; }, std::chrono::microseconds(50000));
-					if (seen) {
-						done_at = hf[1];
-					} else {
-						c->kept.n_stream_syncs++;
-						HIP_TRY(c, hipMemcpyAsync(c->h_flag, ctl + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-						HIP_TRY(c, hipStreamSynchronize(st));
-						done_at = *c->h_flag;
-					}
-					keep = (done_at == 0);
-				}
-			} else {
-				keep = (it != last_it);
-			}
-		}
-		if (done_at > 0) { // the iterations enqueued behind the converged one did nothing: the result is where iteration done_at left it
-			it = done_at;
-			c->mu_cur = (mu_start + done_at) & 1;
-		}
-		c->iters = lazy ? o.polar_max_iter : it; // (what the solve comes to once its dipoles are asked for)
-		c->polar_pending = lazy ? mpmc_ctx::PEND_OPEN : mpmc_ctx::PEND_NONE;
-		c->pend_done = it, c->pend_target = o.polar_max_iter;
-		if (moments) {
-			ProfScope p(c, MPMC_K_REDUCE);
-			if (reduce_in_tail)
-				launch_polar_moments_and_pairs(st, at, c->d_dk_ring, c->d_e_static, o.polar_max_iter, c->d_block_part, c->d_block_cnt, c->n_tile_pairs, c->d_scal,
-				                               c->d_cnt);
-			else launch_polar_moments(st, at, c->d_dk_ring, c->d_e_static, o.polar_max_iter, c->d_scal);
-		} else {
-			ProfScope p(c, MPMC_K_REDUCE);
-			if (reduce_in_tail)
-				launch_polar_energy_and_pairs(st, at, c->d_mu[c->mu_cur], c->d_e_static, want_rrms ? c->d_rrms : nullptr, c->d_block_part, c->d_block_cnt,
-				                              c->n_tile_pairs, c->d_scal, c->d_cnt);
-			else launch_polar_energy(st, at, c->d_mu[c->mu_cur], c->d_e_static, want_rrms ? c->d_rrms : nullptr, c->d_scal);
-		}
-		// `polar_palmo` (:3517-3519, palmo_contraction :3602-3627): one more contraction with the final dipoles.  Under Jacobi the reference
-		// contracts the dipoles the last iteration read (mu is overwritten with new_mu only afterwards, :3526-3536), so it subtracts from the
-		// induced field that very field: zero to the bit, and nothing runs here.  Under Gauss-Seidel sweeps the dipoles are the swept ones:
-		// F = -(A_off mu) through the matrix-free Jacobi contraction (Gauss-Seidel contexts store nothing), against the induced field the
-		// last sweep used.  A failed iteration leaves the correction at 0 (:3483-3488).
-		if (c->kept.palmo_enabled && o.polar_gs && !c->failed) {
-			double *mu = c->d_mu[c->mu_cur];
-			{
-				ProfScope p(c, MPMC_K_DIPOLE_ITER);
-				launch_dipole_iter_hybrid(st, at, c->box, mu, c->d_tile_pairs, c->d_cls, shift_view(c),
-				                          c->n_tile_pairs, nullptr, c->d_part, o.polar_damp, nullptr);
-			}
-			ProfScope p(c, MPMC_K_REDUCE);
-			// (the slots summed by the update kernel: d_palmo_f = F; its new dipoles go to the spare vector and are dropped, rrms untouched)
-			launch_dipole_update(st, at, c->d_e_static, c->d_part, c->n_tiles, mu, c->d_mu[1 - c->mu_cur], c->d_palmo_f, 0, c->d_rrms, 0.0, nullptr, nullptr, 1);
-			launch_palmo_reduce(st, at, mu, c->d_palmo_f, c->d_e_induced, c->d_palmo_change, c->d_scal);
-			c->palmo_ran = true;
-		}
-		c->have_polar = true;
-	}
-	// ---- Axilrod-Teller, System::axilrod_teller (:129-136): into its slot of the scalar block, in front of the post below ----------------
-	if (mask & RUN_THREE_BODY) {
-		ProfScope p(c, MPMC_K_THREE_BODY);
-		launch_three_body(st, at, c->d_tb_au, c->box, kThreeBodyScale, c->d_tb_part, c->d_scal + S_THREE_BODY);
-	}
-	// ---- disp-expansion, System::disp_expansion (:121-122, 1939-2018): pair sum and the cached corrections into their three slots ----------
-	if (mask & RUN_DISP) {
-		ProfScope p(c, MPMC_K_PAIR);
-		launch_disp_expansion(st, at, c->d_de_co, c->d_de_t10, c->d_tile_pairs, c->n_tile_pairs, c->box, disp_params(c), c->de_lrc[0], c->de_lrc[1],
-		                      c->d_de_part, c->d_scal + S_DISP);
-	}
-	// ---- rd_crystal, System::lj (:916-963): the lattice sum and its image-term count into their two slots ---------------------------------
-	if (mask & RUN_CRYSTAL) {
-		ProfScope p(c, MPMC_K_PAIR);
-		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL,
-		               c->d_scal + S_CRYSTAL_TERMS);
-	}
-	HIP_TRY(c, hipGetLastError());
-	// results to the pinned block by a kernel of ours (a blit and a stream synchronisation cost more than the whole reciprocal space of a
-	// small box): copy, zero the device block for the next evaluation, launch number last
-	c->single_seq += 1.0;
-	launch_post_results(st, c->d_scal, c->h_scal, c->single_seq);
-	HIP_TRY(c, hipGetLastError());
-	c->scal_clean = true;
-	// short evaluations are polled for (a few us against ~10-15 for the synchronisation); long ones, and profiled ones (the event
-	// harvest needs an idle stream), are waited for the ordinary way
-	// (round 4: long evaluations are polled for as well, with a budget of a few of their own durations -- one evaluation at a time the
-	// posted launch number is seen ~10 us before hipStreamSynchronize returns; an ensemble's first wait outlasts the budget and synchronises)
-	c->spin_on_post = c->ev_used.empty() && (c->kept.tune.poll_long || c->n_tile_pairs <= kOneStreamMaxPairs);
-	c->poll_budget_us = (c->n_tile_pairs <= kOneStreamMaxPairs) ? 1000 : 4000;
-	c->pending = true;
+	if (plan.single) return stage_single_launch(c, plan, at, rcp);
+	for (Stage stage : kStages)
+		if ((rc = stage(c, plan, at, rcp)) != MPMC_OK) return rc;
 	return MPMC_OK;
 }
 
@@ -799,20 +942,7 @@ extern "C" int mpmc_debug_time_pair(mpmc_ctx *c, int reps, double *ms_per_launch
 	const FusedParams &fp = c->last_fp;
 	const bool compact = c->solver_used == MPMC_SOLVER_COMPACT && fp.do_thole;
 	bool timed = false; // (the warm-up launches run the plain grid; the timed ones carry the replicas of "panel_replicas", if any)
-	auto launch = [&] {
-		if (c->last_pair_was_sweep) {
-			launch_pair_sweep(c->stream, at, c->box, fp, c->n_molecules != c->n, c->d_sweep_blocks, c->n_sweep_blocks, c->d_cls,
-			                  shift_view(c), c->d_erf_tab, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr, sweep_split_mode(c), sweep_split_tail(c), c->kept.tune.fast_geometry,
-			                  c->two_streams ? c->kept.tune.sweep_lds_pad : 0, timed ? c->debug_panel_replicas : 1);
-			if (c->n_generic > 0)
-				launch_pair_fused(c->stream, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_generic, c->d_block_part, c->d_block_cnt, c->d_part,
-				                  compact ? c->d_ab : nullptr, c->d_generic_list);
-		} else {
-			launch_pair_fused(c->stream, at, c->box, fp, c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_block_part, c->d_block_cnt, c->d_part,
-			                  compact ? c->d_ab : nullptr);
-		}
-	};
+	auto launch = [&] { launch_pair_pass(c, at, fp, compact, c->two_streams ? c->kept.tune.sweep_lds_pad : 0, timed ? c->debug_panel_replicas : 1); };
 	hipEvent_t e0, e1;
 	HIP_TRY(c, hipEventCreate(&e0));
 	HIP_TRY(c, hipEventCreate(&e1));

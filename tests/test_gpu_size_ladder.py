@@ -96,7 +96,7 @@ def options(*base, **kw):
     return o
 
 
-# four iterations: the AUTO solver takes the compact store from four fixed iterations on (resolve_solver); the 8 000-atom rung runs two,
+# four iterations: the AUTO solver takes the compact store from four fixed iterations on (choose_solver); the 8 000-atom rung runs two,
 # with the solver named
 POLAR = dict(polarization=1, polar_iterative=1, polar_ewald=1, polar_damp=2.1304, polar_max_iter=4)
 # (rung, case, cell, options of the nt-tile box, options of the nt + 1-tile box); "solver" reaches the library only (the oracle ignores it)
@@ -185,7 +185,7 @@ DEVIATIONS = {}
 
 
 def compact_store_expected(opts):
-    """resolve_solver (evaluate.cpp): Gauss-Seidel and matrix_free recompute the tensors; AUTO stores them for a precision-terminated
+    """choose_solver (evaluate.cpp): Gauss-Seidel and matrix_free recompute the tensors; AUTO stores them for a precision-terminated
     solve or more than three fixed iterations (the store fits the default budget at every rung)"""
     solver = opts.get("solver", "auto")
     if opts["polar_gs"] or solver == "matrix_free":

@@ -6,7 +6,7 @@ out=${OUT_DIR:-$(mktemp -d)}; mkdir -p $out  # the JSON lines of every run
 for rep in 1 2 3; do
 for spec in "$@"; do
   label="${spec%%=*}"; lib="${spec#*=}"
-  MPMC_ENERGY_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-baseline none > $out/abl_${label}_${rep}.json 2>$out/abl_${label}_${rep}.err || { echo "rep${rep} ${label}: bench failed"; tail -3 $out/abl_${label}_${rep}.err; continue; }
+  MPMC_ENERGY_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-baseline none > $out/abl_${label}_${rep}.json 2>$out/abl_${label}_${rep}.err || { echo "rep${rep} ${label}: bench failed"; tail -3 $out/abl_${label}_${rep}.err; exit 1; }  # (nothing more on a device that a run has just failed on)
   python - <<PY
 import json
 d=json.load(open("$out/abl_${label}_${rep}.json"))
