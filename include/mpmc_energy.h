@@ -369,6 +369,49 @@ int mpmc_set_polar_wolf(mpmc_ctx *ctx, int enabled, double polar_wolf_alpha);
 int mpmc_set_polar_palmo(mpmc_ctx *ctx, int enabled);
 int mpmc_polar_palmo_info(mpmc_ctx *ctx, double *energy_correction, double *ef_induced_change /*[n][3], may be NULL*/);
 
+/* ---- `polar_ewald_full`: the induced field as an Ewald sum too, System::ewald_full (src/System.Energy.cpp:2785-2830, 2944-3143) -----------
+ * The one fully periodic dipole solve of the reference, which System::polar() tries before every other.  With polarization on and
+ * rd_only off the setting replaces the whole solve; mpmc_polar and mpmc_thole_field follow it.  a = polar_ewald_alpha (unset: 3.5 /
+ * cutoff), l = polar_damp, V the cell volume, R the cutoff of the box.
+ *   static field  E0 = recip_term + real_term: the field of `polar_ewald on`, whatever polar_ewald says.  polar_ewald, polar_iterative,
+ *                 polar_gs, polar_gamma, polar_rrms, mpmc_set_polar_wolf and mpmc_options.solver change nothing under the term.
+ *   start         mu = alpha E0 (no polar_gamma)
+ *   one pass      E_ind = real + reciprocal + correction, then mu = alpha (E0 + E_ind):
+ *     real        every unordered pair with alpha_i != 0 and alpha_j != 0 that is not dropped by rimg > R (r = R is kept; frozen-frozen and
+ *                 same-molecule pairs contribute), d the minimum-image vector, r = rimg, e = erfc(a r), g = exp(-a^2 r^2), t = l r:
+ *                   s1 = e + 2 a r g / sqrt(pi) - (1 + t + t^2/2) exp(-t)
+ *                   s2 = e + 2 a r g / sqrt(pi) + 4/3 a^3 r^3 g / sqrt(pi) - (1 + t + t^2/2 + t^3/6) exp(-t)
+ *                   T = 3 d d^T s2 / r^5 - I s1 / r^3;   E_ind,i += T mu_j,  E_ind,j += T mu_i
+ *     reciprocal  over the hemisphere of k vectors of recip_term: Pc = sum_j (k . mu_j) cos(k . r_j), Ps likewise with sin, over all atoms;
+ *                 E_ind,i[p] += w_p (-sin(k . r_i) Ps - cos(k . r_i) Pc) for every atom, non-polarizable ones included.  The reference
+ *                 overwrites its weight in a loop over p (:3015-3016), so w_p = (8 pi / V) exp(-k^2 / 4 a^2) / k^2 * k_z for all three
+ *                 components: that is what it computes and what this library returns by default.  MPMC_PEF_VECTOR_KWEIGHT puts k_p in the
+ *                 place of k_z, the weight the formula intends (ion216_polar: -785.44 K instead of -808.05 K).
+ *     correction  E_ind,i += -4 pi / (3 V) sum_j mu_j + 4 a^3 / (3 sqrt(pi)) mu_i for every atom
+ *   pass count    polar_precision == 0: polar_max_iter + 1 passes; otherwise until no component of the change of mu has a square above
+ *                 (polar_precision * DEBYE2SKA)^2; after 128 passes the solve stops with iterator_failed = 1 and keeps its dipoles.
+ *   results       polarization_energy = -1/2 sum mu . E0; polar_iterations and dipole_rrms are 0 (the reference never writes them on this
+ *                 path); mpmc_get_dipoles returns the dipoles after the last update and the induced field of the last pass, which is
+ *                 non-zero on non-polarizable atoms.
+ * The setting has the lifetime of mpmc_set_polar_wolf's; enabled = 0 restores the context's behaviour to the bit.  Unknown flag bits are
+ * refused with MPMC_ERR_INVALID_SETTING.  MPMC_FLAG_POLAR_EWALD_FULL in unsupported_flags is still refused: this call alone switches
+ * the term on.  An evaluation with mpmc_set_polar_palmo on as well fails with MPMC_ERR_UNSUPPORTED (ewald_palmo_contraction, :3243-3267,
+ * is not part of the library).  Every evaluation runs all its passes at once: the energy-from-moments form and mpmc_set_dipoles_on_demand
+ * do not apply, and trial moves evaluate the trial configuration in full.  The pair factors (-s1 / r^3, 3 s2 / r^5) are stored once per
+ * evaluation, 16 bytes per pair of the 64 x 64 tile-pair table, and streamed once per pass; a store or phase table that does not fit
+ * the free device memory fails the evaluation with MPMC_ERR_MEMORY and a text that names the size.  Time: the store and the phases in
+ * MPMC_K_TENSOR, the real-space contraction and the dipole structure factors in MPMC_K_DIPOLE_ITER, the update in MPMC_K_REDUCE.
+ * mpmc_polar_ewald_full_info: of the last evaluation with the term on. */
+#define MPMC_PEF_VECTOR_KWEIGHT 1 /* w_p uses k_p (the intended physics) instead of the reference's k_z for every p */
+int mpmc_set_polar_ewald_full(mpmc_ctx *ctx, int enabled, int flags);
+typedef struct mpmc_ewald_full_info {
+	int32_t passes;       /* passes run                                                     */
+	int32_t n_k;          /* k vectors of the reciprocal-space sum                          */
+	int64_t n_real_pairs; /* pairs that pass the real-space predicate                       */
+	int64_t store_bytes;  /* device bytes of the pair-factor store                          */
+} mpmc_ewald_full_info;
+int mpmc_polar_ewald_full_info(mpmc_ctx *ctx, mpmc_ewald_full_info *out);
+
 /* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL.  After an on-demand evaluation
  * (mpmc_set_dipoles_on_demand above) the remaining Jacobi iterations run here first; MPMC_ERR_ARG when they no longer can. */
 int mpmc_get_dipoles(mpmc_ctx *ctx, double *mu, double *ef_static, double *ef_induced /* each [n][3] */);

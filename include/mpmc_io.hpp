@@ -172,6 +172,10 @@ inline std::string read_input(const std::string &path, System &s) {
 			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_RD_CRYSTAL;
 			s.rd_crystal = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
 		}
+		else if (k == "polar_ewald_full") { // (likewise: the facade clears the flag when it hands the term to mpmc_set_polar_ewald_full)
+			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_POLAR_EWALD_FULL;
+			s.polar_ewald_full = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
+		}
 		else if (k == "rd_crystal_order") { need(1); s.rd_crystal_order = (int)dval(1); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }

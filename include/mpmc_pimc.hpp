@@ -155,6 +155,7 @@ public:
 			if (uses_three_body(*s, 0)) throw 4004;     // unsupported_setting: the three-body term is not part of this driver (yet)
 			if (uses_disp_expansion(*s, 0)) throw 4004; // unsupported_setting: nor is the disp-expansion term
 			if (uses_polar_wolf_or_palmo(*s, 0)) throw 4004; // unsupported_setting: nor are polar_wolf / polar_palmo
+			if (uses_polar_ewald_full(*s, 0)) throw 4004;    // unsupported_setting: nor is polar_ewald_full
 			s->temperature = cfg.temperature;
 		}
 		pi.systems = systems;

@@ -70,6 +70,11 @@ template <class T>
 auto uses_polar_wolf_or_palmo(const T &s, int) -> decltype(bool(s.polar_wolf || s.polar_palmo)) { return s.polar_wolf || s.polar_palmo; }
 template <class T>
 bool uses_polar_wolf_or_palmo(const T &, long) { return false; }
+// the same for the fully periodic dipole solve
+template <class T>
+auto uses_polar_ewald_full(const T &s, int) -> decltype(bool(s.polar_ewald_full)) { return s.polar_ewald_full; }
+template <class T>
+bool uses_polar_ewald_full(const T &, long) { return false; }
 
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
@@ -99,6 +104,8 @@ public:
 	int dipoles_on_demand = 0; // energy() / energy_async() stop at the Jacobi iterations the energy needs; fetch_dipoles() runs the rest (mpmc_set_dipoles_on_demand)
 	int polar_wolf = 0, polar_palmo = 0; // Wolf static field (mpmc_set_polar_wolf), Palmo-Krimm correction (mpmc_set_polar_palmo), src/System.h:685-694
 	int rd_crystal = 0, rd_crystal_order = 0; // lattice-summed Lennard-Jones (mpmc_set_rd_crystal), src/System.h:632-633
+	int polar_ewald_full = 0;            // Ewald-summed induced field (mpmc_set_polar_ewald_full), src/System.h: polar_ewald_full
+	int polar_ewald_full_vector_kweight = 0; // MPMC_PEF_VECTOR_KWEIGHT: the intended reciprocal-space weight (no keyword: the reference has none)
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
@@ -296,6 +303,7 @@ private:
 	int polar_wolf_on_ = 0, polar_palmo_on_ = 0; // what the context's Wolf-field / Palmo settings are (sync_state)
 	int on_demand_on_ = 0;                       // ... and its dipoles-on-demand switch
 	int rd_crystal_on_ = 0, rd_crystal_order_ = 0; // ... and its rd_crystal setting
+	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
@@ -319,6 +327,7 @@ private:
 			polar_wolf_on_ = polar_palmo_on_ = on_demand_on_ = 0; // (a new context starts with all of them off)
 			polar_wolf_alpha_ = 0;
 			rd_crystal_on_ = rd_crystal_order_ = 0;
+			ewald_full_on_ = ewald_full_flags_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -348,7 +357,8 @@ private:
 		o.polar_ewald_alpha = polar_ewald_alpha;
 		// (polar_iterative off is the library's direct dipole solve: no flag; `rd_crystal on` goes to mpmc_set_rd_crystal below: the reader's
 		// flag for the keyword is cleared here, a caller's flag without the field is still refused)
-		o.unsupported_flags = rd_crystal ? (unsupported_flags & ~(uint64_t)MPMC_FLAG_RD_CRYSTAL) : unsupported_flags;
+		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full)
+		o.unsupported_flags = unsupported_flags & ~(uint64_t)((rd_crystal ? MPMC_FLAG_RD_CRYSTAL : 0) | (polar_ewald_full ? MPMC_FLAG_POLAR_EWALD_FULL : 0));
 		check(mpmc_set_options(ctx_, &o), "mpmc_set_options");
 		if (atoms_dirty_) {
 			std::vector<double> pos(3 * (size_t)n), q(n), al(n), ep(n), sg(n), ms(n);
@@ -398,6 +408,12 @@ private:
 			check(mpmc_set_rd_crystal(ctx_, rd_crystal ? 1 : 0, rd_crystal_order), "mpmc_set_rd_crystal");
 			rd_crystal_on_ = rd_crystal ? 1 : 0;
 			rd_crystal_order_ = rd_crystal_order;
+		}
+		const int pef_flags = polar_ewald_full_vector_kweight ? MPMC_PEF_VECTOR_KWEIGHT : 0;
+		if ((polar_ewald_full != 0) != (ewald_full_on_ != 0) || (polar_ewald_full && pef_flags != ewald_full_flags_)) {
+			check(mpmc_set_polar_ewald_full(ctx_, polar_ewald_full ? 1 : 0, pef_flags), "mpmc_set_polar_ewald_full");
+			ewald_full_on_ = polar_ewald_full ? 1 : 0;
+			ewald_full_flags_ = pef_flags;
 		}
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");

@@ -292,7 +292,9 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 	if (c->opts_set && std::memcmp(&c->opts, o, sizeof(mpmc_options)) == 0) return MPMC_OK; // unchanged: keep the accepted configuration's totals
 	{ // Gauss-Seidel sweeps run in the reference's atom order (System.Energy.cpp:3569): whenever "this evaluation sweeps in atom order"
 	  // changes -- through polar_gs, polarization or rd_only, or on the first options after an upload under the defaults -- re-upload
-		auto atom_order = [](const mpmc_options &q) { return q.polar_gs && q.polarization && !q.rd_only; };
+		// (not under `polar_ewald_full`, where polar_gs changes nothing: the spatial order stays)
+		const bool pef = c->kept.pef_enabled;
+		auto atom_order = [pef](const mpmc_options &q) { return q.polar_gs && q.polarization && !q.rd_only && !pef; };
 		const bool was = c->opts_set && atom_order(c->opts);
 		if (was != (bool)atom_order(*o)) c->atoms_dirty = c->atoms_dirty_order = true;
 	}
@@ -317,7 +319,7 @@ static void compute_spatial_order(mpmc_ctx *c) {
 	c->slot_of.resize(n);
 	for (int i = 0; i < n; i++) c->perm[i] = i;
 	bool enable = c->box_set && n > 2 * kTile;
-	if (c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only) enable = false; // the sweep order IS the atom order (:3569)
+	if (c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only && !c->kept.pef_enabled) enable = false; // the sweep order IS the atom order (:3569)
 	if (c->kept.tune.no_sort) enable = false;
 	if (enable) {
 		// fractional coordinates counted from the smallest one in each dimension: with all atoms inside one period (the usual case) the
@@ -721,6 +723,30 @@ extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_palmo: an evaluation or a trial move is open");
 	if ((enabled != 0) != c->kept.palmo_enabled) c->cache_valid = false; // (the accepted totals carry the correction)
 	c->kept.palmo_enabled = enabled != 0;
+	return MPMC_OK;
+}
+
+// ---- `polar_ewald_full` (System::ewald_full :2785-2830) ------------------------------------------------------------------------------------
+extern "C" int mpmc_set_polar_ewald_full(mpmc_ctx *c, int enabled, int flags) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_ewald_full: an evaluation or a trial move is open");
+	if (flags & ~MPMC_PEF_VECTOR_KWEIGHT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_ewald_full: unknown flag bits");
+	const bool on = enabled != 0;
+	if (on != c->kept.pef_enabled || (on && flags != c->kept.pef_flags)) {
+		c->cache_valid = false; // (the accepted totals, the resident real-space field and an open on-demand solve belong to the other solve)
+		c->e_real_valid = false;
+		drop_pending_dipoles(c);
+		// (Gauss-Seidel sweeps run in atom order, the term keeps the spatial order whatever polar_gs says: mpmc_set_options has the rule)
+		if (on != c->kept.pef_enabled && c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only) c->atoms_dirty = c->atoms_dirty_order = true;
+	}
+	c->kept.pef_enabled = on;
+	c->kept.pef_flags = on ? flags : 0;
+	return MPMC_OK;
+}
+extern "C" int mpmc_polar_ewald_full_info(mpmc_ctx *c, mpmc_ewald_full_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_ewald_full_info: an evaluation is in flight");
+	*out = c->pef_info;
 	return MPMC_OK;
 }
 
@@ -1154,6 +1180,7 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 //   side_stream -1 | 0 | 1     pair_kernel 0 | 1 | 2     pair_waves 0 | 1 | 4     panels     uniform_images     tile_classes
 //   single_launch     recip_table     spatial_sort     order_carry     polar_delta     inline_move     trace_panel     tensor_budget_mb N
 //   direct_budget_mb N (-1: free device memory)     dipoles_on_demand (0: every evaluation runs all its Jacobi iterations at once)
+//   pef_phase_table (0: `polar_ewald_full` recomputes its phases in every pass)
 extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) {
 	if (!key) return MPMC_ERR_ARG;
 	std::unique_lock<std::mutex> tuning_lk(g_tuning_mu, std::defer_lock);
@@ -1215,6 +1242,7 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 	else if (k == "inline_move") t.no_inline_move = !on;
 	else if (k == "trace_panel") t.trace_panel = on;
 	else if (k == "dipoles_on_demand") t.dipoles_on_demand = on;
+	else if (k == "pef_phase_table") t.pef_phase_table = on;
 	else if (k == "virtual_device") {
 		if (!c || v < -1 || v > 63) return MPMC_ERR_ARG;
 		t.virtual_device = v;

@@ -112,6 +112,7 @@ struct mpmc_tuning {
 	int fail_next_wait = 0;      // "fail_next_wait" = 1: the next wait of this context fails as if the runtime had refused it (test of the recovery path)
 	bool trace_panel = false;    // "trace_panel" = 1: per-workgroup time stamps of the panel kernel (tools/panel_trace.py)
 	bool dipoles_on_demand = true; // "dipoles_on_demand" = 0: every evaluation runs all its Jacobi iterations at once (A/B against the on-demand path-integral loop)
+	bool pef_phase_table = true;   // "pef_phase_table" = 0: `polar_ewald_full` recomputes (cos, sin)(k . r) in every pass instead of reading its table (A/B: profiles/ewald_full.txt)
 	long long tensor_budget_mb = 4096; // "tensor_budget_mb": AUTO solver: largest tensor store it will allocate
 	long long direct_budget_mb = -1;   // "direct_budget_mb": direct dipole solve: largest factor it will allocate (-1: what the device has free)
 };
@@ -134,6 +135,8 @@ struct mpmc_kept {
 	bool palmo_enabled = false;             // `polar_palmo` (mpmc_set_polar_palmo), likewise
 	bool rc_enabled = false;                // `rd_crystal` (mpmc_set_rd_crystal), kept across mpmc_set_box and mpmc_set_options too
 	int rc_order = 0;                       // rd_crystal_order
+	bool pef_enabled = false;               // `polar_ewald_full` (mpmc_set_polar_ewald_full), likewise
+	int pef_flags = 0;                      // MPMC_PEF_*
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 };
 
@@ -365,6 +368,16 @@ struct mpmc_ctx {
 	double palmo_correction = 0.0;   // of the last evaluation with a dipole solve (wait_and_fill)
 	DevBuf<double> d_palmo_f, d_palmo_change; // [max_pad][3]: -(A_off mu) of the final dipoles; ef_induced_change
 
+	// `polar_ewald_full` (mpmc_set_polar_ewald_full, kernels_ewald_full.hip; switched on: kept.pef_enabled, kept.pef_flags)
+	DevBuf<double2> d_pef_store;     // [n_tile_pairs][64 * 64] (-s1 / r^3, 3 s2 / r^5), filled once per evaluation
+	DevBuf<int> d_pef_cnt;           // [n_tile_pairs] pairs inside the real-space predicate
+	DevBuf<double2> d_pef_phases;    // [K][n_pad] (cos, sin)(k . r_i)
+	DevBuf<double> d_pef_psum;       // [2 K + 3] Pc, Ps per k; sum of the dipoles
+	DevBuf<long long> d_pef_pairs;   // [1] sum of d_pef_cnt
+	PinnedBuf<long long> h_pef_pairs;
+	bool pef_ran = false;            // the pending / last evaluation solved the dipoles with the term
+	mpmc_ewald_full_info pef_info{}; // of the last such evaluation (n_real_pairs filled by wait_and_fill)
+
 	std::vector<EvPair> ev_free, ev_used; // profiling (kept.prof): event pairs to reuse / recorded and not yet harvested into kept.tim
 
 	int64_t bytes_total = 0; // device memory held by this context's DevBuf members (mpmc_memory_usage)
@@ -551,6 +564,7 @@ unsigned full_mask(const mpmc_ctx *c);           // what double System::energy()
 // Gauss-Seidel sweeps (the only place where `polar_palmo` acts) or the direct solve.
 inline bool polar_moments_apply(const mpmc_ctx *c) {
 	const mpmc_options &o = c->opts;
+	if (c->kept.pef_enabled) return false; // (ewald_full is not the symmetric Jacobi iteration; the setting acts only where the line below holds anyway)
 	return o.polarization && !o.rd_only && o.polar_iterative && o.polar_max_iter >= 1 && o.polar_max_iter <= kMomentsMaxIter && o.polar_gamma == 1.0 && o.polar_precision == 0.0 && !o.polar_rrms &&
 	       !o.polar_gs; // (`polar_palmo` acts under Gauss-Seidel sweeps only: under Jacobi its correction is zero and nothing runs)
 }
@@ -559,13 +573,19 @@ inline int reserve_dk_ring(mpmc_ctx *c) { return c->d_dk_ring.reserve(c, (size_t
 // Every reader of the dipoles, the induced field or anything else the remaining iterations write calls this first: runs what an on-demand
 // evaluation left undone and waits for it (nothing to do otherwise); MPMC_ERR_ARG when the open solve's inputs are gone (evaluate.cpp)
 int finish_pending_dipoles(mpmc_ctx *c);
+// `polar_ewald_full` acts with polarization on and rd_only off, and then replaces the whole dipole solve: System::polar() tries it first (:2558)
+inline bool ewald_full_on(const mpmc_ctx *c) { return c->kept.pef_enabled && c->opts.polarization && !c->opts.rd_only; }
+// the static field is the Ewald one: `polar_ewald on`, or ewald_full (recip_term + real_term whatever polar_ewald says, :2790-2793)
+inline bool field_is_ewald(const mpmc_ctx *c) { return c->opts.polar_ewald || ewald_full_on(c); }
 // whoever is about to overwrite positions, cell, options, tensor store or dipole vectors: the open solve can no longer be finished
 inline void drop_pending_dipoles(mpmc_ctx *c) {
 	if (c->polar_pending == mpmc_ctx::PEND_OPEN) c->polar_pending = mpmc_ctx::PEND_DROPPED;
 }
-inline bool direct_solve(const mpmc_ctx *c) { return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative; } // `polar_iterative off`
+inline bool direct_solve(const mpmc_ctx *c) { // `polar_iterative off` (ewald_full comes first, :2558-2563)
+	return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative && !ewald_full_on(c);
+}
 // `polar_wolf` replaces the static field whenever polar_ewald is off (thole_field :3289-3294: polar_ewald wins)
-inline bool wolf_field_on(const mpmc_ctx *c) { return c->kept.pw_enabled && c->opts.polarization && !c->opts.rd_only && !c->opts.polar_ewald; }
+inline bool wolf_field_on(const mpmc_ctx *c) { return c->kept.pw_enabled && c->opts.polarization && !c->opts.rd_only && !field_is_ewald(c); }
 void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Feynman-Hibbs fields of the pair parameters (evaluate.cpp)
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);

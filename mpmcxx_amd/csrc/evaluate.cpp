@@ -236,11 +236,13 @@ struct EvalPlan {
 	int want_rrms = 0, half = 0, last_it = 0, check_every = kCheckEvery;
 	double allowed = 0.0;
 	bool palmo = false;
+	bool pef = false;         // `polar_ewald_full`: the solve is stage_ewald_full_solve's (by_precision and allowed as for the iterative solves)
 };
 
 static inline size_t store_elements(const mpmc_ctx *c) { return (size_t)c->n_tile_pairs * (kTile * kTile); } // double2 elements, 16 B each
 // how the dipole iteration runs (room for what it stores: reserve_solver_store)
 static int choose_solver(const mpmc_ctx *c) {
+	if (ewald_full_on(c)) return MPMC_SOLVER_MATRIX_FREE; // `polar_ewald_full` keeps a store of its own (stage_ewald_full_solve): the sweep stores nothing
 	if (direct_solve(c)) return MPMC_SOLVER_MATRIX_FREE; // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
 	int want = c->opts.solver;
 	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
@@ -277,7 +279,7 @@ static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand
 	if (p.single) return p;
 
 	// ---- reciprocal space + O(N) atom terms on the side stream, next to the pair sweep ------------------------------
-	p.need_sf = (mask & RUN_RECIP) || ((mask & RUN_FIELD) && o.polar_ewald);
+	p.need_sf = (mask & RUN_RECIP) || ((mask & RUN_FIELD) && field_is_ewald(c));
 	// intramolecular charge-to-screen term of coulombic_real: position dependent but independent of the pair sweep; identically zero
 	// when every molecule is a single atom
 	p.need_intra = (mask & RUN_PAIR) && (mask & RUN_PAIR_ES) && !(o.wolf && (mask & RUN_WOLF)) && (c->n_molecules != c->n);
@@ -307,7 +309,7 @@ static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand
 		fp.rd_lrc = o.rd_lrc;
 		fp.do_es = ((mask & RUN_PAIR_ES) || (mask & RUN_FIELD)) ? 1 : 0;
 		// (`polar_wolf`: the field is k_wolf_field's, below; the sweep keeps its energies and the tensor store)
-		fp.do_field = ((mask & RUN_FIELD) && !wolf_field_on(c)) ? (o.polar_ewald ? 1 : 2) : 0;
+		fp.do_field = ((mask & RUN_FIELD) && !wolf_field_on(c)) ? (field_is_ewald(c) ? 1 : 2) : 0;
 		ext_params(c, fp, (o.wolf && (mask & RUN_WOLF)) != 0);
 		fp.thole_far_x = kTholeFarX;
 		fp.pair_waves = t.pair_waves ? t.pair_waves : (c->n_tile_pairs <= kPairSplitMax ? 4 : 1);
@@ -330,7 +332,11 @@ static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand
 	plan_solver(c, p, (mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) ? choose_solver(c) : c->solver_used);
 	p.solve = (mask & RUN_SOLVE) != 0;
 	p.direct = p.solve && direct_solve(c);
-	if (p.direct) {
+	p.pef = p.solve && ewald_full_on(c);
+	if (p.pef) { // (no rrms, no moments, never lazy: every entry runs all its passes)
+		p.by_precision = (o.polar_precision != 0.0);
+		p.allowed = p.by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
+	} else if (p.direct) {
 		for (int i = 0; i < c->n; i++) p.n_pol += (c->h_alpha[i] != 0.0) ? 1 : 0;
 		p.chol_np = chol_padded(p.n_pol);
 	} else if (p.solve) {
@@ -416,6 +422,32 @@ static int reserve_direct_solve(mpmc_ctx *c, const EvalPlan &p) {
 	// (room for every slot of the context: the number of polarizable atoms changes with the atom list and can then never outgrow it)
 	return c->d_chol_list.reserve(c, (size_t)p.n_pol, (size_t)c->max_pad);
 }
+// `polar_ewald_full`: the pair-factor store and the phase table must fit what the device has free; then the small tables
+static int reserve_ewald_full(mpmc_ctx *c) {
+	const size_t store = store_elements(c), phases = c->kept.tune.pef_phase_table ? (size_t)c->K * (size_t)c->max_pad : 0;
+	const size_t grow = (store > c->d_pef_store.cap ? store * sizeof(double2) : 0) + (phases > c->d_pef_phases.cap ? phases * sizeof(double2) : 0);
+	int rc;
+	if (grow) { // size guard
+		size_t free_b = 0, total_b = 0;
+		HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+		const size_t avail = free_b + (store > c->d_pef_store.cap ? c->d_pef_store.cap * sizeof(double2) : 0) +
+		                     (phases > c->d_pef_phases.cap ? c->d_pef_phases.cap * sizeof(double2) : 0);
+		if (grow > avail) {
+			char buf[256];
+			std::snprintf(buf, sizeof buf, "polar_ewald_full: the pair-factor store of %d tile pairs and the phase table of %d k vectors need %.1f MB, %.1f MB are available",
+			              c->n_tile_pairs, c->K, (double)grow / 1048576.0, (double)avail / 1048576.0);
+			return fail(c, MPMC_ERR_MEMORY, buf);
+		}
+	}
+	if (c->d_pef_store.reserve(c, store) != MPMC_OK || c->d_pef_phases.reserve(c, phases) != MPMC_OK) {
+		(void)hipGetLastError();
+		return fail(c, MPMC_ERR_MEMORY, "polar_ewald_full: cannot allocate the pair-factor store and the phase table (" + std::to_string(grow) + " bytes): " + c->err);
+	}
+	if ((rc = c->d_pef_cnt.reserve(c, (size_t)c->n_tile_pairs)) != MPMC_OK) return rc;
+	if ((rc = c->d_pef_psum.reserve(c, 2 * (size_t)c->K + 4)) != MPMC_OK) return rc;
+	if ((rc = c->d_pef_pairs.reserve(c, 1)) != MPMC_OK) return rc;
+	return c->h_pef_pairs.reserve(c, 1);
+}
 static int make_room(mpmc_ctx *c, EvalPlan &p) {
 	int rc;
 	if (p.mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) {
@@ -425,6 +457,7 @@ static int make_room(mpmc_ctx *c, EvalPlan &p) {
 	if (p.sf_part && (rc = c->d_sf_part.reserve(c, (size_t)c->n_tiles * (size_t)c->K)) != MPMC_OK) return rc;
 	if (p.use_panels && (rc = reserve_panels(c)) != MPMC_OK) return rc;
 	if (p.direct && (rc = reserve_direct_solve(c, p)) != MPMC_OK) return rc;
+	if (p.pef && (rc = reserve_ewald_full(c)) != MPMC_OK) return rc;
 	// the in-tile blocks of the Gauss-Seidel sweeps
 	if (p.gs && (rc = c->d_gs_blocks.reserve(c, gs_block_store_elements(c->n_tiles))) != MPMC_OK) return rc;
 	return MPMC_OK;
@@ -535,7 +568,7 @@ static void enqueue_side_work(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at
 		if (p.need_sf) launch_recip_sf(s2, at, c->box, rcp, o.ewald_kmax, c->d_sf_part);
 		if (p.mask & RUN_RECIP) launch_recip_energy(s2, rcp, c->box, c->d_scal); // (the LRC and self terms are cached: prepare())
 	}
-	if ((p.mask & RUN_FIELD) && o.polar_ewald) {
+	if ((p.mask & RUN_FIELD) && field_is_ewald(c)) {
 		ProfScope ps(c, MPMC_K_FIELD, s2);
 		launch_field_recip(s2, at, c->box, rcp, o.ewald_kmax, c->d_e_recip_part);
 	}
@@ -630,7 +663,8 @@ static int stage_static_field(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at
 	c->mu_cur = 0;
 	if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
 		launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
-	launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_part, c->n_tiles, o.polar_gamma, c->d_e_static,
+	// (`polar_ewald_full`: mu_0 = alpha E0 without polar_gamma, init_dipoles_ewald :2944-2956)
+	launch_field_finalize(st, at, c->box, field_is_ewald(c) ? 1 : 0, c->d_e_recip_part, c->d_part, c->n_tiles, ewald_full_on(c) ? 1.0 : o.polar_gamma, c->d_e_static,
 	                      c->d_mu[0], c->d_e_real, polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 	c->e_real_valid = (p.mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
 	return MPMC_OK;
@@ -681,7 +715,7 @@ static void close_solve(mpmc_ctx *c, const EvalPlan &p, int it) {
 
 // Gauss-Seidel sweeps: in place, in atom order; the host asks for the verdict of a precision-terminated solve after every sweep
 static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
-	if (!p.solve || p.direct || !p.gs) return MPMC_OK;
+	if (!p.solve || p.direct || p.pef || !p.gs) return MPMC_OK;
 	hipStream_t st = c->stream;
 	const mpmc_options &o = c->opts;
 	{ // the in-tile blocks of the sweeps: positions and polarizabilities only, once per evaluation
@@ -722,7 +756,7 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 }
 
 static int stage_jacobi_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
-	if (!p.solve || p.direct || p.gs) return MPMC_OK;
+	if (!p.solve || p.direct || p.pef || p.gs) return MPMC_OK;
 	hipStream_t st = c->stream;
 	const mpmc_options &o = c->opts;
 	const size_t dk_stride = 3 * (size_t)at.n_pad;
@@ -776,6 +810,65 @@ static int stage_jacobi_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at
 		c->mu_cur = (mu_start + done_at) & 1;
 	}
 	close_solve(c, p, it);
+	return MPMC_OK;
+}
+
+// `polar_ewald_full` (System::ewald_full :2785-2830), behind the static field: the pair-factor store and the phases once, then per pass the
+// real-space contraction, the dipole structure factors and the update.  A precision-terminated solve asks for the verdict after every
+// pass, as the Gauss-Seidel sweeps do.  Leaves the dipoles after the last update in d_mu[mu_cur] and the last pass's field in d_e_induced.
+static int stage_ewald_full_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &rcp) {
+	if (!p.pef) return MPMC_OK;
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	const double a = c->polar_ewald_alpha;
+	EwaldFullParams ep;
+	ep.vector_weight = (c->kept.pef_flags & MPMC_PEF_VECTOR_KWEIGHT) ? 1 : 0;
+	ep.recip_scale = 8.0 * kPi / c->box.volume;
+	ep.c_total = -4.0 * kPi / (3.0 * c->box.volume);
+	ep.c_self = 4.0 * a * a * a / (3.0 * std::sqrt(kPi));
+	ep.allowed_sqerr = p.allowed;
+	double2 *phases = c->kept.tune.pef_phase_table ? c->d_pef_phases.p : nullptr;
+	{
+		ProfScope ps(c, MPMC_K_TENSOR);
+		launch_pef_fill(st, at, c->box, a, o.polar_damp, c->d_tile_pairs, p.pair_pass ? c->d_cls.p : nullptr /*made by this evaluation's pair pass*/, c->n_tile_pairs,
+		                c->d_pef_store, c->d_pef_cnt, c->d_pef_pairs);
+		if (phases) launch_pef_phases(st, at, rcp.kvec, c->K, phases);
+	}
+	HIP_TRY(c, hipMemcpyAsync(c->h_pef_pairs, c->d_pef_pairs, sizeof(long long), hipMemcpyDeviceToHost, st));
+	int passes = 0;
+	for (bool keep = true; keep;) {
+		if (passes >= kMaxIterationCount && p.by_precision) { // :2802-2805: the dipoles stay as they are
+			c->failed = 1;
+			break;
+		}
+		if (p.by_precision) HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), st));
+		{
+			ProfScope ps(c, MPMC_K_DIPOLE_ITER);
+			launch_pef_contract(st, at, c->box, c->d_mu[c->mu_cur], c->d_tile_pairs, c->n_tile_pairs, c->d_pef_cnt, c->d_pef_store, c->d_part);
+			launch_pef_sf(st, at, rcp.kvec, c->K, phases, c->d_mu[c->mu_cur], c->d_pef_psum);
+		}
+		{
+			ProfScope ps(c, MPMC_K_REDUCE);
+			launch_pef_finish(st, at, ep, c->d_e_static, c->d_part, c->n_tiles, phases, rcp.kvec, rcp.kw, c->K, c->d_pef_psum, c->d_mu[c->mu_cur],
+			                  c->d_mu[1 - c->mu_cur], c->d_e_induced, p.by_precision ? c->d_flag.p : nullptr);
+		}
+		c->mu_cur = 1 - c->mu_cur;
+		if (p.by_precision) { // are_we_done_yet :3227-3236
+			HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipStreamSynchronize(st));
+			keep = (*c->h_flag != 0);
+		} else {
+			keep = (passes != o.polar_max_iter); // :3222-3225: the 0-based counter against polar_max_iter
+		}
+		passes++;
+	}
+	HIP_TRY(c, hipGetLastError());
+	c->iters = 0; // (the reference never writes polarization_iterations on this path)
+	c->polar_pending = mpmc_ctx::PEND_NONE;
+	c->pef_ran = true;
+	c->pef_info.passes = passes;
+	c->pef_info.n_k = c->K;
+	c->pef_info.store_bytes = (int64_t)(c->d_pef_store.cap * sizeof(double2));
 	return MPMC_OK;
 }
 
@@ -855,7 +948,8 @@ static int stage_post(mpmc_ctx *c, const EvalPlan &, const AtomsDev &, const Rec
 
 using Stage = int (*)(mpmc_ctx *, const EvalPlan &, const AtomsDev &, const RecipDev &);
 static constexpr Stage kStages[] = {stage_clear_and_static_terms, stage_side_work,         stage_pair_pass,    stage_pair_reduce, stage_static_field,
-                                    stage_direct_solve,           stage_gauss_seidel_solve, stage_jacobi_solve, stage_polar_energy, stage_palmo,
+                                    stage_direct_solve,           stage_gauss_seidel_solve, stage_jacobi_solve, stage_ewald_full_solve, stage_polar_energy,
+                                    stage_palmo,
                                     stage_added_terms,            stage_post};
 
 int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
@@ -868,9 +962,16 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_SOLVE) && ewald_full_on(c)) {
+		if (c->kept.palmo_enabled)
+			return fail(c, MPMC_ERR_UNSUPPORTED, "polar_ewald_full with polar_palmo: ewald_palmo_contraction (System.Energy.cpp:3243-3267) is not part of the library");
+		if (c->opts.polar_precision == 0.0 && c->opts.polar_max_iter < 0)
+			return fail(c, MPMC_ERR_INVALID_SETTING, "polar_ewald_full: polar_max_iter must be >= 0 when polar_precision is 0 (the reference never terminates)");
+		if (c->opts.polar_precision < 0.0) return fail(c, MPMC_ERR_INVALID_SETTING, "polar_ewald_full: polar_precision < 0");
+	}
 	c->static_ride_gen = 0;
 	c->run_mask = mask;
-	c->have_polar = c->direct_ran = c->palmo_ran = false;
+	c->have_polar = c->direct_ran = c->palmo_ran = c->pef_ran = false;
 	c->iters = c->failed = 0;
 	c->last_was_single = c->spin_on_post = false;
 
@@ -1010,6 +1111,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 			         std::to_string((long long)c->direct.n_unknowns) + " is not positive): dipoles and polarization energy set to 0";
 		}
 	}
+	if (c->pef_ran) c->pef_info.n_real_pairs = (int64_t)c->h_pef_pairs[0]; // (copied in front of the post)
 	if (!out) return MPMC_OK;
 	std::memset(out, 0, sizeof(*out));
 	const double *s = c->h_scal;

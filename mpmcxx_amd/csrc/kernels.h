@@ -374,6 +374,32 @@ void launch_wolf_field_delta(hipStream_t st, const AtomsDev &at, const Box &bx, 
 // change = f_new - e_induced for polarizable atoms, 0 for the others; scal[S_PALMO] = -1/2 sum mu . change, added to scal[S_POLAR]
 void launch_palmo_reduce(hipStream_t st, const AtomsDev &at, const double *mu, const double *f_new, const double *e_induced, double *change, double *scal);
 
+// ---- `polar_ewald_full`: the induced field as an Ewald sum (kernels_ewald_full.hip) ----------------------------------------------------
+struct EwaldFullParams {
+	int vector_weight;    // MPMC_PEF_VECTOR_KWEIGHT: w_p = (8 pi / V) kw_p; 0: the reference's (8 pi / V) kw_z for every p
+	double recip_scale;   // 8 pi / V
+	double c_total;       // -4 pi / (3 V), on sum_j mu_j
+	double c_self;        // 4 a^3 / (3 sqrt(pi)), on mu_i
+	double allowed_sqerr; // (polar_precision DEBYE2SKA)^2
+};
+// once per evaluation: store[n_tile_pairs][64 * 64] = (-s1 / r^3, 3 s2 / r^5) per pair in the order the contraction walks it, zeros outside
+// the predicate; cnt[tp] = pairs inside it (a tile pair with none is not written); n_pairs_out[0] = their sum
+void launch_pef_fill(hipStream_t st, const AtomsDev &at, const Box &bx, double ewald_a, double polar_damp, const int2 *tile_pairs,
+                     const int *cls /*this evaluation's tile-pair classes (CLS_BEYOND_CUTOFF tile pairs are skipped), or null*/, int n_tile_pairs, double2 *store,
+                     int *cnt, long long *n_pairs_out);
+// phases[K][n_pad] = (cos, sin)(k . r_i), raw positions (launch_pef_sf and launch_pef_finish take null for it: the phases are then recomputed)
+void launch_pef_phases(hipStream_t st, const AtomsDev &at, const double4 *kvec, int K, double2 *phases);
+// once per pass: part[source tile][n_pad][3] = the real-space induced field of `mu`, every slot written
+void launch_pef_contract(hipStream_t st, const AtomsDev &at, const Box &bx, const double *mu, const int2 *tile_pairs, int n_tile_pairs, const int *cnt,
+                         const double2 *store, double *part);
+// psum[2 k], psum[2 k + 1] = Pc, Ps of k < K; psum[2 K .. 2 K + 2] = sum_j mu_j (fixed-order block sums)
+void launch_pef_sf(hipStream_t st, const AtomsDev &at, const double4 *kvec, int K, const double2 *phases, const double *mu, double *psum);
+// e_induced = slots + reciprocal + correction; mu_new = alpha (E0 + e_induced); not_done (may be null): set to 1 when a component moved by
+// more than the allowed amount
+void launch_pef_finish(hipStream_t st, const AtomsDev &at, const EwaldFullParams &ep, const double *e_static, const double *part, int n_tiles,
+                       const double2 *phases, const double4 *kvec, const double4 *kw, int K, const double *psum, const double *mu_old, double *mu_new,
+                       double *e_induced, int *not_done);
+
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);
 

@@ -79,6 +79,14 @@ class RdCrystalInfo(C.Structure):
     _fields_ = [("order", C.c_int32), ("n_images", C.c_int32), ("cutoff", C.c_double), ("n_image_terms", C.c_int64), ("crystal_self", C.c_double)]
 
 
+class EwaldFullInfo(C.Structure):
+    """mpmc_ewald_full_info: the last evaluation of a context with `polar_ewald_full` on."""
+    _fields_ = [("passes", C.c_int32), ("n_k", C.c_int32), ("n_real_pairs", C.c_int64), ("store_bytes", C.c_int64)]
+
+
+PEF_VECTOR_KWEIGHT = 1  # MPMC_PEF_VECTOR_KWEIGHT
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -153,6 +161,9 @@ def lib():
     if hasattr(L, "mpmc_set_rd_crystal") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the lattice-summed Lennard-Jones)
         L.mpmc_set_rd_crystal.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_rd_crystal_info.argtypes = [vp, C.POINTER(RdCrystalInfo)]
+    if hasattr(L, "mpmc_set_polar_ewald_full") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the fully periodic dipole solve)
+        L.mpmc_set_polar_ewald_full.argtypes = [vp, C.c_int, C.c_int]
+        L.mpmc_polar_ewald_full_info.argtypes = [vp, C.POINTER(EwaldFullInfo)]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -344,6 +355,11 @@ class System:
             self._rd_crystal_set = True
             self.set_rd_crystal(bool(options.get("rd_crystal")), int(options.get("rd_crystal_order") or 0))
 
+        # `polar_ewald_full` likewise ("polar_ewald_full_flags": PEF_VECTOR_KWEIGHT or 0; the reference has no keyword for it)
+        if "polar_ewald_full" in options or getattr(self, "_polar_ewald_full_set", False):
+            self._polar_ewald_full_set = True
+            self.set_polar_ewald_full(bool(options.get("polar_ewald_full")), int(options.get("polar_ewald_full_flags") or 0))
+
     def set_atoms(self, atoms: Dict[str, np.ndarray]):
         f = lambda k: np.ascontiguousarray(atoms[k], dtype=np.float64)
         g = lambda k: np.ascontiguousarray(atoms[k], dtype=np.int32)
@@ -388,6 +404,17 @@ class System:
         v = RdCrystalInfo()
         self._check(self._L.mpmc_rd_crystal_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdCrystalInfo._fields_}
+
+    def set_polar_ewald_full(self, enabled: bool, flags: int = 0):
+        """`polar_ewald_full`: the induced field of the dipole solve as an Ewald sum as well (mpmc_set_polar_ewald_full); it replaces the
+        whole solve.  flags: PEF_VECTOR_KWEIGHT for the intended reciprocal-space weight instead of the reference's scalar one."""
+        self._check(self._L.mpmc_set_polar_ewald_full(self._h, int(bool(enabled)), int(flags)))
+
+    def ewald_full_info(self) -> Dict[str, int]:
+        """passes, n_k, n_real_pairs and store_bytes of the last evaluation with the term on (mpmc_polar_ewald_full_info)"""
+        v = EwaldFullInfo()
+        self._check(self._L.mpmc_polar_ewald_full_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in EwaldFullInfo._fields_}
 
     def set_polar_wolf(self, enabled: bool, polar_wolf_alpha: float = 0.0):
         """`polar_wolf`: the static field of the dipole solve as a Wolf sum with damping parameter polar_wolf_alpha in [0, 1]

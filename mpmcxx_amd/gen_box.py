@@ -337,6 +337,8 @@ def fixture(name: str):
         return _disp_fixture(name)
     if name in RD_CRYSTAL_FIXTURES:
         return _rd_crystal_fixture(name)
+    if name in EWALD_FULL_FIXTURES:
+        return _ewald_full_fixture(name)
     raise KeyError(name)
 
 
@@ -690,6 +692,96 @@ def rd_crystal_golden(golden_dir: str, name: str) -> Dict[str, object]:
         return json.load(f)[name]
 
 
+# ---- `polar_ewald_full on` (reference src/System.Energy.cpp:2785-2830, 2944-3143) -------------------------------------------------------------
+# NAME = BASE_pef[_VARIANT]: the box BASE with the fully periodic dipole solve.  Variants: it3 = polar_max_iter 3 (4 passes); prec =
+# polar_precision 1e-8 and no polar_max_iter.  Bases that exist only here:
+#   ion4000_polar       63 tiles, cutoff 32 A: many tile pairs lie wholly beyond it (golden sample only)
+#   pol2_eq / pol2_gt   two charged polarizable atoms in a cubic 10 A cell at x = 0 and x = 5.0 / 5.000001: at 5.0 the pair sits exactly at
+#                       the cutoff and is kept (the reference drops rimg > cutoff only); polar_ewald_alpha EWALD_FULL_POL2_ALPHA
+EWALD_FULL_FIXTURES = [
+    "ion216_polar_pef", "ion216_polar_pef_it3", "ion216_polar_pef_prec", "ion216_polar_nopbc_pef", "ion216_alpha_pef", "water64_polar_pef",
+    "ion216_framework_pef", "ion216_frozen_pef", "ion216_triclinic_pef", "ion1000_polar_pef", "ion1000_triclinic_pef", "ion4000_polar_pef",
+    "pol2_eq_pef", "pol2_gt_pef"]
+EWALD_FULL_POL2_X = {"eq": 5.0, "gt": 5.000001}
+EWALD_FULL_POL2_ALPHA = 0.7  # 3.5 / cutoff: the reference's iteration contracts at it (10 against 40 passes agree to 2e-5, iterator_failed 0)
+EWALD_FULL_SAMPLE_EVERY = 16  # boxes of more than 216 atoms keep the per-atom results of every 16th atom
+EWALD_FULL_GOLDEN = ("polar_ewald_full.json", "polar_ewald_full_atoms.npz")  # under tests/golden/: every fixture's scalars; the per-atom arrays
+
+
+def _ewald_full_fixture(name: str):
+    base, _, variant = name.partition("_pef")
+    if base.startswith("pol2_"):
+        x = EWALD_FULL_POL2_X[base[5:]]
+        rows = [AtomRow(1, "Ar", "Ar", "M", 1, 0.0, 0.0, 0.0, 39.948, 0.1, 1.6411, 119.8, 3.405),
+                AtomRow(2, "Ar", "Ar", "M", 2, x, 0.0, 0.0, 39.948, -0.1, 1.6411, 119.8, 3.405)]
+        basis, o = cubic(10.0), dict(POLAR_OPTS, polar_ewald_alpha=EWALD_FULL_POL2_ALPHA)
+    elif base == "ion4000_polar":
+        rows, basis, o = lattice_box(4000, 64.0, 17), cubic(64.0), dict(POLAR_OPTS)
+    else:
+        rows, basis, o = fixture(base)
+        o = dict(o)
+    if variant == "_it3":
+        o["polar_max_iter"] = 3
+    elif variant == "_prec":
+        o.pop("polar_max_iter", None)
+        o["polar_precision"] = 1e-8
+    elif variant:
+        raise KeyError(name)
+    return rows, basis, dict(o, polar_ewald_full="on")
+
+
+def keep_ewald_full_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <EWALD_FULL_FIXTURES>`: the per-fixture files are folded into EWALD_FULL_GOLDEN and removed, the
+    box text too (the tests regenerate it with `materialize`, which writes the same bytes the reference read).  The json holds every
+    fixture's scalars and cell; the npz holds ef_static, mu and ef_induced as float64 -- of every atom for boxes of up to 216 atoms, of
+    every EWALD_FULL_SAMPLE_EVERY-th atom for larger ones (whatever sample the harness printed is cut down to those) -- each distinct
+    array stored once."""
+    import json
+
+    import numpy as np
+
+    scalars, arrays, by_bytes = {}, {}, {}
+    for name in (names or EWALD_FULL_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        n = res["natoms"]
+        every = EWALD_FULL_SAMPLE_EVERY if n > 216 else 1
+        out = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+        out["sample_every"] = every
+        out["arrays"] = {}
+        for k in ("ef_static", "mu", "ef_induced"):
+            a = np.asarray(res[k], dtype=np.float64).reshape(-1, 3)
+            assert a.shape[0] == n, (name, k, a.shape)
+            a = a[::every]
+            key = by_bytes.setdefault(a.tobytes(), f"{name}.{k}")
+            arrays.setdefault(key, a)
+            out["arrays"][k] = key
+        scalars[name] = out
+    with open(os.path.join(golden_dir, EWALD_FULL_GOLDEN[0]), "w") as f:
+        json.dump(scalars, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    np.savez_compressed(os.path.join(golden_dir, EWALD_FULL_GOLDEN[1]), **arrays)
+    for name in (names or EWALD_FULL_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def ewald_full_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    """one fixture of EWALD_FULL_GOLDEN: scalars, `sample_atoms`, and ef_static / mu / ef_induced as [k, 3] arrays"""
+    import json
+
+    import numpy as np
+
+    with open(os.path.join(golden_dir, EWALD_FULL_GOLDEN[0])) as f:
+        g = json.load(f)[name]
+    with np.load(os.path.join(golden_dir, EWALD_FULL_GOLDEN[1])) as z:
+        for k, key in g.pop("arrays").items():
+            g[k] = z[key]
+    g["sample_atoms"] = list(range(0, g["natoms"], g.pop("sample_every")))
+    return g
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -734,6 +826,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-rd-crystal-golden"]:
         keep_rd_crystal_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-ewald-full-golden"]:
+        keep_ewald_full_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)

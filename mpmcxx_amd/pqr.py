@@ -21,7 +21,7 @@ E2REDUCED = 408.7816  # reference src/constants.h:35
 
 # keywords that select physics outside SURVEY §8 -- the replacement must refuse them (§8a note 7)
 UNSUPPORTED_ON = [
-    "spectre", "gwp", "sg", "polarvdw", "cdvdw", "polar_ewald_full",
+    "spectre", "gwp", "sg", "polarvdw", "cdvdw",
     "polar_wolf_full", "polar_wolf_alpha_lookup", "polar_gs_ranked", "polar_sor", "polar_esor", "polar_zodid",
     "waldmanhagler", "halgren_mixing", "c6_mixing", "dreiding", "lj_buffered_14_7",
     "disp_expansion_mbvdw", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
@@ -137,6 +137,8 @@ def read_input(path: str) -> Dict[str, object]:
             elif k in ("polar_wolf", "polar_palmo"):  # (likewise; the Wolf static field and the Palmo-Krimm correction)
                 opts[k] = _onoff(v[0])
             elif k == "rd_crystal":  # (likewise; the lattice-summed Lennard-Jones, mpmc_set_rd_crystal)
+                opts[k] = _onoff(v[0])
+            elif k == "polar_ewald_full":  # (likewise; the fully periodic dipole solve, mpmc_set_polar_ewald_full)
                 opts[k] = _onoff(v[0])
             elif k == "rd_crystal_order":
                 opts[k] = int(v[0])
