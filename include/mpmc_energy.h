@@ -71,8 +71,10 @@ extern "C" {
 #define MPMC_FLAG_POLAR_GS_RANKED (1ull << 10)
 #define MPMC_FLAG_POLAR_SOR (1ull << 11)
 #define MPMC_FLAG_POLAR_ZODID (1ull << 12)
-#define MPMC_FLAG_NON_LB_MIXING (1ull << 13) /* waldmanhagler / halgren / c6_mixing / cdvdw_* */
-#define MPMC_FLAG_OTHER_RD (1ull << 14)      /* dreiding / lj_buffered_14_7 / disp_expansion / anharmonic / exp_repulsion */
+#define MPMC_FLAG_NON_LB_MIXING (1ull << 13) /* cdvdw_* mixing; waldmanhagler / halgren_mixing / c6_mixing too when passed here -- still refused:
+                                              * those three are switched on by mpmc_set_rd_model alone */
+#define MPMC_FLAG_OTHER_RD (1ull << 14)      /* rd_anharmonic / cdvdw_exp_repulsion / disp_expansion_mbvdw; dreiding / lj_buffered_14_7 too when
+                                              * passed here -- still refused: those two are switched on by mpmc_set_rd_model alone */
 #define MPMC_FLAG_AXILROD_TELLER (1ull << 15) /* still refused here: the term is switched on by mpmc_set_axilrod_teller alone */
 #define MPMC_FLAG_CAVITY_AUTOREJECT (1ull << 16)
 #define MPMC_FLAG_POLAR_MATRIX_INVERSION (1ull << 17) /* polarization on with polar_iterative off (now supported: the direct solve
@@ -136,7 +138,7 @@ typedef struct mpmc_result {
 
 /* accumulated device time of the kernels of one context, measured with HIP events on the context's stream
  * (only while profiling is enabled with mpmc_set_profiling).  Index with MPMC_K_*. */
-#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel; the disp-expansion and rd_crystal sums / trial differences too */
+#define MPMC_K_PAIR 0        /* LJ + real-space Coulomb pair kernel; the disp-expansion, rd_crystal and rd-model sums / trial differences too */
 #define MPMC_K_RECIP 1       /* structure factors + reciprocal energy + atom terms  */
 #define MPMC_K_FIELD 2       /* static field (recip + real, or nopbc)               */
 #define MPMC_K_TENSOR 3      /* dense thole_amatrix rows (mpmc_thole_amatrix)        */
@@ -302,8 +304,55 @@ struct mpmc_rd_crystal_info {
 int mpmc_set_rd_crystal(mpmc_ctx *ctx, int enabled, int order);
 int mpmc_rd_crystal_info(mpmc_ctx *ctx, struct mpmc_rd_crystal_info *out);
 
+/* ---- the rd model: `waldmanhagler` / `halgren_mixing` / `c6_mixing` and `lj_buffered_14_7` / `dreiding` ------------------------------------
+ * (mixing: System::pair_exclusions, src/System.cpp:1069-1177; forms: System::lj src/System.Energy.cpp:897-1032, lj_buffered_14_7 :1212-1248,
+ * dreiding :2098-2215 with DREIDING_GAMMA = 12; dispatch :113-127, where dreiding comes before lj_buffered_14_7)
+ * One setting per context: a potential form and a mixing rule for sigma_ij, eps_ij.  (LJ, LB) is the default: it runs none of this and
+ * returns the bits of a context that never made the call.  Under any other model the pair sum inside the cutoff is
+ *   LJ:        4 eps_ij (t12 - t6), t6 = (sigma_ij / rimg)^6, for pairs with rimg - 1e-12 < cutoff;  + lj_fh_corr with eps_ij under feynman_hibbs
+ *   14-7:      eps_ij (1.07 / (rho + 0.07))^7 (1.12 / (rho^7 + 0.12) - 2), rho = rimg / sigma_ij, for pairs with !(rimg > cutoff)
+ *   DREIDING:  eps_ij (termexp - 2 rho^-6), termexp = exp(12 (1 - rho)), or 1e40 (MAXVALUE) for rimg < 0.4 sigma_ij; !(rimg > cutoff)
+ * over the pairs that are neither rd_excluded nor both frozen (the rules of the plain term), with
+ *   LB:               sigma_ij = (s_i + s_j) / 2 (0 when either is 0),         eps_ij = sqrt(e_i e_j)
+ *   Waldman-Hagler:   sigma_ij^6 = (s_i^6 + s_j^6) / 2 (0 when either is 0),  eps_ij = sqrt(e_i e_j) 2 s_i^3 s_j^3 / (s_i^6 + s_j^6)
+ *   Halgren:          sigma_ij = (s_i^3 + s_j^3) / (s_i^2 + s_j^2),            eps_ij = 4 e_i e_j / (sqrt e_i + sqrt e_j)^2 (each 0 unless both > 0)
+ *   C6:               sigma_ij = (s_i + s_j) / 2,                              eps_ij = 64 sqrt(e_i e_j) s_i^3 s_j^3 / (s_i + s_j)^6
+ * A pair that is not excluded but whose sigma_ij or eps_ij is 0 (an atom with dispersion coefficients and no sigma) contributes exactly 0.
+ * LJ form: lrc_pair = sum of lj_lrc_corr with the mixed parameters over every pair that is not frozen and has eps_ij != 0 and sigma_ij != 0
+ * (intramolecular pairs too), lrc_self as ever; rd_energy = (lj_pairs + lrc_pair) + lrc_self.  14-7 and DREIDING have no long-range and no
+ * Feynman-Hibbs correction whatever rd_lrc and feynman_hibbs say: lrc_pair = lrc_self = 0, rd_energy = lj_pairs; they ignore rd_crystal as
+ * disp-expansion does (result unchanged to the bit).  mpmc_lj returns this rd_energy.  n_lj_in_cutoff keeps its meaning (the LJ test) under
+ * every form; n_terms below counts by the form's own test (the two differ for rimg in (cutoff, cutoff + 1e-12) only).
+ * Electrostatics, polarization and the Axilrod-Teller term are untouched.
+ * sigma < 0 or epsilon < 0 on any atom is refused with MPMC_ERR_INVALID_DATUM at the evaluation (epsilon < 0 already by mpmc_set_atoms):
+ * the reference's Waldman-Hagler branch leaves eps_ij unassigned for such atoms, its Halgren branch zeroes it and its C6 branch averages
+ * signed values; no force field uses any of these.  Refused at the evaluation, with a message: MPMC_ERR_INCOMPATIBLE together with
+ * mpmc_set_disp_expansion (the reference never reaches the disp-expansion mixing behind these rules); MPMC_ERR_UNSUPPORTED for the LJ form
+ * with a non-LB rule together with mpmc_set_rd_crystal.  cavity_autoreject stays refused.
+ * The setting has the lifetime of mpmc_set_polar_wolf's: it survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates,
+ * accepted trials and capacity growth; it is refused while an evaluation or a trial move is open.  An unknown form or rule is refused
+ * with MPMC_ERR_INVALID_SETTING.  MPMC_FLAG_NON_LB_MIXING and MPMC_FLAG_OTHER_RD in unsupported_flags are still refused: this call alone
+ * switches the term on.  Cost O(N^2) per evaluation (tile pairs wholly beyond the cutoff are skipped in orthorhombic cells), O(m N) per
+ * trial move of m <= MPMC_TRIAL_MAX_ATOMS atoms; time is counted in MPMC_K_PAIR. */
+#define MPMC_RD_FORM_LJ 0
+#define MPMC_RD_FORM_BUFFERED_14_7 1
+#define MPMC_RD_FORM_DREIDING 2
+#define MPMC_RD_MIX_LB 0
+#define MPMC_RD_MIX_WALDMAN_HAGLER 1
+#define MPMC_RD_MIX_HALGREN 2
+#define MPMC_RD_MIX_C6 3
+/* (a struct tag, not a typedef: the entry point below carries the same name) */
+struct mpmc_rd_model_info {
+	int32_t form, mixing;          /* of the last evaluation (complete, component or trial) with a non-default model; 0, 0: none has run */
+	int64_t n_terms;               /* pairs that contributed: not excluded, not frozen, inside the form's own distance test               */
+	int64_t n_tile_pairs;          /* 64 x 64 tile pairs of the table ...                                                                  */
+	int64_t n_tile_pairs_skipped;  /* ... and how many of them lay wholly beyond the cutoff and were not walked (0 in triclinic cells)    */
+};
+int mpmc_set_rd_model(mpmc_ctx *ctx, int form, int mixing);
+int mpmc_rd_model_info(mpmc_ctx *ctx, struct mpmc_rd_model_info *out);
+
 /* ---- public component entry points of the reference (src/System.h:346-402), for parity tests ----------- */
-int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj() (rd_crystal: its lattice sum) */
+int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj() (rd_crystal: its lattice sum; a non-default rd model: its rd_energy) */
 int mpmc_coulombic(mpmc_ctx *ctx, double *out);           /* System::coulombic()            */
 int mpmc_coulombic_real(mpmc_ctx *ctx, double *out);      /* System::coulombic_real()       */
 int mpmc_coulombic_reciprocal(mpmc_ctx *ctx, double *out);/* System::coulombic_reciprocal() */

@@ -125,9 +125,9 @@ inline std::string read_input(const std::string &path, System &s) {
 	    {"gwp", MPMC_FLAG_GWP}, {"sg", MPMC_FLAG_USE_SG}, {"polarvdw", MPMC_FLAG_POLARVDW}, {"cdvdw", MPMC_FLAG_POLARVDW},
 	    {"polar_ewald_full", MPMC_FLAG_POLAR_EWALD_FULL}, {"polar_wolf_full", MPMC_FLAG_POLAR_WOLF},
 	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED}, {"polar_sor", MPMC_FLAG_POLAR_SOR},
-	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"waldmanhagler", MPMC_FLAG_NON_LB_MIXING},
-	    {"halgren_mixing", MPMC_FLAG_NON_LB_MIXING}, {"c6_mixing", MPMC_FLAG_NON_LB_MIXING}, {"dreiding", MPMC_FLAG_OTHER_RD},
-	    {"lj_buffered_14_7", MPMC_FLAG_OTHER_RD}, {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
+	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"cdvdw_exp_repulsion", MPMC_FLAG_OTHER_RD},
+	    {"cdvdw_sig_repulsion", MPMC_FLAG_NON_LB_MIXING}, {"cdvdw_9th_repulsion", MPMC_FLAG_NON_LB_MIXING},
+	    {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
 	    {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
 	    {"cavity_autoreject_absolute", MPMC_FLAG_CAVITY_AUTOREJECT}};
 	std::string pqr, line;
@@ -176,6 +176,12 @@ inline std::string read_input(const std::string &path, System &s) {
 			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_POLAR_EWALD_FULL;
 			s.polar_ewald_full = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
 		}
+		// (the rd model: read into fields, no flag; the facade hands them to mpmc_set_rd_model)
+		else if (k == "waldmanhagler") { need(1); s.waldmanhagler = onoff(t[1]); }
+		else if (k == "halgren_mixing") { need(1); s.halgren_mixing = onoff(t[1]); }
+		else if (k == "c6_mixing") { need(1); s.c6_mixing = onoff(t[1]); }
+		else if (k == "lj_buffered_14_7") { need(1); s.using_lj_buffered_14_7 = onoff(t[1]) != 0; }
+		else if (k == "dreiding") { need(1); s.use_dreiding = onoff(t[1]); }
 		else if (k == "rd_crystal_order") { need(1); s.rd_crystal_order = (int)dval(1); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
@@ -196,6 +202,7 @@ inline std::string read_input(const std::string &path, System &s) {
 			// everything else (job_name, ensemble, temperature, numsteps, output switches ...) does not enter energy()
 		}
 	}
+	if ((s.waldmanhagler != 0) + (s.halgren_mixing != 0) + (s.c6_mixing != 0) > 1) throw 3000; // more than one mixing rule (SimulationControl.cpp:1706-1713)
 	if (pqr.empty()) throw 4003; // missing_setting
 	if (pqr[0] != '/') pqr = dirname_of(path) + "/" + pqr;
 	return pqr;

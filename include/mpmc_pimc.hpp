@@ -156,6 +156,7 @@ public:
 			if (uses_disp_expansion(*s, 0)) throw 4004; // unsupported_setting: nor is the disp-expansion term
 			if (uses_polar_wolf_or_palmo(*s, 0)) throw 4004; // unsupported_setting: nor are polar_wolf / polar_palmo
 			if (uses_polar_ewald_full(*s, 0)) throw 4004;    // unsupported_setting: nor is polar_ewald_full
+			if (uses_rd_model(*s, 0)) throw 4004;            // unsupported_setting: nor is a non-default rd model
 			s->temperature = cfg.temperature;
 		}
 		pi.systems = systems;

@@ -75,6 +75,11 @@ template <class T>
 auto uses_polar_ewald_full(const T &s, int) -> decltype(bool(s.polar_ewald_full)) { return s.polar_ewald_full; }
 template <class T>
 bool uses_polar_ewald_full(const T &, long) { return false; }
+// the same for a non-default rd model (another mixing rule, the buffered 14-7 or the DREIDING form)
+template <class T>
+auto uses_rd_model(const T &s, int) -> decltype(bool(s.rd_model_form() || s.rd_model_mixing())) { return s.rd_model_form() || s.rd_model_mixing(); }
+template <class T>
+bool uses_rd_model(const T &, long) { return false; }
 
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
@@ -104,6 +109,15 @@ public:
 	int dipoles_on_demand = 0; // energy() / energy_async() stop at the Jacobi iterations the energy needs; fetch_dipoles() runs the rest (mpmc_set_dipoles_on_demand)
 	int polar_wolf = 0, polar_palmo = 0; // Wolf static field (mpmc_set_polar_wolf), Palmo-Krimm correction (mpmc_set_polar_palmo), src/System.h:685-694
 	int rd_crystal = 0, rd_crystal_order = 0; // lattice-summed Lennard-Jones (mpmc_set_rd_crystal), src/System.h:632-633
+	// the rd model (mpmc_set_rd_model): mixing rules src/System.h: waldmanhagler, halgren_mixing, c6_mixing; forms use_dreiding, using_lj_buffered_14_7
+	int waldmanhagler = 0, halgren_mixing = 0, c6_mixing = 0, use_dreiding = 0;
+	bool using_lj_buffered_14_7 = false;
+	// dreiding wins over lj_buffered_14_7 (the dispatch order of System::energy, src/System.Energy.cpp:113-127); lj_buffered_14_7 does not switch
+	// Halgren mixing on; the branches of pair_exclusions come in the order Waldman-Hagler, Halgren, C6 (src/System.cpp:1072-1165)
+	int rd_model_form() const { return use_dreiding ? MPMC_RD_FORM_DREIDING : using_lj_buffered_14_7 ? MPMC_RD_FORM_BUFFERED_14_7 : MPMC_RD_FORM_LJ; }
+	int rd_model_mixing() const {
+		return waldmanhagler ? MPMC_RD_MIX_WALDMAN_HAGLER : halgren_mixing ? MPMC_RD_MIX_HALGREN : c6_mixing ? MPMC_RD_MIX_C6 : MPMC_RD_MIX_LB;
+	}
 	int polar_ewald_full = 0;            // Ewald-summed induced field (mpmc_set_polar_ewald_full), src/System.h: polar_ewald_full
 	int polar_ewald_full_vector_kweight = 0; // MPMC_PEF_VECTOR_KWEIGHT: the intended reciprocal-space weight (no keyword: the reference has none)
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
@@ -304,6 +318,7 @@ private:
 	int on_demand_on_ = 0;                       // ... and its dipoles-on-demand switch
 	int rd_crystal_on_ = 0, rd_crystal_order_ = 0; // ... and its rd_crystal setting
 	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
+	int rd_model_form_ = 0, rd_model_mixing_ = 0;  // ... and its rd model
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
@@ -328,6 +343,7 @@ private:
 			polar_wolf_alpha_ = 0;
 			rd_crystal_on_ = rd_crystal_order_ = 0;
 			ewald_full_on_ = ewald_full_flags_ = 0;
+			rd_model_form_ = rd_model_mixing_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -408,6 +424,11 @@ private:
 			check(mpmc_set_rd_crystal(ctx_, rd_crystal ? 1 : 0, rd_crystal_order), "mpmc_set_rd_crystal");
 			rd_crystal_on_ = rd_crystal ? 1 : 0;
 			rd_crystal_order_ = rd_crystal_order;
+		}
+		if (rd_model_form() != rd_model_form_ || rd_model_mixing() != rd_model_mixing_) {
+			check(mpmc_set_rd_model(ctx_, rd_model_form(), rd_model_mixing()), "mpmc_set_rd_model");
+			rd_model_form_ = rd_model_form();
+			rd_model_mixing_ = rd_model_mixing();
 		}
 		const int pef_flags = polar_ewald_full_vector_kweight ? MPMC_PEF_VECTOR_KWEIGHT : 0;
 		if ((polar_ewald_full != 0) != (ewald_full_on_ != 0) || (polar_ewald_full && pef_flags != ewald_full_flags_)) {

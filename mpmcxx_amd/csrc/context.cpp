@@ -574,6 +574,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	c->atoms_dirty = false;
 	if (c->tb_have) c->tb_dirty = true; // (the three-body coefficients follow the order at the next evaluation that needs them)
 	if (c->de_have) c->de_dirty = true; // (so do the disp-expansion coefficients)
+	c->rdm_dirty = true;                // (and the rd model's per-atom table)
 	return MPMC_OK;
 }
 
@@ -770,6 +771,83 @@ extern "C" int mpmc_set_rd_crystal(mpmc_ctx *c, int enabled, int order) {
 extern "C" int mpmc_rd_crystal_info(mpmc_ctx *c, struct mpmc_rd_crystal_info *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	*out = c->rc_info;
+	return MPMC_OK;
+}
+
+// ---- the rd model (pair_exclusions, src/System.cpp:1069-1177; lj :897-1032, lj_buffered_14_7 :1212-1248, dreiding :2098-2215) ------------------
+static_assert(MPMC_RD_FORM_LJ == RD_FORM_LJ && MPMC_RD_FORM_BUFFERED_14_7 == RD_FORM_BUFFERED_14_7 && MPMC_RD_FORM_DREIDING == RD_FORM_DREIDING, "pair_math.h mirrors the header");
+static_assert(MPMC_RD_MIX_LB == RD_MIX_LB && MPMC_RD_MIX_WALDMAN_HAGLER == RD_MIX_WALDMAN_HAGLER && MPMC_RD_MIX_HALGREN == RD_MIX_HALGREN && MPMC_RD_MIX_C6 == RD_MIX_C6,
+              "pair_math.h mirrors the header");
+extern "C" int mpmc_set_rd_model(mpmc_ctx *c, int form, int mixing) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_model: an evaluation or a trial move is open");
+	if (form < 0 || form >= RD_FORM_COUNT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_model: unknown potential form (MPMC_RD_FORM_*)");
+	if (mixing < 0 || mixing >= RD_MIX_COUNT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_model: unknown mixing rule (MPMC_RD_MIX_*)");
+	if (form != c->kept.rdm_form || mixing != c->kept.rdm_mix) {
+		c->cache_valid = false; // (the accepted totals carry the other term)
+		// (14-7 and DREIDING ignore rd_crystal: the long-range corrections move between the crystal cutoff and the box cutoff, lrc_box)
+		if (c->kept.rc_enabled && (form != 0) != (c->kept.rdm_form != 0)) c->static_dirty = true, c->static_gen++;
+	}
+	c->kept.rdm_form = form;
+	c->kept.rdm_mix = mixing;
+	return MPMC_OK;
+}
+extern "C" int mpmc_rd_model_info(mpmc_ctx *c, struct mpmc_rd_model_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	*out = c->rdm_info;
+	return MPMC_OK;
+}
+
+int mpmc::rd_model_ready(mpmc_ctx *c) {
+	if (!rd_model_on(c)) return fail(c, MPMC_ERR_INVALID_SETTING, "the rd model is the default one (mpmc_set_rd_model)");
+	if (c->kept.de_enabled)
+		return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_rd_model with mpmc_set_disp_expansion: the reference mixes by waldmanhagler / halgren_mixing before it reaches "
+		                                      "the disp-expansion coefficients (System.cpp:1072-1158), and dreiding / lj_buffered_14_7 never read them");
+	if (c->kept.rc_enabled && c->kept.rdm_form == RD_FORM_LJ)
+		return fail(c, MPMC_ERR_UNSUPPORTED, "rd_crystal with a mixing rule other than Lorentz-Berthelot: the lattice sum (kernels_crystal.hip) mixes by Lorentz-Berthelot only");
+	if (c->rdm_dirty) { // (the parameters change with the atom list only, and every new list is uploaded: one scan per upload, none per trial move)
+		c->rdm_bad_atom = -1;
+		for (int i = 0; i < c->n && c->rdm_bad_atom < 0; i++)
+			if (c->h_sigma[i] < 0.0 || c->h_eps[i] < 0.0) c->rdm_bad_atom = i;
+	}
+	if (c->rdm_bad_atom >= 0) {
+		const int i = c->rdm_bad_atom;
+		if (c->h_sigma[i] < 0.0) return fail(c, MPMC_ERR_INVALID_DATUM, "rd model: atom " + std::to_string(i) + " has sigma < 0 (attractive-only sites exist under the plain Lennard-Jones term only)");
+		return fail(c, MPMC_ERR_INVALID_DATUM, "rd model: atom " + std::to_string(i) + " has epsilon < 0");
+	}
+	int rc;
+	if ((rc = c->d_rdm_sp.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_rdm_part.reserve(c, (size_t)3 * kRdModelBlocks)) != MPMC_OK) return rc;
+	if ((rc = c->d_rdm_lrc.reserve(c, 1)) != MPMC_OK) return rc;
+	if (c->rdm_dirty) { // slot order, like every other per-atom array (upload_atoms)
+		std::vector<double4> sp((size_t)c->n_pad, make_double4(0.0, 0.0, 0.0, 0.0));
+		for (int k = 0; k < c->n; k++) {
+			const double s = c->h_sigma[c->perm[k]], s2 = s * s, s3 = s2 * s;
+			sp[k] = make_double4(s, s2, s3, s3 * s3);
+		}
+		HIP_TRY(c, hipMemcpyAsync(c->d_rdm_sp, sp.data(), sp.size() * sizeof(double4), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // (`sp` dies here; once per upload of the atoms)
+		c->rdm_dirty = false;
+		c->rdm_lrc_valid = false;
+	}
+	// the LJ form's pair correction: every pair once, whenever the atoms, the box, rd_lrc or the rule changed (never with the positions)
+	const bool want = c->kept.rdm_form == RD_FORM_LJ && c->opts.rd_lrc;
+	if (!c->rdm_lrc_valid || c->rdm_lrc_volume != c->box.volume || c->rdm_lrc_cutoff != c->box.cutoff || c->rdm_lrc_rd_lrc != (want ? 1 : 0) ||
+	    c->rdm_lrc_mix != c->kept.rdm_mix) {
+		c->rdm_lrc = 0.0;
+		if (want) {
+			launch_rd_model_lrc(c->stream, atoms_view(c), c->d_rdm_sp, c->d_tile_pairs, c->n_tile_pairs, c->kept.rdm_mix, c->box.cutoff, c->box.volume, c->d_rdm_part,
+			                    c->d_rdm_lrc);
+			HIP_TRY(c, hipGetLastError());
+			HIP_TRY(c, hipMemcpyAsync(&c->rdm_lrc, c->d_rdm_lrc, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(c, hipStreamSynchronize(c->stream));
+		}
+		c->rdm_lrc_volume = c->box.volume;
+		c->rdm_lrc_cutoff = c->box.cutoff;
+		c->rdm_lrc_rd_lrc = want ? 1 : 0;
+		c->rdm_lrc_mix = c->kept.rdm_mix;
+		c->rdm_lrc_valid = true;
+	}
 	return MPMC_OK;
 }
 

@@ -135,6 +135,7 @@ struct mpmc_kept {
 	bool palmo_enabled = false;             // `polar_palmo` (mpmc_set_polar_palmo), likewise
 	bool rc_enabled = false;                // `rd_crystal` (mpmc_set_rd_crystal), kept across mpmc_set_box and mpmc_set_options too
 	int rc_order = 0;                       // rd_crystal_order
+	int rdm_form = 0, rdm_mix = 0;          // the rd model (mpmc_set_rd_model), likewise: MPMC_RD_FORM_*, MPMC_RD_MIX_*; (0, 0) = the plain term
 	bool pef_enabled = false;               // `polar_ewald_full` (mpmc_set_polar_ewald_full), likewise
 	int pef_flags = 0;                      // MPMC_PEF_*
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
@@ -362,6 +363,20 @@ struct mpmc_ctx {
 	struct mpmc_rd_crystal_info rc_info{};         // of the last evaluation with the term (mpmc_rd_crystal_info)
 	int64_t rc_terms_accepted = 0, rc_terms_trial = 0; // image terms of the accepted configuration (with last_full) / of the evaluated trial
 
+	// the rd model (mpmc_set_rd_model, kernels_rd_model.hip; kept.rdm_form, kept.rdm_mix): another mixing rule / pair function in place of the
+	// LJ sums of rd_energy.  The per-atom table follows the spatial order (rebuilt behind every upload of the atoms: rd_model_ready); the LJ
+	// form's pair correction follows the parameters, the flags, the volume, the cutoff, rd_lrc and the rule -- never the positions.
+	bool rdm_dirty = true;                  // d_rdm_sp is older than the atom list or than the spatial order
+	int rdm_bad_atom = -1;                  // first atom with sigma < 0 or epsilon < 0 of the current list (-1: none), found when the table is rebuilt
+	DevBuf<double4> d_rdm_sp;               // [max_pad] (sigma, sigma^2, sigma^3, sigma^6) in slot order, padding zeros
+	DevBuf<double> d_rdm_part;              // [3 kRdModelBlocks] per-workgroup partials: energies, kept terms, skipped tile pairs
+	DevBuf<double> d_rdm_lrc;               // [1] the correction kernel's sum on its way to the host
+	bool rdm_lrc_valid = false;             // rdm_lrc belongs to the values below and to the current table
+	double rdm_lrc = 0, rdm_lrc_volume = 0, rdm_lrc_cutoff = 0;
+	int rdm_lrc_rd_lrc = 0, rdm_lrc_mix = -1;
+	struct mpmc_rd_model_info rdm_info{};   // of the last evaluation with a non-default model (mpmc_rd_model_info)
+	int64_t rdm_terms_accepted = 0, rdm_terms_trial = 0; // kept terms of the accepted configuration (with last_full) / of the evaluated trial
+
 	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip; switched on: kept.pw_enabled, kept.pw_alpha,
 	// kept.palmo_enabled)
 	bool palmo_ran = false;          // the pending / last evaluation did the extra contraction (Gauss-Seidel sweeps that did not fail)
@@ -541,7 +556,8 @@ enum : unsigned {
 	RUN_STORE = 128, // tile classes + the Thole tensor store alone (no energies, no field): trial moves of polarizable boxes
 	RUN_THREE_BODY = 256, // the Axilrod-Teller sum (contexts with the term switched on)
 	RUN_DISP = 512,       // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
-	RUN_CRYSTAL = 1024    // the rd_crystal lattice sum (contexts with the term switched on and disp-expansion off: it replaces the LJ sum)
+	RUN_CRYSTAL = 1024,   // the rd_crystal lattice sum (contexts with the term switched on and disp-expansion off: it replaces the LJ sum)
+	RUN_RDM = 2048        // the rd-model sum (contexts with a non-default model: it replaces the LJ part of rd_energy)
 };
 // 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
 // applied once to the sum of the per-triple terms
@@ -549,7 +565,11 @@ constexpr double kThreeBodyScale = 3.0 * (0.0032539449 / (3.166811429 * 0.000001
 int three_body_ready(mpmc_ctx *c); // the term is on and its coefficients are on the device in the current slot order (context.cpp)
 int disp_ready(mpmc_ctx *c);       // the same for the disp-expansion term, and its long-range corrections for the current box (context.cpp)
 DispParams disp_params(const mpmc_ctx *c);
-inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled; } // (disp_expansion() ignores rd_crystal)
+inline bool rd_model_on(const mpmc_ctx *c) { return c->kept.rdm_form != 0 || c->kept.rdm_mix != 0; }
+// (disp_expansion() ignores rd_crystal, and so do lj_buffered_14_7() and dreiding())
+inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled && c->kept.rdm_form == 0; }
+int rd_model_ready(mpmc_ctx *c);   // the model's combinations and atom parameters are valid, its table is on the device in the current slot order, its correction is current (context.cpp)
+RdModelParams rd_model_params(const mpmc_ctx *c); // form, rule, distance test and this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 int crystal_ready(mpmc_ctx *c);    // the image table, cutoff, thresholds and crystal_self of the current cell and atoms are in place (context.cpp)
 CrystalParams crystal_params(const mpmc_ctx *c); // rc_par with this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see it: rd_crystal puts its own cutoff in (evaluate.cpp)

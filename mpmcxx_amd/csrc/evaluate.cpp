@@ -148,6 +148,21 @@ CrystalParams mpmc::crystal_params(const mpmc_ctx *c) {
 	return cp;
 }
 
+RdModelParams mpmc::rd_model_params(const mpmc_ctx *c) {
+	RdModelParams rp{};
+	rp.form = c->kept.rdm_form;
+	rp.mix = c->kept.rdm_mix;
+	rp.t_in = (rp.form == RD_FORM_LJ) ? c->box.t_lj : c->box.t_es; // (rimg - 1e-12 < cutoff :934 | !(rimg > cutoff) :1229, :2127)
+	if (rp.form == RD_FORM_LJ) { // (lj_buffered_14_7() and dreiding() carry no Feynman-Hibbs correction)
+		FusedParams fp{};
+		ext_params(c, fp, false);
+		rp.fh_order = fp.fh_order;
+		rp.fh_c2 = fp.fh_c2;
+		rp.fh_c4 = fp.fh_c4;
+	}
+	return rp;
+}
+
 AtomsDev mpmc::atoms_view(const mpmc_ctx *c) {
 	AtomsDev a;
 	a.xyzq = c->d_xyzq;
@@ -925,6 +940,13 @@ static int stage_added_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at,
 		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL,
 		               c->d_scal + S_CRYSTAL_TERMS);
 	}
+	// ---- the rd model (:113-127): the pair sum, its kept terms and the skipped tile pairs into their three slots.  Tile pairs beyond the
+	// cutoff are skipped by this evaluation's classes, where the pairwise pass made them and the cell is orthorhombic ----------------------
+	if (p.mask & RUN_RDM) {
+		ProfScope ps(c, MPMC_K_PAIR);
+		const int *cls = (p.pair_pass && c->box.ortho && !c->kept.tune.no_classes) ? c->d_cls.p : nullptr;
+		launch_rd_model(st, at, c->d_rdm_sp, c->d_tile_pairs, cls, c->n_tile_pairs, c->box, rd_model_params(c), c->d_rdm_part, c->d_scal + S_RDM);
+	}
 	HIP_TRY(c, hipGetLastError());
 	return MPMC_OK;
 }
@@ -962,6 +984,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if ((mask & RUN_THREE_BODY) && (rc = three_body_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_RDM) && (rc = rd_model_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_SOLVE) && ewald_full_on(c)) {
 		if (c->kept.palmo_enabled)
 			return fail(c, MPMC_ERR_UNSUPPORTED, "polar_ewald_full with polar_palmo: ewald_palmo_contraction (System.Energy.cpp:3243-3267) is not part of the library");
@@ -1144,6 +1167,23 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->rc_info.n_image_terms = (int64_t)s[S_CRYSTAL_TERMS];
 		c->rc_info.crystal_self = c->rc_self;
 	}
+	if (c->run_mask & RUN_RDM) { // the model's sum replaces the LJ sum of the pair kernels; the LJ form keeps lj()'s order of composition
+		out->lj_pairs = s[S_RDM];
+		if (c->kept.rdm_form == RD_FORM_LJ) {
+			const bool lrc = (c->run_mask & RUN_ATOMTERMS) && c->opts.rd_lrc;
+			out->lrc_pair = lrc ? c->rdm_lrc : 0.0;
+			out->lrc_self = lrc ? c->h_static[1] : 0.0;
+			out->rd_energy = (out->lj_pairs + out->lrc_pair) + out->lrc_self;
+		} else { // (lj_buffered_14_7() and dreiding() have no long-range correction)
+			out->lrc_pair = out->lrc_self = 0.0;
+			out->rd_energy = out->lj_pairs;
+		}
+		c->rdm_info.form = c->kept.rdm_form;
+		c->rdm_info.mixing = c->kept.rdm_mix;
+		c->rdm_info.n_terms = (int64_t)s[S_RDM_TERMS];
+		c->rdm_info.n_tile_pairs = c->n_tile_pairs;
+		c->rdm_info.n_tile_pairs_skipped = (int64_t)s[S_RDM_SKIPPED];
+	}
 	out->es_real = s[S_ES_REAL] - s[S_ES_INTRA];
 	out->es_recip = s[S_ES_RECIP];
 	out->es_self = (c->run_mask & RUN_RECIP) ? c->h_static[2] : 0.0;
@@ -1168,6 +1208,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->last_full = *out;
 		c->cache_valid = true;
 		c->rc_terms_accepted = c->rc_info.n_image_terms;
+		c->rdm_terms_accepted = c->rdm_info.n_terms;
 	}
 	return MPMC_OK;
 }
@@ -1182,6 +1223,7 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 	if (c->kept.tb_enabled) m |= RUN_THREE_BODY; // (summed on top of everything else, rd_only too: :129-136)
 	if (c->kept.de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
 	if (crystal_on(c)) m |= RUN_CRYSTAL;         // (in place of the LJ sum; disp_expansion() ignores rd_crystal)
+	if (rd_model_on(c)) m |= RUN_RDM;            // (in place of the LJ part of rd_energy; never the single-launch form)
 	return m;
 }
 
@@ -1222,7 +1264,7 @@ static int run_piece(mpmc_ctx *c, unsigned mask, mpmc_result *r) {
 extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	if (!c) return MPMC_ERR_ARG;
-	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u), &r);
+	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u) | (rd_model_on(c) ? RUN_RDM : 0u), &r);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }

@@ -58,7 +58,8 @@ enum : int {
 	S_DISP, S_DISP_LRC_PAIR, S_DISP_LRC_SELF,    // disp-expansion pair sum and its two long-range corrections (kernels_disp.hip)
 	S_PALMO,                                     // Palmo-Krimm correction, already part of S_POLAR (kernels_wolf_field.hip)
 	S_CRYSTAL, S_CRYSTAL_TERMS,                  // rd_crystal pair sum and its image-term count (a double: exact) (kernels_crystal.hip)
-	S_COUNT = 16
+	S_RDM, S_RDM_TERMS, S_RDM_SKIPPED,           // rd-model pair sum, its kept terms and the tile pairs it skipped (doubles: exact) (kernels_rd_model.hip)
+	S_COUNT = 20
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
 // tile-pair classes written by k_classify (any cell: DESIGN section 3 has the bound used for skewed cells): lower bound of the
@@ -355,6 +356,30 @@ void launch_crystal(hipStream_t st, const AtomsDev &at, const Box &bx, const Cry
 // kernels (marked and cleared again inside); out2 = { change of the pair sum, change of the image-term count }
 void launch_crystal_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const CrystalParams &cp, const double4 *shift, const int *mv_slot,
                           const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
+
+// ---- the rd model: another mixing rule and another pair function for the sum inside the cutoff (kernels_rd_model.hip) --------------
+// sp[slot] = (sigma, sigma^2, sigma^3, sigma^6) per atom, sigma >= 0 (context.cpp: rd_model_ready; padding zeros); sqrt(epsilon) is
+// AtomsDev::lj's.  Every launch leaves kRdModelBlocks (or fewer) partials per quantity in `part` ([3 kRdModelBlocks]) and writes their
+// fixed-order sums.
+constexpr int kRdModelBlocks = 16384;
+struct RdModelParams {
+	int form, mix;       // RD_FORM_*, RD_MIX_* (pair_math.h)
+	double t_in;         // ri2 <= t_in: the form's distance test (Box::t_lj for the LJ form, Box::t_es for 14-7 and DREIDING)
+	int fh_order;        // Feynman-Hibbs (LJ form only): 0 off, 2 or 4, with the constants of FusedParams
+	double fh_c2, fh_c4;
+};
+int rd_model_grid(long long work_items);
+// out3 = { pair sum, kept terms, tile pairs skipped }; cls: this evaluation's tile-pair classes (CLS_BEYOND_CUTOFF tile pairs are not
+// walked), or null: every tile pair is walked
+void launch_rd_model(hipStream_t st, const AtomsDev &at, const double4 *sp, const int2 *tile_pairs, const int *cls, int n_tile_pairs, const Box &bx,
+                     const RdModelParams &rp, double *part, double *out3);
+// out[0] = the LJ form's pair correction with the mixed parameters over every pair that is not frozen (the host caches it)
+void launch_rd_model_lrc(hipStream_t st, const AtomsDev &at, const double4 *sp, const int2 *tile_pairs, int n_tile_pairs, int mix, double cutoff,
+                         double volume, double *part, double *out);
+// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
+// kernels (marked and cleared again inside); out2 = { change of the pair sum, change of the kept terms }
+void launch_rd_model_delta(hipStream_t st, const AtomsDev &at, const double4 *sp, const Box &bx, const RdModelParams &rp, const int *mv_slot,
+                           const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
 
 // ---- `polar_wolf`: the Wolf static field, and the reduce of `polar_palmo` (kernels_wolf_field.hip)--------------------------------------
 struct WolfFieldParams {

@@ -185,6 +185,93 @@ MPMC_HD double lj_term(double sigma_abs, double epsilon, double rimg, bool attra
 	return 4.0 * epsilon * (t12 - s6);
 }
 
+// ---- the rd model (mpmc_set_rd_model): another mixing rule (pair_exclusions, System.cpp:1069-1177) and another function of r / sigma
+// (System::lj :897-1032, lj_buffered_14_7 :1212-1248, dreiding :2098-2215) for the pair sum inside the cutoff ------------------------------
+// The values mirror MPMC_RD_FORM_* / MPMC_RD_MIX_* of the public header (context.cpp asserts it).
+enum : int { RD_FORM_LJ = 0, RD_FORM_BUFFERED_14_7 = 1, RD_FORM_DREIDING = 2, RD_FORM_COUNT = 3 };
+enum : int { RD_MIX_LB = 0, RD_MIX_WALDMAN_HAGLER = 1, RD_MIX_HALGREN = 2, RD_MIX_C6 = 3, RD_MIX_COUNT = 4 };
+constexpr double kDreidingGamma = 12.0; // DREIDING_GAMMA, System.Energy.cpp:2094
+
+// Per atom (host, context.cpp: rd_model_ready): sp = (sigma, sigma^2, sigma^3, sigma^6), sqe = sqrt(epsilon) and e = epsilon, sigma >= 0
+// and epsilon >= 0 (anything else is refused before a kernel runs, so no pair is ever attractive_only here).
+struct RdAtom {
+	double s, s2, s3, s6, sqe, e;
+};
+// The pair's mixed parameters.  No pow: Waldman-Hagler's sixth root is a square root and a cube root; one division (Halgren: one each for
+// sigma and epsilon, which keeps both within a few ulp of the reference's expressions); sqrt(e_i) sqrt(e_j) stands for the reference's
+// sqrt(e_i e_j) as in lj_mix.  A pair with a sigma of 0 gets sigma = 0 (rd_pair_energy returns 0 for it), never a division by zero.
+struct RdMixed {
+	double sigma, eps;
+};
+template <int MIX>
+MPMC_HD RdMixed rd_mix(const RdAtom &a, const RdAtom &b) {
+	RdMixed m;
+	const bool zero = (a.s == 0.0) || (b.s == 0.0);
+	const double ee = a.sqe * b.sqe;
+	if (MIX == RD_MIX_WALDMAN_HAGLER) { // :1072-1091: sigma^6 = (s_i^6 + s_j^6) / 2, eps = sqrt(e_i e_j) 2 s_i^3 s_j^3 / (s_i^6 + s_j^6)
+		const double s6 = 0.5 * (a.s6 + b.s6);
+		m.sigma = zero ? 0.0 : cbrt(sqrt(s6));
+		m.eps = zero ? ee : (ee * (a.s3 * b.s3)) / s6;
+	} else if (MIX == RD_MIX_HALGREN) { // :1093-1106: sigma = (s_i^3 + s_j^3) / (s_i^2 + s_j^2), eps = 4 e_i e_j / (sqrt e_i + sqrt e_j)^2
+		const bool ezero = (a.e == 0.0) || (b.e == 0.0);
+		const double D = a.sqe + b.sqe;
+		m.sigma = zero ? 0.0 : (a.s3 + b.s3) / (a.s2 + b.s2);
+		m.eps = ezero ? 0.0 : (4.0 * (a.e * b.e)) / (D * D);
+	} else if (MIX == RD_MIX_C6) { // :1159-1165: sigma = (s_i + s_j) / 2, eps = 64 sqrt(e_i e_j) s_i^3 s_j^3 / (s_i + s_j)^6
+		m.sigma = 0.5 * (a.s + b.s);
+		const double t = a.s + b.s, t2 = t * t;
+		m.eps = (m.sigma != 0.0) ? ((64.0 * ee) * (a.s3 * b.s3)) / ((t2 * t2) * t2) : 0.0;
+	} else { // Lorentz-Berthelot, :1166-1177 with sigma >= 0
+		m.sigma = zero ? 0.0 : 0.5 * (a.s + b.s);
+		m.eps = ee;
+	}
+	return m;
+}
+// LJ form with mixed parameters (:965-993), in the reference's own order: s = sigma / r, t6 = (s s s)^2, t12 = t6^2 (sigma / r enters at
+// the twelfth power: another order of the same products moves the result by tens of ulp); t12 and t6 go out for fh_lj_corr
+MPMC_HD double rd_lj_term(double eps, double sigma, double r, double &t12, double &t6) {
+	const double s = sigma / r;
+	t6 = s * s * s;
+	t6 *= t6;
+	t12 = t6 * t6;
+	return 4.0 * eps * (t12 - t6);
+}
+// Halgren's buffered 14-7 (:1230-1233): eps (1.07 / (rho + 0.07))^7 (1.12 / (rho^7 + 0.12) - 2), rho = r / sigma; the powers are products
+MPMC_HD double rd_buffered_14_7_term(double eps, double sigma, double r) {
+	const double rho = r / sigma;
+	const double a = 1.07 / (rho + 0.07);
+	const double a2 = a * a, a7 = ((a2 * a2) * a2) * a;
+	const double r2 = rho * rho, r7 = ((r2 * r2) * r2) * rho;
+	return (eps * a7) * (1.12 / (r7 + 0.12) - 2.0);
+}
+// DREIDING exponential-6 (:2129-2145): eps (6 / (g - 6) exp(g (1 - rho)) - g / (g - 6) rho^-6), g = 12; below 0.4 sigma the exponential
+// term is MAXVALUE.  ex: the caller's exponential (exp on the host, exp_fast in the kernels)
+template <class Exp>
+MPMC_HD double rd_dreiding_term(double eps, double sigma, double r, Exp ex) {
+	const double rho = r / sigma;
+	const double r2 = rho * rho;
+	const double term6 = (kDreidingGamma / (kDreidingGamma - 6.0)) / ((r2 * r2) * r2);
+	const double termexp = (r < 0.4 * sigma) ? kMaxValue : (6.0 / (kDreidingGamma - 6.0)) * ex(kDreidingGamma * (1.0 - rho));
+	return eps * (termexp - term6);
+}
+// One pair of the model at the squared minimum-image distance ri2 (the caller applied the exclusions and the form's distance test).  A
+// pair whose mixed sigma or epsilon is 0 contributes exactly 0 (the reference gets there through 0 / r or r / 0 = inf; no NaN here).
+// fh_order != 0 (LJ form only): + fh_lj_corr (below) with the mixed epsilon; imu = 1 / M_i + 1 / M_j.
+MPMC_HD double fh_lj_corr(int order, double c2, double c4, double imu, double eps, double t12, double s6, double ir);
+template <int FORM, class Exp>
+MPMC_HD double rd_pair_energy(const RdMixed &m, double ri2, int fh_order, double fh_c2, double fh_c4, double imu, Exp ex) {
+	if (m.sigma == 0.0 || m.eps == 0.0) return 0.0;
+	const double r = sqrt(ri2);
+	if (FORM == RD_FORM_LJ) {
+		double t12, t6;
+		double e = rd_lj_term(m.eps, m.sigma, r, t12, t6);
+		if (fh_order) e += fh_lj_corr(fh_order, fh_c2, fh_c4, imu, m.eps, t12, t6, 1.0 / r);
+		return e;
+	}
+	if (FORM == RD_FORM_BUFFERED_14_7) return rd_buffered_14_7_term(m.eps, m.sigma, r);
+	return rd_dreiding_term(m.eps, m.sigma, r, ex);
+}
+
 // Feynman-Hibbs corrections (reference System.Energy.cpp: lj_fh_corr :1100-1148, coulombic_real_FH :1521-1557), per pair, shared by the
 // pair sweep and the per-move delta kernels.  c2 = M2A2 hbar^2 / (24 kB T amu2kg), c4 = M2A4 hbar^4 / (1152 kB^2 T^2 amu2kg^2);
 // imu = 1/M_i + 1/M_j (molecule masses, amu): the reduced mass enters as its inverse.

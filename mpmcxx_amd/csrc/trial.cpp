@@ -91,7 +91,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->kept.tune.no_inline_move;
 	// (the three-body, disp-expansion and rd_crystal deltas read the moved atoms from the device lists: a box with one of them always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c);
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c);
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -140,6 +140,15 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_crystal_delta(st, atoms_view(c), c->box, crystal_params(c), c->d_rc_shift, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rc_part,
 		                     c->d_delta_out + 9);
+	}
+	if (rd_model_on(c)) {
+		// the rd model: the change of the pairs with a moved atom, O(m N), old positions still resident; into slots 9 and 10 of the delta
+		// result block (h_delta_out[10], [11]), which a context with the model never shares with rd_crystal (crystal_on, rd_model_ready).  It
+		// replaces the LJ delta of launch_delta; the cached pair correction does not move with the atoms.
+		if ((rc = rd_model_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_rd_model_delta(st, atoms_view(c), c->d_rdm_sp, c->box, rd_model_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rdm_part,
+		                      c->d_delta_out + 9);
 	}
 	{
 		FusedParams fp{};
@@ -216,13 +225,15 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		return MPMC_OK;
 	}
 	if (c->trial_was_full) {
-		const int64_t terms_keep = c->rc_terms_accepted;
+		const int64_t terms_keep = c->rc_terms_accepted, rdm_terms_keep = c->rdm_terms_accepted;
 		int rc = mpmc_energy_wait(c, out);
 		if (rc != MPMC_OK) return rc;
 		c->trial_res = *out;
 		c->last_full = c->trial_keep; // still the ACCEPTED configuration's totals until mpmc_trial_accept
 		c->rc_terms_trial = c->rc_info.n_image_terms; // (rd_crystal: the same for the image-term count)
 		c->rc_terms_accepted = terms_keep;
+		c->rdm_terms_trial = c->rdm_info.n_terms; // (the rd model: the same for its kept terms)
+		c->rdm_terms_accepted = rdm_terms_keep;
 		c->trial_evaluated = true;
 		return MPMC_OK;
 	}
@@ -258,6 +269,12 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		r.rd_energy = ((r.lj_pairs + r.lrc_pair) + c->rc_self) + r.lrc_self;
 		c->rc_terms_trial = c->rc_terms_accepted + (int64_t)c->h_delta_out[11];
 		c->rc_info.n_image_terms = c->rc_terms_trial;
+	}
+	if (rd_model_on(c)) { // (lj_pairs holds the model's sum; the corrections do not move with the atoms)
+		r.lj_pairs = a.lj_pairs + c->h_delta_out[10];
+		r.rd_energy = (c->kept.rdm_form == RD_FORM_LJ) ? (r.lj_pairs + r.lrc_pair) + r.lrc_self : r.lj_pairs;
+		c->rdm_terms_trial = c->rdm_terms_accepted + (int64_t)c->h_delta_out[11];
+		c->rdm_info.n_terms = c->rdm_terms_trial;
 	}
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
@@ -322,6 +339,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 	c->last_full = c->trial_res;
 	c->cache_valid = true;
 	if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
+	if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
 	c->trial_open = false;
 	c->trial_polar_delta = false;
 	return MPMC_OK;

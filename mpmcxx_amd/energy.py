@@ -74,6 +74,28 @@ class DirectInfo(C.Structure):
     _fields_ = [("n_unknowns", C.c_int64), ("status", C.c_int64), ("residual", C.c_double), ("factor_bytes", C.c_int64)]
 
 
+class RdModelInfo(C.Structure):
+    """mpmc_rd_model_info: the last evaluation of a context with a non-default rd model."""
+    _fields_ = [("form", C.c_int32), ("mixing", C.c_int32), ("n_terms", C.c_int64), ("n_tile_pairs", C.c_int64), ("n_tile_pairs_skipped", C.c_int64)]
+
+
+# MPMC_RD_FORM_* / MPMC_RD_MIX_* and the reference keywords that select them
+RD_FORM = {"lj": 0, "lj_buffered_14_7": 1, "dreiding": 2}
+RD_MIX = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}
+RD_MODEL_KEYS = ("waldmanhagler", "halgren_mixing", "c6_mixing", "lj_buffered_14_7", "dreiding")
+
+
+def rd_model_of(options: Dict[str, object]):
+    """(form, mixing) of the reference keywords in `options`: dreiding wins over lj_buffered_14_7 (the dispatch order of System::energy,
+    src/System.Energy.cpp:113-127), lj_buffered_14_7 does not switch Halgren mixing on (the reference only prints that it does), and more than
+    one mixing rule is refused as the reference refuses it (SimulationControl.cpp:1706-1713)."""
+    rules = [k for k in ("waldmanhagler", "halgren_mixing", "c6_mixing") if options.get(k)]
+    if len(rules) > 1:
+        raise MpmcError(ERR_INVALID_SETTING, "more than one mixing rule: " + " and ".join(rules))
+    form = RD_FORM["dreiding"] if options.get("dreiding") else RD_FORM["lj_buffered_14_7"] if options.get("lj_buffered_14_7") else RD_FORM["lj"]
+    return form, (RD_MIX[rules[0]] if rules else RD_MIX["lb"])
+
+
 class RdCrystalInfo(C.Structure):
     """mpmc_rd_crystal_info: the last evaluation of a context with `rd_crystal` on."""
     _fields_ = [("order", C.c_int32), ("n_images", C.c_int32), ("cutoff", C.c_double), ("n_image_terms", C.c_int64), ("crystal_self", C.c_double)]
@@ -161,6 +183,9 @@ def lib():
     if hasattr(L, "mpmc_set_rd_crystal") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the lattice-summed Lennard-Jones)
         L.mpmc_set_rd_crystal.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_rd_crystal_info.argtypes = [vp, C.POINTER(RdCrystalInfo)]
+    if hasattr(L, "mpmc_set_rd_model") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the rd model)
+        L.mpmc_set_rd_model.argtypes = [vp, C.c_int, C.c_int]
+        L.mpmc_rd_model_info.argtypes = [vp, C.POINTER(RdModelInfo)]
     if hasattr(L, "mpmc_set_polar_ewald_full") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the fully periodic dipole solve)
         L.mpmc_set_polar_ewald_full.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_polar_ewald_full_info.argtypes = [vp, C.POINTER(EwaldFullInfo)]
@@ -354,6 +379,10 @@ class System:
         if "rd_crystal" in options or getattr(self, "_rd_crystal_set", False):
             self._rd_crystal_set = True
             self.set_rd_crystal(bool(options.get("rd_crystal")), int(options.get("rd_crystal_order") or 0))
+        # the rd model likewise: `waldmanhagler` / `halgren_mixing` / `c6_mixing` and `lj_buffered_14_7` / `dreiding`
+        if any(k in options for k in RD_MODEL_KEYS) or getattr(self, "_rd_model_set", False):
+            self._rd_model_set = True
+            self.set_rd_model(*rd_model_of(options))
 
         # `polar_ewald_full` likewise ("polar_ewald_full_flags": PEF_VECTOR_KWEIGHT or 0; the reference has no keyword for it)
         if "polar_ewald_full" in options or getattr(self, "_polar_ewald_full_set", False):
@@ -404,6 +433,19 @@ class System:
         v = RdCrystalInfo()
         self._check(self._L.mpmc_rd_crystal_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdCrystalInfo._fields_}
+
+    def set_rd_model(self, form=0, mixing=0):
+        """The rd model (mpmc_set_rd_model): a potential form (RD_FORM: "lj", "lj_buffered_14_7", "dreiding", or its number) and a mixing rule
+        (RD_MIX: "lb", "waldmanhagler", "halgren_mixing", "c6_mixing").  ("lj", "lb") restores the plain term."""
+        f = RD_FORM[form] if isinstance(form, str) else int(form)
+        m = RD_MIX[mixing] if isinstance(mixing, str) else int(mixing)
+        self._check(self._L.mpmc_set_rd_model(self._h, f, m))
+
+    def rd_model_info(self) -> Dict[str, object]:
+        """form, mixing, n_terms, n_tile_pairs and n_tile_pairs_skipped of the last evaluation with a non-default model (mpmc_rd_model_info)"""
+        v = RdModelInfo()
+        self._check(self._L.mpmc_rd_model_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in RdModelInfo._fields_}
 
     def set_polar_ewald_full(self, enabled: bool, flags: int = 0):
         """`polar_ewald_full`: the induced field of the dipole solve as an Ewald sum as well (mpmc_set_polar_ewald_full); it replaces the

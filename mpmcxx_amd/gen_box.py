@@ -339,6 +339,8 @@ def fixture(name: str):
         return _rd_crystal_fixture(name)
     if name in EWALD_FULL_FIXTURES:
         return _ewald_full_fixture(name)
+    if name in RD_MODEL_FIXTURES:
+        return _rd_model_fixture(name)
     raise KeyError(name)
 
 
@@ -692,6 +694,98 @@ def rd_crystal_golden(golden_dir: str, name: str) -> Dict[str, object]:
         return json.load(f)[name]
 
 
+# ---- the rd model: `waldmanhagler` / `halgren_mixing` / `c6_mixing`, `lj_buffered_14_7` / `dreiding` (reference src/System.cpp:1069-1177,
+# src/System.Energy.cpp:897-1032, 1212-1248, 2098-2215) ------------------------------------------------------------------------------------------
+# NAME = BASE_rdm_<form><rule>: the box BASE with three species on its non-H rows (by atom_id % 5: 1 and 3 -> B, 4 -> C, else A; with one
+# species every mixing rule gives the atom's own parameters back), form lj | b147 | drd, rule lb | wh | hal | c6.  In the water64 boxes the
+# first H of every molecule also carries a dispersion coefficient: its pairs are not excluded, and their mixed sigma is 0.  Bases that exist
+# only here:
+#   arkr_eq / arkr_gt / arkr_lt   species A and B alone in a cubic 10 A cell at (0, 0, 0) and (3, 4 | 4.000001 | 3.999999, 0), rd_only: at
+#                                 (3, 4, 0) the pair sits exactly at the cutoff 5 A and every form keeps it
+#   arkr_contact                  the same two atoms 0.9 A apart: below 0.4 sigma_ij DREIDING's exponential term is MAXVALUE
+#   ion216_nolrc                  ion216_polar with rd_lrc off
+#   ion4000_polar                 63 tiles, cutoff 32 A: many tile pairs lie wholly beyond it
+RD_MODEL_SPECIES = {"A": (119.8, 3.405), "B": (36.7, 2.958), "C": (10.22, 2.28)}  # (epsilon K, sigma A)
+RD_MODEL_FORMS = {"lj": {}, "b147": {"lj_buffered_14_7": "on"}, "drd": {"dreiding": "on"}}
+RD_MODEL_RULES = {"lb": {}, "wh": {"waldmanhagler": "on"}, "hal": {"halgren_mixing": "on"}, "c6": {"c6_mixing": "on"}}
+RD_MODEL_COMBOS = [f + r for f in RD_MODEL_FORMS for r in RD_MODEL_RULES if (f, r) != ("lj", "lb")]
+RD_MODEL_ARKR_Y = {"eq": 4.0, "gt": 4.000001, "lt": 3.999999}
+RD_MODEL_FIXTURES = [f"ion216_polar_rdm_{m}" for m in RD_MODEL_COMBOS] + [
+    "water64_polar_rdm_b147hal", "water64_polar_rdm_drdwh", "water64_polar_rdm_ljwh", "ion216_framework_rdm_b147hal", "ion216_framework_rdm_ljc6",
+    "ion216_triclinic_rdm_ljwh", "ion216_triclinic_rdm_drdlb", "ion216_fh4_polar_rdm_ljwh", "ion216_nolrc_rdm_ljhal",
+    "ion4000_polar_rdm_b147hal", "ion4000_polar_rdm_ljwh"] + [
+    f"arkr_{t}_rdm_{m}" for t in ("eq", "gt", "lt") for m in ("ljwh", "b147lb", "drdlb")] + ["arkr_contact_rdm_drdlb"]
+RD_MODEL_GOLDEN = "rd_model.json"  # under tests/golden/: every fixture's scalars
+
+
+def rd_model_species(rows: List[AtomRow]) -> List[AtomRow]:
+    """the three species on every non-H row, by atom_id % 5"""
+    for r in rows:
+        if r.atomtype == "H":
+            continue
+        sp = {1: "B", 3: "B", 4: "C"}.get(r.atom_id % 5, "A")
+        r.eps, r.sigma = RD_MODEL_SPECIES[sp]
+    return rows
+
+
+def rd_model_combo(tag: str):
+    """'b147hal' -> ('b147', 'hal')"""
+    for f in sorted(RD_MODEL_FORMS, key=len, reverse=True):
+        if tag.startswith(f) and tag[len(f):] in RD_MODEL_RULES:
+            return f, tag[len(f):]
+    raise KeyError(tag)
+
+
+def _rd_model_fixture(name: str):
+    base, tag = name.rsplit("_rdm_", 1)
+    form, rule = rd_model_combo(tag)
+    if base.startswith("arkr_"):
+        (ea, sa), (eb, sb) = RD_MODEL_SPECIES["A"], RD_MODEL_SPECIES["B"]
+        at = (0.9, 0.0) if base == "arkr_contact" else (3.0, RD_MODEL_ARKR_Y[base[5:]])
+        rows = [AtomRow(1, "Ar", "Ar", "M", 1, 0.0, 0.0, 0.0, 39.948, 0.0, 0.0, ea, sa),
+                AtomRow(2, "Kr", "Kr", "M", 2, at[0], at[1], 0.0, 83.798, 0.0, 0.0, eb, sb)]
+        basis, o = cubic(10.0), {"rd_only": "on"}
+    elif base == "ion216_nolrc":
+        rows, basis, o = fixture("ion216_polar")
+        o = dict(o, rd_lrc="off")
+    elif base == "ion4000_polar":
+        rows, basis, o = lattice_box(4000, 64.0, 17), cubic(64.0), dict(POLAR_OPTS)
+    else:
+        rows, basis, o = fixture(base)
+    if not base.startswith("arkr_"):
+        rows = rd_model_species(rows)
+    if base.startswith("water64"):
+        for r in rows:  # (every row prints its coefficient columns: the reference's reader carries a row's values on to rows without them)
+            r.c6 = 1.0 if (r.atomtype == "H" and r.alpha != 0.0) else 0.0
+    return rows, basis, dict(o, **RD_MODEL_FORMS[form], **RD_MODEL_RULES[rule])
+
+
+def keep_rd_model_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <RD_MODEL_FIXTURES>`: the per-fixture files are folded into RD_MODEL_GOLDEN (scalars and cell
+    only) and removed, the box text too (the tests regenerate it with `materialize`, which writes the same bytes the reference read)."""
+    import json
+
+    out = {}
+    for name in (names or RD_MODEL_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        out[name] = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+    with open(os.path.join(golden_dir, RD_MODEL_GOLDEN), "w") as f:
+        json.dump(out, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    for name in (names or RD_MODEL_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def rd_model_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    import json
+
+    with open(os.path.join(golden_dir, RD_MODEL_GOLDEN)) as f:
+        return json.load(f)[name]
+
+
 # ---- `polar_ewald_full on` (reference src/System.Energy.cpp:2785-2830, 2944-3143) -------------------------------------------------------------
 # NAME = BASE_pef[_VARIANT]: the box BASE with the fully periodic dipole solve.  Variants: it3 = polar_max_iter 3 (4 passes); prec =
 # polar_precision 1e-8 and no polar_max_iter.  Bases that exist only here:
@@ -826,6 +920,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-rd-crystal-golden"]:
         keep_rd_crystal_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-rd-model-golden"]:
+        keep_rd_model_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-ewald-full-golden"]:
         keep_ewald_full_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))

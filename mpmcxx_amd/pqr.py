@@ -23,7 +23,7 @@ E2REDUCED = 408.7816  # reference src/constants.h:35
 UNSUPPORTED_ON = [
     "spectre", "gwp", "sg", "polarvdw", "cdvdw",
     "polar_wolf_full", "polar_wolf_alpha_lookup", "polar_gs_ranked", "polar_sor", "polar_esor", "polar_zodid",
-    "waldmanhagler", "halgren_mixing", "c6_mixing", "dreiding", "lj_buffered_14_7",
+    "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion",
     "disp_expansion_mbvdw", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
 ]
 
@@ -140,6 +140,8 @@ def read_input(path: str) -> Dict[str, object]:
                 opts[k] = _onoff(v[0])
             elif k == "polar_ewald_full":  # (likewise; the fully periodic dipole solve, mpmc_set_polar_ewald_full)
                 opts[k] = _onoff(v[0])
+            elif k in ("waldmanhagler", "halgren_mixing", "c6_mixing", "lj_buffered_14_7", "dreiding"):  # (likewise; the rd model, mpmc_set_rd_model)
+                opts[k] = _onoff(v[0])
             elif k == "rd_crystal_order":
                 opts[k] = int(v[0])
             elif k in ("polar_wolf_alpha", "polar_wolf_damp"):  # (two names of one setting, SimulationControl.cpp:751-759)
@@ -153,6 +155,8 @@ def read_input(path: str) -> Dict[str, object]:
             elif k in UNSUPPORTED_ON and (not v or v[0].lower() != "off"):
                 raise NotImplementedError(f"{path}: keyword {k!r} selects physics outside the energy hot path (SURVEY §8a note 7)")
             # everything else (job_name, temperature, numsteps, output switches, ...) does not enter energy()
+    if sum(1 for k in ("waldmanhagler", "halgren_mixing", "c6_mixing") if opts.get(k)) > 1:  # (SimulationControl.cpp:1706-1713)
+        raise ValueError(f"{path}: more than one mixing rule specified")
     if pqr is None:
         raise ValueError(f"{path}: no pqr_input")
     return {"basis": basis, "pqr_input": os.path.join(os.path.dirname(os.path.abspath(path)), pqr), "options": opts,
