@@ -461,6 +461,44 @@ typedef struct mpmc_ewald_full_info {
 } mpmc_ewald_full_info;
 int mpmc_polar_ewald_full_info(mpmc_ctx *ctx, mpmc_ewald_full_info *out);
 
+/* ---- `polar_sor`, `polar_esor`, `polar_zodid`: relaxed dipole updates and zeroth-order dipoles (src/System.Energy.cpp:3450-3560, 3181-3211) ---
+ * scheme (gamma = mpmc_options.polar_gamma; `it` = 1, 2, ... the iteration; new_mu = alpha (E0 + E_ind) the unrelaxed update):
+ *   MPMC_POLAR_RELAX_SOR    mu = gamma new_mu + (1 - gamma) old_mu
+ *   MPMC_POLAR_RELAX_ESOR   mu = (1 - exp(-gamma it)) new_mu + exp(-gamma it) old_mu
+ * Under a scheme the start is mu_0 = alpha E0 without the polar_gamma factor (init_dipoles :3555).
+ *   Jacobi iterations and Gauss-Seidel sweeps (thole_iterative): dipole_rrms and the precision test compare the UNRELAXED new_mu with
+ *     old_mu; the blend is what the next iteration reads, and it is applied behind the last iteration too, so the energy and the dipoles
+ *     returned are blended ones.  ef_induced is the last contraction's field.  Under sweeps new_mu is the swept vector; mpmc_set_polar_palmo
+ *     contracts the swept, unblended dipoles and takes its energy term with the blended ones.  At 128 iterations of a precision-terminated
+ *     solve the dipoles are alpha E0 and iterator_failed is set, as without a scheme.  SOR with gamma = 1 is the plain solve.
+ *   mpmc_set_polar_ewald_full: the weight of pass k = 0, 1, ... is that of it = k + 1, new_mu itself is overwritten with the blend, and the
+ *     precision test sees the blended value (new_dipoles :3196-3204); the start never carries polar_gamma.
+ *   polar_iterative off: the scheme is never read.
+ * zodid: "zeroth-order" dipoles, mu = alpha E0 (times polar_gamma when no scheme is on), no A matrix and no iteration: polar_iterations and
+ *   dipole_rrms are 0, ef_induced is 0, the Palmo-Krimm term is 0, polarization_energy = -1/2 sum mu . E0.  No tensor store, panel table or
+ *   dense matrix is built; a trial move of up to MPMC_TRIAL_MAX_ATOMS atoms is O(m N) end to end.  Under mpmc_set_polar_ewald_full zodid
+ *   changes nothing.  With polarization on and polar_iterative off the evaluation fails with MPMC_ERR_INCOMPATIBLE (SimulationControl.cpp:2634).
+ * polar_gamma < 0 with a scheme on fails the evaluation with MPMC_ERR_INVALID_SETTING (SimulationControl.cpp:2714-2730); an unknown scheme
+ * is refused by the setter with the same code.  The energy-from-moments form and mpmc_set_dipoles_on_demand do not apply under a scheme or
+ * zodid: every evaluation runs all its iterations.  The setting has the lifetime of mpmc_set_polar_wolf's and is refused while an
+ * evaluation or a trial move is open; (MPMC_POLAR_RELAX_NONE, 0) restores the behaviour of a context that never called it, to the bit.
+ * MPMC_FLAG_POLAR_SOR and MPMC_FLAG_POLAR_ZODID in unsupported_flags are still refused: this call alone switches the behaviour on.
+ * Still refused, the last member of the family: `polar_gs_ranked` (MPMC_FLAG_POLAR_GS_RANKED).
+ * mpmc_polar_relax_info: of the last evaluation with a dipole solve. */
+#define MPMC_POLAR_RELAX_NONE 0
+#define MPMC_POLAR_RELAX_SOR 1
+#define MPMC_POLAR_RELAX_ESOR 2
+int mpmc_set_polar_relax(mpmc_ctx *ctx, int scheme, int zodid);
+typedef struct mpmc_relax_info {
+	int32_t scheme;        /* MPMC_POLAR_RELAX_* of the context                                                             */
+	int32_t zodid;         /* the context's zodid switch                                                                    */
+	int32_t acted;         /* 1: a relaxed update or the zeroth-order shortcut ran in that evaluation                       */
+	int32_t store_filled;  /* 1: that evaluation filled a tensor store (compact, dense or the ewald_full pair factors)      */
+	int64_t contractions;  /* A . mu contractions it ran: iterations, sweeps or passes, + 1 for Palmo-Krimm; 0 under zodid  */
+	double last_weight;    /* w_new of the last update (1 when none was relaxed)                                            */
+} mpmc_relax_info;
+int mpmc_polar_relax_info(mpmc_ctx *ctx, mpmc_relax_info *out);
+
 /* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL.  After an on-demand evaluation
  * (mpmc_set_dipoles_on_demand above) the remaining Jacobi iterations run here first; MPMC_ERR_ARG when they no longer can. */
 int mpmc_get_dipoles(mpmc_ctx *ctx, double *mu, double *ef_static, double *ef_induced /* each [n][3] */);

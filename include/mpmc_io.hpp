@@ -124,8 +124,8 @@ inline std::string read_input(const std::string &path, System &s) {
 	    {"rd_crystal", MPMC_FLAG_RD_CRYSTAL}, {"spectre", MPMC_FLAG_SPECTRE},
 	    {"gwp", MPMC_FLAG_GWP}, {"sg", MPMC_FLAG_USE_SG}, {"polarvdw", MPMC_FLAG_POLARVDW}, {"cdvdw", MPMC_FLAG_POLARVDW},
 	    {"polar_ewald_full", MPMC_FLAG_POLAR_EWALD_FULL}, {"polar_wolf_full", MPMC_FLAG_POLAR_WOLF},
-	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED}, {"polar_sor", MPMC_FLAG_POLAR_SOR},
-	    {"polar_esor", MPMC_FLAG_POLAR_SOR}, {"polar_zodid", MPMC_FLAG_POLAR_ZODID}, {"cdvdw_exp_repulsion", MPMC_FLAG_OTHER_RD},
+	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED},
+	    {"cdvdw_exp_repulsion", MPMC_FLAG_OTHER_RD},
 	    {"cdvdw_sig_repulsion", MPMC_FLAG_NON_LB_MIXING}, {"cdvdw_9th_repulsion", MPMC_FLAG_NON_LB_MIXING},
 	    {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
 	    {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
@@ -167,6 +167,10 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "schmidt_ff") { need(1); s.schmidt_ff = onoff(t[1]); }
 		else if (k == "polar_wolf") { need(1); s.polar_wolf = onoff(t[1]); }
 		else if (k == "polar_palmo") { need(1); s.polar_palmo = onoff(t[1]); }
+		// (relaxed dipole updates and zeroth-order dipoles: read into fields, no flag; the facade hands them to mpmc_set_polar_relax)
+		else if (k == "polar_sor") { need(1); s.polar_sor = onoff(t[1]); }
+		else if (k == "polar_esor") { need(1); s.polar_esor = onoff(t[1]); }
+		else if (k == "polar_zodid") { need(1); s.polar_zodid = onoff(t[1]); }
 		else if (k == "polar_wolf_alpha" || k == "polar_wolf_damp") { need(1); s.polar_wolf_alpha = dval(1); } // (two names of one setting, SimulationControl.cpp:751-759)
 		else if (k == "rd_crystal") { // (the flag as for every keyword of the table above: the facade clears it when it hands the term to mpmc_set_rd_crystal)
 			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_RD_CRYSTAL;
@@ -203,6 +207,8 @@ inline std::string read_input(const std::string &path, System &s) {
 		}
 	}
 	if ((s.waldmanhagler != 0) + (s.halgren_mixing != 0) + (s.c6_mixing != 0) > 1) throw 3000; // more than one mixing rule (SimulationControl.cpp:1706-1713)
+	if (s.polar_sor && s.polar_esor) throw 3000; // both relaxation schemes (SimulationControl.cpp:2714-2730)
+	if (s.polar_zodid && s.polarization && !s.polar_iterative) throw 3000; // zodid needs the iterative solver (SimulationControl.cpp:2634)
 	if (pqr.empty()) throw 4003; // missing_setting
 	if (pqr[0] != '/') pqr = dirname_of(path) + "/" + pqr;
 	return pqr;

@@ -118,6 +118,8 @@ public:
 	int rd_model_mixing() const {
 		return waldmanhagler ? MPMC_RD_MIX_WALDMAN_HAGLER : halgren_mixing ? MPMC_RD_MIX_HALGREN : c6_mixing ? MPMC_RD_MIX_C6 : MPMC_RD_MIX_LB;
 	}
+	int polar_sor = 0, polar_esor = 0;   // relaxed dipole updates by polar_gamma (mpmc_set_polar_relax), src/System.h: polar_sor, polar_esor
+	int polar_zodid = 0;                 // zeroth-order dipoles, mu = alpha E0 (mpmc_set_polar_relax)
 	int polar_ewald_full = 0;            // Ewald-summed induced field (mpmc_set_polar_ewald_full), src/System.h: polar_ewald_full
 	int polar_ewald_full_vector_kweight = 0; // MPMC_PEF_VECTOR_KWEIGHT: the intended reciprocal-space weight (no keyword: the reference has none)
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
@@ -319,6 +321,7 @@ private:
 	int rd_crystal_on_ = 0, rd_crystal_order_ = 0; // ... and its rd_crystal setting
 	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
 	int rd_model_form_ = 0, rd_model_mixing_ = 0;  // ... and its rd model
+	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	std::vector<double> trial_pos_;
@@ -344,6 +347,7 @@ private:
 			rd_crystal_on_ = rd_crystal_order_ = 0;
 			ewald_full_on_ = ewald_full_flags_ = 0;
 			rd_model_form_ = rd_model_mixing_ = 0;
+			relax_scheme_ = zodid_on_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -435,6 +439,16 @@ private:
 			check(mpmc_set_polar_ewald_full(ctx_, polar_ewald_full ? 1 : 0, pef_flags), "mpmc_set_polar_ewald_full");
 			ewald_full_on_ = polar_ewald_full ? 1 : 0;
 			ewald_full_flags_ = pef_flags;
+		}
+		if (polar_sor && polar_esor) { // (SimulationControl.cpp:2714-2730)
+			last_error_ = "polar_sor and polar_esor are both on";
+			throw (int)MPMC_ERR_INCOMPATIBLE;
+		}
+		const int relax_scheme = polar_sor ? MPMC_POLAR_RELAX_SOR : polar_esor ? MPMC_POLAR_RELAX_ESOR : MPMC_POLAR_RELAX_NONE;
+		if (relax_scheme != relax_scheme_ || (polar_zodid != 0) != (zodid_on_ != 0)) {
+			check(mpmc_set_polar_relax(ctx_, relax_scheme, polar_zodid ? 1 : 0), "mpmc_set_polar_relax");
+			relax_scheme_ = relax_scheme;
+			zodid_on_ = polar_zodid ? 1 : 0;
 		}
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");

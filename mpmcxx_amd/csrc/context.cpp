@@ -727,6 +727,29 @@ extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 	return MPMC_OK;
 }
 
+// ---- `polar_sor` / `polar_esor` / `polar_zodid` (thole_iterative :3450-3560, new_dipoles :3181-3211) ------------------------------------------
+extern "C" int mpmc_set_polar_relax(mpmc_ctx *c, int scheme, int zodid) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_relax: an evaluation or a trial move is open");
+	if (scheme != MPMC_POLAR_RELAX_NONE && scheme != MPMC_POLAR_RELAX_SOR && scheme != MPMC_POLAR_RELAX_ESOR)
+		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_relax: unknown scheme (MPMC_POLAR_RELAX_NONE, _SOR or _ESOR)");
+	const bool z = zodid != 0;
+	if (scheme != c->kept.relax_scheme || z != c->kept.zodid) {
+		c->cache_valid = false; // (the accepted totals, the tensor store and an open on-demand solve belong to the other solve)
+		c->e_real_valid = false; // (the next trial move evaluates in full: zodid keeps no tensor store for a store-only sweep to patch)
+		drop_pending_dipoles(c);
+	}
+	c->kept.relax_scheme = scheme;
+	c->kept.zodid = z;
+	return MPMC_OK;
+}
+extern "C" int mpmc_polar_relax_info(mpmc_ctx *c, mpmc_relax_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_relax_info: an evaluation is in flight");
+	*out = c->relax_info;
+	return MPMC_OK;
+}
+
 // ---- `polar_ewald_full` (System::ewald_full :2785-2830) ------------------------------------------------------------------------------------
 extern "C" int mpmc_set_polar_ewald_full(mpmc_ctx *c, int enabled, int flags) {
 	if (!c) return MPMC_ERR_ARG;

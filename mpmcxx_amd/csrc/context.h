@@ -138,6 +138,8 @@ struct mpmc_kept {
 	int rdm_form = 0, rdm_mix = 0;          // the rd model (mpmc_set_rd_model), likewise: MPMC_RD_FORM_*, MPMC_RD_MIX_*; (0, 0) = the plain term
 	bool pef_enabled = false;               // `polar_ewald_full` (mpmc_set_polar_ewald_full), likewise
 	int pef_flags = 0;                      // MPMC_PEF_*
+	int relax_scheme = 0;                   // `polar_sor` / `polar_esor` (mpmc_set_polar_relax), likewise: MPMC_POLAR_RELAX_*
+	bool zodid = false;                     // `polar_zodid`, likewise
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 };
 
@@ -393,6 +395,9 @@ struct mpmc_ctx {
 	bool pef_ran = false;            // the pending / last evaluation solved the dipoles with the term
 	mpmc_ewald_full_info pef_info{}; // of the last such evaluation (n_real_pairs filled by wait_and_fill)
 
+	// `polar_sor` / `polar_esor` / `polar_zodid` (mpmc_set_polar_relax; kept.relax_scheme, kept.zodid)
+	mpmc_relax_info relax_info{}; // of the pending / last evaluation with a dipole solve
+
 	std::vector<EvPair> ev_free, ev_used; // profiling (kept.prof): event pairs to reuse / recorded and not yet harvested into kept.tim
 
 	int64_t bytes_total = 0; // device memory held by this context's DevBuf members (mpmc_memory_usage)
@@ -584,6 +589,7 @@ unsigned full_mask(const mpmc_ctx *c);           // what double System::energy()
 // Gauss-Seidel sweeps (the only place where `polar_palmo` acts) or the direct solve.
 inline bool polar_moments_apply(const mpmc_ctx *c) {
 	const mpmc_options &o = c->opts;
+	if (c->kept.relax_scheme != 0 || c->kept.zodid) return false; // (relaxed iterations are no longer powers of one symmetric operator; zodid has none)
 	if (c->kept.pef_enabled) return false; // (ewald_full is not the symmetric Jacobi iteration; the setting acts only where the line below holds anyway)
 	return o.polarization && !o.rd_only && o.polar_iterative && o.polar_max_iter >= 1 && o.polar_max_iter <= kMomentsMaxIter && o.polar_gamma == 1.0 && o.polar_precision == 0.0 && !o.polar_rrms &&
 	       !o.polar_gs; // (`polar_palmo` acts under Gauss-Seidel sweeps only: under Jacobi its correction is zero and nothing runs)
@@ -604,6 +610,12 @@ inline void drop_pending_dipoles(mpmc_ctx *c) {
 inline bool direct_solve(const mpmc_ctx *c) { // `polar_iterative off` (ewald_full comes first, :2558-2563)
 	return c->opts.polarization && !c->opts.rd_only && !c->opts.polar_iterative && !ewald_full_on(c);
 }
+// `polar_zodid` acts where thole_iterative runs (:3470): polarization with polar_iterative on, and not under ewald_full (System::polar :2558)
+inline bool zodid_on(const mpmc_ctx *c) {
+	return c->kept.zodid && c->opts.polarization && !c->opts.rd_only && c->opts.polar_iterative && !ewald_full_on(c);
+}
+// the factor on mu_0 = alpha E0: polar_gamma, unless a relaxation scheme is on (init_dipoles :3555) or the solve is ewald_full's (:2944-2956)
+inline double start_gamma(const mpmc_ctx *c) { return (ewald_full_on(c) || c->kept.relax_scheme != 0) ? 1.0 : c->opts.polar_gamma; }
 // `polar_wolf` replaces the static field whenever polar_ewald is off (thole_field :3289-3294: polar_ewald wins)
 inline bool wolf_field_on(const mpmc_ctx *c) { return c->kept.pw_enabled && c->opts.polarization && !c->opts.rd_only && !field_is_ewald(c); }
 void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Feynman-Hibbs fields of the pair parameters (evaluate.cpp)

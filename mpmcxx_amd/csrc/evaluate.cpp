@@ -251,6 +251,8 @@ struct EvalPlan {
 	int want_rrms = 0, half = 0, last_it = 0, check_every = kCheckEvery;
 	double allowed = 0.0;
 	bool palmo = false;
+	bool zodid = false;       // `polar_zodid`: the solve is the start vector (thole_iterative :3470); no stage between the static field and the energy runs
+	int relax = RELAX_NONE;   // `polar_sor` / `polar_esor` in the iterative solves and under ewald_full (never read by the direct solve)
 	bool pef = false;         // `polar_ewald_full`: the solve is stage_ewald_full_solve's (by_precision and allowed as for the iterative solves)
 };
 
@@ -258,6 +260,7 @@ static inline size_t store_elements(const mpmc_ctx *c) { return (size_t)c->n_til
 // how the dipole iteration runs (room for what it stores: reserve_solver_store)
 static int choose_solver(const mpmc_ctx *c) {
 	if (ewald_full_on(c)) return MPMC_SOLVER_MATRIX_FREE; // `polar_ewald_full` keeps a store of its own (stage_ewald_full_solve): the sweep stores nothing
+	if (zodid_on(c)) return MPMC_SOLVER_MATRIX_FREE; // `polar_zodid`: no A matrix at all (System::polar :2548), nothing is stored
 	if (direct_solve(c)) return MPMC_SOLVER_MATRIX_FREE; // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
 	int want = c->opts.solver;
 	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
@@ -348,7 +351,10 @@ static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand
 	p.solve = (mask & RUN_SOLVE) != 0;
 	p.direct = p.solve && direct_solve(c);
 	p.pef = p.solve && ewald_full_on(c);
-	if (p.pef) { // (no rrms, no moments, never lazy: every entry runs all its passes)
+	p.zodid = p.solve && zodid_on(c);
+	p.relax = (p.solve && !p.direct && !p.zodid) ? c->kept.relax_scheme : RELAX_NONE;
+	if (p.zodid) { // (nothing below applies: no iteration, no rrms, no moments, no Palmo-Krimm contraction)
+	} else if (p.pef) { // (no rrms, no moments, never lazy: every entry runs all its passes)
 		p.by_precision = (o.polar_precision != 0.0);
 		p.allowed = p.by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
 	} else if (p.direct) {
@@ -483,7 +489,7 @@ static int make_room(mpmc_ctx *c, EvalPlan &p) {
 // vector.  Shared by the solve inside an evaluation and by finish_pending_dipoles, which runs the iterations an on-demand evaluation
 // left undone: same kernels, same tables, same order.  dk (may be null): this iteration's slot of the ring of dipole differences.
 static void enqueue_jacobi_iteration(mpmc_ctx *c, const AtomsDev &at, const JacobiPlan &jp, int it, int want_rrms, double allowed, int *ctl, int *host_flag,
-                                     double *dk) {
+                                     double *dk, const RelaxWeights *relax = nullptr /*`polar_sor` / `polar_esor`: this iteration's weights*/) {
 	hipStream_t st = c->stream;
 	const mpmc_options &o = c->opts;
 	const int *converged = ctl ? ctl + 1 : nullptr;
@@ -510,10 +516,10 @@ static void enqueue_jacobi_iteration(mpmc_ctx *c, const AtomsDev &at, const Jaco
 		ProfScope p(c, MPMC_K_REDUCE);
 		if (jp.compact && c->panels_built && !jp.dense)
 			launch_dipole_update_panel(st, at, c->d_e_static, c->d_part, c->d_gpart, c->d_seg, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur],
-			                           c->d_e_induced, want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk);
+			                           c->d_e_induced, want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk, relax);
 		else
 			launch_dipole_update(st, at, c->d_e_static, c->d_part, jp.iter_slots, c->d_mu[c->mu_cur], c->d_mu[1 - c->mu_cur], c->d_e_induced,
-			                     want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk);
+			                     want_rrms, c->d_rrms, allowed, ctl, host_flag, it, dk, relax);
 	}
 	c->mu_cur = 1 - c->mu_cur;
 }
@@ -673,13 +679,12 @@ static int stage_pair_reduce(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &, c
 static int stage_static_field(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
 	if (!(p.mask & RUN_FIELD)) return MPMC_OK;
 	hipStream_t st = c->stream;
-	const mpmc_options &o = c->opts;
 	ProfScope ps(c, MPMC_K_FIELD);
 	c->mu_cur = 0;
 	if (wolf_field_on(c)) // thole_field_wolf (:3337-3396) into the real-space slots, behind the classes of the pairwise pass
 		launch_wolf_field(st, at, c->box, wolf_field_params(c->kept.pw_alpha, c->box.cutoff), c->d_tile_pairs, c->d_cls, c->n_tile_pairs, c->d_part);
-	// (`polar_ewald_full`: mu_0 = alpha E0 without polar_gamma, init_dipoles_ewald :2944-2956)
-	launch_field_finalize(st, at, c->box, field_is_ewald(c) ? 1 : 0, c->d_e_recip_part, c->d_part, c->n_tiles, ewald_full_on(c) ? 1.0 : o.polar_gamma, c->d_e_static,
+	// (`polar_ewald_full`: mu_0 = alpha E0 without polar_gamma, init_dipoles_ewald :2944-2956; nor under `polar_sor` / `polar_esor`, :3555)
+	launch_field_finalize(st, at, c->box, field_is_ewald(c) ? 1 : 0, c->d_e_recip_part, c->d_part, c->n_tiles, start_gamma(c), c->d_e_static,
 	                      c->d_mu[0], c->d_e_real, polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 	c->e_real_valid = (p.mask == full_mask(c)); // (with the accepted positions resident: what trial moves update incrementally)
 	return MPMC_OK;
@@ -723,6 +728,11 @@ static int stage_direct_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at
 
 // what an iterative solve leaves behind after `it` iterations
 static void close_solve(mpmc_ctx *c, const EvalPlan &p, int it) {
+	const int ran = c->failed ? it - 1 : it; // (a failed solve stops in front of its 128th contraction)
+	c->relax_info.acted = (p.relax != RELAX_NONE && ran > 0) ? 1 : 0;
+	c->relax_info.contractions = ran;
+	c->relax_info.last_weight = relax_weights(p.relax, c->opts.polar_gamma, ran).w_new;
+	c->relax_info.store_filled = (p.compact || p.jp.dense) ? 1 : 0;
 	c->iters = p.lazy ? c->opts.polar_max_iter : it; // (what the solve comes to once its dipoles are asked for)
 	c->polar_pending = p.lazy ? mpmc_ctx::PEND_OPEN : mpmc_ctx::PEND_NONE;
 	c->pend_done = it, c->pend_target = c->opts.polar_max_iter;
@@ -730,7 +740,7 @@ static void close_solve(mpmc_ctx *c, const EvalPlan &p, int it) {
 
 // Gauss-Seidel sweeps: in place, in atom order; the host asks for the verdict of a precision-terminated solve after every sweep
 static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
-	if (!p.solve || p.direct || p.pef || !p.gs) return MPMC_OK;
+	if (!p.solve || p.direct || p.pef || p.zodid || !p.gs) return MPMC_OK;
 	hipStream_t st = c->stream;
 	const mpmc_options &o = c->opts;
 	{ // the in-tile blocks of the sweeps: positions and polarizabilities only, once per evaluation
@@ -746,9 +756,9 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 			break;
 		}
 		if (p.by_precision) HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), st));
-		// in-place sweep in atom order; old_mu is kept only when rrms / precision need it (:3503-3507)
+		// in-place sweep in atom order; old_mu is kept only when rrms / precision or a relaxation scheme need it (:3503-3507)
 		double *mu = c->d_mu[c->mu_cur], *mu_old = c->d_mu[1 - c->mu_cur];
-		if (p.want_rrms) HIP_TRY(c, hipMemcpyAsync(mu_old, mu, 3 * (size_t)at.n_pad * sizeof(double), hipMemcpyDeviceToDevice, st));
+		if (p.want_rrms || p.relax) HIP_TRY(c, hipMemcpyAsync(mu_old, mu, 3 * (size_t)at.n_pad * sizeof(double), hipMemcpyDeviceToDevice, st));
 		{
 			ProfScope ps(c, MPMC_K_DIPOLE_ITER);
 			launch_gs_sweep(st, at, c->box, o.polar_damp, c->d_e_static, mu, c->d_e_induced, c->d_part, c->d_tile_pairs, c->d_cls,
@@ -757,6 +767,12 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 		if (p.want_rrms) {
 			ProfScope ps(c, MPMC_K_REDUCE);
 			launch_gs_finish(st, at, mu_old, mu, p.want_rrms, c->d_rrms, p.allowed, c->d_flag);
+		}
+		if (p.relax) { // :3526-3536, behind rrms and the verdict, which saw the swept values: the blend goes where old_mu was and becomes the
+			// current vector; the swept one stays in the other buffer, where stage_palmo finds it
+			ProfScope ps(c, MPMC_K_REDUCE);
+			launch_gs_blend(st, at, mu, mu_old, mu_old, relax_weights(p.relax, o.polar_gamma, it));
+			c->mu_cur = 1 - c->mu_cur;
 		}
 		if (p.by_precision) {
 			HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -771,7 +787,7 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 }
 
 static int stage_jacobi_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
-	if (!p.solve || p.direct || p.pef || p.gs) return MPMC_OK;
+	if (!p.solve || p.direct || p.pef || p.zodid || p.gs) return MPMC_OK;
 	hipStream_t st = c->stream;
 	const mpmc_options &o = c->opts;
 	const size_t dk_stride = 3 * (size_t)at.n_pad;
@@ -798,7 +814,9 @@ static int stage_jacobi_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at
 			c->failed = 1;
 			break;
 		}
-		enqueue_jacobi_iteration(c, at, p.jp, it, p.want_rrms, p.allowed, ctl, host_flag, (p.moments && it <= p.half) ? c->d_dk_ring + (size_t)it * dk_stride : nullptr);
+		const RelaxWeights rw = relax_weights(p.relax, o.polar_gamma, it); // (every launch of a batch carries its own: they depend on `it` alone)
+		enqueue_jacobi_iteration(c, at, p.jp, it, p.want_rrms, p.allowed, ctl, host_flag, (p.moments && it <= p.half) ? c->d_dk_ring + (size_t)it * dk_stride : nullptr,
+		                         p.relax ? &rw : nullptr);
 		if (p.by_precision) {
 			if (it % p.check_every == 0 || it + 1 >= kMaxIterationCount) { // the verdict of this batch
 				HIP_TRY(c, hipGetLastError());
@@ -864,8 +882,9 @@ static int stage_ewald_full_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev
 		}
 		{
 			ProfScope ps(c, MPMC_K_REDUCE);
+			const RelaxWeights rw = relax_weights(p.relax, o.polar_gamma, passes + 1); // (the 0-based counter + 1, :3196-3204)
 			launch_pef_finish(st, at, ep, c->d_e_static, c->d_part, c->n_tiles, phases, rcp.kvec, rcp.kw, c->K, c->d_pef_psum, c->d_mu[c->mu_cur],
-			                  c->d_mu[1 - c->mu_cur], c->d_e_induced, p.by_precision ? c->d_flag.p : nullptr);
+			                  c->d_mu[1 - c->mu_cur], c->d_e_induced, p.by_precision ? c->d_flag.p : nullptr, p.relax ? &rw : nullptr);
 		}
 		c->mu_cur = 1 - c->mu_cur;
 		if (p.by_precision) { // are_we_done_yet :3227-3236
@@ -884,6 +903,10 @@ static int stage_ewald_full_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev
 	c->pef_info.passes = passes;
 	c->pef_info.n_k = c->K;
 	c->pef_info.store_bytes = (int64_t)(c->d_pef_store.cap * sizeof(double2));
+	c->relax_info.acted = (p.relax != RELAX_NONE && passes > 0) ? 1 : 0;
+	c->relax_info.contractions = passes;
+	c->relax_info.last_weight = relax_weights(p.relax, o.polar_gamma, passes).w_new;
+	c->relax_info.store_filled = 1;
 	return MPMC_OK;
 }
 
@@ -892,6 +915,12 @@ static int stage_ewald_full_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev
 static int stage_polar_energy(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
 	if (!p.solve) return MPMC_OK;
 	hipStream_t st = c->stream;
+	if (p.zodid) { // mu = mu_0, which the static field's finalize (or the trial move's) has just written; no induced field (:3470)
+		c->mu_cur = 0;
+		HIP_TRY(c, hipMemsetAsync(c->d_e_induced, 0, 3 * (size_t)at.n_pad * sizeof(double), st));
+		c->polar_pending = mpmc_ctx::PEND_NONE;
+		c->relax_info.acted = 1;
+	}
 	const double *mu = c->d_mu[c->mu_cur], *rrms = p.want_rrms ? c->d_rrms.p : nullptr;
 	ProfScope ps(c, MPMC_K_REDUCE);
 	if (p.moments && p.reduce_in_tail)
@@ -914,9 +943,13 @@ static int stage_palmo(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const
 	if (!p.palmo || c->failed) return MPMC_OK;
 	double *mu = c->d_mu[c->mu_cur];
 	// (the slots summed by the update kernel: d_palmo_f = F; its new dipoles go to the spare vector and are dropped, rrms untouched)
-	contract_into_field(c, at, mu, c->d_mu[1 - c->mu_cur], c->d_palmo_f, true,
+	// Under `polar_sor` / `polar_esor` palmo_contraction runs in front of the blend (:3517-3536): it contracts the swept dipoles, which the
+	// last sweep left in the other vector, and the energy term takes the blended ones; the spare is then d_palmo_change, rewritten behind.
+	double *contracted = p.relax ? c->d_mu[1 - c->mu_cur].p : mu, *spare = p.relax ? c->d_palmo_change.p : c->d_mu[1 - c->mu_cur].p;
+	contract_into_field(c, at, contracted, spare, c->d_palmo_f, true,
 	                    [&] { launch_palmo_reduce(c->stream, at, mu, c->d_palmo_f, c->d_e_induced, c->d_palmo_change, c->d_scal); });
 	c->palmo_ran = true;
+	c->relax_info.contractions += 1;
 	return MPMC_OK;
 }
 
@@ -991,6 +1024,18 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 		if (c->opts.polar_precision == 0.0 && c->opts.polar_max_iter < 0)
 			return fail(c, MPMC_ERR_INVALID_SETTING, "polar_ewald_full: polar_max_iter must be >= 0 when polar_precision is 0 (the reference never terminates)");
 		if (c->opts.polar_precision < 0.0) return fail(c, MPMC_ERR_INVALID_SETTING, "polar_ewald_full: polar_precision < 0");
+	}
+	if ((mask & RUN_SOLVE) && c->opts.polarization && !c->opts.rd_only) {
+		if (c->kept.zodid && !c->opts.polar_iterative)
+			return fail(c, MPMC_ERR_INCOMPATIBLE, "polar_zodid with polar_iterative off: the zeroth-order dipoles are the iterative solver's start (SimulationControl.cpp:2634)");
+		if (c->kept.relax_scheme != RELAX_NONE && c->opts.polar_gamma < 0.0)
+			return fail(c, MPMC_ERR_INVALID_SETTING, "polar_sor / polar_esor: polar_gamma must not be negative (SimulationControl.cpp:2714-2730)");
+	}
+	if (mask & RUN_SOLVE) {
+		c->relax_info = mpmc_relax_info{};
+		c->relax_info.scheme = c->kept.relax_scheme;
+		c->relax_info.zodid = c->kept.zodid ? 1 : 0;
+		c->relax_info.last_weight = 1.0;
 	}
 	c->static_ride_gen = 0;
 	c->run_mask = mask;

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "pair_math.h"
+#include "polar_relax.h"
 
 namespace mpmc {
 
@@ -114,7 +115,8 @@ void launch_field_finalize(hipStream_t st, const AtomsDev &at, const Box &bx, in
 void launch_dipole_update(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, int n_split,
                           const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom,
                           double allowed_sqerr, int *ctl, int *host_flag /*pinned {closed iteration, converged-at}, may be null*/, int it,
-                          double *dk = nullptr /*new_mu - mu_old per component: this iteration's slot of the ring of dipole differences*/);
+                          double *dk = nullptr /*new_mu - mu_old per component: this iteration's slot of the ring of dipole differences*/,
+                          const RelaxWeights *relax = nullptr /*`polar_sor` / `polar_esor`: the relaxed instantiation stores w_new new_mu + w_old mu_old*/);
 // iterator failure: mu = alpha * E0
 void launch_dipole_reset(hipStream_t st, const AtomsDev &at, const double *e_static, double *mu);
 // end of an evaluation: the scalar block [S_COUNT doubles][C_COUNT int64] goes to pinned host memory, the launch number behind it (a host
@@ -242,7 +244,7 @@ void launch_dipole_iter_panel(hipStream_t st, const AtomsDev &at, const Box &bx,
 // new_mu = alpha (E0 + F) from the panel kernel's slots, one workgroup per tile (the launch that follows every panel contraction)
 void launch_dipole_update_panel(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, const double *gpart, const int *seg,
                                 const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr,
-                                int *ctl, int *host_flag, int it, double *dk = nullptr /*as launch_dipole_update*/);
+                                int *ctl, int *host_flag, int it, double *dk = nullptr /*as launch_dipole_update*/, const RelaxWeights *relax = nullptr /*likewise*/);
 // lane-rotation primitive self-test: out[l] = lane whose value lane l received (must be (l+1)&63)
 void launch_rot_selftest(hipStream_t st, int *out);
 
@@ -282,6 +284,8 @@ void launch_gs_sweep(hipStream_t st, const AtomsDev &at, const Box &bx, double p
                      const double2 *blocks);
 void launch_gs_finish(hipStream_t st, const AtomsDev &at, const double *mu_old, const double *mu_new, int want_rrms, double *rrms_atom,
                       double allowed_sqerr, int *not_done_flag);
+// `polar_sor` / `polar_esor` behind a sweep (:3526-3536): out = w_new mu_swept + w_old mu_old for every slot; out may be mu_old itself
+void launch_gs_blend(hipStream_t st, const AtomsDev &at, const double *mu_swept, const double *mu_old, double *out, const RelaxWeights &w);
 
 // ---- trial moves (kernels_delta.hip) ----------------------------------------------------------------------
 // out4 = { d lj_pairs, d es_real(erfc part), d intramolecular term, E_recip of the trial structure factors }, dcnt2 = { d n_lj, d n_es }
@@ -423,7 +427,7 @@ void launch_pef_sf(hipStream_t st, const AtomsDev &at, const double4 *kvec, int 
 // more than the allowed amount
 void launch_pef_finish(hipStream_t st, const AtomsDev &at, const EwaldFullParams &ep, const double *e_static, const double *part, int n_tiles,
                        const double2 *phases, const double4 *kvec, const double4 *kw, int K, const double *psum, const double *mu_old, double *mu_new,
-                       double *e_induced, int *not_done);
+                       double *e_induced, int *not_done, const RelaxWeights *relax = nullptr /*new_dipoles :3196-3204: new_mu itself is the blend, the verdict sees it*/);
 
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);

@@ -547,11 +547,14 @@ __device__ __forceinline__ void iteration_verdict(int *__restrict__ ctl, int *__
 }
 
 // contract_dipoles tail :3586-3593, calc_dipole_rrms :3147-3177, are_we_done_yet :3227-3236
+// RELAX (`polar_sor` / `polar_esor`, :3526-3536): rrms, the verdict and dk come from the unrelaxed new_mu; what is stored for the next
+// iteration is w_new new_mu + w_old old_mu.  The plain instantiation never looks at the weights.
+template <bool RELAX>
 __device__ __forceinline__ void dipole_update_block(const AtomsDev &at, const double *__restrict__ e_static, const double *__restrict__ part,
                                                     int n_split, const double *__restrict__ mu_old, double *__restrict__ mu_new,
                                                     double *__restrict__ e_induced, int want_rrms, double *__restrict__ rrms_atom,
                                                     double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it,
-                                                    double *__restrict__ dk) {
+                                                    double *__restrict__ dk, double w_new = 1.0, double w_old = 0.0) {
 	__shared__ double sh[kSlotGroups][kTile][3];
 	if (ctl && ctl[1] != 0) return; // converged in an earlier iteration (block-uniform)
 	const int a = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -571,11 +574,13 @@ __device__ __forceinline__ void dipole_update_block(const AtomsDev &at, const do
 	bool broke = false;
 	double acc = 0, nn = 0;
 	for (int p = 0; p < 3; ++p) {
-		const double d = nm[p] - mu_old[3 * (size_t)i + p];
+		const double mo = mu_old[3 * (size_t)i + p];
+		const double d = nm[p] - mo;
 		acc += d * d;
 		nn += nm[p] * nm[p];
 		if (d * d > allowed_sqerr) broke = true;
-		mu_new[3 * (size_t)i + p] = nm[p];
+		if constexpr (RELAX) mu_new[3 * (size_t)i + p] = relax_blend(w_new, w_old, nm[p], mo);
+		else mu_new[3 * (size_t)i + p] = nm[p];
 		e_induced[3 * (size_t)i + p] = f[p];
 		if (dk) dk[3 * (size_t)i + p] = d;
 	}
@@ -591,7 +596,15 @@ __global__ __launch_bounds__(512) void k_dipole_update(AtomsDev at, const double
                                                        double *__restrict__ e_induced, int want_rrms, double *__restrict__ rrms_atom,
                                                        double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it,
                                                        double *__restrict__ dk) {
-	dipole_update_block(at, e_static, part, n_split, mu_old, mu_new, e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
+	dipole_update_block<false>(at, e_static, part, n_split, mu_old, mu_new, e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
+}
+__global__ __launch_bounds__(512) void k_dipole_update_relax(AtomsDev at, const double *__restrict__ e_static, const double *__restrict__ part,
+                                                             int n_split, const double *__restrict__ mu_old, double *__restrict__ mu_new,
+                                                             double *__restrict__ e_induced, int want_rrms, double *__restrict__ rrms_atom,
+                                                             double allowed_sqerr, int *__restrict__ ctl, int *__restrict__ host_flag, int it,
+                                                             double *__restrict__ dk, RelaxWeights w) {
+	dipole_update_block<true>(at, e_static, part, n_split, mu_old, mu_new, e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk,
+	                          w.w_new, w.w_old);
 }
 
 __global__ __launch_bounds__(256) void k_dipole_reset(AtomsDev at, const double *__restrict__ e_static, double *__restrict__ mu) {
@@ -751,9 +764,13 @@ __global__ __launch_bounds__(256) void k_polar_energy_and_pairs(AtomsDev at, con
 
 void launch_dipole_update(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, int n_split, const double *mu_old,
                           double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr, int *ctl, int *host_flag, int it,
-                          double *dk) {
-	hipLaunchKernelGGL(k_dipole_update, dim3(at.n_pad / kTile), dim3(kTile * kSlotGroups), 0, st, at, e_static, part, n_split, mu_old, mu_new,
-	                   e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
+                          double *dk, const RelaxWeights *relax) {
+	if (relax)
+		hipLaunchKernelGGL(k_dipole_update_relax, dim3(at.n_pad / kTile), dim3(kTile * kSlotGroups), 0, st, at, e_static, part, n_split, mu_old, mu_new,
+		                   e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk, *relax);
+	else
+		hipLaunchKernelGGL(k_dipole_update, dim3(at.n_pad / kTile), dim3(kTile * kSlotGroups), 0, st, at, e_static, part, n_split, mu_old, mu_new,
+		                   e_induced, want_rrms, rrms_atom, allowed_sqerr, ctl, host_flag, it, dk);
 }
 void launch_dipole_reset(hipStream_t st, const AtomsDev &at, const double *e_static, double *mu) {
 	hipLaunchKernelGGL(k_dipole_reset, dim3((at.n_pad + 255) / 256), dim3(256), 0, st, at, e_static, mu);

@@ -202,12 +202,14 @@ __global__ __launch_bounds__(256) void k_pef_sf(AtomsDev at, const double4 *__re
 }
 
 constexpr int kPefGroups = 8; // waves of a finish workgroup: each takes every eighth k vector and every eighth slot of its tile's 64 atoms
-template <bool CACHED>
-__global__ __launch_bounds__(kTile * kPefGroups) void k_pef_finish(AtomsDev at, EwaldFullParams ep, const double *__restrict__ e_static, const double *__restrict__ part,
-                                                                   int n_tiles, const double2 *__restrict__ phases, const double4 *__restrict__ kvec,
-                                                                   const double4 *__restrict__ kw, int K, const double *__restrict__ psum,
-                                                                   const double *__restrict__ mu_old, double *__restrict__ mu_new, double *__restrict__ e_induced,
-                                                                   int *__restrict__ not_done) {
+// RELAX (`polar_sor` / `polar_esor`, new_dipoles :3196-3204): new_mu itself becomes w_new new_mu + w_old old_mu, so the verdict compares the
+// blend with the old dipoles.  The plain instantiation never looks at the weights.
+template <bool CACHED, bool RELAX>
+__device__ __forceinline__ void pef_finish_block(const AtomsDev &at, const EwaldFullParams &ep, const double *__restrict__ e_static, const double *__restrict__ part,
+                                                 int n_tiles, const double2 *__restrict__ phases, const double4 *__restrict__ kvec,
+                                                 const double4 *__restrict__ kw, int K, const double *__restrict__ psum,
+                                                 const double *__restrict__ mu_old, double *__restrict__ mu_new, double *__restrict__ e_induced,
+                                                 int *__restrict__ not_done, double w_new = 1.0, double w_old = 0.0) {
 	__shared__ double sh[kPefGroups][6][kTile];
 	const int a = threadIdx.x & (kTile - 1), g = threadIdx.x >> 6;
 	const int i = blockIdx.x * kTile + a; // (< n_pad: one workgroup per tile)
@@ -241,12 +243,30 @@ __global__ __launch_bounds__(kTile * kPefGroups) void k_pef_finish(AtomsDev at, 
 		const double m = mu_old[b + p];
 		const double ei = (ep_real + ep.recip_scale * ep_recip) + (ep.c_total * psum[2 * K + p] + ep.c_self * m); // :3140
 		e_induced[b + p] = ei;
-		const double nm = at.alpha[i] * (e_static[b + p] + ei); // :3203
+		double nm = at.alpha[i] * (e_static[b + p] + ei); // :3203
+		if constexpr (RELAX) nm = relax_blend(w_new, w_old, nm, m);
 		mu_new[b + p] = nm;
 		const double d = nm - m;
 		broke = broke || (d * d > ep.allowed_sqerr);
 	}
 	if (not_done && broke) *not_done = 1; // (every writer stores the same value)
+}
+template <bool CACHED>
+__global__ __launch_bounds__(kTile * kPefGroups) void k_pef_finish(AtomsDev at, EwaldFullParams ep, const double *__restrict__ e_static, const double *__restrict__ part,
+                                                                   int n_tiles, const double2 *__restrict__ phases, const double4 *__restrict__ kvec,
+                                                                   const double4 *__restrict__ kw, int K, const double *__restrict__ psum,
+                                                                   const double *__restrict__ mu_old, double *__restrict__ mu_new, double *__restrict__ e_induced,
+                                                                   int *__restrict__ not_done) {
+	pef_finish_block<CACHED, false>(at, ep, e_static, part, n_tiles, phases, kvec, kw, K, psum, mu_old, mu_new, e_induced, not_done);
+}
+template <bool CACHED>
+__global__ __launch_bounds__(kTile * kPefGroups) void k_pef_finish_relax(AtomsDev at, EwaldFullParams ep, const double *__restrict__ e_static,
+                                                                         const double *__restrict__ part, int n_tiles, const double2 *__restrict__ phases,
+                                                                         const double4 *__restrict__ kvec, const double4 *__restrict__ kw, int K,
+                                                                         const double *__restrict__ psum, const double *__restrict__ mu_old,
+                                                                         double *__restrict__ mu_new, double *__restrict__ e_induced, int *__restrict__ not_done,
+                                                                         RelaxWeights w) {
+	pef_finish_block<CACHED, true>(at, ep, e_static, part, n_tiles, phases, kvec, kw, K, psum, mu_old, mu_new, e_induced, not_done, w.w_new, w.w_old);
 }
 
 void launch_pef_fill(hipStream_t st, const AtomsDev &at, const Box &bx, double ewald_a, double polar_damp, const int2 *tile_pairs, const int *cls,
@@ -273,10 +293,14 @@ void launch_pef_sf(hipStream_t st, const AtomsDev &at, const double4 *kvec, int 
 }
 void launch_pef_finish(hipStream_t st, const AtomsDev &at, const EwaldFullParams &ep, const double *e_static, const double *part, int n_tiles,
                        const double2 *phases, const double4 *kvec, const double4 *kw, int K, const double *psum, const double *mu_old, double *mu_new,
-                       double *e_induced, int *not_done) {
+                       double *e_induced, int *not_done, const RelaxWeights *relax) {
 	with_flag(phases != nullptr, [&](auto C) {
-		hipLaunchKernelGGL((k_pef_finish<C.value>), dim3(at.n_pad / kTile), dim3(kTile * kPefGroups), 0, st, at, ep, e_static, part, n_tiles, phases, kvec, kw, K, psum,
-		                   mu_old, mu_new, e_induced, not_done);
+		if (relax)
+			hipLaunchKernelGGL((k_pef_finish_relax<C.value>), dim3(at.n_pad / kTile), dim3(kTile * kPefGroups), 0, st, at, ep, e_static, part, n_tiles, phases, kvec, kw, K,
+			                   psum, mu_old, mu_new, e_induced, not_done, *relax);
+		else
+			hipLaunchKernelGGL((k_pef_finish<C.value>), dim3(at.n_pad / kTile), dim3(kTile * kPefGroups), 0, st, at, ep, e_static, part, n_tiles, phases, kvec, kw, K, psum,
+			                   mu_old, mu_new, e_induced, not_done);
 	});
 }
 

@@ -269,6 +269,16 @@ __global__ __launch_bounds__(256) void k_gs_finish(AtomsDev at, const double *__
 	if (allowed_sqerr > 0.0 && broke && i < at.n) atomicOr(not_done_flag, 1);
 }
 
+// (out may alias mu_old: every thread reads its own three components before it writes them)
+__global__ __launch_bounds__(256) void k_gs_blend(AtomsDev at, const double *__restrict__ mu_swept, const double *mu_old, double *out, RelaxWeights w) {
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= at.n_pad) return;
+	for (int p = 0; p < 3; ++p) {
+		const size_t k = 3 * (size_t)i + p;
+		out[k] = relax_blend(w.w_new, w.w_old, mu_swept[k], mu_old[k]);
+	}
+}
+
 void launch_gs_blocks(hipStream_t st, const AtomsDev &at, const Box &bx, double polar_damp, double2 *blocks) {
 	const int nt = at.n_pad / kTile;
 	if (bx.ortho) hipLaunchKernelGGL(k_gs_blocks<true>, dim3(nt), dim3(kTile * kGsWaves), 0, st, at, bx, polar_damp, blocks);
@@ -293,6 +303,9 @@ void launch_gs_finish(hipStream_t st, const AtomsDev &at, const double *mu_old, 
                       double allowed_sqerr, int *not_done_flag) {
 	hipLaunchKernelGGL(k_gs_finish, dim3((at.n_pad + 255) / 256), dim3(256), 0, st, at, mu_old, mu_new, want_rrms, rrms_atom, allowed_sqerr,
 	                   not_done_flag);
+}
+void launch_gs_blend(hipStream_t st, const AtomsDev &at, const double *mu_swept, const double *mu_old, double *out, const RelaxWeights &w) {
+	hipLaunchKernelGGL(k_gs_blend, dim3((at.n_pad + 255) / 256), dim3(256), 0, st, at, mu_swept, mu_old, out, w);
 }
 
 } // namespace mpmc

@@ -444,8 +444,11 @@ struct PanelUpdate {
 	int nt, it, want_rrms;
 };
 
+// RELAX (`polar_sor` / `polar_esor`): as dipole_update_block<true> in kernels.hip
+template <bool RELAX>
 __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const PanelUpdate &u, const double *__restrict__ part, const double *__restrict__ gpart,
-                                                  const double *__restrict__ mu_old, const int X, double (*__restrict__ sh)[kTile][3]) {
+                                                  const double *__restrict__ mu_old, const int X, double (*__restrict__ sh)[kTile][3], double w_new = 1.0,
+                                                  double w_old = 0.0) {
 	constexpr int GW = kUpdGroups / kUpdWaves; // groups per wave
 	const int a = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int i = X * kTile + a;
@@ -520,7 +523,8 @@ __device__ __forceinline__ void panel_update_tile(const AtomsDev &at, const Pane
 		acc += d * d;
 		nn += nm[p] * nm[p];
 		if (d * d > u.allowed_sqerr) broke = true;
-		u.mu_new[3 * (size_t)i + p] = nm[p];
+		if constexpr (RELAX) u.mu_new[3 * (size_t)i + p] = relax_blend(w_new, w_old, nm[p], mo[p]);
+		else u.mu_new[3 * (size_t)i + p] = nm[p];
 		if (u.e_induced) u.e_induced[3 * (size_t)i + p] = fo[p];
 		if (u.dk) u.dk[3 * (size_t)i + p] = d;
 	}
@@ -599,7 +603,13 @@ __global__ __launch_bounds__(64 * kUpdWaves) void k_dipole_update_panel(AtomsDev
                                                                         const double *__restrict__ mu_old, const PanelUpdate u) {
 	__shared__ double sh[kUpdGroups][kTile][3];
 	if (u.ctl && u.ctl[1] != 0) return; // converged in an earlier iteration (block-uniform)
-	panel_update_tile(at, u, part, gpart, mu_old, blockIdx.x, sh);
+	panel_update_tile<false>(at, u, part, gpart, mu_old, blockIdx.x, sh);
+}
+__global__ __launch_bounds__(64 * kUpdWaves) void k_dipole_update_panel_relax(AtomsDev at, const double *__restrict__ part, const double *__restrict__ gpart,
+                                                                              const double *__restrict__ mu_old, const PanelUpdate u, RelaxWeights w) {
+	__shared__ double sh[kUpdGroups][kTile][3];
+	if (u.ctl && u.ctl[1] != 0) return; // converged in an earlier iteration (block-uniform)
+	panel_update_tile<true>(at, u, part, gpart, mu_old, blockIdx.x, sh, w.w_new, w.w_old);
 }
 
 void launch_build_panels(hipStream_t st, const int *cls, int n_tiles, const int *seg, int4 *panels) {
@@ -619,12 +629,13 @@ void launch_dipole_iter_panel(hipStream_t st, const AtomsDev &at, const Box &bx,
 
 void launch_dipole_update_panel(hipStream_t st, const AtomsDev &at, const double *e_static, const double *part, const double *gpart, const int *seg,
                                 const double *mu_old, double *mu_new, double *e_induced, int want_rrms, double *rrms_atom, double allowed_sqerr,
-                                int *ctl, int *host_flag, int it, double *dk) {
+                                int *ctl, int *host_flag, int it, double *dk, const RelaxWeights *relax) {
 	PanelUpdate u{};
 	u.dk = dk;
 	u.e_static = e_static, u.seg = seg, u.mu_new = mu_new, u.e_induced = e_induced, u.rrms_atom = rrms_atom, u.allowed_sqerr = allowed_sqerr;
 	u.ctl = ctl, u.host_flag = host_flag, u.nt = at.n_pad / kTile, u.it = it, u.want_rrms = want_rrms;
-	hipLaunchKernelGGL(k_dipole_update_panel, dim3(at.n_pad / kTile), dim3(kTile * kUpdWaves), 0, st, at, part, gpart, mu_old, u);
+	if (relax) hipLaunchKernelGGL(k_dipole_update_panel_relax, dim3(at.n_pad / kTile), dim3(kTile * kUpdWaves), 0, st, at, part, gpart, mu_old, u, *relax);
+	else hipLaunchKernelGGL(k_dipole_update_panel, dim3(at.n_pad / kTile), dim3(kTile * kUpdWaves), 0, st, at, part, gpart, mu_old, u);
 }
 
 } // namespace mpmc

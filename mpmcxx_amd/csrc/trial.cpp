@@ -188,11 +188,16 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 			}
 			c->mu_cur = 0;
 			if (polar_moments_apply(c) && (rc = reserve_dk_ring(c)) != MPMC_OK) return rc;
-			launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_e_real_trial, 1, o.polar_gamma, c->d_e_static, c->d_mu[0], nullptr,
+			launch_field_finalize(st, at, c->box, o.polar_ewald, c->d_e_recip_part, c->d_e_real_trial, 1, start_gamma(c), c->d_e_static, c->d_mu[0], nullptr,
 			                      polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 		}
 		HIP_TRY(c, hipGetLastError());
 		c->trial_polar_delta = true;
+		if (zodid_on(c)) { // `polar_zodid`: the dipoles are the start vector just written: no classes, no store, no iteration -- the reduction closes the move
+			if ((rc = enqueue(c, RUN_SOLVE)) != MPMC_OK) return rc;
+			c->trial_enqueued = true;
+			return MPMC_OK;
+		}
 		// the store-only sweep rebuilds the tile pairs of the tiles the moved atoms live in, and of the tiles a rejected trial left behind:
 		// no other tile pair's geometry (or class) changed
 		c->trial_tiles.clear();

@@ -109,6 +109,25 @@ class EwaldFullInfo(C.Structure):
 PEF_VECTOR_KWEIGHT = 1  # MPMC_PEF_VECTOR_KWEIGHT
 
 
+class RelaxInfo(C.Structure):
+    """mpmc_relax_info: the last evaluation with a dipole solve of a context (mpmc_polar_relax_info)."""
+    _fields_ = [("scheme", C.c_int32), ("zodid", C.c_int32), ("acted", C.c_int32), ("store_filled", C.c_int32), ("contractions", C.c_int64),
+                ("last_weight", C.c_double)]
+
+
+POLAR_RELAX = {"none": 0, "sor": 1, "esor": 2}  # MPMC_POLAR_RELAX_*
+POLAR_RELAX_KEYS = ("polar_sor", "polar_esor", "polar_zodid")
+
+
+def polar_relax_of(options: Dict[str, object]):
+    """(scheme, zodid) of the option keys `polar_sor` / `polar_esor` / `polar_zodid`; both schemes together are refused as the reference
+    refuses them (SimulationControl.cpp:2714-2730)"""
+    sor, esor = bool(options.get("polar_sor")), bool(options.get("polar_esor"))
+    if sor and esor:
+        raise ValueError("polar_sor and polar_esor are both on")
+    return POLAR_RELAX["sor"] if sor else POLAR_RELAX["esor"] if esor else POLAR_RELAX["none"], bool(options.get("polar_zodid"))
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -189,6 +208,9 @@ def lib():
     if hasattr(L, "mpmc_set_polar_ewald_full") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the fully periodic dipole solve)
         L.mpmc_set_polar_ewald_full.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_polar_ewald_full_info.argtypes = [vp, C.POINTER(EwaldFullInfo)]
+    if hasattr(L, "mpmc_set_polar_relax") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the relaxed updates and zeroth-order dipoles)
+        L.mpmc_set_polar_relax.argtypes = [vp, C.c_int, C.c_int]
+        L.mpmc_polar_relax_info.argtypes = [vp, C.POINTER(RelaxInfo)]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -388,6 +410,10 @@ class System:
         if "polar_ewald_full" in options or getattr(self, "_polar_ewald_full_set", False):
             self._polar_ewald_full_set = True
             self.set_polar_ewald_full(bool(options.get("polar_ewald_full")), int(options.get("polar_ewald_full_flags") or 0))
+        # `polar_sor` / `polar_esor` / `polar_zodid` likewise (gamma stays the option polar_gamma)
+        if any(k in options for k in POLAR_RELAX_KEYS) or getattr(self, "_polar_relax_set", False):
+            self._polar_relax_set = True
+            self.set_polar_relax(*polar_relax_of(options))
 
     def set_atoms(self, atoms: Dict[str, np.ndarray]):
         f = lambda k: np.ascontiguousarray(atoms[k], dtype=np.float64)
@@ -446,6 +472,17 @@ class System:
         v = RdModelInfo()
         self._check(self._L.mpmc_rd_model_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdModelInfo._fields_}
+
+    def set_polar_relax(self, scheme=0, zodid: bool = False):
+        """`polar_sor` / `polar_esor` (scheme "sor" / "esor" or POLAR_RELAX[...]; "none" / 0 switches off) and `polar_zodid`
+        (mpmc_set_polar_relax); gamma is the option polar_gamma."""
+        self._check(self._L.mpmc_set_polar_relax(self._h, POLAR_RELAX[scheme] if isinstance(scheme, str) else int(scheme), int(bool(zodid))))
+
+    def polar_relax_info(self) -> Dict[str, float]:
+        """scheme, zodid, acted, store_filled, contractions and last_weight of the last evaluation with a dipole solve (mpmc_polar_relax_info)"""
+        v = RelaxInfo()
+        self._check(self._L.mpmc_polar_relax_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in RelaxInfo._fields_}
 
     def set_polar_ewald_full(self, enabled: bool, flags: int = 0):
         """`polar_ewald_full`: the induced field of the dipole solve as an Ewald sum as well (mpmc_set_polar_ewald_full); it replaces the

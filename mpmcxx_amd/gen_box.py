@@ -341,6 +341,8 @@ def fixture(name: str):
         return _ewald_full_fixture(name)
     if name in RD_MODEL_FIXTURES:
         return _rd_model_fixture(name)
+    if name in RELAX_FIXTURES:
+        return _relax_fixture(name)
     raise KeyError(name)
 
 
@@ -876,6 +878,97 @@ def ewald_full_golden(golden_dir: str, name: str) -> Dict[str, object]:
     return g
 
 
+# ---- `polar_sor` / `polar_esor` / `polar_zodid` (reference src/System.Energy.cpp:3450-3560, 3181-3211) ---------------------------------------
+# NAME = BASE_rx_VARIANT: the box BASE with a relaxed dipole update or zeroth-order dipoles.  None = the keyword is taken out.
+RELAX_VARIANTS = {
+    "sor08": {"polar_sor": "on", "polar_gamma": 0.8},                                      # Jacobi, 10 iterations
+    "sor12": {"polar_sor": "on", "polar_gamma": 1.2},                                      # over-relaxed
+    "esor06": {"polar_esor": "on", "polar_gamma": 0.6},
+    "sorp": {"polar_sor": "on", "polar_gamma": 0.8, "polar_precision": 1e-7, "polar_rrms": "on", "polar_max_iter": None},
+    "esorp": {"polar_esor": "on", "polar_gamma": 0.6, "polar_precision": 1e-7, "polar_rrms": "on", "polar_max_iter": None},
+    "sorfail": {"polar_sor": "on", "polar_gamma": 2.5, "polar_precision": 1e-7, "polar_max_iter": None},  # diverges: 128 iterations, iterator_failed
+    "gssor": {"polar_gs": "on", "polar_sor": "on", "polar_gamma": 0.9, "polar_max_iter": 6},   # Gauss-Seidel sweeps, blended behind each
+    "gsesorp": {"polar_gs": "on", "polar_esor": "on", "polar_gamma": 0.7, "polar_max_iter": 6, "polar_palmo": "on"},  # ... + Palmo-Krimm
+    "gsesor4": {"polar_gs": "on", "polar_esor": "on", "polar_gamma": 0.7, "polar_max_iter": 4},
+    "zodid": {"polar_zodid": "on"},
+    "zodidg": {"polar_zodid": "on", "polar_gamma": 1.03},                                  # the start vector carries polar_gamma
+    "zodidsor": {"polar_zodid": "on", "polar_gamma": 1.03, "polar_sor": "on"},             # ... but not under a scheme
+    "zodidpalmo": {"polar_zodid": "on", "polar_palmo": "on"},                              # the correction is exactly 0
+    "zodidwolf": {"polar_zodid": "on", "polar_ewald": "off", "polar_wolf": "on", "polar_wolf_alpha": 0.13},
+    "pefsor": {"polar_ewald_full": "on", "polar_sor": "on", "polar_gamma": 0.8},
+    "pefesor": {"polar_ewald_full": "on", "polar_esor": "on", "polar_gamma": 0.6},
+    "pefsorp": {"polar_ewald_full": "on", "polar_sor": "on", "polar_gamma": 0.8, "polar_precision": 1e-7, "polar_max_iter": None},
+    "pefzodid": {"polar_ewald_full": "on", "polar_zodid": "on"},                           # zodid changes nothing under ewald_full
+}
+RELAX_FIXTURES = [f"ion216_polar_rx_{v}" for v in RELAX_VARIANTS if v != "gsesor4"] + [
+    f"{b}_rx_{v}" for b in ("ion216_polar_nopbc", "ion216_triclinic", "water64_polar") for v in ("sor08", "esor06", "gssor", "zodid")] + [
+    "water64_polar_rx_sorp", "water64_polar_rx_gsesorp",  # non-polarizable sites, exclusions, strong coupling
+    "ion1000_gs_rx_gsesor4"]                              # 16 tiles: the blocked sweep, blended
+RELAX_SAMPLE_EVERY = 16  # boxes of more than 216 atoms keep the per-atom results of every 16th atom
+RELAX_GOLDEN = ("polar_relax.json", "polar_relax_atoms.npz")  # under tests/golden/: every fixture's scalars; the per-atom arrays
+
+
+def _relax_fixture(name: str):
+    base, variant = name.rsplit("_rx_", 1)
+    rows, basis, o = fixture(base)
+    o = dict(o, polar_gs="off", polar_max_iter=10)  # (ion1000_gs brings its own; the variant decides)
+    for k, v in RELAX_VARIANTS[variant].items():
+        if v is None:
+            o.pop(k, None)
+        else:
+            o[k] = v
+    return rows, basis, o
+
+
+def keep_relax_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <RELAX_FIXTURES>`: the per-fixture files are folded into RELAX_GOLDEN and removed, the box text
+    too (the tests regenerate it with `materialize`), the way keep_ewald_full_golden keeps its family."""
+    import json
+
+    import numpy as np
+
+    scalars, arrays, by_bytes = {}, {}, {}
+    for name in (names or RELAX_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        n = res["natoms"]
+        every = RELAX_SAMPLE_EVERY if n > 216 else 1
+        out = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+        out["sample_every"] = every
+        out["arrays"] = {}
+        for k in ("ef_static", "mu", "ef_induced"):
+            a = np.asarray(res[k], dtype=np.float64).reshape(-1, 3)
+            assert a.shape[0] == n, (name, k, a.shape)
+            a = a[::every]
+            key = by_bytes.setdefault(a.tobytes(), f"{name}.{k}")
+            arrays.setdefault(key, a)
+            out["arrays"][k] = key
+        scalars[name] = out
+    with open(os.path.join(golden_dir, RELAX_GOLDEN[0]), "w") as f:
+        json.dump(scalars, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    np.savez_compressed(os.path.join(golden_dir, RELAX_GOLDEN[1]), **arrays)
+    for name in (names or RELAX_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def relax_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    """one fixture of RELAX_GOLDEN: scalars, `sample_atoms`, and ef_static / mu / ef_induced as [k, 3] arrays"""
+    import json
+
+    import numpy as np
+
+    with open(os.path.join(golden_dir, RELAX_GOLDEN[0])) as f:
+        g = json.load(f)[name]
+    with np.load(os.path.join(golden_dir, RELAX_GOLDEN[1])) as z:
+        for k, key in g.pop("arrays").items():
+            g[k] = z[key]
+    g["sample_atoms"] = list(range(0, g["natoms"], g.pop("sample_every")))
+    return g
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -926,6 +1019,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-ewald-full-golden"]:
         keep_ewald_full_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-relax-golden"]:
+        keep_relax_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)

@@ -22,7 +22,7 @@ E2REDUCED = 408.7816  # reference src/constants.h:35
 # keywords that select physics outside SURVEY §8 -- the replacement must refuse them (§8a note 7)
 UNSUPPORTED_ON = [
     "spectre", "gwp", "sg", "polarvdw", "cdvdw",
-    "polar_wolf_full", "polar_wolf_alpha_lookup", "polar_gs_ranked", "polar_sor", "polar_esor", "polar_zodid",
+    "polar_wolf_full", "polar_wolf_alpha_lookup", "polar_gs_ranked",
     "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion",
     "disp_expansion_mbvdw", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
 ]
@@ -140,6 +140,8 @@ def read_input(path: str) -> Dict[str, object]:
                 opts[k] = _onoff(v[0])
             elif k == "polar_ewald_full":  # (likewise; the fully periodic dipole solve, mpmc_set_polar_ewald_full)
                 opts[k] = _onoff(v[0])
+            elif k in ("polar_sor", "polar_esor", "polar_zodid"):  # (likewise; relaxed dipole updates and zeroth-order dipoles, mpmc_set_polar_relax)
+                opts[k] = _onoff(v[0])
             elif k in ("waldmanhagler", "halgren_mixing", "c6_mixing", "lj_buffered_14_7", "dreiding"):  # (likewise; the rd model, mpmc_set_rd_model)
                 opts[k] = _onoff(v[0])
             elif k == "rd_crystal_order":
@@ -157,6 +159,8 @@ def read_input(path: str) -> Dict[str, object]:
             # everything else (job_name, temperature, numsteps, output switches, ...) does not enter energy()
     if sum(1 for k in ("waldmanhagler", "halgren_mixing", "c6_mixing") if opts.get(k)) > 1:  # (SimulationControl.cpp:1706-1713)
         raise ValueError(f"{path}: more than one mixing rule specified")
+    if opts.get("polar_sor") and opts.get("polar_esor"):  # (SimulationControl.cpp:2714-2730)
+        raise ValueError(f"{path}: polar_sor and polar_esor are both on")
     if pqr is None:
         raise ValueError(f"{path}: no pqr_input")
     return {"basis": basis, "pqr_input": os.path.join(os.path.dirname(os.path.abspath(path)), pqr), "options": opts,
