@@ -323,9 +323,8 @@ struct mpmc_ctx {
 	int touch_n = -1, touch[8] = {0}; // what enqueue(RUN_STORE) passes to the store-only sweep (-1: all tile pairs)
 	DevBuf<unsigned char> d_mv_blob; // device / pinned host staging of a trial's moved-atom list
 	PinnedBuf<unsigned char> h_mv_blob;
-	DevBuf<double> d_delta_out;
-	PinnedBuf<double> h_delta_out; // [12] = 5 doubles, 2 int64 counts, three-body delta (d_delta_out[7]), launch number (k_delta_finish posts it), disp-expansion delta (d_delta_out[8]),
-	                               // rd_crystal delta and the change of its image-term count (d_delta_out[9], [10])
+	DevBuf<double> d_delta_out;    // [D_COUNT]
+	PinnedBuf<double> h_delta_out; // [kDeltaHostCount]: d_delta_out's D_* slots at delta_host_index, the launch number k_delta_finish posts at kDeltaHostSeq (kernels.h)
 	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish

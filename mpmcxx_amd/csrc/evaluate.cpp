@@ -970,8 +970,7 @@ static int stage_added_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at,
 	// ---- rd_crystal, System::lj (:916-963): the lattice sum and its image-term count into their two slots ---------------------------------
 	if (p.mask & RUN_CRYSTAL) {
 		ProfScope ps(c, MPMC_K_PAIR);
-		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL,
-		               c->d_scal + S_CRYSTAL_TERMS);
+		launch_crystal(st, at, c->box, crystal_params(c), c->d_rc_shift, c->d_tile_pairs, c->n_tile_pairs, c->d_rc_part, c->d_scal + S_CRYSTAL);
 	}
 	// ---- the rd model (:113-127): the pair sum, its kept terms and the skipped tile pairs into their three slots.  Tile pairs beyond the
 	// cutoff are skipped by this evaluation's classes, where the pairwise pass made them and the cell is orthorhombic ----------------------

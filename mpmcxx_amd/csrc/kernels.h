@@ -1,4 +1,5 @@
-// kernels.h -- launch wrappers of the gfx950 kernels (implemented in kernels.hip), used by context.cpp.
+// kernels.h -- launch wrappers of the gfx950 kernels (implemented in the kernels*.hip files named section by section), the slots of the
+// result blocks, and the constants the host shares with them; used by context.cpp, evaluate.cpp and trial.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,6 +64,24 @@ enum : int {
 	S_COUNT = 20
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
+// slots of a trial move's result block on the device (d_delta_out): what launch_delta leaves, then one change per further term
+enum : int {
+	D_LJ = 0, D_ES_REAL, D_ES_INTRA, D_ES_RECIP, D_SPARE, // the five pair values (kernels_delta.hip; the spare one is written 0)
+	D_CNT_LJ, D_CNT_ES,                                   // the two int64 counts
+	D_THREE_BODY,                                         // Axilrod-Teller (kernels_three_body.hip)
+	D_DISP,                                               // disp-expansion (kernels_disp.hip)
+	D_RD, D_RD_TERMS,                                     // rd_crystal's lattice sum and image terms, OR the rd model's sum and kept terms
+	D_COUNT
+};
+// rd_crystal and the rd model share D_RD and D_RD_TERMS.  They never meet: a context with a model is not `rd_crystal on` (crystal_on is false
+// for it, context.h) and rd_model_ready refuses the combination, so at most one of launch_crystal_delta and launch_rd_model_delta runs
+// per move; each writes both slots.
+static_assert(D_RD_TERMS == D_RD + 1, "the delta launchers of the rd terms write { sum, terms } side by side");
+// the pinned host mirror (h_delta_out) holds the same slots with the launch number of k_delta_finish, which the host polls, in between:
+// that slot stays where it was before the later terms came
+constexpr int kDeltaHostSeq = D_THREE_BODY + 1;
+constexpr int kDeltaHostCount = D_COUNT + 1;
+constexpr int delta_host_index(int d) { return d < kDeltaHostSeq ? d : d + 1; }
 // tile-pair classes written by k_classify (any cell: DESIGN section 3 has the bound used for skewed cells): lower bound of the
 // minimum-image distance between the two tiles' bounding boxes
 enum : int {
@@ -300,7 +319,7 @@ void launch_delta(hipStream_t st, const AtomsDev &at, const int *slot_of, const 
                   const FusedParams &fp /*ewald_alpha and the Wolf / Feynman-Hibbs fields*/, int do_es,
                   const int *mv_slot, const int *orig_of_mv, const double4 *mv_new, int m, int *moved_idx, double4 *sf_trial,
                   double *block_part, int *block_cnt, double *out4, long long *dcnt2,
-                  double *host_out /*pinned [9]: the result and, last, the launch number `seq`*/, double seq,
+                  double *host_out /*pinned [kDeltaHostCount]: the D_* slots at delta_host_index, the launch number `seq` stored last*/, double seq,
                   const MvInline *inl = nullptr /*non-null: the move is in here (m <= kMvInline), the device lists are not read*/);
 void launch_commit_positions(hipStream_t st, double4 *xyzq, const int *mv_slot, const double4 *mv_new, int m);
 // polarizable boxes: e_real_trial = e_real + (real-space static field of the pairs with a moved atom, new minus old geometry);
@@ -323,27 +342,28 @@ void launch_three_body(hipStream_t st, const AtomsDev &at, const double2 *au, co
 void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, const int *mv_slot, const double4 *mv_new,
                              int m, int *moved_idx, double *part, double *out);
 
+// ---- the pair-sum energy terms: disp-expansion, rd_crystal, the rd model.  One tile-pair walk and one moved-atom walk serve them all
+// (pair_term_walk.h); each term's file states its payload, its admission rule and its pair function.  Every sum launch leaves kXBlocks (or
+// fewer) partials per quantity in `part` (arrays kXBlocks apart) and writes their fixed-order sums side by side; every delta launch takes the
+// old positions as resident and the moved atoms' new ones in mv_new, marks and clears again the all -1 slot map moved_idx, and writes the
+// change of each quantity side by side.
+//
 // ---- dispersion-expansion repulsion/dispersion (kernels_disp.hip) ---------------------------------------------------------------
 // co[slot] = (alpha, r0, s6, s8), t10[slot] = s10 with c_n,ij = s_n,i s_n,j (unit factors included; context.cpp: disp_coefficients;
-// padding zeros).  Both launches leave kDispBlocks (or fewer) partials in `part` and write their
-// fixed-order sum to out[0]; the full sum also writes lrc_pair and lrc_self to out[1] and out[2].
+// padding zeros).  out[0] = the pair sum; the full sum also writes lrc_pair and lrc_self to out[1] and out[2].
 constexpr int kDispBlocks = 16384; // (12 403 tile pairs at 10 000 atoms: one per workgroup, no tail of doubled waves)
 struct DispParams {
 	int damp, schmidt; // damp_dispersion, schmidt_ff
 };
-int disp_grid(long long work_items); // partials a launch over this many tile pairs / (moved atom, tile) items leaves
 void launch_disp_expansion(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const int2 *tile_pairs, int n_tile_pairs,
                            const Box &bx, const DispParams &dp, double lrc_pair, double lrc_self, double *part, double *out);
-// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
-// kernels (marked and cleared again inside)
 void launch_disp_expansion_delta(hipStream_t st, const AtomsDev &at, const double4 *co, const double *t10, const Box &bx, const DispParams &dp,
                                  const int *mv_slot, const double4 *mv_new, int m, int *moved_idx, double *part, double *out);
 
 // ---- `rd_crystal`: the lattice-summed Lennard-Jones of System::lj (kernels_crystal.hip) --------------------------------------------
 // shift[n] = the lattice vector S(n) = ((B[0] n0 + B[1] n1) + B[2] n2) of image n, n in [-(order-1), order-1]^3 in the reference's loop
 // order (context.cpp: crystal_ready builds it on the host with the cutoff and the two thresholds below, after every change of the cell).
-// Both launches leave kCrystalBlocks (or fewer) energy partials in part[0 ..] and as many image-term counts (as doubles: exact) in
-// part[kCrystalBlocks ..], and write the two fixed-order sums to out_e[0] and out_terms[0].
+// out2 = { pair sum, image terms kept (a double: exact) }, or their changes; part: [2 kCrystalBlocks].
 constexpr int kCrystalBlocks = 16384;
 constexpr int kCrystalMinItems = 2048; // small tables split every tile pair's j range until about this many waves share the sum
 struct CrystalParams {
@@ -355,16 +375,13 @@ struct CrystalParams {
 };
 int crystal_jsplit(int n_tile_pairs); // waves per tile pair of the sum (a function of the table alone: repeated evaluations agree to the bit)
 void launch_crystal(hipStream_t st, const AtomsDev &at, const Box &bx, const CrystalParams &cp, const double4 *shift, const int2 *tile_pairs,
-                    int n_tile_pairs, double *part /*[2 kCrystalBlocks]*/, double *out_e, double *out_terms);
-// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
-// kernels (marked and cleared again inside); out2 = { change of the pair sum, change of the image-term count }
+                    int n_tile_pairs, double *part, double *out2);
 void launch_crystal_delta(hipStream_t st, const AtomsDev &at, const Box &bx, const CrystalParams &cp, const double4 *shift, const int *mv_slot,
                           const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
 
 // ---- the rd model: another mixing rule and another pair function for the sum inside the cutoff (kernels_rd_model.hip) --------------
 // sp[slot] = (sigma, sigma^2, sigma^3, sigma^6) per atom, sigma >= 0 (context.cpp: rd_model_ready; padding zeros); sqrt(epsilon) is
-// AtomsDev::lj's.  Every launch leaves kRdModelBlocks (or fewer) partials per quantity in `part` ([3 kRdModelBlocks]) and writes their
-// fixed-order sums.
+// AtomsDev::lj's.  part: [3 kRdModelBlocks].
 constexpr int kRdModelBlocks = 16384;
 struct RdModelParams {
 	int form, mix;       // RD_FORM_*, RD_MIX_* (pair_math.h)
@@ -372,7 +389,6 @@ struct RdModelParams {
 	int fh_order;        // Feynman-Hibbs (LJ form only): 0 off, 2 or 4, with the constants of FusedParams
 	double fh_c2, fh_c4;
 };
-int rd_model_grid(long long work_items);
 // out3 = { pair sum, kept terms, tile pairs skipped }; cls: this evaluation's tile-pair classes (CLS_BEYOND_CUTOFF tile pairs are not
 // walked), or null: every tile pair is walked
 void launch_rd_model(hipStream_t st, const AtomsDev &at, const double4 *sp, const int2 *tile_pairs, const int *cls, int n_tile_pairs, const Box &bx,
@@ -380,8 +396,7 @@ void launch_rd_model(hipStream_t st, const AtomsDev &at, const double4 *sp, cons
 // out[0] = the LJ form's pair correction with the mixed parameters over every pair that is not frozen (the host caches it)
 void launch_rd_model_lrc(hipStream_t st, const AtomsDev &at, const double4 *sp, const int2 *tile_pairs, int n_tile_pairs, int mix, double cutoff,
                          double volume, double *part, double *out);
-// the change under a trial move: old positions resident, the moved atoms' new ones in mv_new; moved_idx: the all -1 slot map of the delta
-// kernels (marked and cleared again inside); out2 = { change of the pair sum, change of the kept terms }
+// out2 = { change of the pair sum, change of the kept terms }
 void launch_rd_model_delta(hipStream_t st, const AtomsDev &at, const double4 *sp, const Box &bx, const RdModelParams &rp, const int *mv_slot,
                            const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
 

@@ -221,9 +221,9 @@ __global__ __launch_bounds__(64) void k_delta_all(AtomsDev at, Box bx, RecipDev 
 // sums the per-tile partials, the reciprocal energy of the trial structure factors, into out[0..3] and counts
 __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__ block_part, const int *__restrict__ block_cnt, int nb,
                                                       RecipDev rc, const double4 *__restrict__ sf_trial, Box bx, int do_es,
-                                                      double *__restrict__ out /* dlj, des_real, (dintra at [2]), e_recip_trial at [3] */,
+                                                      double *__restrict__ out /* the D_* block (kernels.h): D_LJ, D_ES_REAL, D_ES_RECIP written here, D_ES_INTRA by the intramolecular block */,
                                                       long long *__restrict__ dcnt,
-                                                      double *__restrict__ host_out /* pinned [12]: the same 5 doubles + 2 counts, three-body delta, launch number, disp-expansion delta, rd_crystal delta and count */,
+                                                      double *__restrict__ host_out /* pinned [kDeltaHostCount]: the same block at delta_host_index, the launch number at kDeltaHostSeq */,
                                                       double seq) {
 	__shared__ double sh[4];
 	__shared__ long long shc[256];
@@ -244,11 +244,11 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 	s1 = block_sum_256(s1, sh);
 	e = block_sum_256(e, sh);
 	if (threadIdx.x == 0) {
-		out[0] = s0;
-		out[1] = s1;
-		if (!do_es) out[2] = 0.0; // (k_delta_intra wrote it otherwise)
-		out[3] = e * (4.0 * kPi / bx.volume);
-		out[4] = (double)0;
+		out[D_LJ] = s0;
+		out[D_ES_REAL] = s1;
+		if (!do_es) out[D_ES_INTRA] = 0.0; // (k_delta_intra wrote it otherwise)
+		out[D_ES_RECIP] = e * (4.0 * kPi / bx.volume);
+		out[D_SPARE] = (double)0;
 	}
 	c0 = block_count_256(c0, shc);
 	c1 = block_count_256(c1, shc);
@@ -259,20 +259,17 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
 	// the result goes to the caller's pinned block from here (no copy-back command, no stream synchronisation: the host polls the launch
 	// number, which is stored last, behind a system-scope fence)
 	if (host_out && threadIdx.x == 0) {
-		host_out[0] = s0;
-		host_out[1] = s1;
-		host_out[2] = do_es ? out[2] : 0.0;
-		host_out[3] = e * (4.0 * kPi / bx.volume);
-		host_out[4] = 0.0;
-		long long *hc = reinterpret_cast<long long *>(host_out + 5);
+		host_out[D_LJ] = s0;
+		host_out[D_ES_REAL] = s1;
+		host_out[D_ES_INTRA] = do_es ? out[D_ES_INTRA] : 0.0;
+		host_out[D_ES_RECIP] = e * (4.0 * kPi / bx.volume);
+		host_out[D_SPARE] = 0.0;
+		long long *hc = reinterpret_cast<long long *>(host_out + D_CNT_LJ);
 		hc[0] = c0;
 		hc[1] = c1;
-		host_out[7] = out[7]; // (the three-body delta of contexts with the term, kernels_three_body.hip; 0 for every other context)
-		host_out[9] = out[8]; // (the disp-expansion delta likewise, kernels_disp.hip; behind the launch number's slot 8, which stays where it was)
-		host_out[10] = out[9]; // (the rd_crystal delta and the change of its image-term count, kernels_crystal.hip)
-		host_out[11] = out[10];
+		for (int d = D_THREE_BODY; d < D_COUNT; d++) host_out[delta_host_index(d)] = out[d]; // (the further terms' changes; 0 in a context without the term)
 		__threadfence_system();
-		__hip_atomic_store(host_out + 8, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(host_out + kDeltaHostSeq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 	}
 }
 
@@ -347,7 +344,7 @@ void launch_delta(hipStream_t st, const AtomsDev &at, const int *slot_of, const 
 	const int grid = do_ewald ? nt + 1 + rc.K : nt;
 #define MPMC_DELTA(O, E, MVT, MVV, MAP)                                                                                                              \
 	hipLaunchKernelGGL((k_delta_all<O, E, MVT>), dim3(grid), dim3(kTile), 0, st, at, bx, rc, slot_of, fp, do_es, MVV, m, MAP, sf_trial, block_part, block_cnt, \
-	                   out4 + 2)
+	                   out4 + D_ES_INTRA)
 #define MPMC_DELTA_OE(MVT, MVV, MAP)              \
 	if (bx.ortho) {                               \
 		if (ext) MPMC_DELTA(true, true, MVT, MVV, MAP);   \

@@ -190,7 +190,7 @@ void launch_three_body(hipStream_t st, const AtomsDev &at, const double2 *au, co
 	const int nt3 = (int)three_body_tile_triples(at.n_pad / kTile); // (mpmc_set_axilrod_teller refuses boxes beyond INT_MAX tile triples)
 	const int grid = three_body_grid(nt3);
 	with_flag(bx.ortho, [&](auto O) { hipLaunchKernelGGL(k_three_body<O.value>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, nt3, bx, part); });
-	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 1, scale, 0, 0.0, 0.0, nullptr, nullptr, 0);
+	launch_sum_partials(st, part, 0, grid, 1, out, 1, scale);
 }
 
 void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *au, const Box &bx, double scale, const int *mv_slot, const double4 *mv_new,
@@ -202,7 +202,7 @@ void launch_three_body_delta(hipStream_t st, const AtomsDev &at, const double2 *
 	with_flag(bx.ortho, [&](auto O) {
 		hipLaunchKernelGGL(k_three_body_delta<O.value>, dim3(grid), dim3(kTile), 0, st, at.xyzq, at.mf, au, at.n, ntp, bx, mv_slot, mv_new, m, moved_idx, part);
 	});
-	hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, part, grid, out, 1, scale, 0, 0.0, 0.0, moved_idx, mv_slot, m); // (clears the map)
+	launch_sum_partials(st, part, 0, grid, 1, out, 1, scale, 0, 0.0, 0.0, moved_idx, mv_slot, m); // (clears the map)
 }
 
 } // namespace mpmc

@@ -18,13 +18,13 @@ static int ensure_trial_buffers(mpmc_ctx *c) {
 		c->d_mv_slot = reinterpret_cast<int *>(c->d_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		c->d_mv_orig = c->d_mv_slot + MPMC_TRIAL_MAX_ATOMS;
 		if ((rc = c->d_moved_idx.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
-		if ((rc = c->d_delta_out.reserve(c, 11)) != MPMC_OK) return rc; // 5 doubles + 2 int64 counts + the three-body, disp-expansion and rd_crystal (2) deltas
-		HIP_TRY(c, hipMemsetAsync(c->d_delta_out, 0, 11 * sizeof(double), c->stream));
-		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + 5);
+		if ((rc = c->d_delta_out.reserve(c, D_COUNT)) != MPMC_OK) return rc; // (the D_* slots, kernels.h)
+		HIP_TRY(c, hipMemsetAsync(c->d_delta_out, 0, D_COUNT * sizeof(double), c->stream));
+		c->d_delta_cnt = reinterpret_cast<long long *>(c->d_delta_out + D_CNT_LJ);
 		HIP_TRY(c, hipMemsetAsync(c->d_moved_idx, 0xff, (size_t)c->max_pad * sizeof(int), c->stream)); // all -1; on our stream (ordered before the first delta kernel)
-		if ((rc = c->h_delta_out.reserve(c, 12)) != MPMC_OK) return rc;
-		c->h_delta_out[8] = c->h_delta_out[9] = c->h_delta_out[10] = c->h_delta_out[11] = 0.0;
-		c->h_delta_cnt = reinterpret_cast<long long *>(c->h_delta_out + 5);
+		if ((rc = c->h_delta_out.reserve(c, kDeltaHostCount)) != MPMC_OK) return rc;
+		for (int k = kDeltaHostSeq; k < kDeltaHostCount; k++) c->h_delta_out[k] = 0.0;
+		c->h_delta_cnt = reinterpret_cast<long long *>(c->h_delta_out + delta_host_index(D_CNT_LJ));
 		if ((rc = c->h_mv_blob.reserve(c, kMvBlobBytes)) != MPMC_OK) return rc;
 	}
 	return c->d_sf_trial.reserve(c, (size_t)c->K);
@@ -119,36 +119,36 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	const int do_es = o.rd_only ? 0 : 1;
 	if (c->kept.tb_enabled) {
 		// Axilrod-Teller: the change of the triples with a moved atom, O(m N^2), with the accepted positions still resident; its sum lands in
-		// the spare slot 7 of the delta result block, which k_delta_finish copies out in front of the launch number it posts
+		// D_THREE_BODY of the delta result block, which k_delta_finish copies out with the launch number it posts
 		if ((rc = three_body_ready(c)) != MPMC_OK) return rc;
 		ProfScope p(c, MPMC_K_THREE_BODY);
 		launch_three_body_delta(st, atoms_view(c), c->d_tb_au, c->box, kThreeBodyScale, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_tb_part,
-		                        c->d_delta_out + 7);
+		                        c->d_delta_out + D_THREE_BODY);
 	}
 	if (c->kept.de_enabled) {
-		// disp-expansion: the change of the pairs with a moved atom, O(m N), old positions still resident; into slot 8 of the delta result
-		// block, which k_delta_finish copies out behind the launch number's slot (h_delta_out[9]).  It replaces the LJ delta of launch_delta.
+		// disp-expansion: the change of the pairs with a moved atom, O(m N), old positions still resident; into D_DISP of the delta result
+		// block.  It replaces the LJ delta of launch_delta.
 		if ((rc = disp_ready(c)) != MPMC_OK) return rc;
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_disp_expansion_delta(st, atoms_view(c), c->d_de_co, c->d_de_t10, c->box, disp_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx,
-		                            c->d_de_part, c->d_delta_out + 8);
+		                            c->d_de_part, c->d_delta_out + D_DISP);
 	}
 	if (crystal_on(c)) {
-		// rd_crystal: the change of the lattice sums of the pairs with a moved atom, O(m N images), old positions still resident; into slots
-		// 9 and 10 of the delta result block (h_delta_out[10], [11]).  It replaces the LJ delta of launch_delta.
+		// rd_crystal: the change of the lattice sums of the pairs with a moved atom, O(m N images), old positions still resident; into D_RD
+		// and D_RD_TERMS of the delta result block.  It replaces the LJ delta of launch_delta.
 		if ((rc = crystal_ready(c)) != MPMC_OK) return rc;
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_crystal_delta(st, atoms_view(c), c->box, crystal_params(c), c->d_rc_shift, c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rc_part,
-		                     c->d_delta_out + 9);
+		                     c->d_delta_out + D_RD);
 	}
 	if (rd_model_on(c)) {
-		// the rd model: the change of the pairs with a moved atom, O(m N), old positions still resident; into slots 9 and 10 of the delta
-		// result block (h_delta_out[10], [11]), which a context with the model never shares with rd_crystal (crystal_on, rd_model_ready).  It
+		// the rd model: the change of the pairs with a moved atom, O(m N), old positions still resident; into D_RD and D_RD_TERMS of the
+		// delta result block, which a context with the model never shares with rd_crystal (crystal_on, rd_model_ready).  It
 		// replaces the LJ delta of launch_delta; the cached pair correction does not move with the atoms.
 		if ((rc = rd_model_ready(c)) != MPMC_OK) return rc;
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_rd_model_delta(st, atoms_view(c), c->d_rdm_sp, c->box, rd_model_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rdm_part,
-		                      c->d_delta_out + 9);
+		                      c->d_delta_out + D_RD);
 	}
 	{
 		FusedParams fp{};
@@ -254,7 +254,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		// synchronisation alone costs 10-15); with profiling events outstanding, or past the budget, wait the ordinary way
 		bool seen = false;
 		if (c->ev_used.empty()) {
-			volatile const double *flag = c->h_delta_out + 8;
+			volatile const double *flag = c->h_delta_out + kDeltaHostSeq;
 			const double want = c->trial_seq;
 			seen = poll_posted(c, [&] { return *flag == want; }, std::chrono::microseconds(1000));
 		}
@@ -266,25 +266,26 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	}
 	const int do_es = c->opts.rd_only ? 0 : 1;
 	const mpmc_result &a = c->last_full;
+	const double *dh = c->h_delta_out.p; // (the D_* slots at delta_host_index)
 	mpmc_result r = a;
-	r.lj_pairs = a.lj_pairs + (c->kept.de_enabled ? c->h_delta_out[9] : c->h_delta_out[0]); // (with the disp-expansion term lj_pairs holds its pair sum)
+	r.lj_pairs = a.lj_pairs + (c->kept.de_enabled ? dh[delta_host_index(D_DISP)] : dh[delta_host_index(D_LJ)]); // (with the disp-expansion term lj_pairs holds its pair sum)
 	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
 	if (crystal_on(c)) { // (lj_pairs holds the lattice sum; crystal_self and the corrections do not move with the atoms)
-		r.lj_pairs = a.lj_pairs + c->h_delta_out[10];
+		r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_RD)];
 		r.rd_energy = ((r.lj_pairs + r.lrc_pair) + c->rc_self) + r.lrc_self;
-		c->rc_terms_trial = c->rc_terms_accepted + (int64_t)c->h_delta_out[11];
+		c->rc_terms_trial = c->rc_terms_accepted + (int64_t)dh[delta_host_index(D_RD_TERMS)];
 		c->rc_info.n_image_terms = c->rc_terms_trial;
 	}
 	if (rd_model_on(c)) { // (lj_pairs holds the model's sum; the corrections do not move with the atoms)
-		r.lj_pairs = a.lj_pairs + c->h_delta_out[10];
+		r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_RD)];
 		r.rd_energy = (c->kept.rdm_form == RD_FORM_LJ) ? (r.lj_pairs + r.lrc_pair) + r.lrc_self : r.lj_pairs;
-		c->rdm_terms_trial = c->rdm_terms_accepted + (int64_t)c->h_delta_out[11];
+		c->rdm_terms_trial = c->rdm_terms_accepted + (int64_t)dh[delta_host_index(D_RD_TERMS)];
 		c->rdm_info.n_terms = c->rdm_terms_trial;
 	}
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
-		r.es_real = a.es_real + (c->h_delta_out[1] - c->h_delta_out[2]);
-		r.es_recip = c->h_delta_out[3];
+		r.es_real = a.es_real + (dh[delta_host_index(D_ES_REAL)] - dh[delta_host_index(D_ES_INTRA)]);
+		r.es_recip = dh[delta_host_index(D_ES_RECIP)];
 		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
 		r.n_es_in_cutoff = a.n_es_in_cutoff + c->h_delta_cnt[1];
 	}
@@ -294,7 +295,7 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		r.polar_iterations = solved.polar_iterations;
 		r.iterator_failed = solved.iterator_failed;
 	}
-	if (c->kept.tb_enabled) r.three_body_energy = a.three_body_energy + c->h_delta_out[7];
+	if (c->kept.tb_enabled) r.three_body_energy = a.three_body_energy + dh[delta_host_index(D_THREE_BODY)];
 	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
 	r.NU = r.N * r.energy;
 	c->trial_res = r;

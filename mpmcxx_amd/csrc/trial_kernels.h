@@ -1,7 +1,8 @@
 // trial_kernels.h -- the scaffold the trial-move ("delta") terms share: the moved-atom map, the real-space delta-field kernel with its
 // finish, the launch sequence around them, and the fixed-order sum of per-workgroup partials.  Included after kernels.h by the HIP
-// translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, kernels_disp.hip); the kernels
-// are static, one copy per code object.  A new trial-move term brings its pair arithmetic and calls these.
+// translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, and through pair_term_walk.h
+// kernels_disp.hip, kernels_crystal.hip and kernels_rd_model.hip); the kernels are static, one copy per code object.  A new trial-move
+// field term brings its pair arithmetic and calls these; a new pair-sum energy term brings a Term for the two walks of pair_term_walk.h.
 #pragma once
 
 #include "kernels.h"
@@ -90,22 +91,27 @@ inline void launch_field_delta(hipStream_t st, const AtomsDev &at, const Box &bx
 	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 0);
 }
 
-// ---- out[0] = the per-workgroup partials summed in a fixed order (times `scale` when `scaled`; an unscaled sum is not multiplied at all);
-// n_extra: out[1], out[2] = extra1, extra2 (values the host keeps and the result block carries); mv_slot non-null: clears the moved-atom
-// map behind a delta launch ---------------------------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__ part, int nparts, double *__restrict__ out, int scaled, double scale,
-                                                             int n_extra, double extra1, double extra2, int *__restrict__ moved_idx,
+// ---- out[a] = the per-workgroup partials of array a (part + a stride) summed in a fixed order (times `scale` when `scaled`; an unscaled
+// sum is not multiplied at all), one block per array; n_extra (one array only): out[1], out[2] = extra1, extra2 (values the host keeps and
+// the result block carries); mv_slot non-null: block 0 clears the moved-atom map behind a delta launch -----------------------------------
+static __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__ part, int stride, int nparts, double *__restrict__ out, int scaled,
+                                                             double scale, int n_extra, double extra1, double extra2, int *__restrict__ moved_idx,
                                                              const int *__restrict__ mv_slot, int m) {
 	__shared__ double sh[4];
+	const double *p = part + (size_t)blockIdx.x * stride;
 	double s = 0.0;
-	for (int b = threadIdx.x; b < nparts; b += 256) s += part[b];
+	for (int b = threadIdx.x; b < nparts; b += 256) s += p[b];
 	s = block_sum_256(s, sh);
 	if (threadIdx.x == 0) {
-		out[0] = scaled ? s * scale : s;
+		out[blockIdx.x] = scaled ? s * scale : s;
 		if (n_extra) out[1] = extra1, out[2] = extra2;
 	}
-	if (mv_slot)
+	if (mv_slot && blockIdx.x == 0)
 		for (int k = threadIdx.x; k < m; k += 256) moved_idx[mv_slot[k]] = -1;
+}
+inline void launch_sum_partials(hipStream_t st, const double *part, int stride, int nparts, int n_arrays, double *out, int scaled, double scale, int n_extra = 0,
+                                double extra1 = 0.0, double extra2 = 0.0, int *moved_idx = nullptr, const int *mv_slot = nullptr, int m = 0) {
+	hipLaunchKernelGGL(k_sum_partials, dim3(n_arrays), dim3(256), 0, st, part, stride, nparts, out, scaled, scale, n_extra, extra1, extra2, moved_idx, mv_slot, m);
 }
 
 } // namespace mpmc

@@ -114,8 +114,8 @@ def test_library_exports_the_entry_points():
 
 def test_disp_kernels_spill_nothing():
     notes = _kernel_notes("kernels_disp.hip.o")
-    full = [k for k in notes if "k_disp_expansion" in k and "delta" not in k]
-    delta = [k for k in notes if "k_disp_expansion_delta" in k]
+    full = [k for k in notes if "k_pair_term_sum" in k and "DispTerm" in k]  # (the shared walks of pair_term_walk.h with this file's term)
+    delta = [k for k in notes if "k_pair_term_delta" in k and "DispTerm" in k]
     assert len(full) == 4 and len(delta) == 4, list(notes)  # orthorhombic / skewed x damped / undamped
     for name in full + delta:
         meta = notes[name]

@@ -298,12 +298,12 @@ def test_kernels_compile_for_gfx950_and_the_library_exports_the_entry_points():
 
 
 def test_rd_model_kernels_need_no_scratch():
-    """every instantiation of the three kernels (cell shape x form x rule; rule alone for the correction) is in the gfx950 code object,
+    """every instantiation of the two walks with the model's terms (cell shape x form x rule; rule alone for the correction) is in the gfx950 code object,
     spills nothing and keeps at least four waves per SIMD"""
     notes = _kernel_notes("kernels_rd_model.hip.o")
-    full = [k for k in notes if re.search(r"k_rd_modelILb", k)]
-    delta = [k for k in notes if "k_rd_model_delta" in k]
-    lrc = [k for k in notes if "k_rd_model_lrc" in k]
+    full = [k for k in notes if "k_pair_term_sum" in k and "RdModelTermI" in k]  # (the shared walks of pair_term_walk.h with this file's terms)
+    delta = [k for k in notes if "k_pair_term_delta" in k and "RdModelTermI" in k]
+    lrc = [k for k in notes if "k_pair_term_sum" in k and "RdModelLrcTermI" in k]
     assert len(full) == 24 and len(delta) == 24 and len(lrc) == 4, (len(full), len(delta), len(lrc))
     for name in full + delta + lrc:
         meta = notes[name]
