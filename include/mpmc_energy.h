@@ -247,6 +247,31 @@ int mpmc_trial_energy_wait(mpmc_ctx *ctx, mpmc_result *out);
 int mpmc_trial_accept(mpmc_ctx *ctx);
 int mpmc_trial_reject(mpmc_ctx *ctx);
 
+/* ---- exchange trials: insertion and removal of one molecule (uVT insert / remove, the particle transfers of the Gibbs ensemble) --------
+ * The same five calls serve a trial that changes the composition: mpmc_trial_energy (or _async / _wait), then mpmc_trial_accept or
+ * mpmc_trial_reject.  Preconditions as for mpmc_trial_begin: an accepted configuration (mpmc_energy), no open trial, finite positions
+ * (MPMC_ERR_INVALID_DATUM otherwise).  A range that is not exactly one whole molecule, an at_index inside a molecule and the removal of the
+ * last molecule are MPMC_ERR_ARG with a text in mpmc_last_error.
+ *   The mpmc_result of the trial is that of the trial composition in every field (energies and their parts, N, NU and all counts).
+ *   Boxes without polarization, with the default rd model and without rd_crystal, for count <= MPMC_TRIAL_MAX_ATOMS, take a delta path:
+ * O(count * N) pair terms of the molecule with everybody else (each pair once, added or subtracted), the molecule's own pairs, the
+ * structure factors plus or minus the molecule's phases, and the position-independent terms (es_self, lrc_pair, lrc_self, N) of the trial
+ * composition.  Ewald or Wolf electrostatics, rd_only and the Feynman-Hibbs corrections are included.  Everything else (polarizable boxes,
+ * rd_crystal, another rd model, longer molecules) evaluates the trial composition in full; mpmc_debug_last_trial_was_full tells.  A context
+ * with Axilrod-Teller or disp-expansion coefficients refuses both calls with MPMC_ERR_UNSUPPORTED: those coefficients belong to one atom
+ * list (mpmc_set_atoms, then the coefficients again).
+ *   accept: the context's atom list is the new one (the molecule of an insertion gets a molecule id of its own; the context grows as under
+ * mpmc_set_atoms), the accepted totals are the trial totals, and the next trial of either kind or mpmc_energy works on the new composition
+ * -- on the delta path without a re-basing evaluation: the list is edited on the host, the spatial order is carried, and the next call
+ * uploads it.  reject: nothing of a delta trial is left; after a full evaluation the accepted list is put back as a rejected displacement
+ * of that branch puts the positions back. */
+/* trial insertion of ONE molecule of `count` atoms in front of atom `at_index` of the current list (at_index == n: appended;
+ * at_index must be a molecule boundary).  Arrays as in mpmc_set_atoms, `count` long; the new atoms form one new molecule. */
+int mpmc_trial_insert_begin(mpmc_ctx *ctx, int at_index, int count, const double *pos, const double *charge, const double *polarizability,
+                            const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass);
+/* trial removal of the whole molecule that occupies atoms [first, first+count) */
+int mpmc_trial_remove_begin(mpmc_ctx *ctx, int first, int count);
+
 /* ---- the Axilrod-Teller triple-dipole dispersion, System::axilrod_teller (src/System.Energy.cpp:129-136, 1653-1770) --------------------
  * Sum over every unordered triple of distinct atoms that are not all in one molecule, no cutoff, frozen atoms included; each pair vector is
  * that pair's own minimum image.  Added to energy (and NU) as three_body_energy; the path-integral sums stay {rd, coulombic, polarization,

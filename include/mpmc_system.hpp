@@ -235,7 +235,7 @@ public:
 			mpmc_trial_reject(ctx_);
 			check(rc, "mpmc_trial_energy");
 		}
-		trial_first_ = first;
+		trial_first_ = first, trial_kind_ = 0;
 		trial_pos_.assign(new_pos, new_pos + 3 * (size_t)count);
 		trial_result_ = r;
 		return r.energy;
@@ -249,7 +249,7 @@ public:
 			mpmc_trial_reject(ctx_);
 			check(rc, "mpmc_trial_energy_async");
 		}
-		trial_first_ = first;
+		trial_first_ = first, trial_kind_ = 0;
 		trial_pos_.assign(new_pos, new_pos + 3 * (size_t)count);
 	}
 	double energy_trial_wait() {
@@ -265,11 +265,65 @@ public:
 	const mpmc_result &trial_result() const { return trial_result_; } // the trial configuration's totals (observables keep the accepted ones)
 	void accept_trial() {
 		check(mpmc_trial_accept(ctx_), "mpmc_trial_accept");
+		if (trial_kind_ > 0) { // the list follows the library's: the context is not told again
+			int id = 0;
+			for (const Atom &a : atoms) id = a.molecule >= id ? a.molecule + 1 : id;
+			for (Atom &a : trial_mol_) a.molecule = id;
+			atoms.insert(atoms.begin() + trial_first_, trial_mol_.begin(), trial_mol_.end());
+			if ((int)atoms.size() > capacity_) capacity_ = (int)atoms.size(); // (the library has grown its context itself)
+		} else if (trial_kind_ < 0) {
+			atoms.erase(atoms.begin() + trial_first_, atoms.begin() + trial_first_ + trial_count_);
+		}
+		if (trial_kind_) natoms = (int)atoms.size();
+		trial_kind_ = 0;
 		for (size_t k = 0; k < trial_pos_.size() / 3; k++)
 			for (int d = 0; d < 3; d++) atoms[trial_first_ + k].pos[d] = trial_pos_[3 * k + d];
 		absorb(trial_result_);
 	}
-	void reject_trial() { check(mpmc_trial_reject(ctx_), "mpmc_trial_reject"); }
+	void reject_trial() {
+		check(mpmc_trial_reject(ctx_), "mpmc_trial_reject");
+		trial_kind_ = 0;
+	}
+
+	// ---- exchange trials: one molecule in or out (uVT insert / remove, Gibbs transfers; mpmc_trial_insert_begin / mpmc_trial_remove_begin) ----
+	// energy of the composition with the atoms of `mol` (one new molecule; their `molecule` index is not read) in front of atom `at` (a
+	// molecule boundary, or atoms.size(): appended) / without the whole molecule that occupies atoms [first, first+count); then
+	// accept_trial() -- which edits `atoms` accordingly (an inserted molecule gets an index no other has), so that the next energy() finds
+	// the list it knows and uploads nothing -- or reject_trial().  Needs a prior energy() of the accepted state.  trial_result() holds the
+	// trial composition's totals, counts and N.  Contexts with the Axilrod-Teller or disp-expansion term refuse (change `atoms`, then
+	// atoms_changed()).
+	double energy_trial_insert(int at, const std::vector<Atom> &mol) {
+		energy_trial_insert_async(at, mol);
+		return energy_trial_wait();
+	}
+	double energy_trial_remove(int first, int count) {
+		energy_trial_remove_async(first, count);
+		return energy_trial_wait();
+	}
+	void energy_trial_insert_async(int at, const std::vector<Atom> &mol) {
+		sync_state();
+		const int m = (int)mol.size();
+		std::vector<double> pos(3 * (size_t)m), q(m), al(m), ep(m), sg(m), ms(m);
+		std::vector<int32_t> fr(m), dp(m);
+		for (int i = 0; i < m; i++) {
+			const Atom &a = mol[i];
+			for (int p = 0; p < 3; p++) pos[3 * i + p] = a.pos[p];
+			q[i] = a.charge, al[i] = a.polarizability, ep[i] = a.epsilon, sg[i] = a.sigma, ms[i] = a.mass;
+			fr[i] = a.frozen;
+			dp[i] = (a.c6 != 0.0 || a.c8 != 0.0 || a.c10 != 0.0) ? 1 : 0;
+		}
+		check(mpmc_trial_insert_begin(ctx_, at, m, pos.data(), q.data(), al.data(), ep.data(), sg.data(), fr.data(), dp.data(), ms.data()), "mpmc_trial_insert_begin");
+		trial_kind_ = +1, trial_first_ = at, trial_mol_ = mol;
+		trial_pos_.clear();
+		exchange_enqueue();
+	}
+	void energy_trial_remove_async(int first, int count) {
+		sync_state();
+		check(mpmc_trial_remove_begin(ctx_, first, count), "mpmc_trial_remove_begin");
+		trial_kind_ = -1, trial_first_ = first, trial_count_ = count;
+		trial_pos_.clear();
+		exchange_enqueue();
+	}
 
 	double lj() { return piece(mpmc_lj); }
 	double coulombic() { return piece(mpmc_coulombic); }
@@ -324,6 +378,16 @@ private:
 	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
+	int trial_kind_ = 0, trial_count_ = 0; // the open trial: 0 a displacement, +1 an insertion (trial_mol_), -1 a removal
+	std::vector<Atom> trial_mol_;
+	void exchange_enqueue() {
+		const int rc = mpmc_trial_energy_async(ctx_);
+		if (rc != MPMC_OK) {
+			mpmc_trial_reject(ctx_);
+			trial_kind_ = 0;
+			check(rc, "mpmc_trial_energy_async");
+		}
+	}
 	std::vector<double> trial_pos_;
 	mpmc_result trial_result_{};
 

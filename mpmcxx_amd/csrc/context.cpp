@@ -492,14 +492,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 			slot[i] = k;
 			xyzq[k] = make_double4(c->h_pos[3 * i], c->h_pos[3 * i + 1], c->h_pos[3 * i + 2], c->h_q[i]);
 			lj[k] = make_double2(std::fabs(c->h_sigma[i]), std::sqrt(c->h_eps[i]));
-			int fl = 0;
-			if (c->h_frozen[i]) fl |= AF_FROZEN;
-			if (c->h_eps[i] == 0.0 || c->h_sigma[i] == 0.0) fl |= AF_NULL_RD;
-			if (c->h_disp[i]) fl |= c->kept.de_enabled ? AF_DISP_RD : AF_HAS_DISP; // (disp-expansion: LJ mixing no longer matters, pair_math.h)
-			if (c->h_sigma[i] < 0.0) fl |= AF_NEG_SIGMA;
-			if (c->h_sigma[i] == 0.0) fl |= AF_ZERO_SIGMA;
-			if (c->h_q[i] == 0.0) fl |= AF_ZERO_Q;
-			if (c->h_alpha[i] == 0.0) fl |= AF_ZERO_ALPHA;
+			const int fl = atom_flag_word(c, c->h_frozen[i], c->h_eps[i], c->h_sigma[i], c->h_disp[i], c->h_q[i], c->h_alpha[i]);
 			mf[k] = make_int2(c->h_mol[i], fl);
 			al[k] = c->h_alpha[i];
 			ep[k] = c->h_eps[i];
@@ -602,6 +595,43 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	return MPMC_OK;
 }
 
+// what follows the tile count of the current atom list: the upper-triangular tile-pair schedule, the work table of the fast sweep, the
+// j-range split of the row kernels
+static int size_tile_tables(mpmc_ctx *c) {
+	int rc = MPMC_OK;
+	// upper-triangular tile-pair schedule of the pair kernel
+	const int nt = c->n_tiles;
+	const size_t ntp = (size_t)nt * (nt + 1) / 2;
+	if ((rc = c->d_tile_pairs.reserve(c, ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_block_part.reserve(c, 2 * ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_block_cnt.reserve(c, 4 * ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_cls.reserve(c, ntp)) != MPMC_OK) return rc;
+	if ((rc = c->d_tp_shift.reserve(c, ntp)) != MPMC_OK) return rc;
+	std::vector<int2> tp;
+	tp.reserve(ntp);
+	for (int I = 0; I < nt; I++)
+		for (int J = I; J < nt; J++) tp.push_back(make_int2(I, J));
+	HIP_TRY(c, hipMemcpyAsync(c->d_tile_pairs, tp.data(), ntp * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream)); // `tp` dies with this function
+	c->n_tile_pairs = (int)ntp;
+
+	if (c->sweep_tiles != nt) { // work table of the fast pair sweep: a function of the tile count
+		const int nb = pair_sweep_blocks(nt, nullptr);
+		std::vector<int2> blocks((size_t)nb);
+		pair_sweep_blocks(nt, blocks.data());
+		if (c->kept.tune.sweep_order == 1) std::reverse(blocks.begin(), blocks.end()); // j-tiles descending (measurement)
+		if ((rc = c->d_sweep_blocks.reserve(c, (size_t)nb)) != MPMC_OK) return rc;
+		HIP_TRY(c, hipMemcpyAsync(c->d_sweep_blocks, blocks.data(), (size_t)nb * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // `blocks` dies here
+		c->n_sweep_blocks = nb;
+		c->sweep_tiles = nt;
+	}
+
+	// j-range split of the per-atom (row) kernels: aim for >= ~4096 one-wave blocks
+	c->n_split = std::max(1, std::min(nt, (4096 + nt - 1) / nt));
+	return MPMC_OK;
+}
+
 extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const double *charge, const double *polarizability, const double *epsilon,
                               const double *sigma, const int32_t *mol_id, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
 	if (!c || n <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !mol_id || !frozen) return MPMC_ERR_ARG;
@@ -661,36 +691,7 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->static_dirty = true;
 	c->static_gen++;
 
-	// upper-triangular tile-pair schedule of the pair kernel
-	const int nt = c->n_tiles;
-	const size_t ntp = (size_t)nt * (nt + 1) / 2;
-	if ((rc = c->d_tile_pairs.reserve(c, ntp)) != MPMC_OK) return rc;
-	if ((rc = c->d_block_part.reserve(c, 2 * ntp)) != MPMC_OK) return rc;
-	if ((rc = c->d_block_cnt.reserve(c, 4 * ntp)) != MPMC_OK) return rc;
-	if ((rc = c->d_cls.reserve(c, ntp)) != MPMC_OK) return rc;
-	if ((rc = c->d_tp_shift.reserve(c, ntp)) != MPMC_OK) return rc;
-	std::vector<int2> tp;
-	tp.reserve(ntp);
-	for (int I = 0; I < nt; I++)
-		for (int J = I; J < nt; J++) tp.push_back(make_int2(I, J));
-	HIP_TRY(c, hipMemcpyAsync(c->d_tile_pairs, tp.data(), ntp * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(c, hipStreamSynchronize(c->stream)); // `tp` dies with this function
-	c->n_tile_pairs = (int)ntp;
-
-	if (c->sweep_tiles != nt) { // work table of the fast pair sweep: a function of the tile count
-		const int nb = pair_sweep_blocks(nt, nullptr);
-		std::vector<int2> blocks((size_t)nb);
-		pair_sweep_blocks(nt, blocks.data());
-		if (c->kept.tune.sweep_order == 1) std::reverse(blocks.begin(), blocks.end()); // j-tiles descending (measurement)
-		if ((rc = c->d_sweep_blocks.reserve(c, (size_t)nb)) != MPMC_OK) return rc;
-		HIP_TRY(c, hipMemcpyAsync(c->d_sweep_blocks, blocks.data(), (size_t)nb * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-		HIP_TRY(c, hipStreamSynchronize(c->stream)); // `blocks` dies here
-		c->n_sweep_blocks = nb;
-		c->sweep_tiles = nt;
-	}
-
-	// j-range split of the per-atom (row) kernels: aim for >= ~4096 one-wave blocks
-	c->n_split = std::max(1, std::min(nt, (4096 + nt - 1) / nt));
+	if ((rc = size_tile_tables(c)) != MPMC_OK) return rc;
 	c->atoms_set = true;
 	c->pending = false;
 	c->cache_valid = false;
@@ -702,6 +703,138 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->h_de.clear();
 	c->h_de_raw.clear();
 	return MPMC_OK;
+}
+
+// ---- exchange trials: editing the atom list in place, and the position-independent terms on the host ---------------------------------------
+void mpmc::copy_atom_run(const mpmc_ctx *c, int first, int count, AtomRun &out) {
+	const size_t a = (size_t)first, b = (size_t)first + (size_t)count;
+	out.pos.assign(c->h_pos.begin() + 3 * a, c->h_pos.begin() + 3 * b);
+	out.q.assign(c->h_q.begin() + a, c->h_q.begin() + b);
+	out.alpha.assign(c->h_alpha.begin() + a, c->h_alpha.begin() + b);
+	out.eps.assign(c->h_eps.begin() + a, c->h_eps.begin() + b);
+	out.sigma.assign(c->h_sigma.begin() + a, c->h_sigma.begin() + b);
+	out.mol.assign(c->h_mol.begin() + a, c->h_mol.begin() + b);
+	out.frozen.assign(c->h_frozen.begin() + a, c->h_frozen.begin() + b);
+	out.disp.assign(c->h_disp.begin() + a, c->h_disp.begin() + b);
+	if (c->h_mass.empty()) out.mass.clear();
+	else out.mass.assign(c->h_mass.begin() + a, c->h_mass.begin() + b);
+}
+
+int mpmc::set_atoms_from(mpmc_ctx *c, const AtomRun &l) {
+	return mpmc_set_atoms(c, l.size(), l.pos.data(), l.q.data(), l.alpha.data(), l.eps.data(), l.sigma.data(), l.mol.data(), l.frozen.data(), l.disp.data(),
+	                      l.mass.empty() ? nullptr : l.mass.data());
+}
+
+template <class T>
+static void splice_vec(std::vector<T> &v, size_t at, size_t n_remove, const std::vector<T> *ins, size_t per = 1) {
+	v.erase(v.begin() + per * at, v.begin() + per * (at + n_remove));
+	if (ins) v.insert(v.begin() + per * at, ins->begin(), ins->end());
+}
+
+// The accepted exchange of the delta path.  The caller has checked the range and the capacity (n_new <= max_atoms).  Nothing on the device
+// is touched here: the next evaluation or trial uploads the list (atoms_dirty) in the carried order, as after mpmc_set_atoms -- but the
+// accepted totals, the structure factors and the position-independent terms stay the caller's.
+int mpmc::splice_atoms(mpmc_ctx *c, int at, int n_remove, const AtomRun *ins) {
+	const int n_ins = ins ? ins->size() : 0, n_new = c->n - n_remove + n_ins;
+	if (at < 0 || n_remove < 0 || at + n_remove > c->n || n_new <= 0 || n_new > c->max_atoms) return fail(c, MPMC_ERR_ARG, "exchange trial: bad splice of the atom list");
+	if (ins && !c->h_mass.empty() && ins->mass.empty()) return fail(c, MPMC_ERR_INVALID_DATUM, "exchange trial: the atom list has masses, the inserted molecule has none");
+	std::vector<double> np_(c->h_pos);
+	splice_vec(np_, (size_t)at, (size_t)n_remove, ins ? &ins->pos : nullptr, 3);
+	c->order_carried = carry_spatial_order(c, np_.data(), n_new); // (before the old positions go)
+	c->h_pos.swap(np_);
+	splice_vec(c->h_q, (size_t)at, (size_t)n_remove, ins ? &ins->q : nullptr);
+	splice_vec(c->h_alpha, (size_t)at, (size_t)n_remove, ins ? &ins->alpha : nullptr);
+	splice_vec(c->h_eps, (size_t)at, (size_t)n_remove, ins ? &ins->eps : nullptr);
+	splice_vec(c->h_sigma, (size_t)at, (size_t)n_remove, ins ? &ins->sigma : nullptr);
+	splice_vec(c->h_mol, (size_t)at, (size_t)n_remove, ins ? &ins->mol : nullptr);
+	splice_vec(c->h_frozen, (size_t)at, (size_t)n_remove, ins ? &ins->frozen : nullptr);
+	splice_vec(c->h_disp, (size_t)at, (size_t)n_remove, ins ? &ins->disp : nullptr);
+	if (!c->h_mass.empty()) splice_vec(c->h_mass, (size_t)at, (size_t)n_remove, ins ? &ins->mass : nullptr);
+	const int nt_old = c->n_tiles;
+	c->n = n_new;
+	c->n_pad = ((n_new + kTile - 1) / kTile) * kTile;
+	c->n_tiles = c->n_pad / kTile;
+	c->n_molecules = 0;
+	c->N_movable = 0;
+	for (int i = 0; i < n_new; i++)
+		if (i == n_new - 1 || c->h_mol[i + 1] != c->h_mol[i]) {
+			c->n_molecules++;
+			if (!c->h_frozen[i]) c->N_movable += 1.0;
+		}
+	c->atoms_dirty = true;
+	if (c->n_tiles != nt_old) {
+		HIP_TRY(c, hipSetDevice(c->device));
+		const int rc = size_tile_tables(c);
+		if (rc != MPMC_OK) return rc;
+	}
+	return MPMC_OK;
+}
+
+static const double kHostBinom6[7] = {1, 6, 15, 20, 15, 6, 1};
+static const double kHostBinom12[13] = {1, 12, 66, 220, 495, 792, 924, 792, 495, 220, 66, 12, 1};
+static int xch_class(int fl) { return ((fl & AF_FROZEN) ? 1 : 0) | ((fl & AF_NULL_RD) ? 2 : 0) | ((fl & (AF_HAS_DISP | AF_DISP_RD)) ? 4 : 0) | ((fl & AF_ZERO_Q) ? 8 : 0); }
+
+// one atom's share of the sums of k_atom_terms_part (slot for slot), times sg
+void mpmc::xch_sum_atom(const mpmc_ctx *c, XchSums &xs, double sg, int fl, double sigma, double eps, double q) {
+	const Box bx = lrc_box(c);
+	const int rd_lrc = c->opts.rd_lrc;
+	const double lx = std::fabs(sigma), ly = std::sqrt(eps);
+	double *s = xs.s;
+	xs.cls[xch_class(fl)] += (sg > 0) ? 1 : -1;
+	if (rd_lrc && !(fl & (AF_NULL_RD | AF_NEG_SIGMA))) {
+		double pw = ly;
+		const bool fr = (fl & AF_FROZEN) != 0;
+		for (int k = 0; k < 13; ++k) {
+			s[2 + k] += sg * pw;
+			if (fr) s[15 + k] += sg * pw;
+			pw *= lx;
+		}
+		const double t2 = 2.0 * lx, t6 = (t2 * t2 * t2) * (t2 * t2 * t2), e2 = ly * ly;
+		s[28] += sg * (e2 * t6);
+		s[29] += sg * (e2 * t6 * t6);
+		s[32] += sg;
+		if (fr) {
+			s[30] += sg * (e2 * t6);
+			s[31] += sg * (e2 * t6 * t6);
+			s[33] += sg;
+		}
+	}
+	if (fl & AF_FROZEN) return;
+	s[0] -= sg * (c->ewald_alpha * q * q / std::sqrt(kPi));
+	if (rd_lrc && !(fl & AF_NULL_RD)) s[1] += sg * lrc_term(lx, eps, bx.cutoff, bx.volume);
+}
+
+void mpmc::xch_sum_list(const mpmc_ctx *c, XchSums &out) {
+	out = XchSums{};
+	int32_t mx = c->n > 0 ? c->h_mol[0] : 0;
+	for (int i = 0; i < c->n; i++) {
+		xch_sum_atom(c, out, 1.0, atom_flag_word(c, c->h_frozen[i], c->h_eps[i], c->h_sigma[i], c->h_disp[i], c->h_q[i], c->h_alpha[i]), c->h_sigma[i], c->h_eps[i], c->h_q[i]);
+		mx = std::max(mx, c->h_mol[i]);
+	}
+	out.mol_max = mx;
+}
+
+// lrc_pair, lrc_self, es_self from the sums: k_atom_terms_finish, line by line
+void mpmc::xch_static_terms(const mpmc_ctx *c, const XchSums &xs, double out3[3]) {
+	const Box bx = lrc_box(c);
+	const double *s = xs.s, *m = s + 2, *mf = s + 15;
+	const double d6 = s[28], d12 = s[29], df6 = s[30], df12 = s[31];
+	double s6 = 0, s12 = 0, f6 = 0, f12 = 0;
+	for (int k = 0; k <= 6; ++k) {
+		s6 += kHostBinom6[k] * m[k] * m[6 - k];
+		f6 += kHostBinom6[k] * mf[k] * mf[6 - k];
+	}
+	for (int k = 0; k <= 12; ++k) {
+		s12 += kHostBinom12[k] * m[k] * m[12 - k];
+		f12 += kHostBinom12[k] * mf[k] * mf[12 - k];
+	}
+	const double p6 = (0.5 * (s6 - d6) - 0.5 * (f6 - df6)) / 64.0;
+	const double p12 = (0.5 * (s12 - d12) - 0.5 * (f12 - df12)) / 4096.0;
+	const double rc3 = bx.cutoff * bx.cutoff * bx.cutoff, rc9 = rc3 * rc3 * rc3;
+	const bool no_pair = s[32] * (s[32] - 1.0) == s[33] * (s[33] - 1.0);
+	out3[0] = (c->opts.rd_lrc && !no_pair) ? (16.0 / 3.0) * kPi * (p12 / (3.0 * rc9) - p6 / rc3) / bx.volume : 0.0;
+	out3[1] = s[1];
+	out3[2] = s[0];
 }
 
 // ---- `polar_wolf` / `polar_palmo` ------------------------------------------------------------------------------------------------------

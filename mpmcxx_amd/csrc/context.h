@@ -143,6 +143,21 @@ struct mpmc_kept {
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 };
 
+// A contiguous run of atoms with every per-atom array of mpmc_set_atoms: the molecule of an exchange trial, or a whole atom list
+struct AtomRun {
+	std::vector<double> pos, q, alpha, eps, sigma, mass; // (mass empty: none given)
+	std::vector<int32_t> mol, frozen, disp;
+	int size() const { return (int)q.size(); }
+	void clear() { pos.clear(), q.clear(), alpha.clear(), eps.clear(), sigma.clear(), mass.clear(), mol.clear(), frozen.clear(), disp.clear(); }
+};
+// The sums of k_atom_terms_part (kernels.hip) over an atom list, on the host, and the atoms per flag class
+constexpr int kXchSums = 34, kXchClasses = 16, kXchResum = 1024;
+struct XchSums {
+	double s[kXchSums] = {0};
+	long long cls[kXchClasses] = {0}; // atoms by (AF_FROZEN, AF_NULL_RD, dispersion coefficients, AF_ZERO_Q): all pair_flags reads of an atom of another molecule
+	int32_t mol_max = 0;              // largest molecule id of the list
+};
+
 struct mpmc_ctx {
 	mpmc_kept kept;
 	int device = 0;
@@ -329,6 +344,22 @@ struct mpmc_ctx {
 	bool trial_inline = false;
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
 	long long *d_delta_cnt = nullptr, *h_delta_cnt = nullptr; // (the counts' part of d_delta_out / h_delta_out)
+
+	// exchange trials (mpmc_trial_insert_begin / mpmc_trial_remove_begin): the open trial changes the composition by ONE molecule
+	int xch_kind = 0;            // of the open trial: 0 a displacement, +1 an insertion, -1 a removal
+	int xch_at = 0;              // index the molecule goes in front of / of its first atom (original order); trial_count atoms
+	AtomRun xch_mol;             // the molecule: as given (insertion) or copied from the host mirrors (removal)
+	AtomRun xch_saved;           // full-evaluation trials: the accepted atom list, which a rejection puts back
+	DevBuf<XchAtom> d_xch_mol;   // [MPMC_TRIAL_MAX_ATOMS] the staged molecule of the delta path
+	PinnedBuf<XchAtom> h_xch_mol;
+	// The position-independent terms of the trial composition come from the sums of k_atom_terms_part, kept on the host for the accepted
+	// list (made at the first exchange trial after static_gen moved, O(N); an accepted exchange adds or subtracts its molecule, and every
+	// kXchResum accepted ones the sums are made afresh so that rounding does not accumulate), with the histogram of the flag classes the
+	// position-independent pair counts follow from.
+	XchSums xs_acc, xs_trial;
+	unsigned xs_gen = 0;         // static_gen of xs_acc (0: none)
+	int xs_edits = 0;            // accepted exchanges since xs_acc was summed over the list
+	double xch_static[3] = {0, 0, 0}, xch_N = 0; // lrc_pair, lrc_self, es_self and countN of the evaluated trial composition
 
 	// Axilrod-Teller three-body term (mpmc_set_axilrod_teller, kernels_three_body.hip)
 	// (switched on: kept.tb_enabled, kept.tb_mk)
@@ -621,5 +652,26 @@ void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Fey
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);
 int upload_atoms(mpmc_ctx *c);                   // spatial order + device atom arrays (context.cpp)
+// the AF_* word of one atom as upload_atoms packs it
+inline int atom_flag_word(const mpmc_ctx *c, int frozen, double eps, double sigma, int disp, double q, double alpha) {
+	int fl = 0;
+	if (frozen) fl |= AF_FROZEN;
+	if (eps == 0.0 || sigma == 0.0) fl |= AF_NULL_RD;
+	if (disp) fl |= c->kept.de_enabled ? AF_DISP_RD : AF_HAS_DISP; // (disp-expansion: LJ mixing no longer matters, pair_math.h)
+	if (sigma < 0.0) fl |= AF_NEG_SIGMA;
+	if (sigma == 0.0) fl |= AF_ZERO_SIGMA;
+	if (q == 0.0) fl |= AF_ZERO_Q;
+	if (alpha == 0.0) fl |= AF_ZERO_ALPHA;
+	return fl;
+}
+// exchange trials (context.cpp): the host list with atoms [at, at + n_remove) taken out and `ins` (may be null) put in their place, the
+// spatial order carried, the tables that follow the tile count resized; everything else of the context stays (totals, structure factors)
+int splice_atoms(mpmc_ctx *c, int at, int n_remove, const AtomRun *ins);
+void copy_atom_run(const mpmc_ctx *c, int first, int count, AtomRun &out); // out = atoms [first, first + count) of the host mirrors
+int set_atoms_from(mpmc_ctx *c, const AtomRun &list);                     // mpmc_set_atoms with a whole list
+// the host sums: of the current list / one atom added (sg = +1) or taken out (-1) / lrc_pair, lrc_self, es_self from them (k_atom_terms_finish)
+void xch_sum_list(const mpmc_ctx *c, XchSums &out);
+void xch_sum_atom(const mpmc_ctx *c, XchSums &xs, double sg, int fl, double sigma, double eps, double q);
+void xch_static_terms(const mpmc_ctx *c, const XchSums &xs, double out3[3]);
 
 } // namespace mpmc

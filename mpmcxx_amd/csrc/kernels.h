@@ -328,6 +328,27 @@ void launch_delta_field(hipStream_t st, const AtomsDev &at, const Box &bx, doubl
                         const double4 *mv_new, int m, int *moved_idx, const double *e_real, double *e_real_trial, double *dk_part);
 // resident positions of the moved atoms <-> mv_new (call again to undo)
 void launch_swap_positions(hipStream_t st, double4 *xyzq, const int *mv_slot, double4 *mv_new, int m);
+// the reduction and post of launch_delta alone: nb block partials, the energy of sf_trial (do_ewald), the result into out4 / dcnt2 / host_out
+void launch_delta_finish(hipStream_t st, const double *block_part, const int *block_cnt, int nb, const RecipDev &rc, const double4 *sf_trial, const Box &bx,
+                         int do_ewald, double *out4, long long *dcnt2, double *host_out, double seq);
+
+// ---- exchange moves (kernels_exchange.hip): trial insertion / removal of ONE molecule -------------------------------------------------------
+// The molecule travels as a staged list of these records, whether its atoms are resident (removal) or not (insertion): what the slot arrays
+// hold for an atom.  mf.x is the molecule's id: a resident atom with that id is one of the molecule's own (removal) and is never a partner;
+// for an insertion it is an id no resident atom has.
+struct XchAtom {
+	double4 xyzq;  // position, charge
+	double2 lj;    // |sigma|, sqrt(epsilon)
+	int2 mf;       // molecule id, AF_* flags
+	double inv_molmass;
+};
+static_assert(sizeof(XchAtom) == 64, "one staged exchange atom is 64 bytes");
+// sg (+1 insertion, -1 removal) times [ pairs of the molecule's atoms with every other resident atom + the molecule's own pairs and
+// intramolecular term ], sf_trial = sf + sg * (the molecule's phases); block partials [nt + 1][2] (the last one: the molecule's own block),
+// then launch_delta_finish: the result block is that of launch_delta, signed changes of the accepted totals
+void launch_exchange(hipStream_t st, const AtomsDev &at, const Box &bx, const RecipDev &rc, const FusedParams &fp, int do_es, const XchAtom *mol, int m,
+                     double sg, double4 *sf_trial, double *block_part /*[nt + 1][2]*/, int *block_cnt /*[nt + 1][2]*/, double *out4, long long *dcnt2,
+                     double *host_out, double seq);
 
 // ---- Axilrod-Teller three-body dispersion (kernels_three_body.hip) --------------------------------------------------------------
 // au[slot] = (a, u) per atom (context.cpp: three_body_coefficients; padding a = 0, u = 1).  Both launches leave kThreeBodyBlocks (or fewer)

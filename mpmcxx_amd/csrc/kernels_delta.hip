@@ -15,41 +15,7 @@
 
 namespace mpmc {
 
-// u(i,j) of lj() and coulombic_real() (erfc part) for one geometry; adds to e_lj/e_re and the in-cutoff counts with sign sg.
-// EXT: the adjacent physics of the pair sweep's extended variant -- coulombic_wolf (:1420-1462) instead of the erfc term, Feynman-Hibbs
-// corrections of both terms (:1100-1148, :1521-1557) -- with the same per-pair arithmetic (pair_math.h); imu = 1/M_i + 1/M_j.
-template <bool ORTHO, bool EXT>
-__device__ __forceinline__ void pair_terms(const Box &bx, const FusedParams &fp, int do_es, const double4 &pi, const double4 &pj, double sig,
-                                           double eps, const PairFlags &f, double imu, double sg, double &e_lj, double &e_re, int &n_lj, int &n_es) {
-	double ox, oy, oz;
-	const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
-	const double ir = fast_rsqrt(ri2);
-	if ((ri2 <= bx.t_lj) && !f.rd_excluded) {
-		const double sr = sig * ir;
-		double s6 = sr * sr * sr;
-		s6 *= s6;
-		const double t12 = f.attractive_only ? 0.0 : s6 * s6;
-		e_lj = fma(sg * 4.0 * eps, t12 - s6, e_lj);
-		n_lj += (sg > 0) ? 1 : -1;
-		if (EXT && fp.fh_order) e_lj = fma(sg, fh_lj_corr(fp.fh_order, fp.fh_c2, fp.fh_c4, imu, eps, t12, s6, ir), e_lj);
-	}
-	if (!do_es || f.es_excluded) return;
-	if (EXT && fp.wolf) {
-		if (ri2 <= bx.t_wolf) { // r < R
-			e_re = fma(sg * (pi.w * pj.w), ir - fp.wolf_erfa_over_r - fp.wolf_inv_r2 * (bx.cutoff - ri2 * ir), e_re);
-			n_es += (sg > 0) ? 1 : -1;
-		}
-		return;
-	}
-	if (ri2 <= bx.t_es) {
-		double g;
-		const double r = ri2 * ir;
-		const double ec = erfc_and_gauss(fp.ewald_alpha * r, g);
-		e_re = fma(sg * (pi.w * pj.w) * ec, ir, e_re);
-		n_es += (sg > 0) ? 1 : -1;
-		if (EXT && fp.fh_order) e_re = fma(sg, fh_es_corr(fp.fh_order, fp.fh_c2, fp.fh_c4, imu, fp.ewald_alpha, ec, g, ri2, r, ir), e_re);
-	}
-}
+// (u(i,j) of one geometry, pair_terms, lives in trial_kernels.h: the exchange moves of kernels_exchange.hip evaluate the same pairs)
 
 // Where the kernels read the move from: device arrays (any m; staged by one host-to-device copy) or the kernel arguments themselves
 // (MvInline, m <= kMvInline: no copy command at all -- a trial move is launch-bound on the host, and every call counts).
@@ -369,6 +335,11 @@ void launch_delta(hipStream_t st, const AtomsDev &at, const int *slot_of, const 
 #undef MPMC_DELTA
 	hipLaunchKernelGGL(k_delta_finish, dim3(1), dim3(256), 0, st, block_part, block_cnt, nt, rc, sf_trial, bx, do_ewald, out4, dcnt2, host_out, seq);
 	if (use_map) launch_mark_moved(st, moved_idx, mv_slot, m, 0);
+}
+// the finish alone: the exchange moves (kernels_exchange.hip) end in the same reduction and the same post
+void launch_delta_finish(hipStream_t st, const double *block_part, const int *block_cnt, int nb, const RecipDev &rc, const double4 *sf_trial, const Box &bx,
+                         int do_ewald, double *out4, long long *dcnt2, double *host_out, double seq) {
+	hipLaunchKernelGGL(k_delta_finish, dim3(1), dim3(256), 0, st, block_part, block_cnt, nb, rc, sf_trial, bx, do_ewald, out4, dcnt2, host_out, seq);
 }
 // accept, the move in the kernel arguments
 __global__ void k_commit_positions_arg(double4 *__restrict__ xyzq, MvArg mv, int m) {

@@ -37,6 +37,7 @@ extern "C" int mpmc_trial_begin(mpmc_ctx *c, int first, int count, const double 
 	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, "mpmc_trial_begin: no accepted configuration (call mpmc_energy first)");
 	for (int t = 0; t < 3 * count; t++)
 		if (!std::isfinite(new_pos[t])) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_begin: non-finite position");
+	c->xch_kind = 0;
 	c->trial_first = first;
 	c->trial_count = count;
 	c->trial_new.assign(new_pos, new_pos + 3 * (size_t)count);
@@ -47,6 +48,267 @@ extern "C" int mpmc_trial_begin(mpmc_ctx *c, int first, int count, const double 
 	// a "move" that leaves every coordinate as it is (e.g. the box a two-box move does not touch): the trial totals ARE the accepted
 	// totals, nothing is evaluated.  (The reference's bead moves re-centre the whole chain, so they do touch every image.)
 	c->trial_noop = (std::memcmp(new_pos, c->h_pos.data() + 3 * (size_t)first, 3 * (size_t)count * sizeof(double)) == 0);
+	return MPMC_OK;
+}
+
+// ---- exchange trials: insertion / removal of one molecule ----------------------------------------------------------------------------------
+static int xch_begin_checks(mpmc_ctx *c, const char *who) {
+	const std::string w(who);
+	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, w + ": no atoms set");
+	if (c->trial_open) return fail(c, MPMC_ERR_ARG, w + ": a trial move is already open (accept or reject it first)");
+	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, w + ": no accepted configuration (call mpmc_energy first)");
+	// (the per-atom coefficients of these two terms belong to one atom list, and an exchange trial has no way to hand over the new atoms')
+	if (c->kept.tb_enabled || c->kept.de_enabled)
+		return fail(c, MPMC_ERR_UNSUPPORTED, w + ": a context with Axilrod-Teller or disp-expansion coefficients changes its composition through mpmc_set_atoms");
+	return MPMC_OK;
+}
+static void xch_open(mpmc_ctx *c, int kind, int at, int count) {
+	c->xch_kind = kind;
+	c->xch_at = c->trial_first = at;
+	c->trial_count = count;
+	c->xch_saved.clear();
+	c->trial_open = true;
+	c->trial_evaluated = c->trial_enqueued = c->trial_noop = false;
+}
+
+extern "C" int mpmc_trial_insert_begin(mpmc_ctx *c, int at_index, int count, const double *pos, const double *charge, const double *polarizability,
+                                       const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
+	if (!c || count <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !frozen) return MPMC_ERR_ARG;
+	int rc = xch_begin_checks(c, "mpmc_trial_insert_begin");
+	if (rc != MPMC_OK) return rc;
+	if (at_index < 0 || at_index > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index outside the atom list");
+	if (at_index > 0 && at_index < c->n && c->h_mol[at_index - 1] == c->h_mol[at_index])
+		return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index lies inside a molecule (it must be a molecule boundary)");
+	for (int t = 0; t < 3 * count; t++)
+		if (!std::isfinite(pos[t])) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: non-finite position");
+	for (int i = 0; i < count; i++)
+		if (epsilon[i] < 0.0 || !std::isfinite(epsilon[i]) || !std::isfinite(sigma[i]) || !std::isfinite(charge[i]) || !std::isfinite(polarizability[i]))
+			return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: epsilon < 0 or non-finite atom parameter");
+	if (!c->h_mass.empty() && !mass) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: the atom list has masses, the molecule needs them too");
+	int32_t id = c->h_mol[0]; // the largest molecule id in use: known from the host sums of the accepted list, else found now
+	if (c->xs_gen == c->static_gen) id = c->xs_acc.mol_max;
+	else
+		for (int i = 1; i < c->n; i++) id = std::max(id, c->h_mol[i]);
+	if (id == INT32_MAX) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: no molecule id left");
+	AtomRun &m = c->xch_mol;
+	m.pos.assign(pos, pos + 3 * (size_t)count);
+	m.q.assign(charge, charge + count);
+	m.alpha.assign(polarizability, polarizability + count);
+	m.eps.assign(epsilon, epsilon + count);
+	m.sigma.assign(sigma, sigma + count);
+	m.frozen.assign(frozen, frozen + count);
+	if (has_disp) m.disp.assign(has_disp, has_disp + count);
+	else m.disp.assign(count, 0);
+	if (!c->h_mass.empty()) m.mass.assign(mass, mass + count); // (a list without masses takes none)
+	else m.mass.clear();
+	m.mol.assign(count, id + 1); // one new molecule, with an id no resident atom has
+	xch_open(c, +1, at_index, count);
+	return MPMC_OK;
+}
+
+extern "C" int mpmc_trial_remove_begin(mpmc_ctx *c, int first, int count) {
+	if (!c || count <= 0) return MPMC_ERR_ARG;
+	int rc = xch_begin_checks(c, "mpmc_trial_remove_begin");
+	if (rc != MPMC_OK) return rc;
+	if (first < 0 || first + count > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_remove_begin: range outside the atom list");
+	bool whole = (first == 0 || c->h_mol[first - 1] != c->h_mol[first]) && (first + count == c->n || c->h_mol[first + count] != c->h_mol[first + count - 1]);
+	for (int i = first + 1; i < first + count; i++) whole = whole && c->h_mol[i] == c->h_mol[first];
+	if (!whole) return fail(c, MPMC_ERR_ARG, "mpmc_trial_remove_begin: the range is not exactly one whole molecule");
+	if (count == c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_remove_begin: the last molecule cannot be removed");
+	copy_atom_run(c, first, count, c->xch_mol);
+	xch_open(c, -1, first, count);
+	return MPMC_OK;
+}
+
+// the trial list: the accepted one with the molecule in or out
+static void xch_trial_list(const mpmc_ctx *c, const AtomRun &acc, AtomRun &out) {
+	out = acc;
+	const size_t at = (size_t)c->xch_at, m = (size_t)c->trial_count;
+	const AtomRun &mol = c->xch_mol;
+	auto edit = [&](auto &v, const auto &ins, size_t per) {
+		if (c->xch_kind > 0) v.insert(v.begin() + per * at, ins.begin(), ins.end());
+		else v.erase(v.begin() + per * at, v.begin() + per * (at + m));
+	};
+	edit(out.pos, mol.pos, 3);
+	edit(out.q, mol.q, 1);
+	edit(out.alpha, mol.alpha, 1);
+	edit(out.eps, mol.eps, 1);
+	edit(out.sigma, mol.sigma, 1);
+	edit(out.mol, mol.mol, 1);
+	edit(out.frozen, mol.frozen, 1);
+	edit(out.disp, mol.disp, 1);
+	if (!out.mass.empty()) edit(out.mass, mol.mass, 1);
+}
+
+// mpmc_set_atoms may rebuild the context in place (growth): the open trial's own state crosses the call in the caller's hands
+static int xch_replace_list(mpmc_ctx *c, const AtomRun &list, AtomRun &&saved) {
+	const int kind = c->xch_kind, at = c->xch_at, count = c->trial_count, last_kind = c->trial_last_kind;
+	const bool evaluated = c->trial_evaluated, was_full = c->trial_was_full;
+	const mpmc_result keep = c->trial_keep, res = c->trial_res;
+	const int64_t rc_terms = c->rc_terms_accepted, rdm_terms = c->rdm_terms_accepted;
+	AtomRun mol = std::move(c->xch_mol);
+	const int rc = set_atoms_from(c, list);
+	c->xch_mol = std::move(mol);
+	c->xch_saved = std::move(saved);
+	c->xch_kind = kind, c->xch_at = c->trial_first = at, c->trial_count = count, c->trial_last_kind = last_kind;
+	c->trial_evaluated = evaluated, c->trial_was_full = was_full;
+	c->trial_keep = keep, c->trial_res = res;
+	c->rc_terms_accepted = rc_terms, c->rdm_terms_accepted = rdm_terms;
+	c->trial_open = true;
+	c->trial_enqueued = c->trial_noop = false;
+	return rc;
+}
+
+static int xch_energy_async(mpmc_ctx *c) {
+	const mpmc_options &o = c->opts;
+	const bool polar = o.polarization && !o.rd_only;
+	const int m = c->trial_count, kind = c->xch_kind;
+	c->trial_polar_delta = false;
+	c->trial_inline = false;
+	if (polar || m > MPMC_TRIAL_MAX_ATOMS || crystal_on(c) || rd_model_on(c)) {
+		// the dipole solve couples every atom, and the further terms have no exchange delta: the trial composition is evaluated in full
+		AtomRun acc, list;
+		copy_atom_run(c, 0, c->n, acc);
+		xch_trial_list(c, acc, list);
+		c->trial_keep = c->last_full;
+		int rc = xch_replace_list(c, list, std::move(acc));
+		if (rc != MPMC_OK) return rc;
+		if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) return rc;
+		c->trial_was_full = true;
+		c->trial_last_kind = 1;
+		c->trial_enqueued = true;
+		return MPMC_OK;
+	}
+	drop_pending_dipoles(c);
+	int rc = prepare(c);
+	if (rc != MPMC_OK) return rc;
+	if ((rc = ensure_trial_buffers(c)) != MPMC_OK) return rc;
+	if ((rc = c->d_xch_mol.reserve(c, MPMC_TRIAL_MAX_ATOMS)) != MPMC_OK) return rc;
+	if ((rc = c->h_xch_mol.reserve(c, MPMC_TRIAL_MAX_ATOMS)) != MPMC_OK) return rc;
+	// (one more pair of partials than tiles: the molecule's own block; a one-tile table is shorter than that)
+	if ((rc = c->d_block_part.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
+	if ((rc = c->d_block_cnt.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
+	const AtomRun &mol = c->xch_mol;
+	const double sg = kind > 0 ? 1.0 : -1.0;
+	// the position-independent terms of the trial composition, from the sums of the accepted list
+	if (c->xs_gen != c->static_gen || c->xs_edits >= kXchResum) {
+		xch_sum_list(c, c->xs_acc);
+		c->xs_gen = c->static_gen;
+		c->xs_edits = 0;
+	}
+	c->xs_trial = c->xs_acc;
+	double molmass = 0.0;
+	for (double v : mol.mass) molmass += v;
+	for (int k = 0; k < m; k++) {
+		const int fl = atom_flag_word(c, mol.frozen[k], mol.eps[k], mol.sigma[k], mol.disp[k], mol.q[k], mol.alpha[k]);
+		xch_sum_atom(c, c->xs_trial, sg, fl, mol.sigma[k], mol.eps[k], mol.q[k]);
+		XchAtom &g = c->h_xch_mol[k];
+		g.xyzq = make_double4(mol.pos[3 * k], mol.pos[3 * k + 1], mol.pos[3 * k + 2], mol.q[k]);
+		g.lj = make_double2(std::fabs(mol.sigma[k]), std::sqrt(mol.eps[k]));
+		g.mf = make_int2(mol.mol[k], fl);
+		g.inv_molmass = (molmass > 0.0) ? 1.0 / molmass : 0.0;
+	}
+	if (kind > 0) c->xs_trial.mol_max = std::max(c->xs_trial.mol_max, mol.mol[0]);
+	xch_static_terms(c, c->xs_trial, c->xch_static);
+	c->xch_N = c->N_movable + (mol.frozen[m - 1] ? 0.0 : sg); // (a molecule's flag is its last atom's, mpmc_set_atoms)
+	hipStream_t st = c->stream;
+	HIP_TRY(c, hipMemcpyAsync(c->d_xch_mol, c->h_xch_mol, (size_t)m * sizeof(XchAtom), hipMemcpyHostToDevice, st));
+	const int do_es = o.rd_only ? 0 : 1;
+	{
+		FusedParams fp{};
+		fp.ewald_alpha = c->ewald_alpha;
+		ext_params(c, fp, o.wolf && do_es);
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_exchange(st, atoms_view(c), c->box, recip_view(c), fp, do_es, c->d_xch_mol, m, sg, c->d_sf_trial, c->d_block_part, c->d_block_cnt, c->d_delta_out,
+		                c->d_delta_cnt, c->h_delta_out, (c->trial_seq += 1.0));
+	}
+	HIP_TRY(c, hipGetLastError());
+	c->trial_was_full = false;
+	c->trial_last_kind = 0;
+	c->trial_enqueued = true;
+	return MPMC_OK;
+}
+
+// the result of an exchange trial of the delta path: the accepted totals, the signed changes the device posted, the position-independent
+// terms and counts of the trial composition
+static void xch_result(mpmc_ctx *c, mpmc_result &r) {
+	const mpmc_options &o = c->opts;
+	const int do_es = o.rd_only ? 0 : 1, m = c->trial_count;
+	const mpmc_result &a = c->last_full;
+	const double *dh = c->h_delta_out.p;
+	const AtomRun &mol = c->xch_mol;
+	r = a;
+	r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_LJ)];
+	r.lrc_pair = o.rd_lrc ? c->xch_static[0] : 0.0;
+	r.lrc_self = o.rd_lrc ? c->xch_static[1] : 0.0;
+	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
+	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
+	if (do_es) {
+		r.es_real = a.es_real + (dh[delta_host_index(D_ES_REAL)] - dh[delta_host_index(D_ES_INTRA)]);
+		r.es_recip = dh[delta_host_index(D_ES_RECIP)];
+		r.es_self = o.wolf ? 0.0 : c->xch_static[2];
+		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
+		r.n_es_in_cutoff = a.n_es_in_cutoff + c->h_delta_cnt[1];
+	}
+	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
+	r.N = c->xch_N;
+	r.NU = r.N * r.energy;
+	const int64_t n_new = (int64_t)c->n + (c->xch_kind > 0 ? m : -m);
+	r.n_pairs = n_new * (n_new - 1) / 2;
+	// the position-independent pair counts (k_static_counts): the molecule's atoms against the classes of everybody else, and among themselves
+	const long long *others = (c->xch_kind > 0) ? c->xs_acc.cls : c->xs_trial.cls;
+	long long d[4] = {0, 0, 0, 0};
+	std::vector<int> fl((size_t)m);
+	for (int k = 0; k < m; k++) fl[k] = atom_flag_word(c, mol.frozen[k], mol.eps[k], mol.sigma[k], mol.disp[k], mol.q[k], mol.alpha[k]);
+	for (int cl = 0; cl < kXchClasses; cl++) {
+		if (!others[cl]) continue;
+		const int cf = ((cl & 1) ? AF_FROZEN : 0) | ((cl & 2) ? AF_NULL_RD : 0) | ((cl & 4) ? AF_HAS_DISP : 0) | ((cl & 8) ? AF_ZERO_Q : 0);
+		for (int k = 0; k < m; k++) {
+			const PairFlags f = pair_flags(0, fl[k], 1, cf);
+			d[1] += f.rd_excluded ? others[cl] : 0;
+			d[2] += f.es_excluded ? others[cl] : 0;
+			d[3] += f.frozen ? others[cl] : 0;
+		}
+	}
+	for (int k = 0; k < m; k++)
+		for (int l = k + 1; l < m; l++) {
+			const PairFlags f = pair_flags(0, fl[k], 0, fl[l]);
+			d[0] += f.intra, d[1] += f.rd_excluded, d[2] += f.es_excluded, d[3] += f.frozen;
+		}
+	const long long sgn = c->xch_kind > 0 ? 1 : -1;
+	r.n_intra = a.n_intra + sgn * d[0];
+	r.n_rd_excluded = a.n_rd_excluded + sgn * d[1];
+	r.n_es_excluded = a.n_es_excluded + sgn * d[2];
+	r.n_frozen = a.n_frozen + sgn * d[3];
+}
+
+// accept of the delta path: the list is edited in place; a context that has to grow is rebuilt around the new list and re-based
+static int xch_accept_delta(mpmc_ctx *c) {
+	const int m = c->trial_count, kind = c->xch_kind;
+	const int n_new = c->n + (kind > 0 ? m : -m);
+	if (n_new > c->max_atoms) { // (rare: the capacity grows by a quarter each time)
+		const mpmc_result res = c->trial_res;
+		AtomRun acc, list;
+		copy_atom_run(c, 0, c->n, acc);
+		xch_trial_list(c, acc, list);
+		int rc = xch_replace_list(c, list, AtomRun{});
+		c->trial_open = false;
+		mpmc_result tmp;
+		if (rc == MPMC_OK) rc = mpmc_energy(c, &tmp); // the fresh context's structure factors and position-independent terms
+		if (rc != MPMC_OK) return rc;
+		c->last_full = res; // the accepted totals are the trial's
+		c->cache_valid = true;
+		return MPMC_OK;
+	}
+	std::swap(c->d_sf, c->d_sf_trial); // (each buffer with its own capacity)
+	const int rc = splice_atoms(c, c->xch_at, kind < 0 ? m : 0, kind > 0 ? &c->xch_mol : nullptr);
+	if (rc != MPMC_OK) return rc;
+	for (int k = 0; k < 3; k++) c->h_static[k] = c->xch_static[k];
+	c->static_dirty = false;
+	c->xs_acc = c->xs_trial;
+	c->xs_edits++;
+	c->last_full = c->trial_res;
+	c->cache_valid = true;
 	return MPMC_OK;
 }
 
@@ -61,6 +323,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		c->trial_enqueued = true;
 		return MPMC_OK;
 	}
+	if (c->xch_kind) return xch_energy_async(c);
 	const mpmc_options &o = c->opts;
 	const bool polar = o.polarization && !o.rd_only;
 	const int m = c->trial_count;
@@ -264,6 +527,12 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		}
 		prof_harvest(c);
 	}
+	if (c->xch_kind) {
+		xch_result(c, c->trial_res);
+		c->trial_evaluated = true;
+		*out = c->trial_res;
+		return MPMC_OK;
+	}
 	const int do_es = c->opts.rd_only ? 0 : 1;
 	const mpmc_result &a = c->last_full;
 	const double *dh = c->h_delta_out.p; // (the D_* slots at delta_host_index)
@@ -320,6 +589,21 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 		c->trial_open = false;
 		return MPMC_OK;
 	}
+	if (c->xch_kind) { // an exchange: the full evaluation left the trial list resident; the delta path edits the list now
+		if (!c->trial_was_full) {
+			const int rc_x = xch_accept_delta(c);
+			if (rc_x != MPMC_OK) return rc_x;
+		} else {
+			c->last_full = c->trial_res;
+			c->cache_valid = true;
+			if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
+			if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
+		}
+		c->xch_saved.clear();
+		c->xch_kind = 0;
+		c->trial_open = false;
+		return MPMC_OK;
+	}
 	if (!c->trial_was_full) {
 		if (c->trial_polar_delta) { // the trial positions are already resident; the trial real-space field becomes the accepted one
 			std::swap(c->d_e_real, c->d_e_real_trial);
@@ -358,6 +642,28 @@ extern "C" int mpmc_trial_reject(mpmc_ctx *c) {
 		mpmc_result drop;
 		int rc = mpmc_trial_energy_wait(c, &drop);
 		if (rc != MPMC_OK) return rc;
+	}
+	if (c->xch_kind) { // an exchange: the delta path left nothing behind; after a full evaluation the accepted list goes back
+		if (c->xch_saved.size() > 0) {
+			const mpmc_result keep = c->trial_keep;
+			AtomRun acc = std::move(c->xch_saved);
+			int rc = xch_replace_list(c, acc, AtomRun{});
+			c->xch_kind = 0;
+			c->trial_open = false;
+			if (rc != MPMC_OK) return rc;
+			c->last_full = keep;
+			c->cache_valid = true;
+			c->e_real_valid = false;
+			const bool polar = c->opts.polarization && !c->opts.rd_only;
+			if (!polar && !c->opts.wolf) { // the resident structure factors are the trial ones: re-base on the restored list
+				mpmc_result tmp;
+				if ((rc = mpmc_energy(c, &tmp)) != MPMC_OK) return rc;
+			}
+			return MPMC_OK;
+		}
+		c->xch_kind = 0;
+		c->trial_open = false;
+		return MPMC_OK;
 	}
 	c->trial_open = false;
 	if (c->trial_polar_delta) { // (enqueued or evaluated) the device holds the trial positions: swap the accepted ones back

@@ -1,4 +1,5 @@
-// trial_kernels.h -- the scaffold the trial-move ("delta") terms share: the moved-atom map, the real-space delta-field kernel with its
+// trial_kernels.h -- the scaffold the trial-move ("delta") terms share: one pair's energy terms (pair_terms: kernels_delta.hip and
+// kernels_exchange.hip), the moved-atom map, the real-space delta-field kernel with its
 // finish, the launch sequence around them, and the fixed-order sum of per-workgroup partials.  Included after kernels.h by the HIP
 // translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, and through pair_term_walk.h
 // kernels_disp.hip, kernels_crystal.hip and kernels_rd_model.hip); the kernels are static, one copy per code object.  A new trial-move
@@ -9,6 +10,42 @@
 #include "device_math.h"
 
 namespace mpmc {
+
+// u(i,j) of lj() and coulombic_real() (erfc part) for one geometry; adds to e_lj/e_re and the in-cutoff counts with sign sg.
+// EXT: the adjacent physics of the pair sweep's extended variant -- coulombic_wolf (:1420-1462) instead of the erfc term, Feynman-Hibbs
+// corrections of both terms (:1100-1148, :1521-1557) -- with the same per-pair arithmetic (pair_math.h); imu = 1/M_i + 1/M_j.
+template <bool ORTHO, bool EXT>
+__device__ __forceinline__ void pair_terms(const Box &bx, const FusedParams &fp, int do_es, const double4 &pi, const double4 &pj, double sig,
+                                           double eps, const PairFlags &f, double imu, double sg, double &e_lj, double &e_re, int &n_lj, int &n_es) {
+	double ox, oy, oz;
+	const double ri2 = min_image_sq<ORTHO>(bx, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, ox, oy, oz);
+	const double ir = fast_rsqrt(ri2);
+	if ((ri2 <= bx.t_lj) && !f.rd_excluded) {
+		const double sr = sig * ir;
+		double s6 = sr * sr * sr;
+		s6 *= s6;
+		const double t12 = f.attractive_only ? 0.0 : s6 * s6;
+		e_lj = fma(sg * 4.0 * eps, t12 - s6, e_lj);
+		n_lj += (sg > 0) ? 1 : -1;
+		if (EXT && fp.fh_order) e_lj = fma(sg, fh_lj_corr(fp.fh_order, fp.fh_c2, fp.fh_c4, imu, eps, t12, s6, ir), e_lj);
+	}
+	if (!do_es || f.es_excluded) return;
+	if (EXT && fp.wolf) {
+		if (ri2 <= bx.t_wolf) { // r < R
+			e_re = fma(sg * (pi.w * pj.w), ir - fp.wolf_erfa_over_r - fp.wolf_inv_r2 * (bx.cutoff - ri2 * ir), e_re);
+			n_es += (sg > 0) ? 1 : -1;
+		}
+		return;
+	}
+	if (ri2 <= bx.t_es) {
+		double g;
+		const double r = ri2 * ir;
+		const double ec = erfc_and_gauss(fp.ewald_alpha * r, g);
+		e_re = fma(sg * (pi.w * pj.w) * ec, ir, e_re);
+		n_es += (sg > 0) ? 1 : -1;
+		if (EXT && fp.fh_order) e_re = fma(sg, fh_es_corr(fp.fh_order, fp.fh_c2, fp.fh_c4, imu, fp.ewald_alpha, ec, g, ri2, r, ir), e_re);
+	}
+}
 
 // moved_idx[slot] = index of the slot in the move list (set) or -1 as for every other slot (clear)
 static __global__ void k_mark_moved(int *__restrict__ moved_idx, const int *__restrict__ mv_slot, int m, int set) {

@@ -216,6 +216,9 @@ def lib():
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
     L.mpmc_trial_accept.argtypes = [vp]
     L.mpmc_trial_reject.argtypes = [vp]
+    if hasattr(L, "mpmc_trial_insert_begin") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no exchange trials)
+        L.mpmc_trial_insert_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip, dp]
+        L.mpmc_trial_remove_begin.argtypes = [vp, C.c_int, C.c_int]
     L.mpmc_gibbs_energy.argtypes = [vp, vp, C.POINTER(Result), C.POINTER(Result)]
     L.mpmc_gibbs_boltzmann_factor.argtypes = [C.POINTER(GibbsMove), dp, dp]
     L.mpmc_rccl_version.argtypes = [C.POINTER(C.c_int)]
@@ -425,6 +428,11 @@ class System:
         self._check(self._L.mpmc_set_atoms(self._h, n, _dp(pos), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
                                            _dp(f("sigma")), _ip(g("mol_id")), _ip(g("frozen")), _ip(disp), _dp(mass)))
         self.n = n
+        # the object's own copy of the list: accepted trials and update_positions keep it current (set_positions_device does not: the positions
+        # stay on the device)
+        self._atoms = {k: np.array(v) for k, v in atoms.items()}
+        self._atoms["pos"] = np.array(pos.reshape(n, 3))
+        self._exchange = self._move = None
         # the library discards three-body coefficients with every atom list: the term follows the options (`axilrod_teller on`)
         if self.options.get("axilrod_teller"):
             mk = bool(self.options.get("midzuno_kihara_approx"))
@@ -527,6 +535,8 @@ class System:
     def update_positions(self, first: int, pos: np.ndarray):
         p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
         self._check(self._L.mpmc_update_positions(self._h, int(first), p.size // 3, _dp(p)))
+        if getattr(self, "_atoms", None) is not None:
+            self._atoms["pos"][int(first):int(first) + p.size // 3] = p.reshape(-1, 3)
 
     def set_positions_device(self, data_ptr: int):
         """positions from device memory ([n][3] fp64).  The caller synchronizes the stream that produced them first (torch: `torch.cuda.current_stream().synchronize()`);
@@ -558,6 +568,7 @@ class System:
         """energy of the configuration in which atoms first.. take the positions `pos`; follow with accept() or reject()."""
         p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
         self._check(self._L.mpmc_trial_begin(self._h, int(first), p.size // 3, _dp(p)))
+        self._exchange, self._move = None, (int(first), p.reshape(-1, 3))
         r = Result()
         rc = self._L.mpmc_trial_energy(self._h, C.byref(r))
         if rc != MPMC_OK:
@@ -566,12 +577,65 @@ class System:
         self.trial_observables = r.as_dict()
         return r.energy
 
+    @property
+    def atoms(self) -> Dict[str, np.ndarray]:
+        """the object's own copy of the atom list: what set_atoms was given, followed by update_positions and every accepted trial"""
+        return self._atoms
+
+    def _trial(self):
+        r = Result()
+        rc = self._L.mpmc_trial_energy(self._h, C.byref(r))
+        if rc != MPMC_OK:
+            msg = (self._L.mpmc_last_error(self._h) or b"").decode()
+            self._L.mpmc_trial_reject(self._h)
+            self._exchange = None
+            raise MpmcError(rc, msg)
+        self.trial_observables = r.as_dict()
+        return r.energy
+
+    def trial_insert_energy(self, at_index: int, mol_atoms: Dict[str, np.ndarray]) -> float:
+        """energy of the composition with ONE more molecule: the atoms of `mol_atoms` (the keys of the atoms dict; mol_id is not read, the
+        molecule gets an id of its own) in front of atom at_index (a molecule boundary, or n: appended); follow with accept() or reject()."""
+        f = lambda k: np.ascontiguousarray(mol_atoms[k], dtype=np.float64)
+        g = lambda k: np.ascontiguousarray(mol_atoms[k], dtype=np.int32)
+        own = self._atoms
+        pos = f("pos").reshape(-1)
+        m = pos.size // 3
+        disp = g("has_disp") if "has_disp" in mol_atoms else None
+        mass = f("mass") if "mass" in mol_atoms else None
+        self._check(self._L.mpmc_trial_insert_begin(self._h, int(at_index), m, _dp(pos), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
+                                                    _dp(f("sigma")), _ip(g("frozen")), _ip(disp), _dp(mass)))
+        mol = {k: np.asarray(mol_atoms[k]) if k in mol_atoms else np.zeros((m,) + own[k].shape[1:], dtype=own[k].dtype) for k in own}
+        mol["pos"] = pos.reshape(m, 3)
+        mol["mol_id"] = np.full(m, int(np.max(own["mol_id"])) + 1, dtype=own["mol_id"].dtype)
+        self._exchange, self._move = (int(at_index), 0, mol), None
+        return self._trial()
+
+    def trial_remove_energy(self, first: int, count: int) -> float:
+        """energy of the composition without the molecule that occupies atoms [first, first + count); follow with accept() or reject()."""
+        self._check(self._L.mpmc_trial_remove_begin(self._h, int(first), int(count)))
+        self._exchange, self._move = (int(first), int(count), None), None
+        return self._trial()
+
     def accept(self):
         self._check(self._L.mpmc_trial_accept(self._h))
         self.observables = dict(self.trial_observables)
+        if getattr(self, "_exchange", None) is not None:  # the object's own atom arrays follow an accepted exchange
+            at, n_remove, mol = self._exchange
+            own = self.atoms
+            for k in own:
+                kept = np.delete(own[k], np.s_[at:at + n_remove], axis=0)
+                own[k] = kept if mol is None else np.insert(kept, at, mol[k], axis=0)
+            self.n = int(own["pos"].shape[0])
+            self._exchange = None
+        elif getattr(self, "_move", None) is not None:
+            first, p = self._move
+            self._atoms["pos"][first:first + p.shape[0]] = p
+        self._move = None
 
     def reject(self):
         self._check(self._L.mpmc_trial_reject(self._h))
+        self._exchange = self._move = None
 
     def _scalar(self, fn) -> float:
         v = C.c_double()
