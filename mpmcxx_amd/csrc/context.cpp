@@ -1521,6 +1521,16 @@ extern "C" int mpmc_debug_upload_counts(mpmc_ctx *c, long long *out2) {
 	return 0;
 }
 
+// diagnostics only (tests assert which path an exchange trial took and that the host sums were re-made): exchange trials evaluated on the
+// delta path / in full, and summations of xs_acc over the whole list
+extern "C" int mpmc_debug_exchange_counts(mpmc_ctx *c, long long *out3) {
+	if (!c || !out3) return -1;
+	out3[0] = c->kept.n_xch_delta;
+	out3[1] = c->kept.n_xch_full;
+	out3[2] = c->kept.n_xch_resums;
+	return 0;
+}
+
 // measurement only: per-workgroup time stamps of the last panel launch (tools/panel_trace.py); 0 entries unless the context was configured with trace_panel = 1
 extern "C" int mpmc_debug_panel_trace(mpmc_ctx *c, long long *out4, int max_entries) {
 	if (!c || !out4) return -1;

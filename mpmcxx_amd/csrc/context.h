@@ -127,6 +127,7 @@ struct mpmc_kept {
 	// wait then fell back to a stream synchronisation), plain stream synchronisations, and yields taken inside long polls
 	long long n_poll_hits = 0, n_poll_timeouts = 0, n_stream_syncs = 0, n_poll_yields = 0;
 	long long n_uploads_carried = 0, n_uploads_sorted = 0; // (diagnostics: mpmc_debug_upload_counts)
+	long long n_xch_delta = 0, n_xch_full = 0, n_xch_resums = 0; // (diagnostics: mpmc_debug_exchange_counts)
 	bool tb_enabled = false, tb_mk = false; // Axilrod-Teller term switched on; Midzuno-Kihara c9 (mpmc_set_axilrod_teller)
 	bool de_enabled = false;                // disp-expansion term switched on (mpmc_set_disp_expansion); the atoms' dispersion flag is AF_DISP_RD then
 	int de_flags = 0;                       // MPMC_DISP_*

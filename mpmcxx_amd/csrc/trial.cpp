@@ -56,10 +56,12 @@ static int xch_begin_checks(mpmc_ctx *c, const char *who) {
 	const std::string w(who);
 	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, w + ": no atoms set");
 	if (c->trial_open) return fail(c, MPMC_ERR_ARG, w + ": a trial move is already open (accept or reject it first)");
-	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, w + ": no accepted configuration (call mpmc_energy first)");
-	// (the per-atom coefficients of these two terms belong to one atom list, and an exchange trial has no way to hand over the new atoms')
+	// (the per-atom coefficients of these two terms belong to one atom list, and an exchange trial has no way to hand over the new atoms';
+	// in front of the accepted-configuration check: switching either term on drops the accepted totals, and the answer to an exchange trial
+	// on such a context is "never", not "call mpmc_energy first")
 	if (c->kept.tb_enabled || c->kept.de_enabled)
 		return fail(c, MPMC_ERR_UNSUPPORTED, w + ": a context with Axilrod-Teller or disp-expansion coefficients changes its composition through mpmc_set_atoms");
+	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, w + ": no accepted configuration (call mpmc_energy first)");
 	return MPMC_OK;
 }
 static void xch_open(mpmc_ctx *c, int kind, int at, int count) {
@@ -177,6 +179,7 @@ static int xch_energy_async(mpmc_ctx *c) {
 		c->trial_was_full = true;
 		c->trial_last_kind = 1;
 		c->trial_enqueued = true;
+		c->kept.n_xch_full++;
 		return MPMC_OK;
 	}
 	drop_pending_dipoles(c);
@@ -195,6 +198,7 @@ static int xch_energy_async(mpmc_ctx *c) {
 		xch_sum_list(c, c->xs_acc);
 		c->xs_gen = c->static_gen;
 		c->xs_edits = 0;
+		c->kept.n_xch_resums++;
 	}
 	c->xs_trial = c->xs_acc;
 	double molmass = 0.0;
@@ -226,6 +230,7 @@ static int xch_energy_async(mpmc_ctx *c) {
 	c->trial_was_full = false;
 	c->trial_last_kind = 0;
 	c->trial_enqueued = true;
+	c->kept.n_xch_delta++;
 	return MPMC_OK;
 }
 

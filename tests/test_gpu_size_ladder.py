@@ -30,9 +30,9 @@ LADDER = util.size_ladder()
 CONST = util.ladder_constants()
 
 
-def ladder_box(n, cell, seed):
+def ladder_box(n, cell, seed, n_frame=N_FRAME):
     """n atoms at about 45 A^3 each: molecule centres (and the framework's sites) on a jittered cubic lattice of the cell's fractional
-    coordinates, every molecule shifted by a random whole cell vector (unwrapped coordinates)."""
+    coordinates, every molecule shifted by a random whole cell vector (unwrapped coordinates).  n_frame: sites of the frozen framework molecule."""
     rng = np.random.default_rng(seed)
     L = (45.0 * n) ** (1.0 / 3.0)
     if cell == "cubic":
@@ -45,16 +45,16 @@ def ladder_box(n, cell, seed):
     # molecule sizes in list order: mobile molecules of 1-4 sites, the framework somewhere in between
     sizes = rng.choice([1, 1, 1, 2, 3, 4], size=n)
     cs = np.cumsum(sizes)
-    k = int(np.searchsorted(cs, n - N_FRAME))
+    k = int(np.searchsorted(cs, n - n_frame))
     sizes = sizes[:k + 1].copy()
-    sizes[-1] -= cs[k] - (n - N_FRAME)
+    sizes[-1] -= cs[k] - (n - n_frame)
     sizes = sizes[sizes > 0]
     at = int(rng.integers(1, len(sizes)))
-    sizes = np.concatenate([sizes[:at], [N_FRAME], sizes[at:]])
+    sizes = np.concatenate([sizes[:at], [n_frame], sizes[at:]])
     frame = np.zeros(len(sizes), dtype=bool)
     frame[at] = True
     # one lattice point per mobile molecule and per framework site
-    n_pts = int((sizes[~frame]).size + N_FRAME)
+    n_pts = int((sizes[~frame]).size + n_frame)
     g = math.ceil(n_pts ** (1.0 / 3.0))
     sites = rng.permutation(g ** 3)[:n_pts]
     ijk = np.stack([sites // (g * g), (sites // g) % g, sites % g], axis=1).astype(np.float64)
@@ -65,8 +65,8 @@ def ladder_box(n, cell, seed):
     pt_of_mol = np.full(len(sizes), -1)
     pt_of_mol[~frame] = np.arange((~frame).sum())
     pt_of_atom = pt_of_mol[mol].copy()
-    fr_atoms = np.arange(first[at], first[at] + N_FRAME)
-    pt_of_atom[fr_atoms] = (~frame).sum() + np.arange(N_FRAME)
+    fr_atoms = np.arange(first[at], first[at] + n_frame)
+    pt_of_atom[fr_atoms] = (~frame).sum() + np.arange(n_frame)
     pos = frac[pt_of_atom] @ basis
     rank = np.arange(n) - first[mol]  # position inside the molecule
     off = rng.normal(scale=0.45, size=(n, 3))

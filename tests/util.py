@@ -149,6 +149,37 @@ def check_trial_against_oracle(obs, atoms, basis, opts, pos, rel=REL_TOL, label=
     return ref
 
 
+# ---- the library's diagnostic counters (context.cpp) ---------------------------------------------------------------------------------------
+def debug_counts(S, name, count):
+    """`count` long longs of the diagnostic entry point `name(ctx, out)`"""
+    import ctypes
+
+    from mpmcxx_amd import energy
+
+    fn = getattr(energy.lib(), name)
+    fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    out = (ctypes.c_longlong * count)()
+    assert fn(S.handle, out) == 0, name
+    return [int(v) for v in out]
+
+
+def upload_counts(S):
+    """(uploads of the atom list that carried the spatial order, uploads that sorted) since the context was made"""
+    return tuple(debug_counts(S, "mpmc_debug_upload_counts", 2))
+
+
+def exchange_counts(S):
+    """(exchange trials on the delta path, exchange trials evaluated in full, summations of the host sums over the whole list)"""
+    return tuple(debug_counts(S, "mpmc_debug_exchange_counts", 3))
+
+
+def xch_resum():
+    """kXchResum of context.h: accepted exchanges after which the host sums of the exchange delta are re-made from the list"""
+    found = re.findall(r"\bkXchResum\s*=\s*(\d+)\s*[;,]", csrc_text("context.h"))
+    assert len(found) == 1, found
+    return int(found[0])
+
+
 # ---- one comparison with the oracle: test_gpu_random.check (and through it test_gpu_pair_sweep), test_gpu_edge_cases, test_gpu_box_moves and
 # test_gpu_size_ladder -------------------------------------------------------------------------------------------------------------------
 def oracle_energy(atoms, basis, opts):
