@@ -609,6 +609,61 @@ typedef struct mpmc_gibbs_move {
  * reference's throw codes 20000 / 102, or MPMC_ERR_UNSUPPORTED for spin-flip moves (quantum rotation is outside the path). */
 int mpmc_gibbs_boltzmann_factor(const mpmc_gibbs_move *move, double boltzmann_factor[2], double energy[2]);
 
+/* ---- `cavity_bias on`: the cavity grid of uVT moves, System::cavity_update_grid (src/System.Cavity.cpp:15-188) ---------------------------
+ * In front of every move (System::make_move, src/System.MonteCarlo.cpp:731-735) the reference bins every atom against a G x G x G grid of
+ * sphere centres, counts the spheres that hold no atom (cavities_open, cavity_bias_probability) and estimates their joint volume with
+ * (int)(0.1 V) darts (update_cavity_volume).  A biased insertion then puts the molecule's centre of mass on one empty centre (:742-764) and
+ * the acceptance factor carries cavity_volume * cavity_bias_probability (:1368-1389).  Here the binning, the count, the ordered list of empty
+ * centres and the darts run on the device; the random stream stays the driver's.
+ *   mpmc_set_cavity_grid   grid_size = 0 switches the grid off.  On: grid_size < 0, radius <= 0 or non-finite, or grid_size above
+ *                          MPMC_CAVITY_MAX_GRID is MPMC_ERR_INVALID_SETTING (SimulationControl.cpp:2157-2162).  The setting has the lifetime of
+ *                          mpmc_set_polar_wolf's (it survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options and capacity growth).  A context
+ *                          that never switches the grid on allocates nothing for it, launches nothing more and returns the same bits.
+ *   mpmc_cavity_update     works on the accepted atom list (it needs masses: the atoms enter at the reference's wrapped_pos, what
+ *                          mpmc_update_com returns: the position minus the lattice shift of the molecule's centre of mass, frozen molecules
+ *                          unshifted).  dart_frac: the caller's `-0.5 + get_rand()` triples in draw order, n_darts of them (the reference throws
+ *                          mpmc_cavity_num_darts(volume)); n_darts = 0 is allowed, dart_frac may then be NULL and cavity_volume is 0.0 / 0.0 *
+ *                          volume, NaN, as in the reference.  Refused with MPMC_ERR_ARG and a text: the grid is off, no box or atoms, no
+ *                          masses, a trial move open.  It may follow an accepted exchange trial directly; it changes nothing an evaluation
+ *                          or a trial reads.
+ *   arithmetic             sphere centre (i, j, k): comp[q] = (idx_q + 1) / (G + 1); v[p] = sum_q basis[q][p] comp[q], then minus
+ *                          0.5 basis[q][p] for q = 0, 1, 2.  dart: pos[p] = sum_q basis[q][p] dart_frac[q].  r = sum_p d_p d_p with d = centre -
+ *                          atom, respectively dart - centre; inside means sqrt(r) < radius, strict, decided on r itself against
+ *                          mpmc_cavity_r2_threshold(radius).  No minimum image.  Products and sums are not fused.  occupancy = atoms inside
+ *                          (a count); cavities_open = centres with none; probability = open / G^3; a dart hits when it lies inside some
+ *                          empty sphere; cavity_volume = (hits / n_darts) * volume.  All counts are exact; the doubles are the reference's bits.
+ *   mpmc_cavity_point      the open_rank-th empty centre in the reference's enumeration order (i outermost, k innermost): cavities_array[
+ *                          random_index] of make_move.  MPMC_ERR_ARG when the rank is out of range, or when no update has been made since
+ *                          the grid setting, the cell or the atom list (positions included) last changed.
+ *   mpmc_cavity_get        occupancy [G^3], centres [G^3][3] and the flat indices (i G + j) G + k of the empty centres, ascending
+ *                          [cavities_open]; any pointer may be NULL.  Same validity rule.
+ * Host only, no device needed (like mpmc_pbc_compute): mpmc_cavity_num_darts = (int)(volume * 0.1); mpmc_cavity_grid_point;
+ * mpmc_cavity_r2_threshold = the smallest double whose correctly rounded square root is >= radius (NaN for radius <= 0 or non-finite);
+ * mpmc_uvt_boltzmann_factor = the ENSEMBLE_UVT branch of System::boltzmann_factor (:1358-1422) for INSERT / REMOVE / DISPLACE in the reference's
+ * operand order, the biased form when biased_move != 0, with ATM2REDUCED = 0.0073389366; fugacity is the value the reference would pick
+ * (pressure, fugacities[0] or fugacities[sorbateInsert]), N = observables->N as the reference reads it there, avg_cavity_probability the
+ * driver's running average.  Any other move type: MPMC_ERR_UNSUPPORTED.
+ * Not part of the library: a uVT driver, the fugacity equations of state, cavity_autoreject (still refused). */
+#define MPMC_CAVITY_MAX_GRID 128 /* 128^3 = 2 M sphere centres */
+int mpmc_set_cavity_grid(mpmc_ctx *ctx, int grid_size, double radius);
+typedef struct mpmc_cavity_result {
+	int64_t total_points, cavities_open, n_darts, hits;
+	double probability, cavity_volume;
+} mpmc_cavity_result;
+int mpmc_cavity_update(mpmc_ctx *ctx, int n_darts, const double *dart_frac /* [n_darts][3] */, mpmc_cavity_result *out);
+int mpmc_cavity_point(mpmc_ctx *ctx, int64_t open_rank, double pos[3]);
+int mpmc_cavity_get(mpmc_ctx *ctx, int32_t *occupancy /* [G^3] */, double *grid_pos /* [G^3][3] */, int32_t *open_flat_index /* [cavities_open] */);
+int mpmc_cavity_num_darts(double volume);
+int mpmc_cavity_grid_point(const double basis[9], int grid_size, int i, int j, int k, double pos[3]);
+double mpmc_cavity_r2_threshold(double radius);
+typedef struct mpmc_uvt_move {
+	int32_t movetype, biased_move, sorbate_count; /* checkpoint->movetype (MPMC_MOVETYPE_*), checkpoint->biased_move, sorbateCount */
+	double temperature, fugacity, volume, N, init_energy, final_energy, cavity_volume, avg_cavity_probability;
+} mpmc_uvt_move;
+int mpmc_uvt_boltzmann_factor(const mpmc_uvt_move *move, double *boltzmann_factor);
+/* (measurement) device milliseconds of the last mpmc_cavity_update made under mpmc_set_profiling: { occupancy, compaction, darts } */
+int mpmc_debug_cavity_times(mpmc_ctx *ctx, double ms3[3]);
+
 /* ---- SimulationControl::PI_calculate_kinetic (PathIntegral.cpp:806-824) and its chain measure (:851-965) ----
  * Host-side O(P * n_molecules); no device work.  com: centres of mass [P][n_molecules][3] of the P images of every
  * molecule (Molecule::update_COM, src/Molecule.cpp:259-281; mpmc_update_com returns one bead's block),

@@ -186,6 +186,11 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "c6_mixing") { need(1); s.c6_mixing = onoff(t[1]); }
 		else if (k == "lj_buffered_14_7") { need(1); s.using_lj_buffered_14_7 = onoff(t[1]) != 0; }
 		else if (k == "dreiding") { need(1); s.use_dreiding = onoff(t[1]); }
+		// (the cavity-bias grid: read into fields, no flag; the facade hands them to mpmc_set_cavity_grid.  `cavity_grid` is the reference's
+		// keyword for cavity_grid_size, SimulationControl.cpp:608-624)
+		else if (k == "cavity_bias") { need(1); s.cavity_bias = onoff(t[1]); }
+		else if (k == "cavity_grid" || k == "cavity_grid_size") { need(1); s.cavity_grid_size = (int)dval(1); }
+		else if (k == "cavity_radius") { need(1); s.cavity_radius = dval(1); }
 		else if (k == "rd_crystal_order") { need(1); s.rd_crystal_order = (int)dval(1); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }

@@ -22,8 +22,10 @@
 // INTEGRATION.md does for the real reference objects).  Header-only; link with -lmpmc_energy.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <functional>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -122,6 +124,13 @@ public:
 	int polar_zodid = 0;                 // zeroth-order dipoles, mu = alpha E0 (mpmc_set_polar_relax)
 	int polar_ewald_full = 0;            // Ewald-summed induced field (mpmc_set_polar_ewald_full), src/System.h: polar_ewald_full
 	int polar_ewald_full_vector_kweight = 0; // MPMC_PEF_VECTOR_KWEIGHT: the intended reciprocal-space weight (no keyword: the reference has none)
+	// the cavity-bias grid of uVT moves (mpmc_set_cavity_grid), src/System.h: cavity_bias, cavity_grid_size, cavity_radius; what
+	// cavity_update_grid() leaves behind: cavities_open, cavity_volume and (nodestats->) cavity_bias_probability
+	int cavity_bias = 0, cavity_grid_size = 0;
+	double cavity_radius = 0;
+	int cavities_open = 0;
+	double cavity_volume = 0, cavity_bias_probability = 0;
+	mpmc_cavity_result cavity_result{}; // of the last cavity_update_grid (hits and dart count too)
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
@@ -325,6 +334,31 @@ public:
 		exchange_enqueue();
 	}
 
+	// ---- System::cavity_update_grid, src/System.Cavity.cpp:15-188 (the reference calls it in front of every move of a cavity_bias run) ----
+	// The darts of update_cavity_volume come from the caller's generator through the distribution System::get_rand uses: three uniforms per
+	// dart, dart-major, each entered as -0.5 + u; (int)(0.1 volume) of them.
+	template <class Rng>
+	void cavity_update_grid(Rng &rng) {
+		sync_state();
+		std::uniform_real_distribution<double> dist{0, 1};
+		const int n_darts = mpmc_cavity_num_darts(pbc.volume);
+		std::vector<double> frac(3 * (size_t)(n_darts > 0 ? n_darts : 0));
+		for (size_t t = 0; t < frac.size(); t++) frac[t] = -0.5 + dist(rng);
+		check(mpmc_cavity_update(ctx_, n_darts > 0 ? n_darts : 0, frac.empty() ? nullptr : frac.data(), &cavity_result), "mpmc_cavity_update");
+		cavities_open = (int)cavity_result.cavities_open;
+		cavity_volume = cavity_result.cavity_volume;
+		cavity_bias_probability = cavity_result.probability;
+	}
+	// the centre of mass of a biased insertion (System::make_move, src/System.MonteCarlo.cpp:742-764): u is the caller's get_rand()
+	void cavity_insertion_point(double u, double pos[3]) {
+		if (cavities_open <= 0) { // (the reference takes the unbiased branch then)
+			last_error_ = "cavity_insertion_point: no empty cavity";
+			throw (int)MPMC_ERR_INTERNAL;
+		}
+		const int random_index = (cavities_open - 1) - (int)std::rint(((double)((size_t)cavities_open - 1)) * u);
+		check(mpmc_cavity_point(ctx_, random_index, pos), "mpmc_cavity_point");
+	}
+
 	double lj() { return piece(mpmc_lj); }
 	double coulombic() { return piece(mpmc_coulombic); }
 	double coulombic_real() { return piece(mpmc_coulombic_real); }
@@ -376,6 +410,8 @@ private:
 	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
 	int rd_model_form_ = 0, rd_model_mixing_ = 0;  // ... and its rd model
 	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
+	int cavity_grid_ = 0;                          // ... and its cavity grid (0: off)
+	double cavity_radius_ = 0;
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
 	int trial_kind_ = 0, trial_count_ = 0; // the open trial: 0 a displacement, +1 an insertion (trial_mol_), -1 a removal
@@ -412,6 +448,8 @@ private:
 			ewald_full_on_ = ewald_full_flags_ = 0;
 			rd_model_form_ = rd_model_mixing_ = 0;
 			relax_scheme_ = zodid_on_ = 0;
+			cavity_grid_ = 0;
+			cavity_radius_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -513,6 +551,16 @@ private:
 			check(mpmc_set_polar_relax(ctx_, relax_scheme, polar_zodid ? 1 : 0), "mpmc_set_polar_relax");
 			relax_scheme_ = relax_scheme;
 			zodid_on_ = polar_zodid ? 1 : 0;
+		}
+		// (cavity_bias on with a grid size or radius that is not positive is refused by the library, SimulationControl.cpp:2157-2162)
+		if (cavity_bias ? (cavity_grid_ == 0 || cavity_grid_size != cavity_grid_ || cavity_radius != cavity_radius_) : cavity_grid_ != 0) {
+			if (cavity_bias && cavity_grid_size == 0) {
+				last_error_ = "cavity_bias is on and cavity_grid_size is 0";
+				throw (int)MPMC_ERR_INVALID_SETTING;
+			}
+			check(mpmc_set_cavity_grid(ctx_, cavity_bias ? cavity_grid_size : 0, cavity_radius), "mpmc_set_cavity_grid");
+			cavity_grid_ = cavity_bias ? cavity_grid_size : 0;
+			cavity_radius_ = cavity_radius;
 		}
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");

@@ -216,6 +216,8 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 	if (c->ev_xyzq) (void)hipEventDestroy(c->ev_xyzq);
 	if (c->ev_kstage) (void)hipEventDestroy(c->ev_kstage);
 	if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
+	for (hipEvent_t e : c->cav_ev)
+		if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	// the buffers free themselves, behind the destruction of the streams: both were synchronised above, so nothing enqueued can still
 	// touch the memory, and freeing needs no stream
@@ -663,6 +665,7 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	// (before the old positions go: is this the list of before with one run of atoms inserted or removed?  Then the spatial order is carried)
 	c->order_carried = carry_spatial_order(c, pos, n);
 	c->h_pos.assign(pos, pos + 3 * (size_t)n);
+	c->pos_gen++;
 	c->h_q.assign(charge, charge + n);
 	c->h_alpha.assign(polarizability, polarizability + n);
 	c->h_eps.assign(epsilon, epsilon + n);
@@ -742,6 +745,7 @@ int mpmc::splice_atoms(mpmc_ctx *c, int at, int n_remove, const AtomRun *ins) {
 	splice_vec(np_, (size_t)at, (size_t)n_remove, ins ? &ins->pos : nullptr, 3);
 	c->order_carried = carry_spatial_order(c, np_.data(), n_new); // (before the old positions go)
 	c->h_pos.swap(np_);
+	c->pos_gen++;
 	splice_vec(c->h_q, (size_t)at, (size_t)n_remove, ins ? &ins->q : nullptr);
 	splice_vec(c->h_alpha, (size_t)at, (size_t)n_remove, ins ? &ins->alpha : nullptr);
 	splice_vec(c->h_eps, (size_t)at, (size_t)n_remove, ins ? &ins->eps : nullptr);
@@ -1254,6 +1258,7 @@ extern "C" int mpmc_update_positions(mpmc_ctx *c, int first, int count, const do
 		c->h_pos[3 * i + 1] = pos[3 * t + 1];
 		c->h_pos[3 * i + 2] = pos[3 * t + 2];
 	}
+	c->pos_gen++;
 	c->cache_valid = false; // the accepted totals no longer describe the resident configuration
 	drop_pending_dipoles(c); // (... nor can an open on-demand solve be finished on them)
 	if (c->atoms_dirty) return MPMC_OK; // a full (re-sorted) upload is pending anyway
@@ -1316,6 +1321,7 @@ extern "C" int mpmc_set_positions_device(mpmc_ctx *c, const double *pos_device) 
 	HIP_TRY(c, hipGetLastError());
 	// keep the host mirror coherent (update_com / later partial updates read it)
 	HIP_TRY(c, hipMemcpyAsync(c->h_pos.data(), pos_device, 3 * (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	c->pos_gen++;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	{
 		const int rc_g = mirror_guard(c);

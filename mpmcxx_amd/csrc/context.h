@@ -142,6 +142,8 @@ struct mpmc_kept {
 	int relax_scheme = 0;                   // `polar_sor` / `polar_esor` (mpmc_set_polar_relax), likewise: MPMC_POLAR_RELAX_*
 	bool zodid = false;                     // `polar_zodid`, likewise
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
+	int cav_grid = 0;                       // `cavity_bias` (mpmc_set_cavity_grid), likewise: cavity_grid_size, 0 = off
+	double cav_radius = 0.0;                // cavity_radius
 };
 
 // A contiguous run of atoms with every per-atom array of mpmc_set_atoms: the molecule of an exchange trial, or a whole atom list
@@ -429,6 +431,32 @@ struct mpmc_ctx {
 	// `polar_sor` / `polar_esor` / `polar_zodid` (mpmc_set_polar_relax; kept.relax_scheme, kept.zodid)
 	mpmc_relax_info relax_info{}; // of the pending / last evaluation with a dipole solve
 
+	// the cavity-bias grid of uVT moves (mpmc_set_cavity_grid / mpmc_cavity_update, cavity.cpp, kernels_cavity.hip; switched on: kept.cav_grid,
+	// kept.cav_radius).  Nothing here is read or written by an evaluation or a trial; every buffer is made by the first update.
+	unsigned pos_gen = 1;                 // counts the events that change h_pos (atom list, position updates, accepted trials)
+	bool cav_valid = false;               // the results below are those of an update ...
+	unsigned cav_pos_gen = 0, cav_static_gen = 0; // ... made at these values of pos_gen / static_gen (cavity_current)
+	int cav_done_grid = 0;                // ... with this grid size
+	double cav_done_radius = 0.0;         // ... and radius
+	int64_t cav_open = 0;                 // cavities_open of that update
+	double cav_basis[9] = {0};            // the cell h_cav_grid / d_cav_grid were made for, with cav_grid_G (0: none)
+	int cav_grid_G = 0;
+	std::vector<double> h_cav_grid;       // [G^3][3] sphere centres, enumeration order (i outermost, k innermost)
+	std::vector<int32_t> h_cav_open;      // the open list on the host, fetched by the first mpmc_cavity_point / mpmc_cavity_get behind an update
+	bool cav_open_cached = false;
+	DevBuf<double> d_cav_grid;            // [G^3][3]
+	DevBuf<double> d_cav_in;              // [n][3] wrapped positions, then [n_darts][3] fractional darts
+	PinnedBuf<double> h_cav_in;           // their staging
+	DevBuf<int> d_cav_part;               // [slices][points padded to 64] occupancy partials
+	DevBuf<int> d_cav_occ;                // [points padded to 64]
+	DevBuf<int> d_cav_wave;               // [point waves] empty points per wave, then their exclusive prefix
+	DevBuf<int> d_cav_open;               // [points] flat indices of the empty points, ascending
+	DevBuf<unsigned long long> d_cav_mask; // [open slices][dart waves] hit masks
+	DevBuf<long long> d_cav_res;          // { cavities_open, hits }
+	PinnedBuf<long long> h_cav_res;
+	hipEvent_t cav_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // profiling: around the three kernel groups of the last update
+	float cav_ms[3] = {0, 0, 0};          // occupancy, compaction, darts of the last update made under mpmc_set_profiling
+
 	std::vector<EvPair> ev_free, ev_used; // profiling (kept.prof): event pairs to reuse / recorded and not yet harvested into kept.tim
 
 	int64_t bytes_total = 0; // device memory held by this context's DevBuf members (mpmc_memory_usage)
@@ -674,5 +702,7 @@ int set_atoms_from(mpmc_ctx *c, const AtomRun &list);                     // mpm
 void xch_sum_list(const mpmc_ctx *c, XchSums &out);
 void xch_sum_atom(const mpmc_ctx *c, XchSums &xs, double sg, int fl, double sigma, double eps, double q);
 void xch_static_terms(const mpmc_ctx *c, const XchSums &xs, double out3[3]);
+// update_com + wrap_all over the host mirror (evaluate.cpp): centres of mass, lattice shifts, wrapped positions; any pointer may be null
+void wrap_molecules(const mpmc_ctx *c, double *com, double *wrapped_com, double *wrapped_pos);
 
 } // namespace mpmc

@@ -1437,12 +1437,10 @@ extern "C" int mpmc_get_dipoles(mpmc_ctx *c, double *mu, double *ef_static, doub
 	return rc;
 }
 
-// update_com + wrap_all, reference src/System.cpp:1347-1425 (host side: O(N), consumed by I/O only)
-extern "C" int mpmc_update_com(mpmc_ctx *c, double *com, double *wrapped_com, double *wrapped_pos, int *n_molecules) {
-	if (!c) return MPMC_ERR_ARG;
-	if (!c->atoms_set || !c->box_set) return fail(c, MPMC_ERR_ARG, "mpmc_update_com: atoms and box must be set");
-	if (c->h_mass.empty()) return fail(c, MPMC_ERR_ARG, "mpmc_update_com: mpmc_set_atoms was called without masses");
-	if (n_molecules) *n_molecules = c->n_molecules;
+// update_com + wrap_all, reference src/System.cpp:1347-1425, over the host mirror of the accepted atom list (which must carry masses): the
+// centres of mass, the lattice shift of each (zero for a frozen molecule) and every atom's wrapped_pos = its position minus that shift.
+// Any pointer may be null.  (host side, O(N): mpmc_update_com hands it out, mpmc_cavity_update bins it)
+void mpmc::wrap_molecules(const mpmc_ctx *c, double *com, double *wrapped_com, double *wrapped_pos) {
 	int m = 0;
 	for (int i0 = 0; i0 < c->n;) {
 		int i1 = i0;
@@ -1477,5 +1475,13 @@ extern "C" int mpmc_update_com(mpmc_ctx *c, double *com, double *wrapped_com, do
 		m++;
 		i0 = i1 + 1;
 	}
+}
+
+extern "C" int mpmc_update_com(mpmc_ctx *c, double *com, double *wrapped_com, double *wrapped_pos, int *n_molecules) {
+	if (!c) return MPMC_ERR_ARG;
+	if (!c->atoms_set || !c->box_set) return fail(c, MPMC_ERR_ARG, "mpmc_update_com: atoms and box must be set");
+	if (c->h_mass.empty()) return fail(c, MPMC_ERR_ARG, "mpmc_update_com: mpmc_set_atoms was called without masses");
+	if (n_molecules) *n_molecules = c->n_molecules;
+	wrap_molecules(c, com, wrapped_com, wrapped_pos);
 	return MPMC_OK;
 }

@@ -465,6 +465,34 @@ void launch_pef_finish(hipStream_t st, const AtomsDev &at, const EwaldFullParams
                        const double2 *phases, const double4 *kvec, const double4 *kw, int K, const double *psum, const double *mu_old, double *mu_new,
                        double *e_induced, int *not_done, const RelaxWeights *relax = nullptr /*new_dipoles :3196-3204: new_mu itself is the blend, the verdict sees it*/);
 
+// ---- the cavity-bias grid (kernels_cavity.hip; System::cavity_update_grid, src/System.Cavity.cpp:15-188) --------------------------------
+// Distances are r = ((dx dx) + dy dy) + dz dz, unfused, d = grid - atom / dart - grid; inside means r < t2 (the exact-threshold form of
+// sqrt(r) < radius, mpmc_cavity_r2_threshold).  No minimum image.  Every result is an integer: nothing depends on an order of summation.
+constexpr int kCavityChunk = 256;       // atoms / empty points staged in LDS at a time
+constexpr int kCavityTargetWaves = 2048; // work items a launch aims for (256 CUs x 4 SIMDs x 2)
+// how many slices of the atom range (n atoms) a grid of `points` sphere centres is binned in: a function of (points, n) alone
+inline int cavity_atom_slices(long long points, int n) {
+	const long long blocks = (points + 63) / 64;
+	const long long want = (kCavityTargetWaves + blocks - 1) / blocks, most = ((long long)n + 63) / 64;
+	return (int)(want < 1 ? 1 : (want > most ? (most < 1 ? 1 : most) : want));
+}
+// ... and how many slices of the open list a launch over n_darts darts walks: a function of (points, n_darts) alone
+inline int cavity_dart_slices(long long points, int n_darts) {
+	const long long blocks = ((long long)n_darts + 63) / 64;
+	if (blocks < 1) return 1;
+	const long long want = (kCavityTargetWaves + blocks - 1) / blocks, most = (points + kCavityChunk - 1) / kCavityChunk;
+	return (int)(want < 1 ? 1 : (want > most ? (most < 1 ? 1 : most) : want));
+}
+// part[s][p] = atoms of slice s inside the sphere of point p; grid [points][3], atoms [n][3]; part is [slices][points rounded up to 64]
+void launch_cavity_occupancy(hipStream_t st, const double *grid, int points, const double *atoms, int n, int slices, double t2, int *part);
+// occ[p] = sum_s part[s][p]; open[] = the flat indices of the points with occ == 0, ascending; res[0] = their number.  wave_cnt: scratch, one
+// int per 64 points.
+void launch_cavity_compact(hipStream_t st, const int *part, int slices, int points, int *occ, int *wave_cnt, int *open, long long *res);
+// res[1] = darts inside at least one empty sphere; darts are basis^T applied to dart_frac [n_darts][3] (the reference's loop order).  mask:
+// scratch, [slices][dart waves].  n_darts == 0: res[1] = 0, no dart kernel runs.
+void launch_cavity_darts(hipStream_t st, const double *grid, const int *open, const double *dart_frac, int n_darts, int slices, const double basis[9], double t2,
+                         unsigned long long *mask, long long *res);
+
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);
 

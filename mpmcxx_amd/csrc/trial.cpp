@@ -622,6 +622,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 		// (no wait: whatever comes next on this context is enqueued behind the commit on the same stream, and the host mirrors below are
 		// the host's own -- the stream synchronisation that stood here cost 13 us of a 41 us accepted move)
 		for (int t = 0; t < 3 * m; t++) c->h_pos[3 * (size_t)c->trial_first + t] = c->trial_new[t];
+		c->pos_gen++;
 		{
 			const int rc_g = mirror_guard(c);
 			if (rc_g != MPMC_OK) return rc_g;

@@ -128,6 +128,24 @@ def polar_relax_of(options: Dict[str, object]):
     return POLAR_RELAX["sor"] if sor else POLAR_RELAX["esor"] if esor else POLAR_RELAX["none"], bool(options.get("polar_zodid"))
 
 
+class CavityResult(C.Structure):
+    """mpmc_cavity_result: one update of the cavity-bias grid (mpmc_cavity_update)."""
+    _fields_ = [("total_points", C.c_int64), ("cavities_open", C.c_int64), ("n_darts", C.c_int64), ("hits", C.c_int64),
+                ("probability", C.c_double), ("cavity_volume", C.c_double)]
+
+
+class UvtMove(C.Structure):
+    """mpmc_uvt_move: what the ENSEMBLE_UVT branch of System::boltzmann_factor reads (mpmc_uvt_boltzmann_factor)."""
+    _fields_ = [("movetype", C.c_int32), ("biased_move", C.c_int32), ("sorbate_count", C.c_int32), ("temperature", C.c_double), ("fugacity", C.c_double),
+                ("volume", C.c_double), ("N", C.c_double), ("init_energy", C.c_double), ("final_energy", C.c_double), ("cavity_volume", C.c_double),
+                ("avg_cavity_probability", C.c_double)]
+
+
+MOVETYPE = {"insert": 0, "remove": 1, "displace": 2, "adiabatic": 3, "spinflip": 4, "volume": 5, "perturb_beads": 6}  # MPMC_MOVETYPE_*
+CAVITY_KEYS = ("cavity_bias", "cavity_grid_size", "cavity_radius")
+CAVITY_MAX_GRID = 128  # MPMC_CAVITY_MAX_GRID
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -219,6 +237,17 @@ def lib():
     if hasattr(L, "mpmc_trial_insert_begin") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no exchange trials)
         L.mpmc_trial_insert_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip, dp]
         L.mpmc_trial_remove_begin.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "mpmc_set_cavity_grid") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no cavity grid)
+        L.mpmc_set_cavity_grid.argtypes = [vp, C.c_int, C.c_double]
+        L.mpmc_cavity_update.argtypes = [vp, C.c_int, dp, C.POINTER(CavityResult)]
+        L.mpmc_cavity_point.argtypes = [vp, C.c_int64, dp]
+        L.mpmc_cavity_get.argtypes = [vp, ip, dp, ip]
+        L.mpmc_cavity_num_darts.argtypes = [C.c_double]
+        L.mpmc_cavity_grid_point.argtypes = [dp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+        L.mpmc_cavity_r2_threshold.argtypes = [C.c_double]
+        L.mpmc_cavity_r2_threshold.restype = C.c_double
+        L.mpmc_uvt_boltzmann_factor.argtypes = [C.POINTER(UvtMove), dp]
+        L.mpmc_debug_cavity_times.argtypes = [vp, dp]
     L.mpmc_gibbs_energy.argtypes = [vp, vp, C.POINTER(Result), C.POINTER(Result)]
     L.mpmc_gibbs_boltzmann_factor.argtypes = [C.POINTER(GibbsMove), dp, dp]
     L.mpmc_rccl_version.argtypes = [C.POINTER(C.c_int)]
@@ -418,6 +447,12 @@ class System:
             self._polar_relax_set = True
             self.set_polar_relax(*polar_relax_of(options))
 
+        # `cavity_bias` likewise: the grid is switched on or off only when the options name one of its keys
+        if any(k in options for k in CAVITY_KEYS) or getattr(self, "_cavity_set", False):
+            self._cavity_set = True
+            on = bool(options.get("cavity_bias"))
+            self.set_cavity_grid(int(options.get("cavity_grid_size") or 0) if on else 0, float(options.get("cavity_radius") or 0.0))
+
     def set_atoms(self, atoms: Dict[str, np.ndarray]):
         f = lambda k: np.ascontiguousarray(atoms[k], dtype=np.float64)
         g = lambda k: np.ascontiguousarray(atoms[k], dtype=np.int32)
@@ -467,6 +502,45 @@ class System:
         v = RdCrystalInfo()
         self._check(self._L.mpmc_rd_crystal_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdCrystalInfo._fields_}
+
+    # -- the cavity-bias grid of uVT moves (System::cavity_update_grid, reference src/System.Cavity.cpp) ---------------
+    def set_cavity_grid(self, grid_size: int, radius: float = 0.0):
+        """`cavity_bias`: a grid_size^3 grid of sphere centres of the given radius (mpmc_set_cavity_grid); grid_size = 0 switches it off"""
+        self._check(self._L.mpmc_set_cavity_grid(self._h, int(grid_size), float(radius)))
+        self._cavity_grid = int(grid_size)
+
+    def cavity_update(self, dart_frac: Optional[np.ndarray] = None) -> Dict[str, float]:
+        """one cavity_update_grid over the accepted atom list (mpmc_cavity_update).  dart_frac: (n_darts, 3) of the caller's `-0.5 + get_rand()`
+        draws in draw order (None or empty: no darts, the volume is NaN as in the reference).  Returns total_points, cavities_open, n_darts,
+        hits, probability and cavity_volume."""
+        d = None if dart_frac is None else np.ascontiguousarray(dart_frac, dtype=np.float64).reshape(-1, 3)
+        n_darts = 0 if d is None else int(d.shape[0])
+        r = CavityResult()
+        self._check(self._L.mpmc_cavity_update(self._h, n_darts, _dp(d) if n_darts else None, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in CavityResult._fields_}
+
+    def cavity_point(self, rank: int) -> np.ndarray:
+        """the rank-th empty sphere centre of the last update in the reference's enumeration order (mpmc_cavity_point)"""
+        pos = np.zeros(3)
+        self._check(self._L.mpmc_cavity_point(self._h, int(rank), _dp(pos)))
+        return pos
+
+    def cavity_grid(self):
+        """(occupancy (G, G, G) int32, centres (G, G, G, 3), flat indices of the empty centres ascending) of the last update (mpmc_cavity_get)"""
+        G = int(getattr(self, "_cavity_grid", 0))
+        occ = np.zeros(G ** 3, dtype=np.int32)
+        pos = np.zeros((G ** 3, 3))
+        open_index = np.zeros(G ** 3, dtype=np.int32)
+        self._check(self._L.mpmc_cavity_get(self._h, _ip(occ), _dp(pos), None))
+        n_open = int(np.count_nonzero(occ == 0))
+        self._check(self._L.mpmc_cavity_get(self._h, None, None, _ip(open_index)))
+        return occ.reshape(G, G, G), pos.reshape(G, G, G, 3), open_index[:n_open].copy()
+
+    def cavity_times(self) -> Dict[str, float]:
+        """device milliseconds of the last cavity_update made under set_profiling(True) (mpmc_debug_cavity_times)"""
+        ms = np.zeros(3)
+        self._check(self._L.mpmc_debug_cavity_times(self._h, _dp(ms)))
+        return {"occupancy": float(ms[0]), "compact": float(ms[1]), "darts": float(ms[2])}
 
     def set_rd_model(self, form=0, mixing=0):
         """The rd model (mpmc_set_rd_model): a potential form (RD_FORM: "lj", "lj_buffered_14_7", "dreiding", or its number) and a mixing rule
@@ -827,6 +901,42 @@ def gibbs_boltzmann_factor(movetype, temperature, init_energy, final_energy, N, 
     en = np.array(final_energy, dtype=np.float64)
     rc = lib().mpmc_gibbs_boltzmann_factor(C.byref(m), _dp(bf), _dp(en))
     return rc, bf, en
+
+
+# ---- the host-only entry points of the cavity grid and the uVT acceptance factor (no device needed) ------------------------------------
+def cavity_num_darts(volume: float) -> int:
+    """darts update_cavity_volume throws at a cell of this volume: (int)(volume * 0.1) (mpmc_cavity_num_darts)"""
+    return int(lib().mpmc_cavity_num_darts(float(volume)))
+
+
+def cavity_grid_point(basis: np.ndarray, grid_size: int, i: int, j: int, k: int) -> np.ndarray:
+    """sphere centre (i, j, k) of a grid_size^3 grid in the cell `basis`, the reference's arithmetic (mpmc_cavity_grid_point)"""
+    b = np.ascontiguousarray(basis, dtype=np.float64).reshape(9)
+    pos = np.zeros(3)
+    rc = lib().mpmc_cavity_grid_point(_dp(b), int(grid_size), int(i), int(j), int(k), _dp(pos))
+    if rc != MPMC_OK:
+        raise MpmcError(rc, f"mpmc_cavity_grid_point: ({i}, {j}, {k}) outside a grid of {grid_size}")
+    return pos
+
+
+def cavity_r2_threshold(radius: float) -> float:
+    """the smallest double whose correctly rounded square root is >= radius (mpmc_cavity_r2_threshold)"""
+    return float(lib().mpmc_cavity_r2_threshold(float(radius)))
+
+
+def uvt_boltzmann_factor(movetype, temperature, fugacity, volume, N, init_energy, final_energy, sorbate_count=1, biased_move=False, cavity_volume=0.0,
+                         avg_cavity_probability=0.0):
+    """the ENSEMBLE_UVT branch of System::boltzmann_factor (reference src/System.MonteCarlo.cpp:1358-1422).  movetype: a MOVETYPE name or
+    number.  Returns (status, boltzmann_factor)."""
+    m = UvtMove()
+    m.movetype = MOVETYPE[movetype] if isinstance(movetype, str) else int(movetype)
+    m.biased_move, m.sorbate_count = int(bool(biased_move)), int(sorbate_count)
+    m.temperature, m.fugacity, m.volume, m.N = float(temperature), float(fugacity), float(volume), float(N)
+    m.init_energy, m.final_energy = float(init_energy), float(final_energy)
+    m.cavity_volume, m.avg_cavity_probability = float(cavity_volume), float(avg_cavity_probability)
+    bf = C.c_double(float("nan"))
+    rc = lib().mpmc_uvt_boltzmann_factor(C.byref(m), C.byref(bf))
+    return rc, bf.value
 
 
 def pi_allreduce(beads: Sequence[System]):

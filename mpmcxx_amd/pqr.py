@@ -144,6 +144,12 @@ def read_input(path: str) -> Dict[str, object]:
                 opts[k] = _onoff(v[0])
             elif k in ("waldmanhagler", "halgren_mixing", "c6_mixing", "lj_buffered_14_7", "dreiding"):  # (likewise; the rd model, mpmc_set_rd_model)
                 opts[k] = _onoff(v[0])
+            elif k == "cavity_bias":  # (likewise; the cavity-bias grid of uVT moves, mpmc_set_cavity_grid)
+                opts[k] = _onoff(v[0])
+            elif k in ("cavity_grid", "cavity_grid_size"):  # (`cavity_grid` is the reference's keyword for cavity_grid_size, SimulationControl.cpp:616)
+                opts["cavity_grid_size"] = int(v[0])
+            elif k == "cavity_radius":
+                opts[k] = float(v[0])
             elif k == "rd_crystal_order":
                 opts[k] = int(v[0])
             elif k in ("polar_wolf_alpha", "polar_wolf_damp"):  # (two names of one setting, SimulationControl.cpp:751-759)
