@@ -508,7 +508,6 @@ int mpmc_polar_ewald_full_info(mpmc_ctx *ctx, mpmc_ewald_full_info *out);
  * zodid: every evaluation runs all its iterations.  The setting has the lifetime of mpmc_set_polar_wolf's and is refused while an
  * evaluation or a trial move is open; (MPMC_POLAR_RELAX_NONE, 0) restores the behaviour of a context that never called it, to the bit.
  * MPMC_FLAG_POLAR_SOR and MPMC_FLAG_POLAR_ZODID in unsupported_flags are still refused: this call alone switches the behaviour on.
- * Still refused, the last member of the family: `polar_gs_ranked` (MPMC_FLAG_POLAR_GS_RANKED).
  * mpmc_polar_relax_info: of the last evaluation with a dipole solve. */
 #define MPMC_POLAR_RELAX_NONE 0
 #define MPMC_POLAR_RELAX_SOR 1
@@ -523,6 +522,44 @@ typedef struct mpmc_relax_info {
 	double last_weight;    /* w_new of the last update (1 when none was relaxed)                                            */
 } mpmc_relax_info;
 int mpmc_polar_relax_info(mpmc_ctx *ctx, mpmc_relax_info *out);
+
+/* ---- `polar_gs_ranked`: Gauss-Seidel sweeps in ranked order (src/System.cpp:1001-1029, src/System.Energy.cpp:3450-3543, 3631-3656) --------
+ * The last member of the iterative family.  The sweeps are those of mpmc_options.polar_gs; what changes is their order from the second
+ * iteration on.
+ *   rank pass     once per evaluation, on the resident positions.  rmin = the smallest minimum-image distance rimg over all pairs of atoms
+ *                 with polarizability != 0 (same-molecule and frozen pairs count; MAXVALUE = 1e40 when there is no such pair), the
+ *                 reference's double to the bit.  rank_metric[i] = the number of such pairs that contain i and have r <= rmin * 1.5, where
+ *                 r = sqrt(((dx dx) + dy dy) + dz dz) is the UNWRAPPED distance pair->r, not rimg: in a periodic box a pair that is close
+ *                 only through an image does not count.  That is what the reference computes and what this library returns.  Atoms
+ *                 that are not polarizable keep rank 0.
+ *   order         update_ranking is a bubble sort run after every iteration that is followed by another: iteration 1 sweeps in atom
+ *                 order, iterations 2, 3, ... in the stable descending order of rank_metric (ties in atom order).  With polar_max_iter 1,
+ *                 or a precision met in iteration 1, no ranked sweep runs and the result is that of polar_gs to the bit.
+ *   unchanged     the start vector, dipole_rrms, the precision test, the failure at 128 iterations, the polar_sor / polar_esor blend
+ *                 (mpmc_set_polar_relax) and mpmc_set_polar_palmo behind the sweeps.
+ * The setting acts with polarization on, rd_only off and polar_iterative on; it has no effect under polar_iterative off, zodid or
+ * mpmc_set_polar_ewald_full (acted = 0, results as without it, to the bit).  An evaluation with mpmc_options.polar_gs on as well fails
+ * with MPMC_ERR_INVALID_SETTING (SimulationControl.cpp:2732).  Where it acts the atoms keep the caller's order on the device and the
+ * solver is matrix-free, as under polar_gs; the energy-from-moments form and mpmc_set_dipoles_on_demand do not apply, and trial moves
+ * evaluate the trial configuration in full.  The setting has the lifetime of mpmc_set_polar_relax's (kept across atoms, cell, accepted
+ * trials and capacity growth; refused while an evaluation or a trial move is open); enabled = 0 restores the context's behaviour to the
+ * bit.  MPMC_FLAG_POLAR_GS_RANKED in unsupported_flags is still refused: this call alone switches the behaviour on.  Time: the rank
+ * pass, the order, the gathers and the view's tile classes in MPMC_K_CLASSES, the view's in-tile blocks in MPMC_K_TENSOR.
+ * mpmc_polar_gs_ranked_info: of the last evaluation with a dipole solve.  mpmc_polar_gs_ranked_get: rank_metric and the sweep order
+ * (order[p] = the atom swept p-th from iteration 2 on) of the last evaluation, in the caller's atom order, either pointer may be NULL;
+ * MPMC_ERR_ARG when no evaluation in which the setting acted has been made since the atoms, the cell or the setting last changed. */
+int mpmc_set_polar_gs_ranked(mpmc_ctx *ctx, int enabled);
+typedef struct mpmc_gs_ranked_info {
+	int32_t enabled;        /* the context's switch                                                      */
+	int32_t acted;          /* 1: that evaluation made the rank pass and swept under the setting         */
+	double rmin;            /* smallest image distance between polarizable atoms (1e40: none)            */
+	int32_t max_rank;       /* largest rank_metric                                                       */
+	int32_t n_moved;        /* places of the sweep order that differ from the identity                   */
+	int32_t ranked_sweeps;  /* sweeps of that evaluation that ran in ranked order                        */
+	int32_t reserved;
+} mpmc_gs_ranked_info;
+int mpmc_polar_gs_ranked_info(mpmc_ctx *ctx, mpmc_gs_ranked_info *out);
+int mpmc_polar_gs_ranked_get(mpmc_ctx *ctx, int32_t *rank_metric /*[n]*/, int32_t *order /*[n]*/);
 
 /* per-atom results written back by energy() in the reference (src/Atom.h:41-47); any pointer may be NULL.  After an on-demand evaluation
  * (mpmc_set_dipoles_on_demand above) the remaining Jacobi iterations run here first; MPMC_ERR_ARG when they no longer can. */
@@ -692,6 +729,10 @@ int mpmc_get_tile_stats(mpmc_ctx *ctx, int64_t out4[4]);
  * Short evaluations and trial moves are polled for (a few microseconds earlier than the driver's completion path); a host with fewer
  * free cores than polling threads shows up here as timeouts and yields. */
 int mpmc_debug_wait_counters(mpmc_ctx *ctx, long long out4[4]);
+/* The sort of `polar_gs_ranked` on keys of the caller's: order[p] = the atom at place p of the stable descending order of keys[0 .. n),
+ * n the atoms of the context.  The rank pass itself cannot produce a key above about 60 (atoms no closer than rmin within 1.5 rmin of
+ * one of them); the sort takes any values.  It overwrites what mpmc_polar_gs_ranked_get hands out. */
+int mpmc_debug_gs_rank_order(mpmc_ctx *ctx, const int32_t *keys /*[n]*/, int32_t *order /*[n]*/);
 /* Measurement / A-B switch, key = value (keys: csrc/context.cpp, struct mpmc_tuning).  ctx == NULL: the default of contexts created
  * afterwards in this process.  The library reads no environment variable for any of these. */
 int mpmc_debug_configure(mpmc_ctx *ctx, const char *key, double value);

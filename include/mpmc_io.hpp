@@ -180,6 +180,10 @@ inline std::string read_input(const std::string &path, System &s) {
 			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_POLAR_EWALD_FULL;
 			s.polar_ewald_full = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
 		}
+		else if (k == "polar_gs_ranked") { // (likewise: the facade clears the flag when it hands the field to mpmc_set_polar_gs_ranked)
+			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_POLAR_GS_RANKED;
+			s.polar_gs_ranked = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
+		}
 		// (the rd model: read into fields, no flag; the facade hands them to mpmc_set_rd_model)
 		else if (k == "waldmanhagler") { need(1); s.waldmanhagler = onoff(t[1]); }
 		else if (k == "halgren_mixing") { need(1); s.halgren_mixing = onoff(t[1]); }

@@ -122,6 +122,7 @@ public:
 	}
 	int polar_sor = 0, polar_esor = 0;   // relaxed dipole updates by polar_gamma (mpmc_set_polar_relax), src/System.h: polar_sor, polar_esor
 	int polar_zodid = 0;                 // zeroth-order dipoles, mu = alpha E0 (mpmc_set_polar_relax)
+	int polar_gs_ranked = 0;             // Gauss-Seidel sweeps in ranked order (mpmc_set_polar_gs_ranked), src/System.h: polar_gs_ranked
 	int polar_ewald_full = 0;            // Ewald-summed induced field (mpmc_set_polar_ewald_full), src/System.h: polar_ewald_full
 	int polar_ewald_full_vector_kweight = 0; // MPMC_PEF_VECTOR_KWEIGHT: the intended reciprocal-space weight (no keyword: the reference has none)
 	// the cavity-bias grid of uVT moves (mpmc_set_cavity_grid), src/System.h: cavity_bias, cavity_grid_size, cavity_radius; what
@@ -410,6 +411,7 @@ private:
 	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
 	int rd_model_form_ = 0, rd_model_mixing_ = 0;  // ... and its rd model
 	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
+	int gs_ranked_on_ = 0;                         // ... and its polar_gs_ranked setting
 	int cavity_grid_ = 0;                          // ... and its cavity grid (0: off)
 	double cavity_radius_ = 0;
 	double polar_wolf_alpha_ = 0;
@@ -434,6 +436,10 @@ private:
 	}
 
 	void sync_state() {
+		if (polar_gs && polar_gs_ranked) { // an input error of the reference (SimulationControl.cpp:2732), found before anything reaches the device
+			last_error_ = "polar_gs and polar_gs_ranked are both on";
+			throw 3000;
+		}
 		natoms = countNatoms();
 		const int n = natoms;
 		if (!ctx_ || capacity_ < n) {
@@ -448,6 +454,7 @@ private:
 			ewald_full_on_ = ewald_full_flags_ = 0;
 			rd_model_form_ = rd_model_mixing_ = 0;
 			relax_scheme_ = zodid_on_ = 0;
+			gs_ranked_on_ = 0;
 			cavity_grid_ = 0;
 			cavity_radius_ = 0;
 		}
@@ -479,8 +486,9 @@ private:
 		o.polar_ewald_alpha = polar_ewald_alpha;
 		// (polar_iterative off is the library's direct dipole solve: no flag; `rd_crystal on` goes to mpmc_set_rd_crystal below: the reader's
 		// flag for the keyword is cleared here, a caller's flag without the field is still refused)
-		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full)
-		o.unsupported_flags = unsupported_flags & ~(uint64_t)((rd_crystal ? MPMC_FLAG_RD_CRYSTAL : 0) | (polar_ewald_full ? MPMC_FLAG_POLAR_EWALD_FULL : 0));
+		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full, and `polar_gs_ranked on` to mpmc_set_polar_gs_ranked)
+		o.unsupported_flags = unsupported_flags & ~(uint64_t)((rd_crystal ? MPMC_FLAG_RD_CRYSTAL : 0) | (polar_ewald_full ? MPMC_FLAG_POLAR_EWALD_FULL : 0) |
+		                                                      (polar_gs_ranked ? MPMC_FLAG_POLAR_GS_RANKED : 0));
 		check(mpmc_set_options(ctx_, &o), "mpmc_set_options");
 		if (atoms_dirty_) {
 			std::vector<double> pos(3 * (size_t)n), q(n), al(n), ep(n), sg(n), ms(n);
@@ -551,6 +559,10 @@ private:
 			check(mpmc_set_polar_relax(ctx_, relax_scheme, polar_zodid ? 1 : 0), "mpmc_set_polar_relax");
 			relax_scheme_ = relax_scheme;
 			zodid_on_ = polar_zodid ? 1 : 0;
+		}
+		if ((polar_gs_ranked != 0) != (gs_ranked_on_ != 0)) {
+			check(mpmc_set_polar_gs_ranked(ctx_, polar_gs_ranked ? 1 : 0), "mpmc_set_polar_gs_ranked");
+			gs_ranked_on_ = polar_gs_ranked ? 1 : 0;
 		}
 		// (cavity_bias on with a grid size or radius that is not positive is refused by the library, SimulationControl.cpp:2157-2162)
 		if (cavity_bias ? (cavity_grid_ == 0 || cavity_grid_size != cavity_grid_ || cavity_radius != cavity_radius_) : cavity_grid_ != 0) {

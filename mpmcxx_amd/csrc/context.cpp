@@ -292,14 +292,10 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 		if (o->wolf && !o->rd_only) return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_options: FH + es_wolf is not implemented"); // System.Energy.cpp:1448-1450
 	}
 	if (c->opts_set && std::memcmp(&c->opts, o, sizeof(mpmc_options)) == 0) return MPMC_OK; // unchanged: keep the accepted configuration's totals
-	{ // Gauss-Seidel sweeps run in the reference's atom order (System.Energy.cpp:3569): whenever "this evaluation sweeps in atom order"
-	  // changes -- through polar_gs, polarization or rd_only, or on the first options after an upload under the defaults -- re-upload
-		// (not under `polar_ewald_full`, where polar_gs changes nothing: the spatial order stays)
-		const bool pef = c->kept.pef_enabled;
-		auto atom_order = [pef](const mpmc_options &q) { return q.polar_gs && q.polarization && !q.rd_only && !pef; };
-		const bool was = c->opts_set && atom_order(c->opts);
-		if (was != (bool)atom_order(*o)) c->atoms_dirty = c->atoms_dirty_order = true;
-	}
+	// Gauss-Seidel sweeps run in the reference's atom order (System.Energy.cpp:3569): whenever "this evaluation sweeps in atom order"
+	// changes -- through polar_gs, polarization, rd_only or polar_iterative (the ranked sweeps), or on the first options after an upload
+	// under the defaults -- re-upload (not under `polar_ewald_full`, where polar_gs changes nothing: the spatial order stays)
+	if ((c->opts_set && sweeps_keep_atom_order(c, c->opts)) != sweeps_keep_atom_order(c, *o)) c->atoms_dirty = c->atoms_dirty_order = true;
 	drop_pending_dipoles(c); // (... and to the old options)
 	c->opts = *o;
 	c->opts_set = true;
@@ -321,7 +317,7 @@ static void compute_spatial_order(mpmc_ctx *c) {
 	c->slot_of.resize(n);
 	for (int i = 0; i < n; i++) c->perm[i] = i;
 	bool enable = c->box_set && n > 2 * kTile;
-	if (c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only && !c->kept.pef_enabled) enable = false; // the sweep order IS the atom order (:3569)
+	if (c->opts_set && sweeps_keep_atom_order(c, c->opts)) enable = false; // the sweep order IS the atom order (:3569)
 	if (c->kept.tune.no_sort) enable = false;
 	if (enable) {
 		// fractional coordinates counted from the smallest one in each dimension: with all atoms inside one period (the usual case) the
@@ -876,14 +872,72 @@ extern "C" int mpmc_set_polar_relax(mpmc_ctx *c, int scheme, int zodid) {
 		c->e_real_valid = false; // (the next trial move evaluates in full: zodid keeps no tensor store for a store-only sweep to patch)
 		drop_pending_dipoles(c);
 	}
+	const bool kept_order = c->opts_set && sweeps_keep_atom_order(c, c->opts);
 	c->kept.relax_scheme = scheme;
 	c->kept.zodid = z;
+	order_rule_changed(c, kept_order); // (`polar_gs_ranked` does not act under zodid)
 	return MPMC_OK;
 }
 extern "C" int mpmc_polar_relax_info(mpmc_ctx *c, mpmc_relax_info *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_relax_info: an evaluation is in flight");
 	*out = c->relax_info;
+	return MPMC_OK;
+}
+
+// ---- `polar_gs_ranked` (System::pairs :1001-1029, thole_iterative :3450-3543, update_ranking :3631-3656) -----------------------------------
+extern "C" int mpmc_set_polar_gs_ranked(mpmc_ctx *c, int enabled) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_gs_ranked: an evaluation or a trial move is open");
+	const bool on = enabled != 0;
+	if (on == c->kept.gs_ranked) return MPMC_OK;
+	c->cache_valid = false; // (the accepted totals, the tensor store and an open on-demand solve belong to the other solve)
+	c->e_real_valid = false;
+	drop_pending_dipoles(c);
+	c->gr_pos_gen = c->gr_static_gen = 0; // (mpmc_polar_gs_ranked_get: nothing of the other setting is handed out)
+	const bool kept_order = c->opts_set && sweeps_keep_atom_order(c, c->opts);
+	c->kept.gs_ranked = on;
+	order_rule_changed(c, kept_order);
+	return MPMC_OK;
+}
+extern "C" int mpmc_polar_gs_ranked_info(mpmc_ctx *c, mpmc_gs_ranked_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_gs_ranked_info: an evaluation is in flight");
+	*out = c->gr_info;
+	out->enabled = c->kept.gs_ranked ? 1 : 0;
+	return MPMC_OK;
+}
+extern "C" int mpmc_polar_gs_ranked_get(mpmc_ctx *c, int32_t *rank_metric, int32_t *order) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_polar_gs_ranked_get: an evaluation is in flight");
+	if (!c->kept.gs_ranked || !c->gr_ran || c->gr_pos_gen != c->pos_gen || c->gr_static_gen != c->static_gen)
+		return fail(c, MPMC_ERR_ARG, "mpmc_polar_gs_ranked_get: no evaluation under polar_gs_ranked has been made since the atoms, the cell or the setting last changed");
+	HIP_TRY(c, hipSetDevice(c->device));
+	// (the sweeps keep the caller's atom order on the device: slot = atom)
+	const size_t bytes = (size_t)c->n * sizeof(int32_t);
+	if (rank_metric) HIP_TRY(c, hipMemcpyAsync(rank_metric, c->d_gr_rank, bytes, hipMemcpyDeviceToHost, c->stream));
+	if (order) HIP_TRY(c, hipMemcpyAsync(order, c->d_gr_rank + c->max_pad, bytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	return MPMC_OK;
+}
+
+// (diagnostics) the device's sort on keys of the caller's: what the sweeps would run in if these were the ranks
+extern "C" int mpmc_debug_gs_rank_order(mpmc_ctx *c, const int32_t *keys, int32_t *order) {
+	if (!c || !keys || !order) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_rank_order: an evaluation or a trial move is open");
+	int rc = prepare(c);
+	if (rc != MPMC_OK) return rc;
+	if ((rc = c->d_gr_rank.reserve(c, 2 * (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_info.reserve(c, 1)) != MPMC_OK) return rc;
+	c->gr_pos_gen = c->gr_static_gen = 0; // (the rank pass's results are overwritten)
+	const size_t bytes = (size_t)c->n * sizeof(int32_t);
+	int *d_order = c->d_gr_rank + c->max_pad;
+	HIP_TRY(c, hipMemcpyAsync(c->d_gr_rank, keys, bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipMemsetAsync(c->d_gr_info, 0, sizeof(GsRankInfoDev), c->stream));
+	launch_gs_rank_order(c->stream, atoms_view(c), c->d_gr_rank, d_order, &c->d_gr_info.p->max_rank);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipMemcpyAsync(order, d_order, bytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	return MPMC_OK;
 }
 
@@ -897,11 +951,12 @@ extern "C" int mpmc_set_polar_ewald_full(mpmc_ctx *c, int enabled, int flags) {
 		c->cache_valid = false; // (the accepted totals, the resident real-space field and an open on-demand solve belong to the other solve)
 		c->e_real_valid = false;
 		drop_pending_dipoles(c);
-		// (Gauss-Seidel sweeps run in atom order, the term keeps the spatial order whatever polar_gs says: mpmc_set_options has the rule)
-		if (on != c->kept.pef_enabled && c->opts_set && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only) c->atoms_dirty = c->atoms_dirty_order = true;
 	}
+	// (Gauss-Seidel sweeps run in atom order, the term keeps the spatial order whatever polar_gs and polar_gs_ranked say: sweeps_keep_atom_order)
+	const bool kept_order = c->opts_set && sweeps_keep_atom_order(c, c->opts);
 	c->kept.pef_enabled = on;
 	c->kept.pef_flags = on ? flags : 0;
+	order_rule_changed(c, kept_order);
 	return MPMC_OK;
 }
 extern "C" int mpmc_polar_ewald_full_info(mpmc_ctx *c, mpmc_ewald_full_info *out) {

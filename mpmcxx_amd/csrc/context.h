@@ -141,6 +141,7 @@ struct mpmc_kept {
 	int pef_flags = 0;                      // MPMC_PEF_*
 	int relax_scheme = 0;                   // `polar_sor` / `polar_esor` (mpmc_set_polar_relax), likewise: MPMC_POLAR_RELAX_*
 	bool zodid = false;                     // `polar_zodid`, likewise
+	bool gs_ranked = false;                 // `polar_gs_ranked` (mpmc_set_polar_gs_ranked), likewise
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 	int cav_grid = 0;                       // `cavity_bias` (mpmc_set_cavity_grid), likewise: cavity_grid_size, 0 = off
 	double cav_radius = 0.0;                // cavity_radius
@@ -431,6 +432,21 @@ struct mpmc_ctx {
 	// `polar_sor` / `polar_esor` / `polar_zodid` (mpmc_set_polar_relax; kept.relax_scheme, kept.zodid)
 	mpmc_relax_info relax_info{}; // of the pending / last evaluation with a dipole solve
 
+	// `polar_gs_ranked` (mpmc_set_polar_gs_ranked, kernels_gs_rank.hip; switched on: kept.gs_ranked): the rank pass of every evaluation and the
+	// second set of per-atom arrays and tile tables, in sweep order, that the sweeps from the second iteration on run on
+	DevBuf<char> d_gr_atoms;          // the view's per-atom arrays, laid out like d_atoms_blob
+	DevBuf<double> d_gr_vec;          // [5][max_pad][3]: E0, the two dipole vectors, the induced field; rrms per atom in the last third
+	DevBuf<int> d_gr_rank;            // [2][max_pad]: rank_metric, order (atom order = slot order: the sweeps keep the identity)
+	DevBuf<GsRankInfoDev> d_gr_info;
+	PinnedBuf<GsRankInfoDev> h_gr_info;
+	DevBuf<double2> d_gr_blocks;      // k_gs_blocks of the view
+	DevBuf<double> d_gr_bounds;       // tile bounding boxes, classes and common images of the view's tiles
+	DevBuf<int> d_gr_cls;
+	DevBuf<double4> d_gr_shift;
+	bool gr_ran = false;              // the pending / last evaluation made a rank pass
+	unsigned gr_pos_gen = 0, gr_static_gen = 0; // ... at these values of pos_gen / static_gen (mpmc_polar_gs_ranked_get asks for the current ones)
+	mpmc_gs_ranked_info gr_info{};    // of the last evaluation with a dipole solve (rmin, max_rank, n_moved filled by wait_and_fill)
+
 	// the cavity-bias grid of uVT moves (mpmc_set_cavity_grid / mpmc_cavity_update, cavity.cpp, kernels_cavity.hip; switched on: kept.cav_grid,
 	// kept.cav_radius).  Nothing here is read or written by an evaluation or a trial; every buffer is made by the first update.
 	unsigned pos_gen = 1;                 // counts the events that change h_pos (atom list, position updates, accepted trials)
@@ -646,8 +662,24 @@ unsigned full_mask(const mpmc_ctx *c);           // what double System::energy()
 // The polarization energy of a Jacobi solve with a fixed iteration count n and mu_0 = alpha E0 is -1/2 sum_k m_k over the moments of the
 // first ceil(n/2) dipole differences: not for polar_gamma != 1, precision-terminated or rrms-reporting solves,
 // Gauss-Seidel sweeps (the only place where `polar_palmo` acts) or the direct solve.
+// `polar_gs_ranked` acts where thole_iterative sweeps (:3450-3543): polarization with polar_iterative on, not under zodid (:3470) and not
+// under ewald_full, which has its own pass loop
+inline bool gs_ranked_acts(const mpmc_ctx *c, const mpmc_options &o) {
+	return c->kept.gs_ranked && o.polarization && !o.rd_only && o.polar_iterative && !c->kept.zodid && !c->kept.pef_enabled;
+}
+inline bool gs_ranked_on(const mpmc_ctx *c) { return gs_ranked_acts(c, c->opts); }
+// Gauss-Seidel sweeps run in the reference's atom order (:3569), so the atoms then keep the caller's order on the device: under polar_gs
+// (not under ewald_full, where it changes nothing) and wherever the ranked sweeps act.  Whoever changes one of the inputs compares the
+// rule before and after and asks for a new upload when it moved (order_rule_changed).
+inline bool sweeps_keep_atom_order(const mpmc_ctx *c, const mpmc_options &o) {
+	return (o.polar_gs && o.polarization && !o.rd_only && !c->kept.pef_enabled) || gs_ranked_acts(c, o);
+}
+inline void order_rule_changed(mpmc_ctx *c, bool was) {
+	if (c->opts_set && was != sweeps_keep_atom_order(c, c->opts)) c->atoms_dirty = c->atoms_dirty_order = true;
+}
 inline bool polar_moments_apply(const mpmc_ctx *c) {
 	const mpmc_options &o = c->opts;
+	if (gs_ranked_on(c)) return false; // (sweeps, like polar_gs below)
 	if (c->kept.relax_scheme != 0 || c->kept.zodid) return false; // (relaxed iterations are no longer powers of one symmetric operator; zodid has none)
 	if (c->kept.pef_enabled) return false; // (ewald_full is not the symmetric Jacobi iteration; the setting acts only where the line below holds anyway)
 	return o.polarization && !o.rd_only && o.polar_iterative && o.polar_max_iter >= 1 && o.polar_max_iter <= kMomentsMaxIter && o.polar_gamma == 1.0 && o.polar_precision == 0.0 && !o.polar_rrms &&

@@ -222,7 +222,7 @@ struct JacobiPlan {
 };
 static JacobiPlan jacobi_plan(const mpmc_ctx *c, int solver) {
 	JacobiPlan jp;
-	jp.dense = (solver == MPMC_SOLVER_DENSE) && !c->opts.polar_gs;
+	jp.dense = (solver == MPMC_SOLVER_DENSE) && !c->opts.polar_gs && !gs_ranked_on(c);
 	jp.dense_sym = jp.dense && c->kept.tune.dense_symmetric;
 	jp.compact = solver == MPMC_SOLVER_COMPACT;
 	jp.iter_slots = (jp.dense && !jp.dense_sym) ? kDenseChunks : c->n_tiles;
@@ -245,6 +245,7 @@ struct EvalPlan {
 	int solver = MPMC_SOLVER_MATRIX_FREE;
 	bool compact = false;     // this evaluation fills and reads the tensor store
 	bool solve = false, direct = false, gs = false;
+	bool ranked = false;      // `polar_gs_ranked`: the sweeps behind the first run on the ranked view (stage_gauss_seidel_solve)
 	int n_pol = 0, chol_np = 0; // direct solve: polarizable atoms, padded order of the factor
 	JacobiPlan jp{};
 	bool by_precision = false, moments = false, lazy = false;
@@ -263,7 +264,7 @@ static int choose_solver(const mpmc_ctx *c) {
 	if (zodid_on(c)) return MPMC_SOLVER_MATRIX_FREE; // `polar_zodid`: no A matrix at all (System::polar :2548), nothing is stored
 	if (direct_solve(c)) return MPMC_SOLVER_MATRIX_FREE; // no iteration: nothing is stored (the one contraction behind the solve, for the residual, is matrix-free)
 	int want = c->opts.solver;
-	if (c->opts.polar_gs) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
+	if (c->opts.polar_gs || gs_ranked_on(c)) want = MPMC_SOLVER_MATRIX_FREE; // Gauss-Seidel sweeps rebuild the tensors row block by row block (kernels_gs.hip)
 	if (want == MPMC_SOLVER_AUTO) {
 		const size_t budget_mb = (size_t)c->kept.tune.tensor_budget_mb;
 		want = (store_elements(c) * sizeof(double2) <= budget_mb * (size_t)1048576) ? MPMC_SOLVER_COMPACT : MPMC_SOLVER_MATRIX_FREE;
@@ -361,7 +362,8 @@ static EvalPlan plan_evaluation(const mpmc_ctx *c, unsigned mask, bool on_demand
 		for (int i = 0; i < c->n; i++) p.n_pol += (c->h_alpha[i] != 0.0) ? 1 : 0;
 		p.chol_np = chol_padded(p.n_pol);
 	} else if (p.solve) {
-		p.gs = o.polar_gs != 0;
+		p.ranked = gs_ranked_on(c);
+		p.gs = o.polar_gs != 0 || p.ranked;
 		p.by_precision = (o.polar_precision != 0.0);
 		p.want_rrms = (o.polar_rrms || o.polar_precision > 0) ? 1 : 0;
 		p.allowed = p.by_precision ? o.polar_precision * o.polar_precision * kDebye2SKA * kDebye2SKA : 0.0;
@@ -469,6 +471,20 @@ static int reserve_ewald_full(mpmc_ctx *c) {
 	if ((rc = c->d_pef_pairs.reserve(c, 1)) != MPMC_OK) return rc;
 	return c->h_pef_pairs.reserve(c, 1);
 }
+// `polar_gs_ranked`: the rank pass's results and the second set of per-atom arrays and tile tables (grow-only, sized for the context's capacity)
+static int reserve_ranked_view(mpmc_ctx *c) {
+	const size_t np = (size_t)c->max_pad, mt = np / kTile, mtp = mt * (mt + 1) / 2;
+	int rc;
+	if ((rc = c->d_gr_info.reserve(c, 1)) != MPMC_OK) return rc;
+	if ((rc = c->h_gr_info.reserve(c, 1)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_rank.reserve(c, 2 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_atoms.reserve(c, np * kAtomRecordBytes)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_vec.reserve(c, 15 * np)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_blocks.reserve(c, gs_block_store_elements(c->n_tiles), gs_block_store_elements((int)mt))) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_bounds.reserve(c, 12 * mt)) != MPMC_OK) return rc;
+	if ((rc = c->d_gr_cls.reserve(c, (size_t)c->n_tile_pairs, mtp)) != MPMC_OK) return rc;
+	return c->d_gr_shift.reserve(c, (size_t)c->n_tile_pairs, mtp);
+}
 static int make_room(mpmc_ctx *c, EvalPlan &p) {
 	int rc;
 	if (p.mask & (RUN_FIELD | RUN_SOLVE | RUN_STORE)) {
@@ -481,6 +497,7 @@ static int make_room(mpmc_ctx *c, EvalPlan &p) {
 	if (p.pef && (rc = reserve_ewald_full(c)) != MPMC_OK) return rc;
 	// the in-tile blocks of the Gauss-Seidel sweeps
 	if (p.gs && (rc = c->d_gs_blocks.reserve(c, gs_block_store_elements(c->n_tiles))) != MPMC_OK) return rc;
+	if (p.ranked && (rc = reserve_ranked_view(c)) != MPMC_OK) return rc;
 	return MPMC_OK;
 }
 
@@ -738,7 +755,56 @@ static void close_solve(mpmc_ctx *c, const EvalPlan &p, int it) {
 	c->pend_done = it, c->pend_target = c->opts.polar_max_iter;
 }
 
-// Gauss-Seidel sweeps: in place, in atom order; the host asks for the verdict of a precision-terminated solve after every sweep
+// What one Gauss-Seidel sweep reads and writes: the context's own arrays (atom order), or the ranked view of `polar_gs_ranked`
+struct SweepView {
+	AtomsDev at;
+	double *e_static, *mu[2], *e_induced, *rrms;
+	const int *cls;
+	const double4 *shift;
+	const double2 *blocks;
+};
+// `polar_gs_ranked`, between the first sweep and the second (update_ranking :3631-3656 behind an iteration that is followed by another): the
+// view in sweep order -- atoms, E0 and the current dipoles gathered, then everything that is derived from the order of the atoms: tile
+// bounding boxes, tile-pair classes and common images, the in-tile blocks
+static SweepView build_ranked_view(mpmc_ctx *c, const SweepView &id) {
+	hipStream_t st = c->stream;
+	const mpmc_options &o = c->opts;
+	const size_t np = (size_t)c->max_pad;
+	const int *order = c->d_gr_rank + np;
+	GsRankView g;
+	int32_t *unused_perm, *unused_slot;
+	atom_block_layout(c->d_gr_atoms, np, [&](double4 *xyzq, double2 *lj, int2 *mf, double *al, double *ep, double *imm, int32_t *perm, int32_t *slot) {
+		g.xyzq = xyzq, g.lj = lj, g.mf = mf, g.alpha = al, g.eps = ep, g.inv_molmass = imm, unused_perm = perm, unused_slot = slot;
+	});
+	(void)unused_perm, (void)unused_slot;
+	double *vec = c->d_gr_vec;
+	SweepView v;
+	v.e_static = g.e_static = vec;
+	v.mu[0] = vec + 3 * np, v.mu[1] = vec + 6 * np;
+	v.e_induced = vec + 9 * np;
+	v.rrms = vec + 12 * np;
+	g.mu = v.mu[c->mu_cur];
+	v.at = id.at;
+	v.at.xyzq = g.xyzq, v.at.lj = g.lj, v.at.mf = g.mf, v.at.alpha = g.alpha, v.at.eps = g.eps, v.at.inv_molmass = g.inv_molmass;
+	{
+		ProfScope ps(c, MPMC_K_CLASSES);
+		launch_gs_rank_gather(st, order, id.at, g, id.e_static, id.mu[c->mu_cur]);
+		if (c->kept.tune.no_classes) (void)hipMemsetAsync(c->d_gr_cls, 0, (size_t)c->n_tile_pairs * sizeof(int), st);
+		else launch_tile_classes(st, v.at, c->box, c->d_tile_pairs, c->n_tile_pairs, o.polar_damp, c->d_gr_bounds, c->d_gr_cls,
+		                         c->kept.tune.no_uniform ? nullptr : c->d_gr_shift.p, c->sort_origin_f, kTholeFarX);
+	}
+	v.cls = c->d_gr_cls;
+	v.shift = (c->kept.tune.no_uniform || c->kept.tune.no_classes) ? nullptr : c->d_gr_shift.p;
+	{
+		ProfScope ps(c, MPMC_K_TENSOR);
+		launch_gs_blocks(st, v.at, c->box, o.polar_damp, c->d_gr_blocks);
+	}
+	v.blocks = c->d_gr_blocks;
+	return v;
+}
+
+// Gauss-Seidel sweeps: in place, in atom order (`polar_gs_ranked`: in ranked order behind the first); the host asks for the verdict of a
+// precision-terminated solve after every sweep
 static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at, const RecipDev &) {
 	if (!p.solve || p.direct || p.pef || p.zodid || !p.gs) return MPMC_OK;
 	hipStream_t st = c->stream;
@@ -747,31 +813,47 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 		ProfScope ps(c, MPMC_K_TENSOR);
 		launch_gs_blocks(st, at, c->box, o.polar_damp, c->d_gs_blocks);
 	}
+	SweepView v{at, c->d_e_static, {c->d_mu[0], c->d_mu[1]}, c->d_e_induced, c->d_rrms, c->d_cls, shift_view(c), c->d_gs_blocks};
+	const SweepView identity = v;
+	const int *order = nullptr;
+	if (p.ranked) { // System::pairs :1001-1029, on every evaluation: the positions changed
+		ProfScope ps(c, MPMC_K_CLASSES);
+		launch_gs_rank(st, at, c->box, c->d_tile_pairs, c->n_tile_pairs, c->d_gr_info, c->d_gr_rank, c->d_gr_rank + c->max_pad);
+		HIP_TRY(c, hipMemcpyAsync(c->h_gr_info, c->d_gr_info, sizeof(GsRankInfoDev), hipMemcpyDeviceToHost, st));
+		c->gr_ran = true;
+		c->gr_pos_gen = c->pos_gen, c->gr_static_gen = c->static_gen;
+		c->gr_info.acted = 1;
+	}
 	int it = 0;
 	for (bool keep = true; keep;) {
 		it++;
 		if (it >= kMaxIterationCount && p.by_precision) { // divergence: mu = alpha E0, iterator_failed (:3483-3494)
-			launch_dipole_reset(st, at, c->d_e_static, c->d_mu[c->mu_cur]);
+			launch_dipole_reset(st, v.at, v.e_static, v.mu[c->mu_cur]);
 			c->failed = 1;
 			break;
 		}
+		if (p.ranked && it == 2) { // the first sweep is followed by another: from here on the sweeps run on the ranked view
+			v = build_ranked_view(c, identity);
+			order = c->d_gr_rank + c->max_pad;
+		}
 		if (p.by_precision) HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), st));
 		// in-place sweep in atom order; old_mu is kept only when rrms / precision or a relaxation scheme need it (:3503-3507)
-		double *mu = c->d_mu[c->mu_cur], *mu_old = c->d_mu[1 - c->mu_cur];
+		double *mu = v.mu[c->mu_cur], *mu_old = v.mu[1 - c->mu_cur];
 		if (p.want_rrms || p.relax) HIP_TRY(c, hipMemcpyAsync(mu_old, mu, 3 * (size_t)at.n_pad * sizeof(double), hipMemcpyDeviceToDevice, st));
 		{
 			ProfScope ps(c, MPMC_K_DIPOLE_ITER);
-			launch_gs_sweep(st, at, c->box, o.polar_damp, c->d_e_static, mu, c->d_e_induced, c->d_part, c->d_tile_pairs, c->d_cls,
-			                shift_view(c), c->n_tile_pairs, c->d_gs_ul, c->d_gs_ul + 3 * (size_t)c->max_pad, c->d_gs_blocks);
+			launch_gs_sweep(st, v.at, c->box, o.polar_damp, v.e_static, mu, v.e_induced, c->d_part, c->d_tile_pairs, v.cls, v.shift, c->n_tile_pairs, c->d_gs_ul,
+			                c->d_gs_ul + 3 * (size_t)c->max_pad, v.blocks);
 		}
+		if (order) c->gr_info.ranked_sweeps++;
 		if (p.want_rrms) {
 			ProfScope ps(c, MPMC_K_REDUCE);
-			launch_gs_finish(st, at, mu_old, mu, p.want_rrms, c->d_rrms, p.allowed, c->d_flag);
+			launch_gs_finish(st, v.at, mu_old, mu, p.want_rrms, v.rrms, p.allowed, c->d_flag);
 		}
 		if (p.relax) { // :3526-3536, behind rrms and the verdict, which saw the swept values: the blend goes where old_mu was and becomes the
 			// current vector; the swept one stays in the other buffer, where stage_palmo finds it
 			ProfScope ps(c, MPMC_K_REDUCE);
-			launch_gs_blend(st, at, mu, mu_old, mu_old, relax_weights(p.relax, o.polar_gamma, it));
+			launch_gs_blend(st, v.at, mu, mu_old, mu_old, relax_weights(p.relax, o.polar_gamma, it));
 			c->mu_cur = 1 - c->mu_cur;
 		}
 		if (p.by_precision) {
@@ -781,6 +863,16 @@ static int stage_gauss_seidel_solve(mpmc_ctx *c, const EvalPlan &p, const AtomsD
 		} else {
 			keep = (it != o.polar_max_iter);
 		}
+	}
+	if (order) { // back to atom order: the dipoles (under a relaxation scheme the swept vector too: stage_palmo contracts it), the induced field of
+		// the last sweep and the per-atom rrms; the energy, rrms and Palmo-Krimm stages then run on the context's own arrays as under polar_gs
+		ProfScope ps(c, MPMC_K_CLASSES);
+		GsRankScatter sc{};
+		sc.src3[0] = v.mu[c->mu_cur], sc.dst3[0] = c->d_mu[c->mu_cur];
+		if (p.relax) sc.src3[1] = v.mu[1 - c->mu_cur], sc.dst3[1] = c->d_mu[1 - c->mu_cur];
+		sc.src3[2] = v.e_induced, sc.dst3[2] = c->d_e_induced;
+		if (p.want_rrms) sc.src1 = v.rrms, sc.dst1 = c->d_rrms;
+		launch_gs_rank_scatter(st, order, at.n_pad, sc);
 	}
 	close_solve(c, p, it);
 	return MPMC_OK;
@@ -1030,7 +1122,11 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 		if (c->kept.relax_scheme != RELAX_NONE && c->opts.polar_gamma < 0.0)
 			return fail(c, MPMC_ERR_INVALID_SETTING, "polar_sor / polar_esor: polar_gamma must not be negative (SimulationControl.cpp:2714-2730)");
 	}
+	if ((mask & RUN_SOLVE) && c->kept.gs_ranked && c->opts.polar_gs && c->opts.polarization && !c->opts.rd_only)
+		return fail(c, MPMC_ERR_INVALID_SETTING, "polar_gs and polar_gs_ranked are both on: choose one (SimulationControl.cpp:2732)");
 	if (mask & RUN_SOLVE) {
+		c->gr_info = mpmc_gs_ranked_info{};
+		c->gr_ran = false;
 		c->relax_info = mpmc_relax_info{};
 		c->relax_info.scheme = c->kept.relax_scheme;
 		c->relax_info.zodid = c->kept.zodid ? 1 : 0;
@@ -1179,6 +1275,11 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		}
 	}
 	if (c->pef_ran) c->pef_info.n_real_pairs = (int64_t)c->h_pef_pairs[0]; // (copied in front of the post)
+	if (c->gr_ran) { // the rank pass's scalars, likewise
+		c->gr_info.rmin = c->h_gr_info[0].rmin;
+		c->gr_info.max_rank = c->h_gr_info[0].max_rank;
+		c->gr_info.n_moved = c->h_gr_info[0].n_moved;
+	}
 	if (!out) return MPMC_OK;
 	std::memset(out, 0, sizeof(*out));
 	const double *s = c->h_scal;

@@ -306,6 +306,33 @@ void launch_gs_finish(hipStream_t st, const AtomsDev &at, const double *mu_old, 
 // `polar_sor` / `polar_esor` behind a sweep (:3526-3536): out = w_new mu_swept + w_old mu_old for every slot; out may be mu_old itself
 void launch_gs_blend(hipStream_t st, const AtomsDev &at, const double *mu_swept, const double *mu_old, double *out, const RelaxWeights &w);
 
+// ---- `polar_gs_ranked` (kernels_gs_rank.hip): the rank pass, the sweep order and the ranked view of the sweeps above -----------------
+struct GsRankInfoDev { // what the rank pass leaves on the device (copied to pinned memory in front of the post)
+	unsigned long long min_r2_bits; // bits of the smallest squared image distance between polarizable atoms (all ones: no such pair)
+	double rmin;                    // its root, or MAXVALUE
+	int max_rank, n_moved;          // largest rank_metric; places of the order that differ from the identity
+	int pad[2];
+};
+struct GsRankView { // the per-atom arrays of the view, each n_pad (x 3) long, in sweep order
+	double4 *xyzq;
+	double2 *lj;
+	int2 *mf;
+	double *alpha, *eps, *inv_molmass, *e_static, *mu;
+};
+struct GsRankScatter { // up to four [n_pad][3] vectors (null: skipped) and one [n_pad] array (may be null) from sweep order to atom order
+	const double *src3[4];
+	double *dst3[4];
+	const double *src1;
+	double *dst1;
+};
+// rmin, rank_metric[n_pad] and order[n_pad] (order[p] = the atom swept p-th; padded slots keep their places) of the resident positions
+void launch_gs_rank(hipStream_t st, const AtomsDev &at, const Box &bx, const int2 *tile_pairs, int n_tile_pairs, GsRankInfoDev *info, int *rank_metric,
+                    int *order);
+// the order alone, of any keys: order[p] = the atom at place p of the stable descending order of key[0 .. n); tally2[1] += places that moved
+void launch_gs_rank_order(hipStream_t st, const AtomsDev &at, const int *key, int *order, int *tally2);
+void launch_gs_rank_gather(hipStream_t st, const int *order, const AtomsDev &src, const GsRankView &dst, const double *e_static, const double *mu);
+void launch_gs_rank_scatter(hipStream_t st, const int *order, int n_pad, const GsRankScatter &v);
+
 // ---- trial moves (kernels_delta.hip) ----------------------------------------------------------------------
 // out4 = { d lj_pairs, d es_real(erfc part), d intramolecular term, E_recip of the trial structure factors }, dcnt2 = { d n_lj, d n_es }
 // a trial move short enough to travel in the kernel arguments (no staging copy): trial positions + charge, slot and original index

@@ -337,8 +337,8 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// (Wolf electrostatics and the Feynman-Hibbs corrections are per-pair terms like the others: the delta kernels carry them; a
 	// polarizable box under Wolf keeps the full evaluation -- its static field is the Ewald one, outside the reference's own combinations;
 	// so does a box whose dipoles are solved directly, polar_iterative off: the matrix is rebuilt and factored again anyway)
-	// (... and a box under `polar_ewald_full`: every pass reads every dipole)
-	const bool polar_delta = polar && c->e_real_valid && !no_polar_delta && m <= MPMC_TRIAL_MAX_ATOMS && !o.wolf && !direct_solve(c) && !ewald_full_on(c);
+	// (... and a box under `polar_ewald_full`: every pass reads every dipole; and one under `polar_gs_ranked`: a move changes the ranks)
+	const bool polar_delta = polar && c->e_real_valid && !no_polar_delta && m <= MPMC_TRIAL_MAX_ATOMS && !o.wolf && !direct_solve(c) && !ewald_full_on(c) && !gs_ranked_on(c);
 	if ((polar && !polar_delta) || m > MPMC_TRIAL_MAX_ATOMS) {
 		// the dipole solve couples every atom: evaluate the trial configuration in full (still on the device)
 		c->trial_keep = c->last_full;

@@ -128,6 +128,12 @@ def polar_relax_of(options: Dict[str, object]):
     return POLAR_RELAX["sor"] if sor else POLAR_RELAX["esor"] if esor else POLAR_RELAX["none"], bool(options.get("polar_zodid"))
 
 
+class GsRankedInfo(C.Structure):
+    """mpmc_gs_ranked_info: the last evaluation with a dipole solve of a context (mpmc_polar_gs_ranked_info)."""
+    _fields_ = [("enabled", C.c_int32), ("acted", C.c_int32), ("rmin", C.c_double), ("max_rank", C.c_int32), ("n_moved", C.c_int32),
+                ("ranked_sweeps", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CavityResult(C.Structure):
     """mpmc_cavity_result: one update of the cavity-bias grid (mpmc_cavity_update)."""
     _fields_ = [("total_points", C.c_int64), ("cavities_open", C.c_int64), ("n_darts", C.c_int64), ("hits", C.c_int64),
@@ -229,6 +235,11 @@ def lib():
     if hasattr(L, "mpmc_set_polar_relax") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the relaxed updates and zeroth-order dipoles)
         L.mpmc_set_polar_relax.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_polar_relax_info.argtypes = [vp, C.POINTER(RelaxInfo)]
+    if hasattr(L, "mpmc_set_polar_gs_ranked") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the ranked Gauss-Seidel sweeps)
+        L.mpmc_set_polar_gs_ranked.argtypes = [vp, C.c_int]
+        L.mpmc_polar_gs_ranked_info.argtypes = [vp, C.POINTER(GsRankedInfo)]
+        L.mpmc_polar_gs_ranked_get.argtypes = [vp, ip, ip]
+        L.mpmc_debug_gs_rank_order.argtypes = [vp, ip, ip]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -446,6 +457,10 @@ class System:
         if any(k in options for k in POLAR_RELAX_KEYS) or getattr(self, "_polar_relax_set", False):
             self._polar_relax_set = True
             self.set_polar_relax(*polar_relax_of(options))
+        # `polar_gs_ranked` likewise
+        if "polar_gs_ranked" in options or getattr(self, "_polar_gs_ranked_set", False):
+            self._polar_gs_ranked_set = True
+            self.set_polar_gs_ranked(bool(options.get("polar_gs_ranked")))
 
         # `cavity_bias` likewise: the grid is switched on or off only when the options name one of its keys
         if any(k in options for k in CAVITY_KEYS) or getattr(self, "_cavity_set", False):
@@ -565,6 +580,23 @@ class System:
         v = RelaxInfo()
         self._check(self._L.mpmc_polar_relax_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RelaxInfo._fields_}
+
+    def set_polar_gs_ranked(self, enabled: bool):
+        """`polar_gs_ranked`: Gauss-Seidel sweeps that run in descending rank order from the second iteration on (mpmc_set_polar_gs_ranked)"""
+        self._check(self._L.mpmc_set_polar_gs_ranked(self._h, int(bool(enabled))))
+
+    def polar_gs_ranked_info(self) -> Dict[str, float]:
+        """enabled, acted, rmin, max_rank, n_moved and ranked_sweeps of the last evaluation with a dipole solve (mpmc_polar_gs_ranked_info)"""
+        v = GsRankedInfo()
+        self._check(self._L.mpmc_polar_gs_ranked_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in GsRankedInfo._fields_ if k != "reserved"}
+
+    def polar_gs_ranked(self):
+        """(rank_metric[n], order[n]) of the last evaluation under the setting, int32, in the caller's atom order; order[p] is the atom swept
+        p-th from the second iteration on (mpmc_polar_gs_ranked_get)"""
+        rank, order = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        self._check(self._L.mpmc_polar_gs_ranked_get(self._h, _ip(rank), _ip(order)))
+        return rank, order
 
     def set_polar_ewald_full(self, enabled: bool, flags: int = 0):
         """`polar_ewald_full`: the induced field of the dipole solve as an Ewald sum as well (mpmc_set_polar_ewald_full); it replaces the

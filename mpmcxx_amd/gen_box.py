@@ -343,6 +343,8 @@ def fixture(name: str):
         return _rd_model_fixture(name)
     if name in RELAX_FIXTURES:
         return _relax_fixture(name)
+    if name in GS_RANKED_FIXTURES:
+        return _gs_ranked_fixture(name)
     raise KeyError(name)
 
 
@@ -969,6 +971,83 @@ def relax_golden(golden_dir: str, name: str) -> Dict[str, object]:
     return g
 
 
+# ---- `polar_gs_ranked` (reference src/System.cpp:1001-1029, src/System.Energy.cpp:3450-3543, 3631-3656) -------------------------------------
+# NAME = BASE_gr_VARIANT: the box BASE with Gauss-Seidel sweeps in ranked order.  None = the keyword is taken out.
+GS_RANKED_VARIANTS = {
+    "it1": {"polar_max_iter": 1},                                                          # no ranked sweep: exactly polar_gs
+    "it2": {"polar_max_iter": 2},                                                          # one sweep in atom order, one in ranked order
+    "it4": {"polar_max_iter": 4},
+    "p": {"polar_precision": 1e-7, "polar_rrms": "on", "polar_max_iter": None},            # sweeps until converged
+    "sor": {"polar_sor": "on", "polar_gamma": 0.9, "polar_max_iter": 6},                   # blended behind each sweep
+    "esorpalmo": {"polar_esor": "on", "polar_gamma": 0.7, "polar_max_iter": 6, "polar_palmo": "on"},  # ... + Palmo-Krimm
+}
+GS_RANKED_BASES = ["ion216_polar", "ion216_polar_nopbc", "water64_polar", "ion216_triclinic", "ion1000_gs"]
+GS_RANKED_FIXTURES = [f"ion216_polar_gr_{v}" for v in GS_RANKED_VARIANTS] + [f"{b}_gr_it4" for b in GS_RANKED_BASES[1:]]
+GS_RANKED_SAMPLE_EVERY = 16  # boxes of more than 216 atoms keep the per-atom results of every 16th atom
+GS_RANKED_GOLDEN = ("polar_gs_ranked.json", "polar_gs_ranked.npz")  # under tests/golden/: every fixture's scalars; the per-atom arrays
+
+
+def _gs_ranked_fixture(name: str):
+    base, variant = name.rsplit("_gr_", 1)
+    rows, basis, o = fixture(base)
+    o = dict(o, polar_gs="off", polar_gs_ranked="on", polar_max_iter=10)  # (ion1000_gs brings its own polar_gs; both together are an input error)
+    for k, v in GS_RANKED_VARIANTS[variant].items():
+        if v is None:
+            o.pop(k, None)
+        else:
+            o[k] = v
+    return rows, basis, o
+
+
+def keep_gs_ranked_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <GS_RANKED_FIXTURES>`: the per-fixture files are folded into GS_RANKED_GOLDEN and removed, the box
+    text too (the tests regenerate it with `materialize`), the way keep_relax_golden keeps its family."""
+    import json
+
+    import numpy as np
+
+    scalars, arrays, by_bytes = {}, {}, {}
+    for name in (names or GS_RANKED_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        n = res["natoms"]
+        every = GS_RANKED_SAMPLE_EVERY if n > 216 else 1
+        out = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+        out["sample_every"] = every
+        out["arrays"] = {}
+        for k in ("ef_static", "mu", "ef_induced"):
+            a = np.asarray(res[k], dtype=np.float64).reshape(-1, 3)
+            assert a.shape[0] == n, (name, k, a.shape)
+            a = a[::every]
+            key = by_bytes.setdefault(a.tobytes(), f"{name}.{k}")
+            arrays.setdefault(key, a)
+            out["arrays"][k] = key
+        scalars[name] = out
+    with open(os.path.join(golden_dir, GS_RANKED_GOLDEN[0]), "w") as f:
+        json.dump(scalars, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    np.savez_compressed(os.path.join(golden_dir, GS_RANKED_GOLDEN[1]), **arrays)
+    for name in (names or GS_RANKED_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def gs_ranked_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    """one fixture of GS_RANKED_GOLDEN: scalars, `sample_atoms`, and ef_static / mu / ef_induced as [k, 3] arrays"""
+    import json
+
+    import numpy as np
+
+    with open(os.path.join(golden_dir, GS_RANKED_GOLDEN[0])) as f:
+        g = json.load(f)[name]
+    with np.load(os.path.join(golden_dir, GS_RANKED_GOLDEN[1])) as z:
+        for k, key in g.pop("arrays").items():
+            g[k] = z[key]
+    g["sample_atoms"] = list(range(0, g["natoms"], g.pop("sample_every")))
+    return g
+
+
 def keep_three_body_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
     """After `python oracle/make_golden.py <THREE_BODY_FIXTURES>` (or <DISP_FIXTURES>, names = DISP_FIXTURES): keep each box's scalar
     results (energies, counts, cell) and drop the per-atom arrays and the box text.  The tests of these terms compare nothing else, and
@@ -1022,6 +1101,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-relax-golden"]:
         keep_relax_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-gs-ranked-golden"]:
+        keep_gs_ranked_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-disp-golden"]:
         keep_three_body_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"), DISP_FIXTURES)
