@@ -733,6 +733,10 @@ int mpmc_debug_wait_counters(mpmc_ctx *ctx, long long out4[4]);
  * n the atoms of the context.  The rank pass itself cannot produce a key above about 60 (atoms no closer than rmin within 1.5 rmin of
  * one of them); the sort takes any values.  It overwrites what mpmc_polar_gs_ranked_get hands out. */
 int mpmc_debug_gs_rank_order(mpmc_ctx *ctx, const int32_t *keys /*[n]*/, int32_t *order /*[n]*/);
+/* The tile-pair classes of the ranked view that the last evaluation under `polar_gs_ranked` swept (rebuilt from the atoms in sweep order):
+ * out6 = { tile pairs, off-diagonal tile pairs, of those: far, beyond the cutoff, with one periodic image index for the whole tile pair
+ * in some dimension, with such an image that is not the zero image }.  Read-only. */
+int mpmc_debug_gs_ranked_pair_stats(mpmc_ctx *ctx, int64_t out6[6]);
 /* Measurement / A-B switch, key = value (keys: csrc/context.cpp, struct mpmc_tuning).  ctx == NULL: the default of contexts created
  * afterwards in this process.  The library reads no environment variable for any of these. */
 int mpmc_debug_configure(mpmc_ctx *ctx, const char *key, double value);

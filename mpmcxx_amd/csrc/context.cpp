@@ -1469,6 +1469,45 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 	return MPMC_OK;
 }
 
+// (diagnostics, read-only) the tile-pair classes of the RANKED VIEW of the last evaluation (build_ranked_view: rebuilt from the gathered atoms),
+// as mpmc_debug_pair_stats counts those of the atom order.  out[6] =
+//   0 tile pairs      1 off-diagonal tile pairs      2 far      3 beyond the cutoff      4 with one image index for the whole tile pair in
+//   some dimension      5 ... where that common image is not the zero image (4 and 5: 0 with uniform_images or tile_classes off)
+extern "C" int mpmc_debug_gs_ranked_pair_stats(mpmc_ctx *c, int64_t out[6]) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_ranked_pair_stats: an evaluation or a trial move is open");
+	if (!c->kept.gs_ranked || !c->gr_ran || c->gr_info.ranked_sweeps < 1 || c->gr_pos_gen != c->pos_gen || c->gr_static_gen != c->static_gen || !c->d_gr_cls)
+		return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_ranked_pair_stats: the last evaluation swept no ranked view");
+	HIP_TRY(c, hipSetDevice(c->device));
+	const bool uni = !(c->kept.tune.no_uniform || c->kept.tune.no_classes) && c->d_gr_shift;
+	std::vector<int> cls((size_t)c->n_tile_pairs);
+	std::vector<double4> shift(uni ? (size_t)c->n_tile_pairs : 0);
+	HIP_TRY(c, hipMemcpyAsync(cls.data(), c->d_gr_cls, cls.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	if (uni) HIP_TRY(c, hipMemcpyAsync(shift.data(), c->d_gr_shift, shift.size() * sizeof(double4), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	for (int k = 0; k < 6; k++) out[k] = 0;
+	const int nt = c->n_tiles;
+	size_t t = 0;
+	for (int I = 0; I < nt; I++)
+		for (int J = I; J < nt; J++, t++) {
+			out[0]++;
+			if (I == J) continue;
+			const int v = cls[t];
+			out[1]++;
+			if (v & CLS_THOLE_FAR) out[2]++;
+			if (v & CLS_BEYOND_CUTOFF) out[3]++;
+			const int um = uni ? ((v / CLS_UNIFORM_X) & 7) : 0;
+			if (!um) continue;
+			out[4]++;
+			const double sh[3] = {shift[t].x, shift[t].y, shift[t].z};
+			bool moved = false;
+			// orthorhombic cell: component d belongs to dimension d; any other: the shift is the sum over the common lattice directions
+			for (int d = 0; d < 3; d++) moved = moved || (sh[d] != 0.0 && (!c->box.ortho || ((um >> d) & 1)));
+			if (moved) out[5]++;
+		}
+	return MPMC_OK;
+}
+
 // Measurement / A-B switches (struct mpmc_tuning, context.h).  With a context: that context, from its next evaluation on; with a null
 // context: the default that contexts created afterwards in this process start from.  The library reads no environment variable for
 // any of this.  Keys (value 1 = on, 0 = off unless said otherwise):

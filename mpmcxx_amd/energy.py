@@ -240,6 +240,8 @@ def lib():
         L.mpmc_polar_gs_ranked_info.argtypes = [vp, C.POINTER(GsRankedInfo)]
         L.mpmc_polar_gs_ranked_get.argtypes = [vp, ip, ip]
         L.mpmc_debug_gs_rank_order.argtypes = [vp, ip, ip]
+        if hasattr(L, "mpmc_debug_gs_ranked_pair_stats") or not os.environ.get("MPMC_ENERGY_LIB"):
+            L.mpmc_debug_gs_ranked_pair_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_get_tile_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.mpmc_trial_begin.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mpmc_trial_energy.argtypes = [vp, C.POINTER(Result)]
@@ -820,6 +822,13 @@ class System:
         self._check(self._L.mpmc_debug_pair_stats(self._h, a))
         keys = ["pairs", "pairs_stored", "pairs_far", "pairs_beyond_cutoff", "nonuniform_dims_x_pairs_stored", "nonuniform_dims_x_pairs_far",
                 "pairs_swept", "nonuniform_dims_x_pairs_swept", "tile_pairs", "tile_pairs_stored", "tile_pairs_far", "tile_pairs_beyond_cutoff"]
+        return {k: int(a[i]) for i, k in enumerate(keys)}
+
+    def gs_ranked_pair_stats(self) -> Dict[str, int]:
+        """tile-pair classes of the ranked view the last evaluation under `polar_gs_ranked` swept (mpmc_debug_gs_ranked_pair_stats)."""
+        a = (C.c_int64 * 6)()
+        self._check(self._L.mpmc_debug_gs_ranked_pair_stats(self._h, a))
+        keys = ["tile_pairs", "tile_pairs_off_diagonal", "tile_pairs_far", "tile_pairs_beyond_cutoff", "tile_pairs_common_image", "tile_pairs_shifted"]
         return {k: int(a[i]) for i, k in enumerate(keys)}
 
     def time_kernel(self, which: str, reps: int = 100) -> float:

@@ -18,6 +18,7 @@ from __future__ import annotations
 import math
 import os
 import random
+import re
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -104,6 +105,80 @@ def lattice_box_cell(n_atoms: int, basis, seed: int, charge: float = 0.1, alpha:
                 x, y, z = (sum(f[q] * basis[q][p] for q in range(3)) for p in range(3))
                 rows.append(AtomRow(k, "Ar", "Ar", "M", k, x, y, z, 39.948, charge if (k % 2 == 1) else -charge, alpha, eps, sigma))
     return rows
+
+
+# ---- slab boxes: a long thin cell whose 64-atom tiles, in list order, are slabs about 5 A thick -----------------------------------------------
+# 7 x 7 sites per layer, the layers stacked in z, z outermost in the list.  With Gauss-Seidel sweeps (no spatial sort) the tile-pair table of
+# such a box has every class: the cutoff is 12.6 A, the Thole far distance 30 / 2.1304 = 14.1 A, and tiles more than half the cell apart
+# share a non-zero periodic image in z.
+SLAB_SPACING = 3.6
+SLAB_SIDE = 7
+SLAB_MIN_LAYERS = 23  # 25.2 x 25.2 x 82.8 A; a box of more than 23 layers is longer
+SLAB_SKEW = [[1.0, 0.0, 0.0], [0.17, 1.0, 0.0], [-0.12, 0.21, 1.0]]  # the triclinic cell: row q of the orthorhombic basis times this
+SLAB_PLANTED = (70, 200, 333, 520, 700, 845, 1000, 1088)  # list indices pulled to 2.0 A from their list predecessor
+SLAB_PLANT_AT = (1.2, 1.6, 0.0)
+SLAB_THIRD = (201, 200, (0.0, 0.0, 2.0))  # (atom, neighbour, displacement): a second atom 2.0 A from the planted atom 200
+SLAB_SHIFTED = 700  # this planted atom (a molecule of its own) is listed one cell vector (the first) away from where it sits
+SLAB_JITTER = {"planted": 0.014, "scrambled": 0.25 / SLAB_SPACING}  # in lattice spacings: +-0.05 A and +-0.25 A
+
+
+def slab_basis(n_atoms: int, triclinic: bool = False):
+    per = SLAB_SIDE * SLAB_SIDE
+    layers = max(SLAB_MIN_LAYERS, (n_atoms + per - 1) // per)
+    edge = [SLAB_SIDE * SLAB_SPACING, SLAB_SIDE * SLAB_SPACING, layers * SLAB_SPACING]
+    skew = SLAB_SKEW if triclinic else [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    return [[edge[q] * skew[q][p] for p in range(3)] for q in range(3)], layers
+
+
+def slab_box(n_atoms: int, variant: str, triclinic: bool = False) -> List[AtomRow]:
+    """The first n_atoms sites of the slab lattice, from the same fractional coordinates whatever the cell.  Charges +-30 (reduced units) in
+    alternation, about 10 % of the sites with alpha = 0, every 37th site the first of a three-site molecule, every sixth of those frozen.
+      planted    jitter +-0.05 A; the atoms SLAB_PLANTED sit 2.0 A (Cartesian SLAB_PLANT_AT) from their list predecessors and SLAB_THIRD
+                 2.0 A from one of them: rmin = 2.0, the threshold of the rank pass 3.0 is clear of every lattice distance, and only the
+                 planted atoms and their neighbours have a rank.  SLAB_SHIFTED is listed a whole cell vector away: the pair has the image
+                 distance 2.0 and, by the unwrapped distance, no rank.
+      scrambled  jitter +-0.25 A: rmin about 2.9, nearly every atom has a rank, the ranked order scatters the list over the cell."""
+    basis, layers = slab_basis(n_atoms, triclinic)
+    jit = SLAB_JITTER[variant]
+    rng, pick = random.Random(41), random.Random(43)
+    planted = [k for k in SLAB_PLANTED if k < n_atoms] if variant == "planted" else []
+    third = SLAB_THIRD if (planted and SLAB_THIRD[0] < n_atoms) else None
+    keep_alpha = set(planted) | {k - 1 for k in planted} | ({third[0]} if third else set())
+    per = SLAB_SIDE * SLAB_SIDE
+    rows: List[AtomRow] = []
+    mol = 0
+    for k in range(n_atoms):
+        iz, rem = divmod(k, per)
+        iy, ix = divmod(rem, SLAB_SIDE)
+        f = [(ix + 0.5 + rng.uniform(-jit, jit)) / SLAB_SIDE - 0.5, (iy + 0.5 + rng.uniform(-jit, jit)) / SLAB_SIDE - 0.5,
+             (iz + 0.5 + rng.uniform(-jit, jit)) / layers - 0.5]
+        x, y, z = (sum(f[q] * basis[q][p] for q in range(3)) for p in range(3))
+        start = k - k % 37
+        in_triple = k - start < 3 and start + 2 < n_atoms
+        if not (in_triple and k > start):
+            mol += 1
+        frozen = in_triple and (start // 37) % 6 == 1
+        dark = pick.random() < 0.1 and k not in keep_alpha
+        q = (30.0 if k % 2 == 0 else -30.0) / 408.7816
+        rows.append(AtomRow(k + 1, "Ar", "Tri" if in_triple else "Ar", "F" if frozen else "M", mol, x, y, z, 39.948, q, 0.0 if dark else 1.6411, 119.8, 3.405))
+    for k in planted:
+        rows[k].x, rows[k].y, rows[k].z = (getattr(rows[k - 1], c) + d for c, d in zip("xyz", SLAB_PLANT_AT))
+    if third:
+        rows[third[0]].x, rows[third[0]].y, rows[third[0]].z = (getattr(rows[third[1]], c) + d for c, d in zip("xyz", third[2]))
+    if SLAB_SHIFTED in planted:
+        r = rows[SLAB_SHIFTED]
+        r.x, r.y, r.z = r.x + basis[0][0], r.y + basis[0][1], r.z + basis[0][2]
+    return rows
+
+
+SLAB_NAME = r"slab(\d+)_(planted|scrambled)(_tri)?"
+
+
+def _slab_fixture(name: str):
+    """slab<N>_<variant>[_tri]: N atoms, Gauss-Seidel sweeps in atom order (the GS_RANKED_FIXTURES swap in the ranked order)"""
+    n, variant, tri = re.fullmatch(SLAB_NAME, name).groups()
+    o = dict(POLAR_OPTS, polar_gs="on", polar_max_iter=3)
+    return slab_box(int(n), variant, bool(tri)), slab_basis(int(n), bool(tri))[0], o
 
 
 def _rot(rng: random.Random):
@@ -345,6 +420,8 @@ def fixture(name: str):
         return _relax_fixture(name)
     if name in GS_RANKED_FIXTURES:
         return _gs_ranked_fixture(name)
+    if re.fullmatch(SLAB_NAME, name):
+        return _slab_fixture(name)
     raise KeyError(name)
 
 
@@ -980,9 +1057,12 @@ GS_RANKED_VARIANTS = {
     "p": {"polar_precision": 1e-7, "polar_rrms": "on", "polar_max_iter": None},            # sweeps until converged
     "sor": {"polar_sor": "on", "polar_gamma": 0.9, "polar_max_iter": 6},                   # blended behind each sweep
     "esorpalmo": {"polar_esor": "on", "polar_gamma": 0.7, "polar_max_iter": 6, "polar_palmo": "on"},  # ... + Palmo-Krimm
+    "it3": {"polar_max_iter": 3},                                                          # (the slab boxes only)
 }
-GS_RANKED_BASES = ["ion216_polar", "ion216_polar_nopbc", "water64_polar", "ion216_triclinic", "ion1000_gs"]
-GS_RANKED_FIXTURES = [f"ion216_polar_gr_{v}" for v in GS_RANKED_VARIANTS] + [f"{b}_gr_it4" for b in GS_RANKED_BASES[1:]]
+GS_RANKED_SLABS = ["slab1089_planted", "slab1089_planted_tri"]  # 18 tiles, the last with one atom: a ranked view whose tile pairs have classes
+GS_RANKED_BASES = ["ion216_polar", "ion216_polar_nopbc", "water64_polar", "ion216_triclinic", "ion1000_gs"] + GS_RANKED_SLABS
+GS_RANKED_FIXTURES = ([f"ion216_polar_gr_{v}" for v in GS_RANKED_VARIANTS if v != "it3"] + [f"{b}_gr_it4" for b in GS_RANKED_BASES[1:5]]
+                      + [f"{b}_gr_it3" for b in GS_RANKED_SLABS])
 GS_RANKED_SAMPLE_EVERY = 16  # boxes of more than 216 atoms keep the per-atom results of every 16th atom
 GS_RANKED_GOLDEN = ("polar_gs_ranked.json", "polar_gs_ranked.npz")  # under tests/golden/: every fixture's scalars; the per-atom arrays
 

@@ -113,6 +113,19 @@ def test_parity_where_a_slice_streams_several_chunks():
         S.close()
 
 
+@pytest.mark.parametrize("G,waves,per,expected_open", [(41, 1077, 2, 9142), (65, 4292, 5, 39271)])
+def test_parity_where_a_scan_thread_sums_several_waves(systems, G, waves, per, expected_open):
+    """k_cavity_compact_scan gives each of its 1024 threads ceil(waves / 1024) wave counts; up to G = 40 (1000 waves) that is one.
+    lj64, radius 2.5: G = 41 has 1077 waves of centres, two per thread, the 539th thread holds one and the rest none; G = 65 has 4292,
+    five per thread.  cavities_open found on the CPU with cavity_ref."""
+    assert (G ** 3 + 63) // 64 == waves and (waves + 1023) // 1024 == per and waves % per != 0
+    S, basis = systems("lj64")
+    res, ref = assert_update(S, basis, G, 2.5, darts_for(basis, seed=1000 + G), f"lj64 G={G}")
+    assert res["cavities_open"] == expected_open, res
+    for rank in (0, 1, expected_open // 2, expected_open - 1):
+        assert np.array_equal(bits(S.cavity_point(rank)), bits(ref["grid"][ref["open_index"][rank]])), (G, rank)
+
+
 # ---- 2. the boundary ---------------------------------------------------------------------------------------------------------------------------
 def frozen_atoms(pos):
     n = len(pos)
