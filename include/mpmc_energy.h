@@ -272,6 +272,30 @@ int mpmc_trial_insert_begin(mpmc_ctx *ctx, int at_index, int count, const double
 /* trial removal of the whole molecule that occupies atoms [first, first+count) */
 int mpmc_trial_remove_begin(mpmc_ctx *ctx, int first, int count);
 
+/* ---- batched insertion candidates: many trial insertions of one molecule in one launch chain ---------------------------------------------
+ * Widom test-particle insertion, orientational-bias / multiple-try insertion at one site and energy-biased site selection ask the same
+ * question many times against an unchanged accepted configuration: what is the energy with this molecule at this pose?  out[c] is the
+ * mpmc_result that mpmc_trial_insert_begin(ctx, n, count, pos + 3*count*c, ...) + mpmc_trial_energy + mpmc_trial_reject would give for
+ * candidate c, in every field and bit for bit (at_index does not enter a delta-path result), for n_cand candidates behind ONE host wait.
+ * The per-atom arrays are those of mpmc_trial_insert_begin, `count` long and shared by all candidates; only the positions differ.
+ *   The call opens no trial and changes nothing an evaluation, a trial or a cavity update reads: accepted totals, structure factors and
+ * atom list are as before, and the chosen candidate is then inserted with mpmc_trial_insert_begin / mpmc_trial_energy / mpmc_trial_accept,
+ * whose result has the bits of out[c].  Preconditions and codes as for mpmc_trial_insert_begin, in the same order: no open trial
+ * (MPMC_ERR_ARG), no Axilrod-Teller or disp-expansion coefficients (MPMC_ERR_UNSUPPORTED), an accepted configuration (MPMC_ERR_ARG), finite
+ * positions in every candidate (MPMC_ERR_INVALID_DATUM).  MPMC_ERR_ARG also for count < 1, n_cand < 1, n_cand > MPMC_INSERT_MAX_CANDIDATES
+ * and null pos or out.
+ *   Only the delta path exists here: a polarizable box (polarization on and not rd_only), rd_crystal, a non-default rd model and
+ * count > MPMC_TRIAL_MAX_ATOMS are MPMC_ERR_UNSUPPORTED with a text in mpmc_last_error -- a batch of full evaluations is the loop of single
+ * trials.  Ewald and Wolf electrostatics, rd_only, the Feynman-Hibbs corrections, frozen and null-rd atoms and any cell are carried.
+ *   Cost O(n_cand count N) pair terms + O(n_cand count K); device time is counted under MPMC_K_PAIR.  Scratch is bounded: large batches run
+ * in internal chunks of 256 candidates (32 B x K of trial structure factors each), all buffers are allocated by the first call. */
+#define MPMC_INSERT_MAX_CANDIDATES 65536
+int mpmc_insert_candidates(mpmc_ctx *ctx, int count, int n_cand, const double *pos /*[n_cand][count][3]*/, const double *charge,
+                           const double *polarizability, const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp,
+                           const double *mass, mpmc_result *out /*[n_cand]*/);
+/* diagnostics only, read-only: out2 = { calls of mpmc_insert_candidates that ran, candidates they evaluated } */
+int mpmc_debug_insert_batch_counts(mpmc_ctx *ctx, long long *out2);
+
 /* ---- the Axilrod-Teller triple-dipole dispersion, System::axilrod_teller (src/System.Energy.cpp:129-136, 1653-1770) --------------------
  * Sum over every unordered triple of distinct atoms that are not all in one molecule, no cutoff, frozen atoms included; each pair vector is
  * that pair's own minimum image.  Added to energy (and NU) as three_body_energy; the path-integral sums stay {rd, coulombic, polarization,

@@ -22,6 +22,7 @@
 // INTEGRATION.md does for the real reference objects).  Header-only; link with -lmpmc_energy.
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <functional>
@@ -95,6 +96,8 @@ struct Atom {
 	// written by energy():
 	double mu[3] = {0, 0, 0}, ef_static[3] = {0, 0, 0}, ef_induced[3] = {0, 0, 0};
 };
+
+using Molecule = std::vector<Atom>; // the atoms of one molecule, in order (a species to insert)
 
 class System {
 public:
@@ -333,6 +336,36 @@ public:
 		trial_kind_ = -1, trial_first_ = first, trial_count_ = count;
 		trial_pos_.clear();
 		exchange_enqueue();
+	}
+
+	// ---- batched insertion candidates (mpmc_insert_candidates): many poses of one species against the accepted state, one wait ----
+	// poses[c][i] is the position of atom i of `species` in candidate c (the species' own `pos` is not read).  Entry c of the result is the
+	// mpmc_result energy_trial_insert(atoms.size(), species at pose c) + reject_trial() would leave in trial_result(), bit for bit.  No trial
+	// is opened and nothing of the accepted state changes: the chosen candidate is then inserted with energy_trial_insert / accept_trial.
+	// Needs a prior energy() of the accepted state; non-polarizable boxes with the plain rd term only (the library refuses the others).
+	std::vector<mpmc_result> energy_insert_candidates(const Molecule &species, const std::vector<std::vector<std::array<double, 3>>> &poses) {
+		sync_state();
+		const int m = (int)species.size(), n_cand = (int)poses.size();
+		std::vector<double> pos(3 * (size_t)m * (size_t)n_cand), q(m), al(m), ep(m), sg(m), ms(m);
+		std::vector<int32_t> fr(m), dp(m);
+		for (int i = 0; i < m; i++) {
+			const Atom &a = species[i];
+			q[i] = a.charge, al[i] = a.polarizability, ep[i] = a.epsilon, sg[i] = a.sigma, ms[i] = a.mass;
+			fr[i] = a.frozen;
+			dp[i] = (a.c6 != 0.0 || a.c8 != 0.0 || a.c10 != 0.0) ? 1 : 0;
+		}
+		for (int c = 0; c < n_cand; c++) {
+			if ((int)poses[c].size() != m) {
+				last_error_ = "energy_insert_candidates: a pose has another number of atoms than the species";
+				throw (int)MPMC_ERR_ARG;
+			}
+			for (int i = 0; i < m; i++)
+				for (int p = 0; p < 3; p++) pos[3 * ((size_t)c * m + i) + p] = poses[c][i][p];
+		}
+		std::vector<mpmc_result> out((size_t)(n_cand > 0 ? n_cand : 0));
+		check(mpmc_insert_candidates(ctx_, m, n_cand, pos.data(), q.data(), al.data(), ep.data(), sg.data(), fr.data(), dp.data(), ms.data(), out.data()),
+		      "mpmc_insert_candidates");
+		return out;
 	}
 
 	// ---- System::cavity_update_grid, src/System.Cavity.cpp:15-188 (the reference calls it in front of every move of a cavity_bias run) ----

@@ -128,6 +128,7 @@ struct mpmc_kept {
 	long long n_poll_hits = 0, n_poll_timeouts = 0, n_stream_syncs = 0, n_poll_yields = 0;
 	long long n_uploads_carried = 0, n_uploads_sorted = 0; // (diagnostics: mpmc_debug_upload_counts)
 	long long n_xch_delta = 0, n_xch_full = 0, n_xch_resums = 0; // (diagnostics: mpmc_debug_exchange_counts)
+	long long n_ins_calls = 0, n_ins_cands = 0;                  // (diagnostics: mpmc_debug_insert_batch_counts)
 	bool tb_enabled = false, tb_mk = false; // Axilrod-Teller term switched on; Midzuno-Kihara c9 (mpmc_set_axilrod_teller)
 	bool de_enabled = false;                // disp-expansion term switched on (mpmc_set_disp_expansion); the atoms' dispersion flag is AF_DISP_RD then
 	int de_flags = 0;                       // MPMC_DISP_*
@@ -364,6 +365,16 @@ struct mpmc_ctx {
 	unsigned xs_gen = 0;         // static_gen of xs_acc (0: none)
 	int xs_edits = 0;            // accepted exchanges since xs_acc was summed over the list
 	double xch_static[3] = {0, 0, 0}, xch_N = 0; // lrc_pair, lrc_self, es_self and countN of the evaluated trial composition
+
+	// batched insertion candidates (mpmc_insert_candidates, kernels_insert_batch.hip): all allocated by the first call.  The staging block
+	// holds one pass of candidates (kInsStageRecords records at the most), the device scratch one launch chain (kInsBatchChunk candidates).
+	PinnedBuf<XchAtom> h_ins_mol;      // [pass][m]
+	DevBuf<XchAtom> d_ins_mol;         // [pass][m]
+	DevBuf<double4> d_ins_sf;          // [kInsBatchChunk][K] trial structure factors (Ewald electrostatics only)
+	DevBuf<double> d_ins_part;         // [kInsBatchChunk][n_tiles + 1][2]
+	DevBuf<int> d_ins_cnt;             // likewise
+	DevBuf<InsCandOut> d_ins_out;      // [n_cand]
+	PinnedBuf<InsCandOut> h_ins_out;   // [n_cand]
 
 	// Axilrod-Teller three-body term (mpmc_set_axilrod_teller, kernels_three_body.hip)
 	// (switched on: kept.tb_enabled, kept.tb_mk)

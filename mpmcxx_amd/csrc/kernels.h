@@ -377,6 +377,18 @@ void launch_exchange(hipStream_t st, const AtomsDev &at, const Box &bx, const Re
                      double sg, double4 *sf_trial, double *block_part /*[nt + 1][2]*/, int *block_cnt /*[nt + 1][2]*/, double *out4, long long *dcnt2,
                      double *host_out, double seq);
 
+// ---- batched insertion candidates (kernels_insert_batch.hip): nc trial poses of one molecule against the same accepted configuration ------
+// What launch_exchange + launch_delta_finish leave for ONE insertion, per candidate: the signed changes and counts of the D_* block.
+struct InsCandOut {
+	double lj, es_real, es_intra, es_recip;
+	long long n_lj, n_es;
+};
+constexpr int kInsBatchBlockCands = 8; // candidates a block runs against the resident loads it made once (no result depends on it)
+constexpr int kInsBatchChunk = 256;    // candidates per launch chain: the scratch is [kInsBatchChunk] x { (nt + 1) partials, K structure factors }
+// mol: [nc][m] staged records (sg = +1); sf_trial: [nc][K]; block_part / block_cnt: [nc][nt + 1][2]; out: [nc], every field written
+void launch_insert_batch(hipStream_t st, const AtomsDev &at, const Box &bx, const RecipDev &rc, const FusedParams &fp, int do_es, const XchAtom *mol, int m, int nc,
+                         double4 *sf_trial, double *block_part, int *block_cnt, InsCandOut *out);
+
 // ---- Axilrod-Teller three-body dispersion (kernels_three_body.hip) --------------------------------------------------------------
 // au[slot] = (a, u) per atom (context.cpp: three_body_coefficients; padding a = 0, u = 1).  Both launches leave kThreeBodyBlocks (or fewer)
 // partials in `part` and write scale * their fixed-order sum to out[0].

@@ -193,32 +193,15 @@ __global__ __launch_bounds__(256) void k_delta_finish(const double *__restrict__
                                                       double seq) {
 	__shared__ double sh[4];
 	__shared__ long long shc[256];
-	double s0 = 0, s1 = 0, e = 0;
-	long long c0 = 0, c1 = 0;
-	for (int b = threadIdx.x; b < nb; b += 256) {
-		s0 += block_part[2 * (size_t)b];
-		s1 += block_part[2 * (size_t)b + 1];
-		c0 += block_cnt[2 * (size_t)b];
-		c1 += block_cnt[2 * (size_t)b + 1];
-	}
-	if (do_es)
-		for (int k = threadIdx.x; k < rc.K; k += 256) {
-			const double4 sf = sf_trial[k];
-			e += rc.w_en[k] * (sf.x * sf.x + sf.y * sf.y);
-		}
-	s0 = block_sum_256(s0, sh);
-	s1 = block_sum_256(s1, sh);
-	e = block_sum_256(e, sh);
+	double s0, s1, e;
+	long long c0, c1;
+	delta_finish_sums(block_part, block_cnt, nb, rc, sf_trial, do_es, sh, shc, s0, s1, e, c0, c1); // (trial_kernels.h: shared with the batched insertion candidates)
 	if (threadIdx.x == 0) {
 		out[D_LJ] = s0;
 		out[D_ES_REAL] = s1;
 		if (!do_es) out[D_ES_INTRA] = 0.0; // (k_delta_intra wrote it otherwise)
 		out[D_ES_RECIP] = e * (4.0 * kPi / bx.volume);
 		out[D_SPARE] = (double)0;
-	}
-	c0 = block_count_256(c0, shc);
-	c1 = block_count_256(c1, shc);
-	if (threadIdx.x == 0) {
 		dcnt[0] = c0;
 		dcnt[1] = c1;
 	}

@@ -73,26 +73,29 @@ static void xch_open(mpmc_ctx *c, int kind, int at, int count) {
 	c->trial_evaluated = c->trial_enqueued = c->trial_noop = false;
 }
 
-extern "C" int mpmc_trial_insert_begin(mpmc_ctx *c, int at_index, int count, const double *pos, const double *charge, const double *polarizability,
-                                       const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
-	if (!c || count <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !frozen) return MPMC_ERR_ARG;
-	int rc = xch_begin_checks(c, "mpmc_trial_insert_begin");
-	if (rc != MPMC_OK) return rc;
-	if (at_index < 0 || at_index > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index outside the atom list");
-	if (at_index > 0 && at_index < c->n && c->h_mol[at_index - 1] == c->h_mol[at_index])
-		return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index lies inside a molecule (it must be a molecule boundary)");
-	for (int t = 0; t < 3 * count; t++)
-		if (!std::isfinite(pos[t])) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: non-finite position");
+// an inserted molecule's data, `n_poses` poses of it: finite positions, sane parameters, masses where the list has them
+static int xch_molecule_checks(mpmc_ctx *c, const char *who, int count, int n_poses, const double *pos, const double *charge, const double *polarizability,
+                               const double *epsilon, const double *sigma, const double *mass) {
+	const std::string w(who);
+	for (size_t t = 0; t < 3 * (size_t)count * (size_t)n_poses; t++)
+		if (!std::isfinite(pos[t])) return fail(c, MPMC_ERR_INVALID_DATUM, w + ": non-finite position");
 	for (int i = 0; i < count; i++)
 		if (epsilon[i] < 0.0 || !std::isfinite(epsilon[i]) || !std::isfinite(sigma[i]) || !std::isfinite(charge[i]) || !std::isfinite(polarizability[i]))
-			return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: epsilon < 0 or non-finite atom parameter");
-	if (!c->h_mass.empty() && !mass) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_insert_begin: the atom list has masses, the molecule needs them too");
-	int32_t id = c->h_mol[0]; // the largest molecule id in use: known from the host sums of the accepted list, else found now
+			return fail(c, MPMC_ERR_INVALID_DATUM, w + ": epsilon < 0 or non-finite atom parameter");
+	if (!c->h_mass.empty() && !mass) return fail(c, MPMC_ERR_INVALID_DATUM, w + ": the atom list has masses, the molecule needs them too");
+	return MPMC_OK;
+}
+// the largest molecule id in use: known from the host sums of the accepted list, else found now
+static int32_t xch_largest_mol_id(const mpmc_ctx *c) {
+	int32_t id = c->h_mol[0];
 	if (c->xs_gen == c->static_gen) id = c->xs_acc.mol_max;
 	else
 		for (int i = 1; i < c->n; i++) id = std::max(id, c->h_mol[i]);
-	if (id == INT32_MAX) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: no molecule id left");
-	AtomRun &m = c->xch_mol;
+	return id;
+}
+// one new molecule with the id `id`, which no resident atom has (pos: the first pose)
+static void xch_fill_molecule(const mpmc_ctx *c, AtomRun &m, int32_t id, int count, const double *pos, const double *charge, const double *polarizability,
+                              const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
 	m.pos.assign(pos, pos + 3 * (size_t)count);
 	m.q.assign(charge, charge + count);
 	m.alpha.assign(polarizability, polarizability + count);
@@ -103,7 +106,21 @@ extern "C" int mpmc_trial_insert_begin(mpmc_ctx *c, int at_index, int count, con
 	else m.disp.assign(count, 0);
 	if (!c->h_mass.empty()) m.mass.assign(mass, mass + count); // (a list without masses takes none)
 	else m.mass.clear();
-	m.mol.assign(count, id + 1); // one new molecule, with an id no resident atom has
+	m.mol.assign(count, id);
+}
+
+extern "C" int mpmc_trial_insert_begin(mpmc_ctx *c, int at_index, int count, const double *pos, const double *charge, const double *polarizability,
+                                       const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
+	if (!c || count <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !frozen) return MPMC_ERR_ARG;
+	int rc = xch_begin_checks(c, "mpmc_trial_insert_begin");
+	if (rc != MPMC_OK) return rc;
+	if (at_index < 0 || at_index > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index outside the atom list");
+	if (at_index > 0 && at_index < c->n && c->h_mol[at_index - 1] == c->h_mol[at_index])
+		return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: at_index lies inside a molecule (it must be a molecule boundary)");
+	if ((rc = xch_molecule_checks(c, "mpmc_trial_insert_begin", count, 1, pos, charge, polarizability, epsilon, sigma, mass)) != MPMC_OK) return rc;
+	const int32_t id = xch_largest_mol_id(c);
+	if (id == INT32_MAX) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: no molecule id left");
+	xch_fill_molecule(c, c->xch_mol, id + 1, count, pos, charge, polarizability, epsilon, sigma, frozen, has_disp, mass);
 	xch_open(c, +1, at_index, count);
 	return MPMC_OK;
 }
@@ -161,6 +178,36 @@ static int xch_replace_list(mpmc_ctx *c, const AtomRun &list, AtomRun &&saved) {
 	return rc;
 }
 
+// What an exchange trial takes from the molecule's species and the accepted list alone, whatever the pose: the host sums of the trial
+// composition (xs_trial) with its position-independent terms st = { lrc_pair, lrc_self, es_self } and its count N of movable molecules, and
+// the staged records (rec[m]; the positions are mol.pos's).  The sums of the accepted list are made first where they are stale.
+static void xch_species_terms(mpmc_ctx *c, int kind, const AtomRun &mol, XchSums &xs_trial, double st[3], double &N, XchAtom *rec) {
+	const int m = mol.size();
+	const double sg = kind > 0 ? 1.0 : -1.0;
+	// the position-independent terms of the trial composition, from the sums of the accepted list
+	if (c->xs_gen != c->static_gen || c->xs_edits >= kXchResum) {
+		xch_sum_list(c, c->xs_acc);
+		c->xs_gen = c->static_gen;
+		c->xs_edits = 0;
+		c->kept.n_xch_resums++;
+	}
+	xs_trial = c->xs_acc;
+	double molmass = 0.0;
+	for (double v : mol.mass) molmass += v;
+	for (int k = 0; k < m; k++) {
+		const int fl = atom_flag_word(c, mol.frozen[k], mol.eps[k], mol.sigma[k], mol.disp[k], mol.q[k], mol.alpha[k]);
+		xch_sum_atom(c, xs_trial, sg, fl, mol.sigma[k], mol.eps[k], mol.q[k]);
+		XchAtom &g = rec[k];
+		g.xyzq = make_double4(mol.pos[3 * k], mol.pos[3 * k + 1], mol.pos[3 * k + 2], mol.q[k]);
+		g.lj = make_double2(std::fabs(mol.sigma[k]), std::sqrt(mol.eps[k]));
+		g.mf = make_int2(mol.mol[k], fl);
+		g.inv_molmass = (molmass > 0.0) ? 1.0 / molmass : 0.0;
+	}
+	if (kind > 0) xs_trial.mol_max = std::max(xs_trial.mol_max, mol.mol[0]);
+	xch_static_terms(c, xs_trial, st);
+	N = c->N_movable + (mol.frozen[m - 1] ? 0.0 : sg); // (a molecule's flag is its last atom's, mpmc_set_atoms)
+}
+
 static int xch_energy_async(mpmc_ctx *c) {
 	const mpmc_options &o = c->opts;
 	const bool polar = o.polarization && !o.rd_only;
@@ -191,30 +238,8 @@ static int xch_energy_async(mpmc_ctx *c) {
 	// (one more pair of partials than tiles: the molecule's own block; a one-tile table is shorter than that)
 	if ((rc = c->d_block_part.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
 	if ((rc = c->d_block_cnt.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
-	const AtomRun &mol = c->xch_mol;
 	const double sg = kind > 0 ? 1.0 : -1.0;
-	// the position-independent terms of the trial composition, from the sums of the accepted list
-	if (c->xs_gen != c->static_gen || c->xs_edits >= kXchResum) {
-		xch_sum_list(c, c->xs_acc);
-		c->xs_gen = c->static_gen;
-		c->xs_edits = 0;
-		c->kept.n_xch_resums++;
-	}
-	c->xs_trial = c->xs_acc;
-	double molmass = 0.0;
-	for (double v : mol.mass) molmass += v;
-	for (int k = 0; k < m; k++) {
-		const int fl = atom_flag_word(c, mol.frozen[k], mol.eps[k], mol.sigma[k], mol.disp[k], mol.q[k], mol.alpha[k]);
-		xch_sum_atom(c, c->xs_trial, sg, fl, mol.sigma[k], mol.eps[k], mol.q[k]);
-		XchAtom &g = c->h_xch_mol[k];
-		g.xyzq = make_double4(mol.pos[3 * k], mol.pos[3 * k + 1], mol.pos[3 * k + 2], mol.q[k]);
-		g.lj = make_double2(std::fabs(mol.sigma[k]), std::sqrt(mol.eps[k]));
-		g.mf = make_int2(mol.mol[k], fl);
-		g.inv_molmass = (molmass > 0.0) ? 1.0 / molmass : 0.0;
-	}
-	if (kind > 0) c->xs_trial.mol_max = std::max(c->xs_trial.mol_max, mol.mol[0]);
-	xch_static_terms(c, c->xs_trial, c->xch_static);
-	c->xch_N = c->N_movable + (mol.frozen[m - 1] ? 0.0 : sg); // (a molecule's flag is its last atom's, mpmc_set_atoms)
+	xch_species_terms(c, kind, c->xch_mol, c->xs_trial, c->xch_static, c->xch_N, c->h_xch_mol);
 	hipStream_t st = c->stream;
 	HIP_TRY(c, hipMemcpyAsync(c->d_xch_mol, c->h_xch_mol, (size_t)m * sizeof(XchAtom), hipMemcpyHostToDevice, st));
 	const int do_es = o.rd_only ? 0 : 1;
@@ -234,35 +259,11 @@ static int xch_energy_async(mpmc_ctx *c) {
 	return MPMC_OK;
 }
 
-// the result of an exchange trial of the delta path: the accepted totals, the signed changes the device posted, the position-independent
-// terms and counts of the trial composition
-static void xch_result(mpmc_ctx *c, mpmc_result &r) {
-	const mpmc_options &o = c->opts;
-	const int do_es = o.rd_only ? 0 : 1, m = c->trial_count;
-	const mpmc_result &a = c->last_full;
-	const double *dh = c->h_delta_out.p;
-	const AtomRun &mol = c->xch_mol;
-	r = a;
-	r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_LJ)];
-	r.lrc_pair = o.rd_lrc ? c->xch_static[0] : 0.0;
-	r.lrc_self = o.rd_lrc ? c->xch_static[1] : 0.0;
-	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
-	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
-	if (do_es) {
-		r.es_real = a.es_real + (dh[delta_host_index(D_ES_REAL)] - dh[delta_host_index(D_ES_INTRA)]);
-		r.es_recip = dh[delta_host_index(D_ES_RECIP)];
-		r.es_self = o.wolf ? 0.0 : c->xch_static[2];
-		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
-		r.n_es_in_cutoff = a.n_es_in_cutoff + c->h_delta_cnt[1];
-	}
-	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
-	r.N = c->xch_N;
-	r.NU = r.N * r.energy;
-	const int64_t n_new = (int64_t)c->n + (c->xch_kind > 0 ? m : -m);
-	r.n_pairs = n_new * (n_new - 1) / 2;
-	// the position-independent pair counts (k_static_counts): the molecule's atoms against the classes of everybody else, and among themselves
-	const long long *others = (c->xch_kind > 0) ? c->xs_acc.cls : c->xs_trial.cls;
-	long long d[4] = {0, 0, 0, 0};
+// the position-independent pair counts an exchange changes (k_static_counts): the molecule's atoms against the classes of everybody else
+// (`others`: the histogram of the list WITHOUT the molecule), and among themselves; d = { intra, rd_excluded, es_excluded, frozen }
+static void xch_pair_counts(const mpmc_ctx *c, const AtomRun &mol, const long long *others, long long d[4]) {
+	const int m = mol.size();
+	d[0] = d[1] = d[2] = d[3] = 0;
 	std::vector<int> fl((size_t)m);
 	for (int k = 0; k < m; k++) fl[k] = atom_flag_word(c, mol.frozen[k], mol.eps[k], mol.sigma[k], mol.disp[k], mol.q[k], mol.alpha[k]);
 	for (int cl = 0; cl < kXchClasses; cl++) {
@@ -280,11 +281,53 @@ static void xch_result(mpmc_ctx *c, mpmc_result &r) {
 			const PairFlags f = pair_flags(0, fl[k], 0, fl[l]);
 			d[0] += f.intra, d[1] += f.rd_excluded, d[2] += f.es_excluded, d[3] += f.frozen;
 		}
-	const long long sgn = c->xch_kind > 0 ? 1 : -1;
+}
+
+// the result of an exchange of `m` atoms (kind +1 | -1) on the delta path: the accepted totals, the signed changes the device left (p), the
+// position-independent terms st and count N of the trial composition, and the changes d of the position-independent pair counts.  The
+// single trial (xch_result) and the batched insertion candidates (mpmc_insert_candidates) both end here.
+static void xch_compose(const mpmc_ctx *c, int kind, int m, const InsCandOut &p, const double st[3], double N, const long long d[4], mpmc_result &r) {
+	const mpmc_options &o = c->opts;
+	const int do_es = o.rd_only ? 0 : 1;
+	const mpmc_result &a = c->last_full;
+	r = a;
+	r.lj_pairs = a.lj_pairs + p.lj;
+	r.lrc_pair = o.rd_lrc ? st[0] : 0.0;
+	r.lrc_self = o.rd_lrc ? st[1] : 0.0;
+	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
+	r.n_lj_in_cutoff = a.n_lj_in_cutoff + p.n_lj;
+	if (do_es) {
+		r.es_real = a.es_real + (p.es_real - p.es_intra);
+		r.es_recip = p.es_recip;
+		r.es_self = o.wolf ? 0.0 : st[2];
+		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
+		r.n_es_in_cutoff = a.n_es_in_cutoff + p.n_es;
+	}
+	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
+	r.N = N;
+	r.NU = r.N * r.energy;
+	const int64_t n_new = (int64_t)c->n + (kind > 0 ? m : -m);
+	r.n_pairs = n_new * (n_new - 1) / 2;
+	const long long sgn = kind > 0 ? 1 : -1;
 	r.n_intra = a.n_intra + sgn * d[0];
 	r.n_rd_excluded = a.n_rd_excluded + sgn * d[1];
 	r.n_es_excluded = a.n_es_excluded + sgn * d[2];
 	r.n_frozen = a.n_frozen + sgn * d[3];
+}
+
+// the result of the open exchange trial of the delta path, from the block k_delta_finish posted
+static void xch_result(mpmc_ctx *c, mpmc_result &r) {
+	const double *dh = c->h_delta_out.p;
+	InsCandOut p;
+	p.lj = dh[delta_host_index(D_LJ)];
+	p.es_real = dh[delta_host_index(D_ES_REAL)];
+	p.es_intra = dh[delta_host_index(D_ES_INTRA)];
+	p.es_recip = dh[delta_host_index(D_ES_RECIP)];
+	p.n_lj = c->h_delta_cnt[0];
+	p.n_es = c->h_delta_cnt[1];
+	long long d[4];
+	xch_pair_counts(c, c->xch_mol, (c->xch_kind > 0) ? c->xs_acc.cls : c->xs_trial.cls, d);
+	xch_compose(c, c->xch_kind, c->trial_count, p, c->xch_static, c->xch_N, d, r);
 }
 
 // accept of the delta path: the list is edited in place; a context that has to grow is rebuilt around the new list and re-based
@@ -693,4 +736,103 @@ extern "C" int mpmc_trial_reject(mpmc_ctx *c) {
 		}
 	}
 	return MPMC_OK;
+}
+
+// ---- batched insertion candidates: n_cand poses of one molecule against the accepted configuration, one launch chain, one wait -------------
+// out[c] is what mpmc_trial_insert_begin(pose c) + mpmc_trial_energy + mpmc_trial_reject would give, bit for bit: the device runs the block
+// roles of k_exchange_all and the reduction of k_delta_finish per candidate (kernels_insert_batch.hip), the host ends in xch_compose like
+// xch_result.  No trial is opened and nothing an evaluation, a trial or a cavity update reads is written: the accepted totals, the
+// structure factors, the atom list.  (The host sums of the ACCEPTED list, xs_acc, are made where they are stale, as a trial makes them.)
+constexpr size_t kInsStageRecords = (size_t)1 << 17; // staged records per pass (8 MiB pinned, as much on the device)
+
+extern "C" int mpmc_insert_candidates(mpmc_ctx *c, int count, int n_cand, const double *pos, const double *charge, const double *polarizability,
+                                      const double *epsilon, const double *sigma, const int32_t *frozen, const int32_t *has_disp, const double *mass,
+                                      mpmc_result *out) {
+	if (!c) return MPMC_ERR_ARG;
+	if (count < 1 || n_cand < 1 || n_cand > MPMC_INSERT_MAX_CANDIDATES || !pos || !out || !charge || !polarizability || !epsilon || !sigma || !frozen)
+		return fail(c, MPMC_ERR_ARG, "mpmc_insert_candidates: count < 1, n_cand outside [1, MPMC_INSERT_MAX_CANDIDATES] or a null array");
+	int rc = xch_begin_checks(c, "mpmc_insert_candidates");
+	if (rc != MPMC_OK) return rc;
+	const mpmc_options &o = c->opts;
+	// only the delta path exists here: a batch of full evaluations is the loop of single trials the caller can already write
+	if (o.polarization && !o.rd_only) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: a polarizable box has no insertion delta (use single trials)");
+	if (crystal_on(c)) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: rd_crystal has no insertion delta (use single trials)");
+	if (rd_model_on(c)) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: a non-default rd model has no insertion delta (use single trials)");
+	if (count > MPMC_TRIAL_MAX_ATOMS) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: count > MPMC_TRIAL_MAX_ATOMS (use single trials)");
+	if ((rc = xch_molecule_checks(c, "mpmc_insert_candidates", count, n_cand, pos, charge, polarizability, epsilon, sigma, mass)) != MPMC_OK) return rc;
+	const int32_t id = xch_largest_mol_id(c);
+	if (id == INT32_MAX) return fail(c, MPMC_ERR_ARG, "mpmc_insert_candidates: no molecule id left");
+	const int m = count;
+	AtomRun mol;
+	xch_fill_molecule(c, mol, id + 1, m, pos, charge, polarizability, epsilon, sigma, frozen, has_disp, mass);
+
+	drop_pending_dipoles(c);
+	if ((rc = prepare(c)) != MPMC_OK) return rc; // (the pending upload behind an accepted exchange, as a trial makes it)
+	// candidates per pass of the staging block: whole launch chains where more than one fits
+	size_t pass = std::max<size_t>(1, kInsStageRecords / (size_t)m);
+	if (pass > (size_t)kInsBatchChunk) pass -= pass % kInsBatchChunk;
+	pass = std::min(pass, (size_t)n_cand);
+	const size_t chunk = std::min((size_t)kInsBatchChunk, (size_t)n_cand), nb = (size_t)c->n_tiles + 1;
+	const int do_es = o.rd_only ? 0 : 1;
+	const bool do_ewald = do_es && !o.wolf;
+	if ((rc = c->h_ins_mol.reserve(c, pass * m)) != MPMC_OK) return rc;
+	if ((rc = c->d_ins_mol.reserve(c, pass * m)) != MPMC_OK) return rc;
+	if ((rc = c->d_ins_sf.reserve(c, do_ewald ? chunk * (size_t)c->K : 1)) != MPMC_OK) return rc;
+	if ((rc = c->d_ins_part.reserve(c, chunk * nb * 2)) != MPMC_OK) return rc;
+	if ((rc = c->d_ins_cnt.reserve(c, chunk * nb * 2)) != MPMC_OK) return rc;
+	if ((rc = c->d_ins_out.reserve(c, (size_t)n_cand)) != MPMC_OK) return rc;
+	if ((rc = c->h_ins_out.reserve(c, (size_t)n_cand)) != MPMC_OK) return rc;
+
+	// the species part, once: the same for every pose
+	XchSums xs_trial;
+	double st3[3], N;
+	std::vector<XchAtom> rec((size_t)m);
+	xch_species_terms(c, +1, mol, xs_trial, st3, N, rec.data());
+	long long d[4];
+	xch_pair_counts(c, mol, c->xs_acc.cls, d);
+
+	FusedParams fp{};
+	fp.ewald_alpha = c->ewald_alpha;
+	ext_params(c, fp, o.wolf && do_es);
+	const AtomsDev at = atoms_view(c);
+	const RecipDev rv = recip_view(c);
+	hipStream_t st = c->stream;
+	for (size_t p0 = 0; p0 < (size_t)n_cand; p0 += pass) {
+		const size_t p1 = std::min(p0 + pass, (size_t)n_cand);
+		if (p0 > 0) { // the staging block is written again: the copies out of it must have been made (long molecules times many candidates only)
+			c->kept.n_stream_syncs++;
+			HIP_TRY(c, hipStreamSynchronize(st));
+		}
+		for (size_t q = p0; q < p1; q++) {
+			const double *x = pos + 3 * (size_t)m * q;
+			XchAtom *g = c->h_ins_mol + (q - p0) * m;
+			for (int k = 0; k < m; k++) {
+				g[k] = rec[k];
+				g[k].xyzq.x = x[3 * k], g[k].xyzq.y = x[3 * k + 1], g[k].xyzq.z = x[3 * k + 2];
+			}
+		}
+		HIP_TRY(c, hipMemcpyAsync(c->d_ins_mol, c->h_ins_mol, (p1 - p0) * m * sizeof(XchAtom), hipMemcpyHostToDevice, st));
+		ProfScope ps(c, MPMC_K_PAIR);
+		for (size_t q0 = p0; q0 < p1; q0 += kInsBatchChunk) {
+			const int nc = (int)std::min((size_t)kInsBatchChunk, p1 - q0);
+			launch_insert_batch(st, at, c->box, rv, fp, do_es, c->d_ins_mol + (q0 - p0) * m, m, nc, c->d_ins_sf, c->d_ins_part, c->d_ins_cnt, c->d_ins_out + q0);
+		}
+	}
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipMemcpyAsync(c->h_ins_out, c->d_ins_out, (size_t)n_cand * sizeof(InsCandOut), hipMemcpyDeviceToHost, st));
+	c->kept.n_stream_syncs++;
+	HIP_TRY(c, hipStreamSynchronize(st)); // the one wait of the call
+	prof_harvest(c);
+	for (int q = 0; q < n_cand; q++) xch_compose(c, +1, m, c->h_ins_out[q], st3, N, d, out[q]);
+	c->kept.n_ins_calls++;
+	c->kept.n_ins_cands += n_cand;
+	return MPMC_OK;
+}
+
+// diagnostics only: calls of mpmc_insert_candidates that ran, and the candidates they evaluated
+extern "C" int mpmc_debug_insert_batch_counts(mpmc_ctx *c, long long *out2) {
+	if (!c || !out2) return -1;
+	out2[0] = c->kept.n_ins_calls;
+	out2[1] = c->kept.n_ins_cands;
+	return 0;
 }

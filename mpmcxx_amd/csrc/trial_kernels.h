@@ -1,7 +1,8 @@
 // trial_kernels.h -- the scaffold the trial-move ("delta") terms share: one pair's energy terms (pair_terms: kernels_delta.hip and
 // kernels_exchange.hip), the moved-atom map, the real-space delta-field kernel with its
 // finish, the launch sequence around them, and the fixed-order sum of per-workgroup partials.  Included after kernels.h by the HIP
-// translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, and through pair_term_walk.h
+// translation units that launch them (kernels_delta.hip, kernels_wolf_field.hip, kernels_three_body.hip, through exchange_kernels.h
+// kernels_exchange.hip and kernels_insert_batch.hip, and through pair_term_walk.h
 // kernels_disp.hip, kernels_crystal.hip and kernels_rd_model.hip); the kernels are static, one copy per code object.  A new trial-move
 // field term brings its pair arithmetic and calls these; a new pair-sum energy term brings a Term for the two walks of pair_term_walk.h.
 #pragma once
@@ -45,6 +46,32 @@ __device__ __forceinline__ void pair_terms(const Box &bx, const FusedParams &fp,
 		n_es += (sg > 0) ? 1 : -1;
 		if (EXT && fp.fh_order) e_re = fma(sg, fh_es_corr(fp.fh_order, fp.fh_c2, fp.fh_c4, imu, fp.ewald_alpha, ec, g, ri2, r, ir), e_re);
 	}
+}
+
+// the reduction that ends a trial, one block of 256 threads: the nb block partials { lj, es_real } and their counts, and (do_es) the sum
+// over k of w_k |S_k|^2 of the trial structure factors (the caller scales it by 4 pi / V).  k_delta_finish (kernels_delta.hip) and the
+// per-candidate finish of kernels_insert_batch.hip both end here, so both add in the same order.  sh: 4 doubles, shc: 256 int64 of LDS.
+__device__ __forceinline__ void delta_finish_sums(const double *__restrict__ block_part, const int *__restrict__ block_cnt, int nb, const RecipDev &rc,
+                                                  const double4 *__restrict__ sf_trial, int do_es, double *sh, long long *shc, double &s0, double &s1, double &e,
+                                                  long long &c0, long long &c1) {
+	s0 = 0, s1 = 0, e = 0;
+	c0 = 0, c1 = 0;
+	for (int b = threadIdx.x; b < nb; b += 256) {
+		s0 += block_part[2 * (size_t)b];
+		s1 += block_part[2 * (size_t)b + 1];
+		c0 += block_cnt[2 * (size_t)b];
+		c1 += block_cnt[2 * (size_t)b + 1];
+	}
+	if (do_es)
+		for (int k = threadIdx.x; k < rc.K; k += 256) {
+			const double4 sf = sf_trial[k];
+			e += rc.w_en[k] * (sf.x * sf.x + sf.y * sf.y);
+		}
+	s0 = block_sum_256(s0, sh);
+	s1 = block_sum_256(s1, sh);
+	e = block_sum_256(e, sh);
+	c0 = block_count_256(c0, shc);
+	c1 = block_count_256(c1, shc);
 }
 
 // moved_idx[slot] = index of the slot in the move list (set) or -1 as for every other slot (clear)

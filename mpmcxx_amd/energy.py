@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -250,6 +250,9 @@ def lib():
     if hasattr(L, "mpmc_trial_insert_begin") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no exchange trials)
         L.mpmc_trial_insert_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip, dp]
         L.mpmc_trial_remove_begin.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "mpmc_insert_candidates") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no candidate batches)
+        L.mpmc_insert_candidates.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip, dp, C.POINTER(Result)]
+        L.mpmc_debug_insert_batch_counts.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "mpmc_set_cavity_grid") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no cavity grid)
         L.mpmc_set_cavity_grid.argtypes = [vp, C.c_int, C.c_double]
         L.mpmc_cavity_update.argtypes = [vp, C.c_int, dp, C.POINTER(CavityResult)]
@@ -718,6 +721,31 @@ class System:
         mol["mol_id"] = np.full(m, int(np.max(own["mol_id"])) + 1, dtype=own["mol_id"].dtype)
         self._exchange, self._move = (int(at_index), 0, mol), None
         return self._trial()
+
+    def insert_candidates(self, mol_atoms: Dict[str, np.ndarray], positions: np.ndarray) -> List[Dict[str, float]]:
+        """the observables of `n_cand` trial insertions of ONE molecule, evaluated in one launch chain behind one wait: `mol_atoms` as for
+        trial_insert_energy (its "pos" is not read), `positions` an (n_cand, m, 3) array of poses.  Entry c is what trial_insert_energy at pose
+        c followed by reject() leaves in trial_observables, bit for bit.  Opens no trial and changes nothing of the accepted configuration."""
+        f = lambda k: np.ascontiguousarray(mol_atoms[k], dtype=np.float64)
+        g = lambda k: np.ascontiguousarray(mol_atoms[k], dtype=np.int32)
+        m = int(np.asarray(mol_atoms["charge"]).size)
+        pos = np.ascontiguousarray(positions, dtype=np.float64)
+        if pos.ndim != 3 or pos.shape[1:] != (m, 3):
+            raise ValueError(f"insert_candidates: positions must be (n_cand, {m}, 3), got {pos.shape}")
+        n_cand = int(pos.shape[0])
+        disp = g("has_disp") if "has_disp" in mol_atoms else None
+        mass = f("mass") if "mass" in mol_atoms else None
+        out = (Result * max(n_cand, 1))()
+        self._check(self._L.mpmc_insert_candidates(self._h, m, n_cand, _dp(pos.reshape(-1)), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
+                                                   _dp(f("sigma")), _ip(g("frozen")), _ip(disp), _dp(mass), out))
+        return [out[c].as_dict() for c in range(n_cand)]
+
+    def insert_batch_counts(self):
+        """(calls of insert_candidates that ran, candidates they evaluated) since the context was created (mpmc_debug_insert_batch_counts)"""
+        v = (C.c_longlong * 2)()
+        if self._L.mpmc_debug_insert_batch_counts(self._h, v) != 0:
+            raise MpmcError(-1, "mpmc_debug_insert_batch_counts: no context")
+        return int(v[0]), int(v[1])
 
     def trial_remove_energy(self, first: int, count: int) -> float:
         """energy of the composition without the molecule that occupies atoms [first, first + count); follow with accept() or reject()."""
