@@ -340,7 +340,7 @@ int mpmc_disp_expansion(mpmc_ctx *ctx, double *out); /* System::disp_expansion()
  * 1688-1692).  Cost O(N^2 (2o-1)^3) per evaluation, O(m N (2o-1)^3) per trial move of m <= MPMC_TRIAL_MAX_ATOMS atoms; time is counted in
  * MPMC_K_PAIR.  System::disp_expansion ignores rd_crystal: a context with mpmc_set_disp_expansion on returns the disp-expansion result
  * unchanged, bit for bit, whatever this setting is.  MPMC_FLAG_RD_CRYSTAL in unsupported_flags is still refused: this call alone
- * switches the term on.  cavity_autoreject stays refused. */
+ * switches the term on.  The sigma rule of mpmc_set_cavity_autoreject is refused together with this term (MPMC_ERR_UNSUPPORTED). */
 #define MPMC_RD_CRYSTAL_MAX_ORDER 8 /* (2 * 8 - 1)^3 = 3375 images */
 /* (a struct tag, not a typedef: the entry point below carries the same name) */
 struct mpmc_rd_crystal_info {
@@ -377,7 +377,7 @@ int mpmc_rd_crystal_info(mpmc_ctx *ctx, struct mpmc_rd_crystal_info *out);
  * the reference's Waldman-Hagler branch leaves eps_ij unassigned for such atoms, its Halgren branch zeroes it and its C6 branch averages
  * signed values; no force field uses any of these.  Refused at the evaluation, with a message: MPMC_ERR_INCOMPATIBLE together with
  * mpmc_set_disp_expansion (the reference never reaches the disp-expansion mixing behind these rules); MPMC_ERR_UNSUPPORTED for the LJ form
- * with a non-LB rule together with mpmc_set_rd_crystal.  cavity_autoreject stays refused.
+ * with a non-LB rule together with mpmc_set_rd_crystal.  The sigma rule of mpmc_set_cavity_autoreject tests the model's sigma_ij.
  * The setting has the lifetime of mpmc_set_polar_wolf's: it survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates,
  * accepted trials and capacity growth; it is refused while an evaluation or a trial move is open.  An unknown form or rule is refused
  * with MPMC_ERR_INVALID_SETTING.  MPMC_FLAG_NON_LB_MIXING and MPMC_FLAG_OTHER_RD in unsupported_flags are still refused: this call alone
@@ -399,6 +399,73 @@ struct mpmc_rd_model_info {
 };
 int mpmc_set_rd_model(mpmc_ctx *ctx, int form, int mixing);
 int mpmc_rd_model_info(mpmc_ctx *ctx, struct mpmc_rd_model_info *out);
+
+/* ---- `cavity_autoreject`, `cavity_autoreject_absolute`, `cavity_autoreject_scale`: contact rejection of uVT moves ---------------------------
+ * (System::lj src/System.Energy.cpp:1001-1004, lj_buffered_14_7 :1237-1239, dreiding :2182-2185; System::cavity_absolute_check
+ * src/System.Cavity.cpp:211-228, called at :167; validation SimulationControl.cpp:2139-2154)
+ *   MPMC_AUTOREJECT_SIGMA     a pair the rd function admits (neither rd_excluded nor frozen, inside the form's own distance test: rimg - 1e-12 <
+ *                             cutoff for LJ, !(rimg > cutoff) for 14-7 and DREIDING) with rimg < scale * sigma_ij gets MAXVALUE = 1e40 as its
+ *                             rd_energy.  sigma_ij is the mixed sigma of the context's rd model (|sigma_ij| for the LJ form).  With n_replaced
+ *                             such pairs:  lj_pairs = S + n_replaced * 1e40, computed on the host in this order, S the sum the pair kernels
+ *                             deliver, untouched; rd_energy, energy and NU follow; mpmc_lj returns this rd_energy.  A replaced pair's own
+ *                             energy stays in S, where the reference replaces it: that differs from the reference by less than 1e-9 relative
+ *                             unless rimg < sigma_ij / 300 (4 eps (sigma / r)^12 reaches 1e31 there).  Overlapping atoms (rimg = 0) give a
+ *                             non-finite S as they do without the rule; every driver rejects a non-finite energy.  n_lj_in_cutoff and the
+ *                             other counts are unchanged; electrostatics and polarization are untouched to the bit.
+ *   MPMC_AUTOREJECT_ABSOLUTE  every measured pair of atoms of different molecules -- excluded, null, beyond the cutoff -- with rimg < scale
+ *                             (Angstrom) is an absolute contact.  System::pairs measures a pair `if (!frozen || polarization)` (System.cpp:985):
+ *                             with mpmc_options.polarization off a pair of two frozen atoms of different molecules keeps rimg = 0 and trips the
+ *                             test in every call (n_unmeasured_frozen, counted on the host from the atom list; 0 with polarization on).  On a
+ *                             hit energy() RETURNS its value plus MAXVALUE; observables->energy, rd_energy and NU stay unpenalised, and so does
+ *                             mpmc_result, which mirrors the observables: the penalty is absolute_penalty / returned_energy of the info struct.
+ *                             PI_calculate_potential reads the observables, so the path-integral entry points carry no absolute penalty.
+ * rules = 0 switches both off: no kernel of this feature is launched, and every result has the bits and the launch counts of a context
+ * that never made the call.  rules != 0 with scale outside (0, 1] or non-finite, or unknown rule bits: MPMC_ERR_INVALID_SETTING.  repulsion
+ * (`cavity_autoreject_repulsion`) is read under mpmc_set_disp_expansion alone, as in the reference (below).  The setting has the lifetime
+ * and the refusal rules of
+ * mpmc_set_rd_model: it survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates, accepted trials and capacity growth, and
+ * is refused while an evaluation or a trial move is open.  MPMC_FLAG_CAVITY_AUTOREJECT in unsupported_flags is still refused: this call alone
+ * switches the behaviour on.
+ *   The counts come from one more pair walk behind the evaluation's kernels (MPMC_K_PAIR), both rules in one walk, posted with the result:
+ * no path gains a host wait.  In orthorhombic cells only the tile pairs whose bounding boxes come closer than dmax = scale * max sigma_ij
+ * (sigma rule) or scale (absolute rule) are walked (tile_pairs_walked / tile_pairs_skipped); the debug key contact_skip = 0 walks all.
+ *   Trial moves: a displacement of up to MPMC_TRIAL_MAX_ATOMS atoms on the delta path adds the (new - old) counts of the moved atoms' pairs
+ * to the accepted counts, O(m N); accept commits the trial counts, reject drops them.  Every branch that evaluates the trial configuration
+ * in full runs the full walk.  An insertion on the delta path adds the molecule's contacts with the residents, a removal subtracts them
+ * (a sibling launch of the exchange kernel, molecule against resident tile, in front of the finish that posts), and the unmeasured frozen
+ * pairs of the trial composition follow from the host's counts: exchange trials stay O(m N) under the setting.
+ *   mpmc_insert_candidates: out[c] is what the single insertion trial delivers, bit for bit (the sigma rule's penalty included), and
+ * mpmc_insert_candidates_contacts returns the last batch's counts per candidate -- n_replaced and n_absolute of candidate c's trial
+ * composition, the values mpmc_cavity_autoreject_info gives behind that single trial (zeros for a rule that is off or a batch made with
+ * the setting off).  Either array may be NULL.  MPMC_ERR_ARG when no batch has run on this context or n_cand differs from the last
+ * batch's.  The counts travel behind the batch's one wait.  n_unmeasured_frozen of a candidate's composition does not depend on the pose:
+ * it is the single trial's.
+ *   Under mpmc_set_disp_expansion the sigma rule is System::disp_expansion's (:1958, 1983-1989): every pair that is neither rd_excluded nor
+ * frozen, with no cutoff, sigma_ij = r0_ij as mixed; and with repulsion != 0 a pair is replaced as well when its repulsion
+ * 315.775 exp(-alpha_ij (rimg - r0_ij)) > repulsion (the exponential is the device's: a pair within an ulp of the threshold may fall on the
+ * other side than in the reference).  The repulsion test has no distance bound here: every tile pair is walked.  mpmc_disp_expansion returns
+ * the penalised rd_energy.
+ *   Refused at the evaluation with MPMC_ERR_UNSUPPORTED and a text: the sigma rule together with mpmc_set_rd_crystal (the reference tests
+ * intramolecular pairs there, which rejects every multi-site molecule: no input means that).
+ * mpmc_cavity_autoreject_info: of the last result delivered (evaluation, component call or trial). */
+#define MPMC_AUTOREJECT_SIGMA 1
+#define MPMC_AUTOREJECT_ABSOLUTE 2
+/* (a struct tag, not a typedef: the entry point below carries the same name) */
+struct mpmc_cavity_autoreject_info {
+	int32_t rules;                /* MPMC_AUTOREJECT_* of the context                                                            */
+	int32_t reserved;
+	double scale, repulsion;      /* cavity_autoreject_scale, cavity_autoreject_repulsion                                        */
+	int64_t n_replaced;           /* pairs whose rd_energy is MAXVALUE (sigma rule)                                              */
+	int64_t n_absolute;           /* measured pairs of different molecules with rimg < scale (absolute rule)                     */
+	int64_t n_unmeasured_frozen;  /* frozen-frozen pairs of different molecules, unmeasured (absolute rule, polarization off)    */
+	double absolute_penalty;      /* MAXVALUE if n_absolute + n_unmeasured_frozen > 0, else 0                                     */
+	double returned_energy;       /* result.energy + absolute_penalty: what System::energy() returns                             */
+	int64_t tile_pairs_walked;    /* of the last full contact walk: tile pairs walked ...                                        */
+	int64_t tile_pairs_skipped;   /* ... and tile pairs whose bounding boxes lie further apart than dmax                         */
+};
+int mpmc_set_cavity_autoreject(mpmc_ctx *ctx, int rules /* OR of MPMC_AUTOREJECT_*, 0 = off */, double scale, double repulsion);
+int mpmc_cavity_autoreject_info(mpmc_ctx *ctx, struct mpmc_cavity_autoreject_info *out);
+int mpmc_insert_candidates_contacts(mpmc_ctx *ctx, int n_cand, int64_t *n_replaced /*[n_cand]*/, int64_t *n_absolute /*[n_cand]*/);
 
 /* ---- public component entry points of the reference (src/System.h:346-402), for parity tests ----------- */
 int mpmc_lj(mpmc_ctx *ctx, double *out);                  /* System::lj() (rd_crystal: its lattice sum; a non-default rd model: its rd_energy) */
@@ -704,7 +771,7 @@ int mpmc_gibbs_boltzmann_factor(const mpmc_gibbs_move *move, double boltzmann_fa
  * operand order, the biased form when biased_move != 0, with ATM2REDUCED = 0.0073389366; fugacity is the value the reference would pick
  * (pressure, fugacities[0] or fugacities[sorbateInsert]), N = observables->N as the reference reads it there, avg_cavity_probability the
  * driver's running average.  Any other move type: MPMC_ERR_UNSUPPORTED.
- * Not part of the library: a uVT driver, the fugacity equations of state, cavity_autoreject (still refused). */
+ * Not part of the library: a uVT driver and the fugacity equations of state.  (cavity_autoreject: mpmc_set_cavity_autoreject.) */
 #define MPMC_CAVITY_MAX_GRID 128 /* 128^3 = 2 M sphere centres */
 int mpmc_set_cavity_grid(mpmc_ctx *ctx, int grid_size, double radius);
 typedef struct mpmc_cavity_result {

@@ -131,7 +131,8 @@ inline GibbsSettings read_gibbs_settings(const std::string &path) {
 			if (lower(t[1]) != "nvt_gibbs") throw 4004; // unsupported_setting: this driver is the nvt_gibbs ensemble
 		} else if (k == "pqr_input") c.pqr_input = t[1];
 		else if (k == "pqr_input_b") c.pqr_input_B = t[1];
-		else if (k == "spinflip_probability" || k == "simulated_annealing" || k == "parallel_tempering" || k == "cavity_bias") {
+		else if (k == "spinflip_probability" || k == "simulated_annealing" || k == "parallel_tempering" || k == "cavity_bias" ||
+		         k == "cavity_autoreject" || k == "cavity_autoreject_absolute") {
 			if (to_double(t[1], v) ? (v != 0.0) : (onoff(t[1]) != 0)) throw 4004;
 		} else if (k == "numsteps" || k == "seed" || k == "preset_seed" || k == "move_factor" || k == "rot_factor" || k == "temperature" ||
 		           k == "volume_probability" || k == "transfer_probability" || k == "volume_change_factor") {

@@ -127,9 +127,7 @@ inline std::string read_input(const std::string &path, System &s) {
 	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED},
 	    {"cdvdw_exp_repulsion", MPMC_FLAG_OTHER_RD},
 	    {"cdvdw_sig_repulsion", MPMC_FLAG_NON_LB_MIXING}, {"cdvdw_9th_repulsion", MPMC_FLAG_NON_LB_MIXING},
-	    {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD},
-	    {"cavity_autoreject", MPMC_FLAG_CAVITY_AUTOREJECT},
-	    {"cavity_autoreject_absolute", MPMC_FLAG_CAVITY_AUTOREJECT}};
+	    {"disp_expansion_mbvdw", MPMC_FLAG_OTHER_RD}, {"rd_anharmonic", MPMC_FLAG_OTHER_RD}};
 	std::string pqr, line;
 	while (std::getline(f, line)) {
 		const std::vector<std::string> t = tokens(line);
@@ -195,6 +193,13 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "cavity_bias") { need(1); s.cavity_bias = onoff(t[1]); }
 		else if (k == "cavity_grid" || k == "cavity_grid_size") { need(1); s.cavity_grid_size = (int)dval(1); }
 		else if (k == "cavity_radius") { need(1); s.cavity_radius = dval(1); }
+		// (cavity_autoreject: the flag as for rd_crystal -- the facade clears it when it hands the rules to mpmc_set_cavity_autoreject)
+		else if (k == "cavity_autoreject" || k == "cavity_autoreject_absolute") {
+			if (t.size() < 2 || lower(t[1]) != "off") s.unsupported_flags |= MPMC_FLAG_CAVITY_AUTOREJECT;
+			(k == "cavity_autoreject" ? s.cavity_autoreject : s.cavity_autoreject_absolute) = (t.size() >= 2 && lower(t[1]) == "on") ? 1 : 0;
+		}
+		else if (k == "cavity_autoreject_scale") { need(1); s.cavity_autoreject_scale = dval(1); }
+		else if (k == "cavity_autoreject_repulsion") { need(1); s.cavity_autoreject_repulsion = dval(1); }
 		else if (k == "rd_crystal_order") { need(1); s.rd_crystal_order = (int)dval(1); }
 		else if (k == "feynman_hibbs_order") { need(1); s.feynman_hibbs_order = (int)dval(1); }
 		else if (k == "temperature") { need(1); s.temperature = dval(1); }
@@ -218,6 +223,8 @@ inline std::string read_input(const std::string &path, System &s) {
 	if ((s.waldmanhagler != 0) + (s.halgren_mixing != 0) + (s.c6_mixing != 0) > 1) throw 3000; // more than one mixing rule (SimulationControl.cpp:1706-1713)
 	if (s.polar_sor && s.polar_esor) throw 3000; // both relaxation schemes (SimulationControl.cpp:2714-2730)
 	if (s.polar_zodid && s.polarization && !s.polar_iterative) throw 3000; // zodid needs the iterative solver (SimulationControl.cpp:2634)
+	if ((s.cavity_autoreject || s.cavity_autoreject_absolute) && !(s.cavity_autoreject_scale > 0.0 && s.cavity_autoreject_scale <= 1.0))
+		throw 3000; // cavity_autoreject_scale outside (0, 1] (SimulationControl.cpp:2139-2154)
 	if (pqr.empty()) throw 4003; // missing_setting
 	if (pqr[0] != '/') pqr = dirname_of(path) + "/" + pqr;
 	return pqr;

@@ -135,6 +135,12 @@ public:
 	int cavities_open = 0;
 	double cavity_volume = 0, cavity_bias_probability = 0;
 	mpmc_cavity_result cavity_result{}; // of the last cavity_update_grid (hits and dart count too)
+	// contact rejection of uVT moves (mpmc_set_cavity_autoreject), src/System.h: cavity_autoreject, cavity_autoreject_absolute,
+	// cavity_autoreject_scale, cavity_autoreject_repulsion.  With a rule on, energy() and the energy_trial* calls return what the reference's
+	// energy() returns -- the absolute rule's MAXVALUE included --, the observables stay unpenalised by it
+	int cavity_autoreject = 0, cavity_autoreject_absolute = 0;
+	double cavity_autoreject_scale = 0, cavity_autoreject_repulsion = 0;
+	int cavity_autoreject_rules() const { return (cavity_autoreject ? MPMC_AUTOREJECT_SIGMA : 0) | (cavity_autoreject_absolute ? MPMC_AUTOREJECT_ABSOLUTE : 0); }
 	double polar_wolf_alpha = 0;         // its damping parameter in [0, 1] (`polar_wolf_alpha` / `polar_wolf_damp`), src/System.h:697
 	double temperature = 0;
 	double polar_precision = 0, polar_gamma = 1.0, polar_damp = 0;
@@ -219,7 +225,7 @@ public:
 		mpmc_result r;
 		check(mpmc_energy(ctx_, &r), "mpmc_energy");
 		absorb(r);
-		return r.energy;
+		return returned(r);
 	}
 	void energy_async() {
 		sync_state();
@@ -233,7 +239,7 @@ public:
 		mpmc_result r;
 		check(mpmc_energy_wait(ctx_, &r), "mpmc_energy_wait");
 		absorb(r);
-		return r.energy;
+		return returned(r);
 	}
 
 	// ---- trial moves: the role of the reference's per-pair recalculate_energy cache (src/System.cpp:1211-1224) ----
@@ -251,7 +257,7 @@ public:
 		trial_first_ = first, trial_kind_ = 0;
 		trial_pos_.assign(new_pos, new_pos + 3 * (size_t)count);
 		trial_result_ = r;
-		return r.energy;
+		return returned(r);
 	}
 	// the same in two halves, so that a driver can put the trials of many Systems in flight before the first wait
 	void energy_trial_async(int first, int count, const double *new_pos) {
@@ -273,7 +279,7 @@ public:
 			check(rc, "mpmc_trial_energy_wait");
 		}
 		trial_result_ = r;
-		return r.energy;
+		return returned(r);
 	}
 	const mpmc_result &trial_result() const { return trial_result_; } // the trial configuration's totals (observables keep the accepted ones)
 	void accept_trial() {
@@ -367,6 +373,26 @@ public:
 		      "mpmc_insert_candidates");
 		return out;
 	}
+	// the contact counts of each candidate's trial composition in the last energy_insert_candidates (mpmc_insert_candidates_contacts)
+	void insert_candidates_contacts(int n_cand, std::vector<int64_t> &n_replaced, std::vector<int64_t> &n_absolute) {
+		n_replaced.assign((size_t)(n_cand > 0 ? n_cand : 0), 0);
+		n_absolute.assign(n_replaced.size(), 0);
+		check(mpmc_insert_candidates_contacts(ctx_, n_cand, n_replaced.data(), n_absolute.data()), "mpmc_insert_candidates_contacts");
+	}
+	// what energy_trial_insert would RETURN for each result of the last energy_insert_candidates: its energy (the sigma rule's penalty is in
+	// it), plus MAXVALUE where the absolute rule finds a contact -- or where the accepted list already trips it through unmeasured frozen pairs
+	std::vector<double> insert_candidates_returned(const std::vector<mpmc_result> &results) {
+		std::vector<double> e(results.size());
+		for (size_t k = 0; k < results.size(); k++) e[k] = results[k].energy;
+		if (!autoreject_rules_) return e;
+		std::vector<int64_t> nr, na;
+		insert_candidates_contacts((int)results.size(), nr, na);
+		struct mpmc_cavity_autoreject_info v;
+		check(mpmc_cavity_autoreject_info(ctx_, &v), "mpmc_cavity_autoreject_info");
+		for (size_t k = 0; k < results.size(); k++)
+			if (na[k] > 0 || v.n_unmeasured_frozen > 0) e[k] += 1.0e40;
+		return e;
+	}
 
 	// ---- System::cavity_update_grid, src/System.Cavity.cpp:15-188 (the reference calls it in front of every move of a cavity_bias run) ----
 	// The darts of update_cavity_volume come from the caller's generator through the distribution System::get_rand uses: three uniforms per
@@ -393,6 +419,13 @@ public:
 		check(mpmc_cavity_point(ctx_, random_index, pos), "mpmc_cavity_point");
 	}
 
+	// the contact counts behind the last result delivered, the absolute rule's penalty and the value the reference's energy() returns
+	struct mpmc_cavity_autoreject_info cavity_autoreject_info() {
+		sync_state();
+		struct mpmc_cavity_autoreject_info v;
+		check(mpmc_cavity_autoreject_info(ctx_, &v), "mpmc_cavity_autoreject_info");
+		return v;
+	}
 	double lj() { return piece(mpmc_lj); }
 	double coulombic() { return piece(mpmc_coulombic); }
 	double coulombic_real() { return piece(mpmc_coulombic_real); }
@@ -446,6 +479,16 @@ private:
 	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
 	int gs_ranked_on_ = 0;                         // ... and its polar_gs_ranked setting
 	int cavity_grid_ = 0;                          // ... and its cavity grid (0: off)
+	int autoreject_rules_ = 0;                     // ... and its cavity_autoreject setting
+	double autoreject_scale_ = 0, autoreject_repulsion_ = 0;
+	// what energy() returns: the observables' energy, plus the absolute rule's penalty when a rule is on (no device work: the info of the
+	// result just delivered)
+	double returned(const mpmc_result &r) {
+		if (!autoreject_rules_) return r.energy;
+		struct mpmc_cavity_autoreject_info v;
+		check(mpmc_cavity_autoreject_info(ctx_, &v), "mpmc_cavity_autoreject_info");
+		return v.returned_energy;
+	}
 	double cavity_radius_ = 0;
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
@@ -490,6 +533,8 @@ private:
 			gs_ranked_on_ = 0;
 			cavity_grid_ = 0;
 			cavity_radius_ = 0;
+			autoreject_rules_ = 0;
+			autoreject_scale_ = autoreject_repulsion_ = 0;
 		}
 		if (box_dirty_) {
 			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
@@ -519,9 +564,11 @@ private:
 		o.polar_ewald_alpha = polar_ewald_alpha;
 		// (polar_iterative off is the library's direct dipole solve: no flag; `rd_crystal on` goes to mpmc_set_rd_crystal below: the reader's
 		// flag for the keyword is cleared here, a caller's flag without the field is still refused)
-		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full, and `polar_gs_ranked on` to mpmc_set_polar_gs_ranked)
+		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full, `polar_gs_ranked on` to mpmc_set_polar_gs_ranked and
+		// `cavity_autoreject on` / `cavity_autoreject_absolute on` to mpmc_set_cavity_autoreject)
 		o.unsupported_flags = unsupported_flags & ~(uint64_t)((rd_crystal ? MPMC_FLAG_RD_CRYSTAL : 0) | (polar_ewald_full ? MPMC_FLAG_POLAR_EWALD_FULL : 0) |
-		                                                      (polar_gs_ranked ? MPMC_FLAG_POLAR_GS_RANKED : 0));
+		                                                      (polar_gs_ranked ? MPMC_FLAG_POLAR_GS_RANKED : 0) |
+		                                                      (cavity_autoreject_rules() ? MPMC_FLAG_CAVITY_AUTOREJECT : 0));
 		check(mpmc_set_options(ctx_, &o), "mpmc_set_options");
 		if (atoms_dirty_) {
 			std::vector<double> pos(3 * (size_t)n), q(n), al(n), ep(n), sg(n), ms(n);
@@ -606,6 +653,14 @@ private:
 			check(mpmc_set_cavity_grid(ctx_, cavity_bias ? cavity_grid_size : 0, cavity_radius), "mpmc_set_cavity_grid");
 			cavity_grid_ = cavity_bias ? cavity_grid_size : 0;
 			cavity_radius_ = cavity_radius;
+		}
+		// (a scale outside (0, 1] with a rule on is refused by the library, SimulationControl.cpp:2139-2154)
+		const int ca_rules = cavity_autoreject_rules();
+		if (ca_rules != autoreject_rules_ || (ca_rules && (cavity_autoreject_scale != autoreject_scale_ || cavity_autoreject_repulsion != autoreject_repulsion_))) {
+			check(mpmc_set_cavity_autoreject(ctx_, ca_rules, cavity_autoreject_scale, cavity_autoreject_repulsion), "mpmc_set_cavity_autoreject");
+			autoreject_rules_ = ca_rules;
+			autoreject_scale_ = cavity_autoreject_scale;
+			autoreject_repulsion_ = cavity_autoreject_repulsion;
 		}
 		if ((polar_palmo != 0) != (polar_palmo_on_ != 0)) {
 			check(mpmc_set_polar_palmo(ctx_, polar_palmo ? 1 : 0), "mpmc_set_polar_palmo");

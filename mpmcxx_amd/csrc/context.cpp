@@ -566,6 +566,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	if (c->tb_have) c->tb_dirty = true; // (the three-body coefficients follow the order at the next evaluation that needs them)
 	if (c->de_have) c->de_dirty = true; // (so do the disp-expansion coefficients)
 	c->rdm_dirty = true;                // (and the rd model's per-atom table)
+	c->ca_dirty = true;                 // (and what cavity_autoreject takes from the list)
 	return MPMC_OK;
 }
 
@@ -1011,6 +1012,108 @@ extern "C" int mpmc_rd_model_info(mpmc_ctx *c, struct mpmc_rd_model_info *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	*out = c->rdm_info;
 	return MPMC_OK;
+}
+
+// ---- cavity_autoreject (System.Energy.cpp:1001-1004, 1237-1239, 2182-2185; System.Cavity.cpp:211-228; SimulationControl.cpp:2139-2154) ----------
+static_assert(MPMC_AUTOREJECT_SIGMA == CA_RULE_SIGMA && MPMC_AUTOREJECT_ABSOLUTE == CA_RULE_ABSOLUTE, "kernels.h mirrors the header");
+extern "C" int mpmc_set_cavity_autoreject(mpmc_ctx *c, int rules, double scale, double repulsion) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_cavity_autoreject: an evaluation or a trial move is open");
+	if (rules & ~(MPMC_AUTOREJECT_SIGMA | MPMC_AUTOREJECT_ABSOLUTE)) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_cavity_autoreject: unknown rule bits (MPMC_AUTOREJECT_*)");
+	if (rules && !(scale > 0.0 && scale <= 1.0)) // SimulationControl.cpp:2139-2154 (a NaN fails the test too)
+		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_cavity_autoreject: cavity_autoreject_scale must be in (0, 1]");
+	if (rules != c->kept.ca_rules || (rules && (scale != c->kept.ca_scale || repulsion != c->kept.ca_repulsion)))
+		c->cache_valid = false; // (the accepted contact counts belong to the other setting: the next trial needs a re-basing evaluation)
+	c->kept.ca_rules = rules;
+	c->kept.ca_scale = rules ? scale : 0.0;
+	c->kept.ca_repulsion = rules ? repulsion : 0.0;
+	if (!rules) c->ca_info = {};
+	return MPMC_OK;
+}
+extern "C" int mpmc_cavity_autoreject_info(mpmc_ctx *c, struct mpmc_cavity_autoreject_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_autoreject_info: an evaluation is in flight");
+	*out = c->ca_info;
+	out->rules = c->kept.ca_rules;
+	out->scale = c->kept.ca_scale;
+	out->repulsion = c->kept.ca_repulsion;
+	return MPMC_OK;
+}
+
+extern "C" int mpmc_insert_candidates_contacts(mpmc_ctx *c, int n_cand, int64_t *n_replaced, int64_t *n_absolute) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->ins_ca_n < 0) return fail(c, MPMC_ERR_ARG, "mpmc_insert_candidates_contacts: no batch of insertion candidates has run");
+	if (n_cand != c->ins_ca_n) return fail(c, MPMC_ERR_ARG, "mpmc_insert_candidates_contacts: n_cand differs from the last batch's");
+	for (int q = 0; q < n_cand; q++) {
+		if (n_replaced) n_replaced[q] = c->ins_ca[2 * (size_t)q];
+		if (n_absolute) n_absolute[q] = c->ins_ca[2 * (size_t)q + 1];
+	}
+	return MPMC_OK;
+}
+
+int mpmc::contact_ready(mpmc_ctx *c) {
+	if (!contact_on(c)) return fail(c, MPMC_ERR_INVALID_SETTING, "cavity_autoreject is off (mpmc_set_cavity_autoreject)");
+	if (c->kept.ca_rules & CA_RULE_SIGMA) {
+		if (crystal_on(c))
+			return fail(c, MPMC_ERR_UNSUPPORTED, "cavity_autoreject with rd_crystal: the reference tests intramolecular pairs there, which rejects every multi-site "
+			                                     "molecule (System.Energy.cpp:916-1004); use the absolute rule, or rd_crystal without the sigma rule");
+	}
+	if (c->ca_dirty) { // (the parameters and the molecules change with the atom list only: one scan per new list, none per trial move)
+		double smax = 0.0;
+		int64_t frozen = 0, same = 0, run = 0;
+		bool sorted = true; // (a molecule's atoms stand together in every list the readers make: one pass; otherwise the ids are sorted first)
+		int32_t last = 0;
+		for (int i = 0; i < c->n; i++) {
+			smax = std::max(smax, std::fabs(c->h_sigma[i]));
+			if (!c->h_frozen[i]) continue;
+			if (frozen && c->h_mol[i] < last) sorted = false;
+			if (frozen && c->h_mol[i] == last) run++;
+			else same += run * (run - 1) / 2, run = 1;
+			last = c->h_mol[i];
+			frozen++;
+		}
+		same += run * (run - 1) / 2;
+		if (!sorted) { // (frozen atoms of one molecule apart in the list: count by sorted ids)
+			std::vector<int32_t> ids;
+			for (int i = 0; i < c->n; i++)
+				if (c->h_frozen[i]) ids.push_back(c->h_mol[i]);
+			std::sort(ids.begin(), ids.end());
+			same = 0, run = 0;
+			for (size_t k = 0; k < ids.size(); k++) {
+				if (k && ids[k] == ids[k - 1]) run++;
+				else same += run * (run - 1) / 2, run = 1;
+			}
+			same += run * (run - 1) / 2;
+		}
+		c->ca_frozen_atoms = frozen;
+		c->ca_sigma_max = smax;
+		c->ca_frozen_pairs = frozen * (frozen - 1) / 2 - same;
+		c->ca_dirty = false;
+	}
+	int rc;
+	if ((rc = c->d_ca_part.reserve(c, (size_t)3 * kContactBlocks)) != MPMC_OK) return rc;
+	if ((rc = c->d_ca_cls.reserve(c, (size_t)std::max(1, c->n_tile_pairs))) != MPMC_OK) return rc;
+	return MPMC_OK;
+}
+
+ContactParams mpmc::contact_params(const mpmc_ctx *c) {
+	ContactParams cp{};
+	cp.rules = c->kept.ca_rules;
+	cp.model = rd_model_on(c) ? 1 : 0;
+	cp.mix = c->kept.rdm_mix;
+	cp.measure_frozen = c->opts.polarization ? 1 : 0;
+	cp.scale = c->kept.ca_scale;
+	cp.disp = c->kept.de_enabled ? 1 : 0; // (disp_expansion() replaces lj(): its own sigma test and, with a threshold, its repulsion test)
+	cp.schmidt = (c->kept.de_flags & MPMC_DISP_SCHMIDT) ? 1 : 0;
+	cp.repulsion = cp.disp ? c->kept.ca_repulsion : 0.0;
+	cp.t_in = (c->kept.rdm_form == RD_FORM_LJ) ? c->box.t_lj : c->box.t_es;
+	// no contact at or beyond dmax: every mixing rule's sigma_ij is a mean of the two sigmas, so at most the larger one (the margin covers
+	// the rounding of the mixed value and of the product)
+	// (disp-expansion: sigma is r0 and r0_ij their mean; its repulsion test has no distance bound here: HUGE_VAL, everything is walked)
+	const double d_sigma = !(cp.rules & CA_RULE_SIGMA) ? 0.0 : (cp.repulsion != 0.0) ? HUGE_VAL : cp.scale * c->ca_sigma_max * (1.0 + 1e-9);
+	const double d_abs = (cp.rules & CA_RULE_ABSOLUTE) ? cp.scale : 0.0;
+	cp.dmax = std::max(d_sigma, d_abs);
+	return cp;
 }
 
 int mpmc::rd_model_ready(mpmc_ctx *c) {
@@ -1515,6 +1618,7 @@ extern "C" int mpmc_debug_gs_ranked_pair_stats(mpmc_ctx *c, int64_t out[6]) {
 //   single_launch     recip_table     spatial_sort     order_carry     polar_delta     inline_move     trace_panel     tensor_budget_mb N
 //   direct_budget_mb N (-1: free device memory)     dipoles_on_demand (0: every evaluation runs all its Jacobi iterations at once)
 //   pef_phase_table (0: `polar_ewald_full` recomputes its phases in every pass)
+//   contact_skip (0: the contact walk of cavity_autoreject walks every tile pair)
 extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) {
 	if (!key) return MPMC_ERR_ARG;
 	std::unique_lock<std::mutex> tuning_lk(g_tuning_mu, std::defer_lock);
@@ -1574,6 +1678,7 @@ extern "C" int mpmc_debug_configure(mpmc_ctx *c, const char *key, double value) 
 	} else if (k == "order_carry") t.no_order_carry = !on;
 	else if (k == "polar_delta") t.no_polar_delta = !on;
 	else if (k == "inline_move") t.no_inline_move = !on;
+	else if (k == "contact_skip") t.no_contact_skip = !on;
 	else if (k == "trace_panel") t.trace_panel = on;
 	else if (k == "dipoles_on_demand") t.dipoles_on_demand = on;
 	else if (k == "pef_phase_table") t.pef_phase_table = on;

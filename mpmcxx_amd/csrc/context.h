@@ -108,6 +108,7 @@ struct mpmc_tuning {
 	bool no_order_carry = false; // "order_carry" = 0: every upload of the atom list sorts
 	bool no_polar_delta = false; // "polar_delta" = 0: trial moves of polarizable boxes run a full evaluation
 	bool no_inline_move = false; // "inline_move" = 0: trial moves always travel through the staging block
+	bool no_contact_skip = false; // "contact_skip" = 0: the contact walk of cavity_autoreject walks every tile pair
 	int virtual_device = -1;     // "virtual_device" = v >= 0 (test hook): mpmc_pi_allreduce treats this context as living on a device of its own (csrc/comm.cpp group_beads)
 	int fail_next_wait = 0;      // "fail_next_wait" = 1: the next wait of this context fails as if the runtime had refused it (test of the recovery path)
 	bool trace_panel = false;    // "trace_panel" = 1: per-workgroup time stamps of the panel kernel (tools/panel_trace.py)
@@ -146,6 +147,8 @@ struct mpmc_kept {
 	bool on_demand = false;                 // mpmc_set_dipoles_on_demand: mpmc_energy / mpmc_energy_async stop at the iterations the energy needs
 	int cav_grid = 0;                       // `cavity_bias` (mpmc_set_cavity_grid), likewise: cavity_grid_size, 0 = off
 	double cav_radius = 0.0;                // cavity_radius
+	int ca_rules = 0;                       // cavity_autoreject (mpmc_set_cavity_autoreject), likewise: MPMC_AUTOREJECT_*, 0 = off
+	double ca_scale = 0.0, ca_repulsion = 0.0; // cavity_autoreject_scale, cavity_autoreject_repulsion
 };
 
 // A contiguous run of atoms with every per-atom array of mpmc_set_atoms: the molecule of an exchange trial, or a whole atom list
@@ -424,6 +427,28 @@ struct mpmc_ctx {
 	struct mpmc_rd_model_info rdm_info{};   // of the last evaluation with a non-default model (mpmc_rd_model_info)
 	int64_t rdm_terms_accepted = 0, rdm_terms_trial = 0; // kept terms of the accepted configuration (with last_full) / of the evaluated trial
 
+	// cavity_autoreject (mpmc_set_cavity_autoreject, kernels_contact.hip; kept.ca_rules, kept.ca_scale): the contact counts.  Every result
+	// the context keeps (last_full, trial_res, trial_keep) is the UNPENALISED one -- lj_pairs = the kernels' sum S --, so that a trial's delta
+	// adds to S and not to S + n 1e40; the penalty is put on the copy that leaves the library (contact_deliver, evaluate.cpp).
+	struct ContactCounts {
+		int64_t replaced = 0, absolute = 0;
+	};
+	ContactCounts ca_eval, ca_accepted, ca_trial; // of the last evaluation waited for / of the accepted configuration (with last_full) / of the evaluated trial
+	int64_t ca_walked = 0, ca_skipped = 0;        // tile pairs of the last full walk
+	bool ca_dirty = true;                         // ca_sigma_max and ca_frozen_pairs are older than the atom list
+	double ca_sigma_max = 0.0;                    // largest |sigma| of the list: scale * it bounds the sigma rule's contact distance
+	int64_t ca_frozen_pairs = 0;                  // pairs of two frozen atoms of different molecules
+	int64_t ca_frozen_atoms = 0;                  // frozen atoms of the list
+	int64_t ca_frozen_pairs_trial = 0;            // ... of the evaluated exchange trial's composition (delta path)
+	DevBuf<int> d_ca_xpart;                       // [candidates of a chain][n_tiles][2] per-tile contacts of a staged molecule (launch_exchange_contact)
+	DevBuf<long long> d_ins_ca;                   // [n_cand][2] per-candidate contacts of the last batch of insertion candidates
+	PinnedBuf<long long> h_ins_ca;                // likewise, on their way to the host
+	std::vector<int64_t> ins_ca;                  // [n_cand][2] the last batch's counts of each candidate's trial composition (mpmc_insert_candidates_contacts)
+	int ins_ca_n = -1;                            // candidates of that batch (-1: none yet)
+	DevBuf<double> d_ca_part;                     // [3 kContactBlocks] per-workgroup partials
+	DevBuf<int> d_ca_cls;                         // [n_tile_pairs] the contact walk's own tile-pair classes (k_contact_classes)
+	struct mpmc_cavity_autoreject_info ca_info{}; // of the last result delivered (mpmc_cavity_autoreject_info)
+
 	// `polar_wolf` / `polar_palmo` (mpmc_set_polar_wolf, mpmc_set_polar_palmo, kernels_wolf_field.hip; switched on: kept.pw_enabled, kept.pw_alpha,
 	// kept.palmo_enabled)
 	bool palmo_ran = false;          // the pending / last evaluation did the extra contraction (Gauss-Seidel sweeps that did not fail)
@@ -648,7 +673,8 @@ enum : unsigned {
 	RUN_THREE_BODY = 256, // the Axilrod-Teller sum (contexts with the term switched on)
 	RUN_DISP = 512,       // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
 	RUN_CRYSTAL = 1024,   // the rd_crystal lattice sum (contexts with the term switched on and disp-expansion off: it replaces the LJ sum)
-	RUN_RDM = 2048        // the rd-model sum (contexts with a non-default model: it replaces the LJ part of rd_energy)
+	RUN_RDM = 2048,       // the rd-model sum (contexts with a non-default model: it replaces the LJ part of rd_energy)
+	RUN_CONTACT = 4096    // the contact walk of cavity_autoreject (contexts with a rule on; never the single-launch form)
 };
 // 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
 // applied once to the sum of the per-triple terms
@@ -661,6 +687,14 @@ inline bool rd_model_on(const mpmc_ctx *c) { return c->kept.rdm_form != 0 || c->
 inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled && c->kept.rdm_form == 0; }
 int rd_model_ready(mpmc_ctx *c);   // the model's combinations and atom parameters are valid, its table is on the device in the current slot order, its correction is current (context.cpp)
 RdModelParams rd_model_params(const mpmc_ctx *c); // form, rule, distance test and this evaluation's Feynman-Hibbs constants (evaluate.cpp)
+inline bool contact_on(const mpmc_ctx *c) { return c->kept.ca_rules != 0; }
+int contact_ready(mpmc_ctx *c);    // the rules' combinations are valid, the list's largest sigma and frozen pairs are current, the buffers stand (context.cpp)
+ContactParams contact_params(const mpmc_ctx *c); // rules, scale, the rd function's distance test and mixing, dmax (context.cpp)
+// the copy of a result that leaves the library: the sigma rule's n 1e40 on lj_pairs (rd_energy, energy, NU follow), and the info struct of
+// this delivery (evaluate.cpp)
+// frozen_pairs: the unmeasured frozen pairs of the delivered composition (-1: the accepted list's)
+void contact_deliver(mpmc_ctx *c, mpmc_result *r, const mpmc_ctx::ContactCounts &n, int64_t frozen_pairs = -1);
+void contact_penalise(const mpmc_ctx *c, mpmc_result *r, int64_t n_replaced); // the sigma rule's n 1e40 on lj_pairs; rd_energy, energy, NU follow
 int crystal_ready(mpmc_ctx *c);    // the image table, cutoff, thresholds and crystal_self of the current cell and atoms are in place (context.cpp)
 CrystalParams crystal_params(const mpmc_ctx *c); // rc_par with this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see it: rd_crystal puts its own cutoff in (evaluate.cpp)

@@ -1071,6 +1071,14 @@ static int stage_added_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at,
 		const int *cls = (p.pair_pass && c->box.ortho && !c->kept.tune.no_classes) ? c->d_cls.p : nullptr;
 		launch_rd_model(st, at, c->d_rdm_sp, c->d_tile_pairs, cls, c->n_tile_pairs, c->box, rd_model_params(c), c->d_rdm_part, c->d_scal + S_RDM);
 	}
+	// ---- cavity_autoreject: the contact counts and the tile pairs it skipped into their three slots.  Its own tile-pair classes come from
+	// this evaluation's tile bounding boxes, where the pairwise pass made them and the cell is orthorhombic ----------------------------------
+	if (p.mask & RUN_CONTACT) {
+		ProfScope ps(c, MPMC_K_PAIR);
+		const bool skip = p.pair_pass && c->box.ortho && !c->kept.tune.no_classes && !c->kept.tune.no_contact_skip;
+		launch_contact(st, at, c->kept.de_enabled ? c->d_de_co.p : c->d_rdm_sp.p, c->d_tile_pairs, c->n_tile_pairs, c->box, contact_params(c),
+		               skip ? c->d_tile_bounds.p : nullptr, c->d_ca_cls, c->d_ca_part, c->d_scal + S_CA_REPLACED);
+	}
 	HIP_TRY(c, hipGetLastError());
 	return MPMC_OK;
 }
@@ -1109,6 +1117,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_RDM) && (rc = rd_model_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_CONTACT) && (rc = contact_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_SOLVE) && ewald_full_on(c)) {
 		if (c->kept.palmo_enabled)
 			return fail(c, MPMC_ERR_UNSUPPORTED, "polar_ewald_full with polar_palmo: ewald_palmo_contraction (System.Energy.cpp:3243-3267) is not part of the library");
@@ -1280,6 +1289,13 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->gr_info.max_rank = c->h_gr_info[0].max_rank;
 		c->gr_info.n_moved = c->h_gr_info[0].n_moved;
 	}
+	if (c->run_mask & RUN_CONTACT) { // cavity_autoreject: the counts of this evaluation (they re-base the accepted ones with a complete energy())
+		c->ca_eval.replaced = (int64_t)c->h_scal[S_CA_REPLACED];
+		c->ca_eval.absolute = (int64_t)c->h_scal[S_CA_ABSOLUTE];
+		c->ca_skipped = (int64_t)c->h_scal[S_CA_SKIPPED];
+		c->ca_walked = (int64_t)c->n_tile_pairs - c->ca_skipped;
+		if (c->run_mask == full_mask(c)) c->ca_accepted = c->ca_eval;
+	}
 	if (!out) return MPMC_OK;
 	std::memset(out, 0, sizeof(*out));
 	const double *s = c->h_scal;
@@ -1369,6 +1385,7 @@ unsigned mpmc::full_mask(const mpmc_ctx *c) {
 	if (c->kept.de_enabled) m |= RUN_DISP;       // (in place of the LJ part of rd_energy; never the single-launch form)
 	if (crystal_on(c)) m |= RUN_CRYSTAL;         // (in place of the LJ sum; disp_expansion() ignores rd_crystal)
 	if (rd_model_on(c)) m |= RUN_RDM;            // (in place of the LJ part of rd_energy; never the single-launch form)
+	if (contact_on(c)) m |= RUN_CONTACT;         // (cavity_autoreject: counts beside the energies; never the single-launch form)
 	return m;
 }
 
@@ -1386,16 +1403,44 @@ extern "C" int mpmc_hint_in_flight(mpmc_ctx *c, int n) {
 	c->inflight_hint = n;
 	return MPMC_OK;
 }
+// What leaves the library under cavity_autoreject.  r is the unpenalised result of a configuration with the contact counts n: the sigma
+// rule's pairs get MAXVALUE in lj_pairs, and rd_energy, energy and NU follow in the order of wait_and_fill; the absolute rule stays out of
+// mpmc_result (it mirrors the observables) and shows in the info struct, which belongs to this delivery.
+void mpmc::contact_penalise(const mpmc_ctx *c, mpmc_result *r, int64_t n_replaced) {
+	if (!(c->kept.ca_rules & CA_RULE_SIGMA)) return;
+	r->lj_pairs = r->lj_pairs + (double)n_replaced * kMaxValue;
+	// (14-7 and DREIDING have no corrections: rd_energy = lj_pairs; disp-expansion composes like lj(); the sigma rule never meets rd_crystal: contact_ready)
+	r->rd_energy = (rd_model_on(c) && c->kept.rdm_form != RD_FORM_LJ) ? r->lj_pairs : (r->lj_pairs + r->lrc_pair) + r->lrc_self;
+	r->energy = r->rd_energy + r->coulombic_energy + r->polarization_energy + r->vdw_energy + r->three_body_energy;
+	r->NU = r->N * r->energy;
+}
+void mpmc::contact_deliver(mpmc_ctx *c, mpmc_result *r, const mpmc_ctx::ContactCounts &n, int64_t frozen_pairs) {
+	if (!contact_on(c) || !r) return;
+	const bool sigma = (c->kept.ca_rules & CA_RULE_SIGMA) != 0, absolute = (c->kept.ca_rules & CA_RULE_ABSOLUTE) != 0;
+	struct mpmc_cavity_autoreject_info &info = c->ca_info;
+	info = {};
+	info.n_replaced = sigma ? n.replaced : 0;
+	info.n_absolute = absolute ? n.absolute : 0;
+	info.n_unmeasured_frozen = (absolute && !c->opts.polarization) ? (frozen_pairs >= 0 ? frozen_pairs : c->ca_frozen_pairs) : 0;
+	info.tile_pairs_walked = c->ca_walked;
+	info.tile_pairs_skipped = c->ca_skipped;
+	contact_penalise(c, r, info.n_replaced);
+	info.absolute_penalty = (info.n_absolute + info.n_unmeasured_frozen > 0) ? kMaxValue : 0.0;
+	info.returned_energy = r->energy + info.absolute_penalty;
+}
+
 extern "C" int mpmc_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	if (!c) return MPMC_ERR_ARG;
-	return wait_and_fill(c, out);
+	const int rc = wait_and_fill(c, out);
+	if (rc == MPMC_OK && (c->run_mask & RUN_CONTACT)) contact_deliver(c, out, c->ca_eval);
+	return rc;
 }
 extern "C" int mpmc_energy(mpmc_ctx *c, mpmc_result *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	c->inflight_hint = 1; // (a synchronous call: nothing else of this caller is in flight)
 	int rc = enqueue(c, full_mask(c), c->kept.on_demand);
 	if (rc != MPMC_OK) return rc;
-	return wait_and_fill(c, out);
+	return mpmc_energy_wait(c, out);
 }
 
 
@@ -1409,7 +1454,10 @@ static int run_piece(mpmc_ctx *c, unsigned mask, mpmc_result *r) {
 extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	if (!c) return MPMC_ERR_ARG;
-	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u) | (rd_model_on(c) ? RUN_RDM : 0u), &r);
+	// (cavity_autoreject: the sigma rule lives inside lj(); the absolute rule belongs to energy() alone)
+	const bool contact = (c->kept.ca_rules & CA_RULE_SIGMA) != 0 && !c->kept.de_enabled; // (under disp-expansion the rule is disp_expansion()'s: mpmc_disp_expansion)
+	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u) | (rd_model_on(c) ? RUN_RDM : 0u) | (contact ? RUN_CONTACT : 0u), &r);
+	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->ca_eval);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }
@@ -1458,7 +1506,9 @@ extern "C" int mpmc_disp_expansion(mpmc_ctx *c, double *out) {
 	if (!c) return MPMC_ERR_ARG;
 	if (!c->kept.de_enabled) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_disp_expansion: the term is off (mpmc_set_disp_expansion)");
 	mpmc_result r;
-	int rc = run_piece(c, RUN_DISP, &r);
+	const bool contact = (c->kept.ca_rules & CA_RULE_SIGMA) != 0; // (cavity_autoreject: the sigma rule lives inside disp_expansion() too)
+	int rc = run_piece(c, RUN_DISP | (contact ? RUN_CONTACT : 0u), &r);
+	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->ca_eval);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }

@@ -61,7 +61,8 @@ enum : int {
 	S_PALMO,                                     // Palmo-Krimm correction, already part of S_POLAR (kernels_wolf_field.hip)
 	S_CRYSTAL, S_CRYSTAL_TERMS,                  // rd_crystal pair sum and its image-term count (a double: exact) (kernels_crystal.hip)
 	S_RDM, S_RDM_TERMS, S_RDM_SKIPPED,           // rd-model pair sum, its kept terms and the tile pairs it skipped (doubles: exact) (kernels_rd_model.hip)
-	S_COUNT = 20
+	S_CA_REPLACED, S_CA_ABSOLUTE, S_CA_SKIPPED,  // cavity_autoreject: pairs replaced by MAXVALUE, absolute contacts, tile pairs not walked (doubles: exact) (kernels_contact.hip)
+	S_COUNT = 24
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
 // slots of a trial move's result block on the device (d_delta_out): what launch_delta leaves, then one change per further term
@@ -71,6 +72,7 @@ enum : int {
 	D_THREE_BODY,                                         // Axilrod-Teller (kernels_three_body.hip)
 	D_DISP,                                               // disp-expansion (kernels_disp.hip)
 	D_RD, D_RD_TERMS,                                     // rd_crystal's lattice sum and image terms, OR the rd model's sum and kept terms
+	D_CA_REPLACED, D_CA_ABSOLUTE,                         // cavity_autoreject: change of the replaced pairs and of the absolute contacts (kernels_contact.hip)
 	D_COUNT
 };
 // rd_crystal and the rd model share D_RD and D_RD_TERMS.  They never meet: a context with a model is not `rd_crystal on` (crystal_on is false
@@ -459,6 +461,36 @@ void launch_rd_model_lrc(hipStream_t st, const AtomsDev &at, const double4 *sp, 
 // out2 = { change of the pair sum, change of the kept terms }
 void launch_rd_model_delta(hipStream_t st, const AtomsDev &at, const double4 *sp, const Box &bx, const RdModelParams &rp, const int *mv_slot,
                            const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
+
+// ---- cavity_autoreject: the contact counts of mpmc_set_cavity_autoreject (kernels_contact.hip) -------------------------------------------
+// Integer pair sums carried as doubles (exact).  sp: the rd model's per-atom table when `model` is set, the disp-expansion term's
+// coefficient table co when `disp` is set (else unused, may be null).
+constexpr int kContactBlocks = 16384;
+enum : int { CA_RULE_SIGMA = 1, CA_RULE_ABSOLUTE = 2 }; // (mirror MPMC_AUTOREJECT_* of the public header: context.cpp asserts it)
+struct ContactParams {
+	int rules;          // CA_RULE_*
+	int model, mix;     // sigma rule: sigma_ij by the rd model's rule RD_MIX_* from sp (model != 0), or by lj_mix (model == 0)
+	int measure_frozen; // absolute rule: pairs of two frozen atoms are measured (polarization on, System.cpp:985)
+	int disp, schmidt;  // sigma rule under the disp-expansion term: sigma_ij = r0_ij and alpha_ij from co = (alpha, r0, ..) in place of sp, no cutoff
+	double repulsion;   // ... and its second test (cavity_autoreject_repulsion != 0): 315.775 exp(-alpha_ij (r - r0_ij)) > repulsion
+	double scale;       // cavity_autoreject_scale
+	double t_in;        // sigma rule: ri2 <= t_in, the rd function's own distance test (Box::t_lj for LJ, Box::t_es for 14-7 and DREIDING)
+	double dmax;        // no contact at or beyond this distance: scale * (largest sigma, with a margin), respectively scale; infinite
+	                    // under the repulsion test, which has no such bound here: every tile pair is walked
+};
+// out3 = { pairs replaced, absolute contacts, tile pairs skipped }.  tile_bounds (this evaluation's k_tile_bounds) and cls (scratch
+// [n_tile_pairs]) non-null in an orthorhombic cell: tile pairs further apart than dmax are not walked; otherwise every tile pair is walked
+void launch_contact(hipStream_t st, const AtomsDev &at, const double4 *sp, const int2 *tile_pairs, int n_tile_pairs, const Box &bx, const ContactParams &cp,
+                    const double *tile_bounds, int *cls, double *part /*[3 kContactBlocks]*/, double *out3);
+// out2 = { change of the pairs replaced, change of the absolute contacts } under a trial move
+void launch_contact_delta(hipStream_t st, const AtomsDev &at, const double4 *sp, const Box &bx, const ContactParams &cp, const int *mv_slot,
+                          const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
+
+// exchange moves: the contacts of a staged molecule (XchAtom records, as launch_exchange's) with the residents, per candidate.  The plain
+// term only (the exchange delta path has no rd model, rd_crystal or disp-expansion).  part: scratch [nc][nt][2] ints.  out2 (may be null; nc = 1):
+// { sg * replaced, sg * absolute } as doubles, side by side; out_ll (may be null): [nc][2] the counts themselves.
+void launch_exchange_contact(hipStream_t st, const AtomsDev &at, const Box &bx, const ContactParams &cp, const XchAtom *mol, int m, int nc, double sg, int *part,
+                             double *out2, long long *out_ll);
 
 // ---- `polar_wolf`: the Wolf static field, and the reduce of `polar_palmo` (kernels_wolf_field.hip)--------------------------------------
 struct WolfFieldParams {

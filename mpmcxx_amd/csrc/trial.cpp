@@ -165,6 +165,7 @@ static int xch_replace_list(mpmc_ctx *c, const AtomRun &list, AtomRun &&saved) {
 	const bool evaluated = c->trial_evaluated, was_full = c->trial_was_full;
 	const mpmc_result keep = c->trial_keep, res = c->trial_res;
 	const int64_t rc_terms = c->rc_terms_accepted, rdm_terms = c->rdm_terms_accepted;
+	const mpmc_ctx::ContactCounts ca_acc = c->ca_accepted, ca_tr = c->ca_trial;
 	AtomRun mol = std::move(c->xch_mol);
 	const int rc = set_atoms_from(c, list);
 	c->xch_mol = std::move(mol);
@@ -173,6 +174,7 @@ static int xch_replace_list(mpmc_ctx *c, const AtomRun &list, AtomRun &&saved) {
 	c->trial_evaluated = evaluated, c->trial_was_full = was_full;
 	c->trial_keep = keep, c->trial_res = res;
 	c->rc_terms_accepted = rc_terms, c->rdm_terms_accepted = rdm_terms;
+	c->ca_accepted = ca_acc, c->ca_trial = ca_tr;
 	c->trial_open = true;
 	c->trial_enqueued = c->trial_noop = false;
 	return rc;
@@ -243,6 +245,17 @@ static int xch_energy_async(mpmc_ctx *c) {
 	hipStream_t st = c->stream;
 	HIP_TRY(c, hipMemcpyAsync(c->d_xch_mol, c->h_xch_mol, (size_t)m * sizeof(XchAtom), hipMemcpyHostToDevice, st));
 	const int do_es = o.rd_only ? 0 : 1;
+	if (contact_on(c)) {
+		// cavity_autoreject: the molecule's contacts with the residents, signed, into D_CA_REPLACED and D_CA_ABSOLUTE of the delta result block,
+		// which k_delta_finish posts with everything else; the unmeasured frozen pairs of the trial composition from the host's counts
+		if ((rc = contact_ready(c)) != MPMC_OK) return rc;
+		if ((rc = c->d_ca_xpart.reserve(c, 2 * (size_t)c->n_tiles)) != MPMC_OK) return rc;
+		int64_t fm = 0;
+		for (int k = 0; k < m; k++) fm += c->xch_mol.frozen[k] ? 1 : 0;
+		c->ca_frozen_pairs_trial = c->ca_frozen_pairs + (kind > 0 ? fm * c->ca_frozen_atoms : -fm * (c->ca_frozen_atoms - fm));
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_exchange_contact(st, atoms_view(c), c->box, contact_params(c), c->d_xch_mol, m, 1, sg, c->d_ca_xpart, c->d_delta_out + D_CA_REPLACED, nullptr);
+	}
 	{
 		FusedParams fp{};
 		fp.ewald_alpha = c->ewald_alpha;
@@ -401,8 +414,8 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// short moves of non-polarizable boxes travel in the kernel arguments: no staging copy (a trial is launch-bound on the host: every
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->kept.tune.no_inline_move;
-	// (the three-body, disp-expansion and rd_crystal deltas read the moved atoms from the device lists: a box with one of them always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c);
+	// (the three-body, disp-expansion, rd_crystal, rd-model and contact deltas read the moved atoms from the device lists: a box with one of them always stages its move)
+	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c) && !contact_on(c);
 	if (c->trial_inline) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial_first + t;
@@ -460,6 +473,14 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_rd_model_delta(st, atoms_view(c), c->d_rdm_sp, c->box, rd_model_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rdm_part,
 		                      c->d_delta_out + D_RD);
+	}
+	if (contact_on(c)) {
+		// cavity_autoreject: the change of the contact counts of the pairs with a moved atom, O(m N), old positions still resident; into
+		// D_CA_REPLACED and D_CA_ABSOLUTE of the delta result block, which k_delta_finish posts with everything else
+		if ((rc = contact_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_contact_delta(st, atoms_view(c), c->kept.de_enabled ? c->d_de_co.p : c->d_rdm_sp.p, c->box, contact_params(c), c->d_mv_slot, c->d_mv_new, m,
+		                     c->d_moved_idx, c->d_ca_part, c->d_delta_out + D_CA_REPLACED);
 	}
 	{
 		FusedParams fp{};
@@ -536,15 +557,21 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	c->trial_enqueued = false;
 	if (c->trial_noop) {
 		c->trial_res = c->last_full;
+		c->ca_trial = c->ca_accepted;
 		c->trial_evaluated = true;
 		*out = c->trial_res;
+		contact_deliver(c, out, c->ca_trial);
 		return MPMC_OK;
 	}
 	if (c->trial_was_full) {
 		const int64_t terms_keep = c->rc_terms_accepted, rdm_terms_keep = c->rdm_terms_accepted;
-		int rc = mpmc_energy_wait(c, out);
+		const mpmc_ctx::ContactCounts ca_keep = c->ca_accepted;
+		int rc = wait_and_fill(c, out); // (the unpenalised result: what leaves is penalised below)
 		if (rc != MPMC_OK) return rc;
 		c->trial_res = *out;
+		c->ca_trial = c->ca_eval; // (cavity_autoreject: the full walk's counts are the trial's; the accepted ones stay until mpmc_trial_accept)
+		c->ca_accepted = ca_keep;
+		contact_deliver(c, out, c->ca_trial);
 		c->last_full = c->trial_keep; // still the ACCEPTED configuration's totals until mpmc_trial_accept
 		c->rc_terms_trial = c->rc_info.n_image_terms; // (rd_crystal: the same for the image-term count)
 		c->rc_terms_accepted = terms_keep;
@@ -579,6 +606,12 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		xch_result(c, c->trial_res);
 		c->trial_evaluated = true;
 		*out = c->trial_res;
+		if (contact_on(c)) { // (cavity_autoreject: the accepted counts plus or minus the molecule's contacts with the residents)
+			const double *dh = c->h_delta_out.p;
+			c->ca_trial.replaced = c->ca_accepted.replaced + (int64_t)dh[delta_host_index(D_CA_REPLACED)];
+			c->ca_trial.absolute = c->ca_accepted.absolute + (int64_t)dh[delta_host_index(D_CA_ABSOLUTE)];
+			contact_deliver(c, out, c->ca_trial, c->ca_frozen_pairs_trial);
+		}
 		return MPMC_OK;
 	}
 	const int do_es = c->opts.rd_only ? 0 : 1;
@@ -615,9 +648,14 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	if (c->kept.tb_enabled) r.three_body_energy = a.three_body_energy + dh[delta_host_index(D_THREE_BODY)];
 	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
 	r.NU = r.N * r.energy;
+	if (contact_on(c)) { // (cavity_autoreject: the accepted counts plus the change of the moved atoms' pairs)
+		c->ca_trial.replaced = c->ca_accepted.replaced + (int64_t)dh[delta_host_index(D_CA_REPLACED)];
+		c->ca_trial.absolute = c->ca_accepted.absolute + (int64_t)dh[delta_host_index(D_CA_ABSOLUTE)];
+	}
 	c->trial_res = r;
 	c->trial_evaluated = true;
 	*out = r;
+	contact_deliver(c, out, c->ca_trial);
 	return MPMC_OK;
 }
 
@@ -641,11 +679,13 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 		if (!c->trial_was_full) {
 			const int rc_x = xch_accept_delta(c);
 			if (rc_x != MPMC_OK) return rc_x;
+			if (contact_on(c)) c->ca_accepted = c->ca_trial;
 		} else {
 			c->last_full = c->trial_res;
 			c->cache_valid = true;
 			if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
 			if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
+			if (contact_on(c)) c->ca_accepted = c->ca_trial;
 		}
 		c->xch_saved.clear();
 		c->xch_kind = 0;
@@ -679,6 +719,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 	c->cache_valid = true;
 	if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
 	if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
+	if (contact_on(c)) c->ca_accepted = c->ca_trial;
 	c->trial_open = false;
 	c->trial_polar_delta = false;
 	return MPMC_OK;
@@ -782,6 +823,14 @@ extern "C" int mpmc_insert_candidates(mpmc_ctx *c, int count, int n_cand, const 
 	if ((rc = c->d_ins_cnt.reserve(c, chunk * nb * 2)) != MPMC_OK) return rc;
 	if ((rc = c->d_ins_out.reserve(c, (size_t)n_cand)) != MPMC_OK) return rc;
 	if ((rc = c->h_ins_out.reserve(c, (size_t)n_cand)) != MPMC_OK) return rc;
+	const bool contact = contact_on(c); // cavity_autoreject: per-candidate contacts by a sibling launch in every chain, behind the same wait
+	if (contact) {
+		if ((rc = contact_ready(c)) != MPMC_OK) return rc;
+		if ((rc = c->d_ca_xpart.reserve(c, chunk * (size_t)c->n_tiles * 2)) != MPMC_OK) return rc;
+		if ((rc = c->d_ins_ca.reserve(c, 2 * (size_t)n_cand)) != MPMC_OK) return rc;
+		if ((rc = c->h_ins_ca.reserve(c, 2 * (size_t)n_cand)) != MPMC_OK) return rc;
+	}
+	c->ins_ca_n = -1;
 
 	// the species part, once: the same for every pose
 	XchSums xs_trial;
@@ -816,14 +865,25 @@ extern "C" int mpmc_insert_candidates(mpmc_ctx *c, int count, int n_cand, const 
 		for (size_t q0 = p0; q0 < p1; q0 += kInsBatchChunk) {
 			const int nc = (int)std::min((size_t)kInsBatchChunk, p1 - q0);
 			launch_insert_batch(st, at, c->box, rv, fp, do_es, c->d_ins_mol + (q0 - p0) * m, m, nc, c->d_ins_sf, c->d_ins_part, c->d_ins_cnt, c->d_ins_out + q0);
+			if (contact)
+				launch_exchange_contact(st, at, c->box, contact_params(c), c->d_ins_mol + (q0 - p0) * m, m, nc, 1.0, c->d_ca_xpart, nullptr, c->d_ins_ca + 2 * q0);
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipMemcpyAsync(c->h_ins_out, c->d_ins_out, (size_t)n_cand * sizeof(InsCandOut), hipMemcpyDeviceToHost, st));
+	if (contact) HIP_TRY(c, hipMemcpyAsync(c->h_ins_ca, c->d_ins_ca, 2 * (size_t)n_cand * sizeof(long long), hipMemcpyDeviceToHost, st));
 	c->kept.n_stream_syncs++;
 	HIP_TRY(c, hipStreamSynchronize(st)); // the one wait of the call
 	prof_harvest(c);
 	for (int q = 0; q < n_cand; q++) xch_compose(c, +1, m, c->h_ins_out[q], st3, N, d, out[q]);
+	// (cavity_autoreject: the counts of each candidate's trial composition, and the sigma rule's penalty on out[q] as the single trial delivers it)
+	c->ins_ca.assign(2 * (size_t)n_cand, 0);
+	for (int q = 0; contact && q < n_cand; q++) {
+		c->ins_ca[2 * (size_t)q] = (c->kept.ca_rules & CA_RULE_SIGMA) ? c->ca_accepted.replaced + c->h_ins_ca[2 * (size_t)q] : 0;
+		c->ins_ca[2 * (size_t)q + 1] = (c->kept.ca_rules & CA_RULE_ABSOLUTE) ? c->ca_accepted.absolute + c->h_ins_ca[2 * (size_t)q + 1] : 0;
+		contact_penalise(c, &out[q], c->ins_ca[2 * (size_t)q]);
+	}
+	c->ins_ca_n = n_cand;
 	c->kept.n_ins_calls++;
 	c->kept.n_ins_cands += n_cand;
 	return MPMC_OK;

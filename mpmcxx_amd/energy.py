@@ -96,6 +96,25 @@ def rd_model_of(options: Dict[str, object]):
     return form, (RD_MIX[rules[0]] if rules else RD_MIX["lb"])
 
 
+class AutorejectInfo(C.Structure):
+    """mpmc_cavity_autoreject_info: the contact counts behind the last result delivered (evaluation, component call or trial)."""
+    _fields_ = [("rules", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("repulsion", C.c_double), ("n_replaced", C.c_int64),
+                ("n_absolute", C.c_int64), ("n_unmeasured_frozen", C.c_int64), ("absolute_penalty", C.c_double), ("returned_energy", C.c_double),
+                ("tile_pairs_walked", C.c_int64), ("tile_pairs_skipped", C.c_int64)]
+
+
+AUTOREJECT_SIGMA, AUTOREJECT_ABSOLUTE = 1, 2  # MPMC_AUTOREJECT_*
+AUTOREJECT_KEYS = ("cavity_autoreject", "cavity_autoreject_absolute", "cavity_autoreject_scale", "cavity_autoreject_repulsion")
+
+
+def autoreject_of(options: Dict[str, object]):
+    """(rules, scale, repulsion) of the reference keywords in `options`; the reference's default scale is 0, which it refuses with a rule on
+    (SimulationControl.cpp:2139-2154)."""
+    on = lambda v: bool(v) and not (isinstance(v, str) and v.lower() in ("off", "0"))  # (1 / True / "on", as the readers and gen_box spell it)
+    rules = (AUTOREJECT_SIGMA if on(options.get("cavity_autoreject")) else 0) | (AUTOREJECT_ABSOLUTE if on(options.get("cavity_autoreject_absolute")) else 0)
+    return rules, float(options.get("cavity_autoreject_scale") or 0.0), float(options.get("cavity_autoreject_repulsion") or 0.0)
+
+
 class RdCrystalInfo(C.Structure):
     """mpmc_rd_crystal_info: the last evaluation of a context with `rd_crystal` on."""
     _fields_ = [("order", C.c_int32), ("n_images", C.c_int32), ("cutoff", C.c_double), ("n_image_terms", C.c_int64), ("crystal_self", C.c_double)]
@@ -229,6 +248,11 @@ def lib():
     if hasattr(L, "mpmc_set_rd_model") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the rd model)
         L.mpmc_set_rd_model.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_rd_model_info.argtypes = [vp, C.POINTER(RdModelInfo)]
+    if hasattr(L, "mpmc_set_cavity_autoreject") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for cavity_autoreject)
+        L.mpmc_set_cavity_autoreject.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+        L.mpmc_cavity_autoreject_info.argtypes = [vp, C.POINTER(AutorejectInfo)]
+        if hasattr(L, "mpmc_insert_candidates_contacts") or not os.environ.get("MPMC_ENERGY_LIB"):
+            L.mpmc_insert_candidates_contacts.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "mpmc_set_polar_ewald_full") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the fully periodic dipole solve)
         L.mpmc_set_polar_ewald_full.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_polar_ewald_full_info.argtypes = [vp, C.POINTER(EwaldFullInfo)]
@@ -453,6 +477,10 @@ class System:
         if any(k in options for k in RD_MODEL_KEYS) or getattr(self, "_rd_model_set", False):
             self._rd_model_set = True
             self.set_rd_model(*rd_model_of(options))
+        # cavity_autoreject likewise: `cavity_autoreject`, `cavity_autoreject_absolute`, `cavity_autoreject_scale`, `cavity_autoreject_repulsion`
+        if any(k in options for k in AUTOREJECT_KEYS) or getattr(self, "_autoreject_set", False):
+            self._autoreject_set = True
+            self.set_cavity_autoreject(*autoreject_of(options))
 
         # `polar_ewald_full` likewise ("polar_ewald_full_flags": PEF_VECTOR_KWEIGHT or 0; the reference has no keyword for it)
         if "polar_ewald_full" in options or getattr(self, "_polar_ewald_full_set", False):
@@ -575,6 +603,31 @@ class System:
         self._check(self._L.mpmc_rd_model_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdModelInfo._fields_}
 
+    def set_cavity_autoreject(self, rules: int = 0, scale: float = 0.0, repulsion: float = 0.0):
+        """cavity_autoreject (mpmc_set_cavity_autoreject): rules = AUTOREJECT_SIGMA | AUTOREJECT_ABSOLUTE (0: off), scale in (0, 1]."""
+        self._check(self._L.mpmc_set_cavity_autoreject(self._h, int(rules), float(scale), float(repulsion)))
+        self._autoreject_on = int(rules) != 0
+
+    def cavity_autoreject_info(self) -> Dict[str, object]:
+        """rules, scale, repulsion, n_replaced, n_absolute, n_unmeasured_frozen, absolute_penalty, returned_energy, tile_pairs_walked and
+        tile_pairs_skipped behind the last result delivered (mpmc_cavity_autoreject_info)"""
+        v = AutorejectInfo()
+        self._check(self._L.mpmc_cavity_autoreject_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in AutorejectInfo._fields_ if k != "reserved"}
+
+    def insert_candidates_contacts(self, n_cand: int):
+        """(n_replaced[n_cand], n_absolute[n_cand]) of the last insert_candidates batch: the contact counts of each candidate's trial
+        composition, as cavity_autoreject_info gives them behind the single insertion trial (mpmc_insert_candidates_contacts)"""
+        r, a = np.zeros(int(n_cand), dtype=np.int64), np.zeros(int(n_cand), dtype=np.int64)
+        self._check(self._L.mpmc_insert_candidates_contacts(self._h, int(n_cand), r.ctypes.data_as(C.POINTER(C.c_int64)), a.ctypes.data_as(C.POINTER(C.c_int64))))
+        return r, a
+
+    def _returned(self, energy: float) -> float:
+        """what System::energy() returns: the observables' energy, plus the absolute-rule penalty of cavity_autoreject when a rule is on"""
+        if not getattr(self, "_autoreject_on", False):
+            return energy
+        return self.cavity_autoreject_info()["returned_energy"]
+
     def set_polar_relax(self, scheme=0, zodid: bool = False):
         """`polar_sor` / `polar_esor` (scheme "sor" / "esor" or POLAR_RELAX[...]; "none" / 0 switches off) and `polar_zodid`
         (mpmc_set_polar_relax); gamma is the option polar_gamma."""
@@ -659,7 +712,7 @@ class System:
         r = Result()
         self._check(self._L.mpmc_energy(self._h, C.byref(r)))
         self.observables = r.as_dict()
-        return r.energy
+        return self._returned(r.energy)
 
     def hint_in_flight(self, n: int):
         """scheduling hint for energy_async: how many evaluations the caller keeps in flight together with this one (mpmc_hint_in_flight)."""
@@ -672,7 +725,7 @@ class System:
         r = Result()
         self._check(self._L.mpmc_energy_wait(self._h, C.byref(r)))
         self.observables = r.as_dict()
-        return r.energy
+        return self._returned(r.energy)
 
     # -- trial moves (reference: per-pair recalculate_energy cache, src/System.cpp:1211-1224) ------------------------------
     def trial_energy(self, first: int, pos: np.ndarray) -> float:
@@ -686,7 +739,7 @@ class System:
             self._L.mpmc_trial_reject(self._h)
             self._check(rc)
         self.trial_observables = r.as_dict()
-        return r.energy
+        return self._returned(r.energy)
 
     @property
     def atoms(self) -> Dict[str, np.ndarray]:
@@ -702,7 +755,7 @@ class System:
             self._exchange = None
             raise MpmcError(rc, msg)
         self.trial_observables = r.as_dict()
-        return r.energy
+        return self._returned(r.energy)
 
     def trial_insert_energy(self, at_index: int, mol_atoms: Dict[str, np.ndarray]) -> float:
         """energy of the composition with ONE more molecule: the atoms of `mol_atoms` (the keys of the atoms dict; mol_id is not read, the
