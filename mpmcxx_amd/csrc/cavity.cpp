@@ -79,7 +79,7 @@ extern "C" int mpmc_uvt_boltzmann_factor(const mpmc_uvt_move *m, double *boltzma
 // ---- the setting --------------------------------------------------------------------------------------------------------------------------
 extern "C" int mpmc_set_cavity_grid(mpmc_ctx *c, int grid_size, double radius) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_cavity_grid: a trial move is open");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_cavity_grid: a trial move is open");
 	if (grid_size != 0) {
 		if (grid_size < 0 || !(radius > 0.0) || !std::isfinite(radius)) // SimulationControl.cpp:2157-2162
 			return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_cavity_grid: cavity_bias needs a grid size and a sphere radius greater than zero");
@@ -124,7 +124,7 @@ extern "C" int mpmc_cavity_update(mpmc_ctx *c, int n_darts, const double *dart_f
 	if (c->kept.cav_grid <= 0) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_update: the cavity grid is off (mpmc_set_cavity_grid)");
 	if (!c->atoms_set || !c->box_set) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_update: atoms and box must be set");
 	if (c->h_mass.empty()) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_update: mpmc_set_atoms was called without masses (the wrapped positions need the centres of mass)");
-	if (c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_update: a trial move is open (accept or reject it first)");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_cavity_update: a trial move is open (accept or reject it first)");
 	// (every path that moves atoms -- mpmc_update_positions, mpmc_set_positions_device, the bead loops, accepted trials -- brings the host
 	// mirror along before it returns: there is no state in which the latest positions live on the device alone)
 	HIP_TRY(c, hipSetDevice(c->device));

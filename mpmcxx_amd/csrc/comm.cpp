@@ -60,7 +60,7 @@ static std::string dir_of_bound_hip_runtime() {
 //   4. the loader's search path.
 // Always RTLD_LOCAL.  Round 4 opened /opt/rocm's copy RTLD_GLOBAL: its librocm_smi64.so.1 then sat in the global scope, the
 // librocm_smi64.so.7 of a PyTorch imported LATER bound its exported statics (amd::smi::Device::devInfoTypesStrings) to the first copy, and
-// both ran the destructor at exit -- "double free or corruption" (tests/test_rccl_loading.py replays that order in a child process).
+// both ran the destructor at exit -- "double free or corruption" (tests/test_ranks.py replays that order in a child process).
 RcclApi *rccl() {
 	RcclApi &api = g_rccl;
 	static std::once_flag once;

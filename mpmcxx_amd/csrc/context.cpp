@@ -695,7 +695,7 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->atoms_set = true;
 	c->pending = false;
 	c->cache_valid = false;
-	c->trial_open = false;
+	c->trial.open = false;
 	c->tb_have = false; // per-atom three-body coefficients belong to the old list (mpmc_set_axilrod_teller again)
 	c->tb_dirty = false;
 	c->h_tb_au.clear();
@@ -841,7 +841,7 @@ void mpmc::xch_static_terms(const mpmc_ctx *c, const XchSums &xs, double out3[3]
 // ---- `polar_wolf` / `polar_palmo` ------------------------------------------------------------------------------------------------------
 extern "C" int mpmc_set_polar_wolf(mpmc_ctx *c, int enabled, double polar_wolf_alpha) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_wolf: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_wolf: an evaluation or a trial move is open");
 	if (enabled && (!std::isfinite(polar_wolf_alpha) || polar_wolf_alpha < 0.0 || polar_wolf_alpha > 1.0)) // SimulationControl.cpp:2652-2660
 		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_wolf: polar_wolf_alpha must be in [0, 1]");
 	const bool on = enabled != 0;
@@ -855,7 +855,7 @@ extern "C" int mpmc_set_polar_wolf(mpmc_ctx *c, int enabled, double polar_wolf_a
 }
 extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_palmo: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_palmo: an evaluation or a trial move is open");
 	if ((enabled != 0) != c->kept.palmo_enabled) c->cache_valid = false; // (the accepted totals carry the correction)
 	c->kept.palmo_enabled = enabled != 0;
 	return MPMC_OK;
@@ -864,7 +864,7 @@ extern "C" int mpmc_set_polar_palmo(mpmc_ctx *c, int enabled) {
 // ---- `polar_sor` / `polar_esor` / `polar_zodid` (thole_iterative :3450-3560, new_dipoles :3181-3211) ------------------------------------------
 extern "C" int mpmc_set_polar_relax(mpmc_ctx *c, int scheme, int zodid) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_relax: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_relax: an evaluation or a trial move is open");
 	if (scheme != MPMC_POLAR_RELAX_NONE && scheme != MPMC_POLAR_RELAX_SOR && scheme != MPMC_POLAR_RELAX_ESOR)
 		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_relax: unknown scheme (MPMC_POLAR_RELAX_NONE, _SOR or _ESOR)");
 	const bool z = zodid != 0;
@@ -889,7 +889,7 @@ extern "C" int mpmc_polar_relax_info(mpmc_ctx *c, mpmc_relax_info *out) {
 // ---- `polar_gs_ranked` (System::pairs :1001-1029, thole_iterative :3450-3543, update_ranking :3631-3656) -----------------------------------
 extern "C" int mpmc_set_polar_gs_ranked(mpmc_ctx *c, int enabled) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_gs_ranked: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_gs_ranked: an evaluation or a trial move is open");
 	const bool on = enabled != 0;
 	if (on == c->kept.gs_ranked) return MPMC_OK;
 	c->cache_valid = false; // (the accepted totals, the tensor store and an open on-demand solve belong to the other solve)
@@ -925,7 +925,7 @@ extern "C" int mpmc_polar_gs_ranked_get(mpmc_ctx *c, int32_t *rank_metric, int32
 // (diagnostics) the device's sort on keys of the caller's: what the sweeps would run in if these were the ranks
 extern "C" int mpmc_debug_gs_rank_order(mpmc_ctx *c, const int32_t *keys, int32_t *order) {
 	if (!c || !keys || !order) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_rank_order: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_rank_order: an evaluation or a trial move is open");
 	int rc = prepare(c);
 	if (rc != MPMC_OK) return rc;
 	if ((rc = c->d_gr_rank.reserve(c, 2 * (size_t)c->max_pad)) != MPMC_OK) return rc;
@@ -945,7 +945,7 @@ extern "C" int mpmc_debug_gs_rank_order(mpmc_ctx *c, const int32_t *keys, int32_
 // ---- `polar_ewald_full` (System::ewald_full :2785-2830) ------------------------------------------------------------------------------------
 extern "C" int mpmc_set_polar_ewald_full(mpmc_ctx *c, int enabled, int flags) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_ewald_full: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_polar_ewald_full: an evaluation or a trial move is open");
 	if (flags & ~MPMC_PEF_VECTOR_KWEIGHT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_polar_ewald_full: unknown flag bits");
 	const bool on = enabled != 0;
 	if (on != c->kept.pef_enabled || (on && flags != c->kept.pef_flags)) {
@@ -970,7 +970,7 @@ extern "C" int mpmc_polar_ewald_full_info(mpmc_ctx *c, mpmc_ewald_full_info *out
 // ---- `rd_crystal` (System::lj :916-963, rd_crystal_self :1152-1208) ----------------------------------------------------------------------
 extern "C" int mpmc_set_rd_crystal(mpmc_ctx *c, int enabled, int order) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_crystal: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_crystal: an evaluation or a trial move is open");
 	if (enabled && order < 1) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_crystal: rd_crystal_order must be at least 1"); // SimulationControl.cpp:1688-1692
 	if (enabled && order > MPMC_RD_CRYSTAL_MAX_ORDER)
 		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_crystal: rd_crystal_order above MPMC_RD_CRYSTAL_MAX_ORDER");
@@ -996,7 +996,7 @@ static_assert(MPMC_RD_MIX_LB == RD_MIX_LB && MPMC_RD_MIX_WALDMAN_HAGLER == RD_MI
               "pair_math.h mirrors the header");
 extern "C" int mpmc_set_rd_model(mpmc_ctx *c, int form, int mixing) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_model: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_rd_model: an evaluation or a trial move is open");
 	if (form < 0 || form >= RD_FORM_COUNT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_model: unknown potential form (MPMC_RD_FORM_*)");
 	if (mixing < 0 || mixing >= RD_MIX_COUNT) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_rd_model: unknown mixing rule (MPMC_RD_MIX_*)");
 	if (form != c->kept.rdm_form || mixing != c->kept.rdm_mix) {
@@ -1018,7 +1018,7 @@ extern "C" int mpmc_rd_model_info(mpmc_ctx *c, struct mpmc_rd_model_info *out) {
 static_assert(MPMC_AUTOREJECT_SIGMA == CA_RULE_SIGMA && MPMC_AUTOREJECT_ABSOLUTE == CA_RULE_ABSOLUTE, "kernels.h mirrors the header");
 extern "C" int mpmc_set_cavity_autoreject(mpmc_ctx *c, int rules, double scale, double repulsion) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_cavity_autoreject: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_cavity_autoreject: an evaluation or a trial move is open");
 	if (rules & ~(MPMC_AUTOREJECT_SIGMA | MPMC_AUTOREJECT_ABSOLUTE)) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_cavity_autoreject: unknown rule bits (MPMC_AUTOREJECT_*)");
 	if (rules && !(scale > 0.0 && scale <= 1.0)) // SimulationControl.cpp:2139-2154 (a NaN fails the test too)
 		return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_cavity_autoreject: cavity_autoreject_scale must be in (0, 1]");
@@ -1240,7 +1240,7 @@ static void three_body_coefficients(int n, const double *alpha, int mk, const do
 
 extern "C" int mpmc_set_axilrod_teller(mpmc_ctx *c, int enabled, int mk, const double *c6, const double *c9) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_axilrod_teller: an evaluation or a trial move is open");
 	if (!enabled) {
 		if (c->kept.tb_enabled) c->cache_valid = false; // (the accepted totals carry the term)
 		c->kept.tb_enabled = c->kept.tb_mk = c->tb_have = c->tb_dirty = false;
@@ -1327,7 +1327,7 @@ static void disp_lrc(mpmc_ctx *c) {
 
 extern "C" int mpmc_set_disp_expansion(mpmc_ctx *c, int enabled, int flags, const double *c6, const double *c8, const double *c10) {
 	if (!c) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: an evaluation or a trial move is open");
 	if (flags & ~(MPMC_DISP_DAMP | MPMC_DISP_EXTRAPOLATE_C10 | MPMC_DISP_SCHMIDT)) return fail(c, MPMC_ERR_ARG, "mpmc_set_disp_expansion: unknown flag bits");
 	// (a context with rd_crystal set takes its long-range corrections at the crystal cutoff only while this term is off: lrc_box)
 	if ((enabled != 0) != c->kept.de_enabled && c->kept.rc_enabled) c->static_dirty = true, c->static_gen++;
@@ -1466,7 +1466,7 @@ extern "C" int mpmc_update_positions(mpmc_ctx *c, int first, int count, const do
 extern "C" int mpmc_set_positions_device(mpmc_ctx *c, const double *pos_device) {
 	if (!c || !pos_device) return MPMC_ERR_ARG;
 	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: no atoms set");
-	if (c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: a trial move is open (accept or reject it first)");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: a trial move is open (accept or reject it first)");
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "mpmc_set_positions_device: an evaluation is in flight (mpmc_energy_wait first)");
 	c->cache_valid = false; // the accepted totals / structure factors no longer describe the resident configuration
 	drop_pending_dipoles(c);
@@ -1578,7 +1578,7 @@ extern "C" int mpmc_debug_pair_stats(mpmc_ctx *c, int64_t out[12]) {
 //   some dimension      5 ... where that common image is not the zero image (4 and 5: 0 with uniform_images or tile_classes off)
 extern "C" int mpmc_debug_gs_ranked_pair_stats(mpmc_ctx *c, int64_t out[6]) {
 	if (!c || !out) return MPMC_ERR_ARG;
-	if (c->pending || c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_ranked_pair_stats: an evaluation or a trial move is open");
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_ranked_pair_stats: an evaluation or a trial move is open");
 	if (!c->kept.gs_ranked || !c->gr_ran || c->gr_info.ranked_sweeps < 1 || c->gr_pos_gen != c->pos_gen || c->gr_static_gen != c->static_gen || !c->d_gr_cls)
 		return fail(c, MPMC_ERR_ARG, "mpmc_debug_gs_ranked_pair_stats: the last evaluation swept no ranked view");
 	HIP_TRY(c, hipSetDevice(c->device));

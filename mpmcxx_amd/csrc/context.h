@@ -166,6 +166,38 @@ struct XchSums {
 	int32_t mol_max = 0;              // largest molecule id of the list
 };
 
+struct ContactCounts { // cavity_autoreject (kernels_contact.hip): pairs replaced by MAXVALUE, absolute contacts
+	int64_t replaced = 0, absolute = 0;
+};
+// What the context remembers of ONE configuration's totals, in three roles: `accepted` (the accepted configuration, valid with cache_valid),
+// `trial.totals` (the evaluated trial) and `eval` (the last evaluation waited for).  wait_and_fill fills `eval` and nothing else; the entry
+// point that waited decides: a complete energy() re-bases (rebase_on_eval), a full-evaluation trial takes `eval` as its trial record,
+// mpmc_trial_accept ends in accepted = trial.totals.
+struct ConfigTotals {
+	mpmc_result res{};         // UNPENALISED: lj_pairs = the kernels' sum S, so that a trial's delta adds to S and not to S + n 1e40; the penalty of
+	                           // cavity_autoreject is put on the copy that leaves the library (contact_deliver, evaluate.cpp)
+	int64_t rc_terms = 0;      // rd_crystal: image terms (mpmc_rd_crystal_info's n_image_terms)
+	int64_t rdm_terms = 0;     // the rd model: kept terms (mpmc_rd_model_info's n_terms)
+	ContactCounts ca;          // cavity_autoreject: the contact counts
+	int64_t frozen_pairs = -1; // cavity_autoreject: unmeasured pairs of two frozen atoms of this composition; -1: the resident list's own (ca_frozen_pairs)
+};
+// The open trial move (trial.cpp), as far as the host describes it: xch_replace_list carries it across mpmc_set_atoms as a whole.  What
+// belongs to buffers or to the device (trial_seq, d_mv_*, mv_inline, the tile lists) stays in the context.
+struct TrialState {
+	bool open = false, evaluated = false, was_full = false, enqueued = false, noop = false;
+	bool polar_delta = false; // took the incremental polarizable path (positions swapped on the device)
+	bool inline_move = false; // the move travelled in the kernel arguments (mv_inline)
+	int first = 0, count = 0;
+	std::vector<double> pos_new, pos_old;
+	// exchange trials (mpmc_trial_insert_begin / mpmc_trial_remove_begin): the open trial changes the composition by ONE molecule
+	int xch_kind = 0;            // 0 a displacement, +1 an insertion, -1 a removal
+	int xch_at = 0;              // index the molecule goes in front of / of its first atom (original order); `count` atoms
+	AtomRun xch_mol;             // the molecule: as given (insertion) or copied from the host mirrors (removal)
+	AtomRun xch_saved;           // full-evaluation trials: the accepted atom list, which a rejection puts back
+	double xch_static[3] = {0, 0, 0}, xch_N = 0; // lrc_pair, lrc_self, es_self and countN of the evaluated trial composition
+	ConfigTotals totals;         // of the evaluated trial
+};
+
 struct mpmc_ctx {
 	mpmc_kept kept;
 	int device = 0;
@@ -323,14 +355,10 @@ struct mpmc_ctx {
 	unsigned run_mask = 0;
 
 	// trial moves (delta energies)
-	bool cache_valid = false;   // last_full = totals of the accepted configuration, d_sf = its structure factors
-	mpmc_result last_full{};
-	mpmc_result trial_res{};
+	bool cache_valid = false;   // `accepted` = totals of the accepted configuration, d_sf = its structure factors
+	ConfigTotals accepted, eval; // (the three roles of the record: ConfigTotals)
+	TrialState trial;
 	int trial_last_kind = -1; // (diagnostics) the last enqueued trial: 1 full evaluation, 0 delta energies
-	bool trial_open = false, trial_evaluated = false, trial_was_full = false, trial_enqueued = false, trial_noop = false;
-	mpmc_result trial_keep{}; // accepted totals while a full-evaluation trial is in flight
-	int trial_first = 0, trial_count = 0;
-	std::vector<double> trial_new, trial_old;
 	int *d_mv_slot = nullptr, *d_mv_orig = nullptr; // d_mv_slot/d_mv_orig/d_mv_new live in ONE allocation (d_mv_blob)
 	double4 *d_mv_new = nullptr;
 	DevBuf<int> d_moved_idx;
@@ -339,7 +367,6 @@ struct mpmc_ctx {
 	// (e_real + delta of the pairs with a moved atom); they trade places on accept.  dk_part: scratch of k_field_delta.
 	DevBuf<double> d_e_real, d_e_real_trial, d_dk_part;
 	bool e_real_valid = false;     // d_e_real describes the accepted configuration
-	bool trial_polar_delta = false; // the open trial took the incremental polarizable path (positions swapped on the device)
 	// the tensor store between trial moves: a trial rebuilds only the tile pairs of the tiles its moved atoms live in; after a REJECTED
 	// trial those tiles hold the rejected geometry's tensors and are rebuilt by the next trial (or by any full evaluation)
 	std::vector<int> store_dirty_tiles, trial_tiles;
@@ -348,16 +375,11 @@ struct mpmc_ctx {
 	PinnedBuf<unsigned char> h_mv_blob;
 	DevBuf<double> d_delta_out;    // [D_COUNT]
 	PinnedBuf<double> h_delta_out; // [kDeltaHostCount]: d_delta_out's D_* slots at delta_host_index, the launch number k_delta_finish posts at kDeltaHostSeq (kernels.h)
-	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial_inline)
-	bool trial_inline = false;
+	MvInline mv_inline{};          // the pending trial's move when it travelled in the kernel arguments (trial.inline_move)
 	double trial_seq = 0;          // launch number of the pending trial's k_delta_finish
 	long long *d_delta_cnt = nullptr, *h_delta_cnt = nullptr; // (the counts' part of d_delta_out / h_delta_out)
 
-	// exchange trials (mpmc_trial_insert_begin / mpmc_trial_remove_begin): the open trial changes the composition by ONE molecule
-	int xch_kind = 0;            // of the open trial: 0 a displacement, +1 an insertion, -1 a removal
-	int xch_at = 0;              // index the molecule goes in front of / of its first atom (original order); trial_count atoms
-	AtomRun xch_mol;             // the molecule: as given (insertion) or copied from the host mirrors (removal)
-	AtomRun xch_saved;           // full-evaluation trials: the accepted atom list, which a rejection puts back
+	// exchange trials (the open one: trial.xch_*)
 	DevBuf<XchAtom> d_xch_mol;   // [MPMC_TRIAL_MAX_ATOMS] the staged molecule of the delta path
 	PinnedBuf<XchAtom> h_xch_mol;
 	// The position-independent terms of the trial composition come from the sums of k_atom_terms_part, kept on the host for the accepted
@@ -367,7 +389,6 @@ struct mpmc_ctx {
 	XchSums xs_acc, xs_trial;
 	unsigned xs_gen = 0;         // static_gen of xs_acc (0: none)
 	int xs_edits = 0;            // accepted exchanges since xs_acc was summed over the list
-	double xch_static[3] = {0, 0, 0}, xch_N = 0; // lrc_pair, lrc_self, es_self and countN of the evaluated trial composition
 
 	// batched insertion candidates (mpmc_insert_candidates, kernels_insert_batch.hip): all allocated by the first call.  The staging block
 	// holds one pass of candidates (kInsStageRecords records at the most), the device scratch one launch chain (kInsBatchChunk candidates).
@@ -411,7 +432,6 @@ struct mpmc_ctx {
 	DevBuf<double4> d_rc_shift;             // [n_img] lattice vectors of the images, reference order
 	DevBuf<double> d_rc_part;               // [2 kCrystalBlocks] per-workgroup partials: energies, image-term counts
 	struct mpmc_rd_crystal_info rc_info{};         // of the last evaluation with the term (mpmc_rd_crystal_info)
-	int64_t rc_terms_accepted = 0, rc_terms_trial = 0; // image terms of the accepted configuration (with last_full) / of the evaluated trial
 
 	// the rd model (mpmc_set_rd_model, kernels_rd_model.hip; kept.rdm_form, kept.rdm_mix): another mixing rule / pair function in place of the
 	// LJ sums of rd_energy.  The per-atom table follows the spatial order (rebuilt behind every upload of the atoms: rd_model_ready); the LJ
@@ -425,21 +445,14 @@ struct mpmc_ctx {
 	double rdm_lrc = 0, rdm_lrc_volume = 0, rdm_lrc_cutoff = 0;
 	int rdm_lrc_rd_lrc = 0, rdm_lrc_mix = -1;
 	struct mpmc_rd_model_info rdm_info{};   // of the last evaluation with a non-default model (mpmc_rd_model_info)
-	int64_t rdm_terms_accepted = 0, rdm_terms_trial = 0; // kept terms of the accepted configuration (with last_full) / of the evaluated trial
 
-	// cavity_autoreject (mpmc_set_cavity_autoreject, kernels_contact.hip; kept.ca_rules, kept.ca_scale): the contact counts.  Every result
-	// the context keeps (last_full, trial_res, trial_keep) is the UNPENALISED one -- lj_pairs = the kernels' sum S --, so that a trial's delta
-	// adds to S and not to S + n 1e40; the penalty is put on the copy that leaves the library (contact_deliver, evaluate.cpp).
-	struct ContactCounts {
-		int64_t replaced = 0, absolute = 0;
-	};
-	ContactCounts ca_eval, ca_accepted, ca_trial; // of the last evaluation waited for / of the accepted configuration (with last_full) / of the evaluated trial
+	// cavity_autoreject (mpmc_set_cavity_autoreject, kernels_contact.hip; kept.ca_rules, kept.ca_scale); the contact counts of a configuration
+	// travel in its record, next to the UNPENALISED result they belong to (ConfigTotals: accepted, trial.totals, eval)
 	int64_t ca_walked = 0, ca_skipped = 0;        // tile pairs of the last full walk
 	bool ca_dirty = true;                         // ca_sigma_max and ca_frozen_pairs are older than the atom list
 	double ca_sigma_max = 0.0;                    // largest |sigma| of the list: scale * it bounds the sigma rule's contact distance
 	int64_t ca_frozen_pairs = 0;                  // pairs of two frozen atoms of different molecules
 	int64_t ca_frozen_atoms = 0;                  // frozen atoms of the list
-	int64_t ca_frozen_pairs_trial = 0;            // ... of the evaluated exchange trial's composition (delta path)
 	DevBuf<int> d_ca_xpart;                       // [candidates of a chain][n_tiles][2] per-tile contacts of a staged molecule (launch_exchange_contact)
 	DevBuf<long long> d_ins_ca;                   // [n_cand][2] per-candidate contacts of the last batch of insertion candidates
 	PinnedBuf<long long> h_ins_ca;                // likewise, on their way to the host
@@ -692,9 +705,22 @@ int contact_ready(mpmc_ctx *c);    // the rules' combinations are valid, the lis
 ContactParams contact_params(const mpmc_ctx *c); // rules, scale, the rd function's distance test and mixing, dmax (context.cpp)
 // the copy of a result that leaves the library: the sigma rule's n 1e40 on lj_pairs (rd_energy, energy, NU follow), and the info struct of
 // this delivery (evaluate.cpp)
-// frozen_pairs: the unmeasured frozen pairs of the delivered composition (-1: the accepted list's)
-void contact_deliver(mpmc_ctx *c, mpmc_result *r, const mpmc_ctx::ContactCounts &n, int64_t frozen_pairs = -1);
+// (t: the record of the delivered configuration; its contact counts and its unmeasured frozen pairs)
+void contact_deliver(mpmc_ctx *c, mpmc_result *r, const ConfigTotals &t);
 void contact_penalise(const mpmc_ctx *c, mpmc_result *r, int64_t n_replaced); // the sigma rule's n 1e40 on lj_pairs; rd_energy, energy, NU follow
+// The one composition of a result's totals (evaluate.cpp): rd_energy from lj_pairs, lrc_pair and lrc_self in the given form, then energy
+// and NU from the components and N already in *r.  A trial's delta adds to the accepted totals because everybody composes here, in one
+// association order.  The caller names the form: an evaluation by what it ran, a trial by the terms that are on (rd_form_of).
+enum class RdForm {
+	PLAIN,          // (lj_pairs + lrc_pair) + lrc_self
+	CRYSTAL_SELF,   // ((lj_pairs + lrc_pair) + crystal_self) + lrc_self: rd_crystal, in lj()'s order
+	NO_CORRECTIONS  // lj_pairs: lj_buffered_14_7() and dreiding() have no long-range correction
+};
+void compose_totals(const mpmc_ctx *c, RdForm form, mpmc_result *r);
+inline RdForm rd_form_of(const mpmc_ctx *c) { // by the terms switched on (the trial paths, contact_penalise)
+	if (rd_model_on(c)) return c->kept.rdm_form == RD_FORM_LJ ? RdForm::PLAIN : RdForm::NO_CORRECTIONS;
+	return crystal_on(c) ? RdForm::CRYSTAL_SELF : RdForm::PLAIN;
+}
 int crystal_ready(mpmc_ctx *c);    // the image table, cutoff, thresholds and crystal_self of the current cell and atoms are in place (context.cpp)
 CrystalParams crystal_params(const mpmc_ctx *c); // rc_par with this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see it: rd_crystal puts its own cutoff in (evaluate.cpp)
@@ -702,7 +728,10 @@ int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (
 // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp: a plan, the room it needs, then the stages); on_demand: where
 // the energy comes from the moments of the first half of the iterations, stop there and leave the rest to finish_pending_dipoles
 int enqueue(mpmc_ctx *c, unsigned mask, bool on_demand = false);
-int wait_and_fill(mpmc_ctx *c, mpmc_result *out); // waits for it and assembles the result (evaluate.cpp)
+// waits for it and assembles the result into *out and c->eval (evaluate.cpp).  It FILLS: the accepted record and cache_valid are its
+// callers' -- mpmc_energy_wait and the component entry points re-base (where run_mask == full_mask), the trial paths do not
+int wait_and_fill(mpmc_ctx *c, mpmc_result *out);
+inline void rebase_on_eval(mpmc_ctx *c) { c->accepted = c->eval, c->cache_valid = true; }
 unsigned full_mask(const mpmc_ctx *c);           // what double System::energy() runs under the current options
 // The polarization energy of a Jacobi solve with a fixed iteration count n and mu_0 = alpha E0 is -1/2 sum_k m_k over the moments of the
 // first ceil(n/2) dipole differences: not for polar_gamma != 1, precision-terminated or rrms-reporting solves,

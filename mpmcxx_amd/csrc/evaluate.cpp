@@ -1289,12 +1289,12 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->gr_info.max_rank = c->h_gr_info[0].max_rank;
 		c->gr_info.n_moved = c->h_gr_info[0].n_moved;
 	}
-	if (c->run_mask & RUN_CONTACT) { // cavity_autoreject: the counts of this evaluation (they re-base the accepted ones with a complete energy())
-		c->ca_eval.replaced = (int64_t)c->h_scal[S_CA_REPLACED];
-		c->ca_eval.absolute = (int64_t)c->h_scal[S_CA_ABSOLUTE];
+	ConfigTotals &ev = c->eval;
+	if (c->run_mask & RUN_CONTACT) { // cavity_autoreject: the counts of this evaluation
+		ev.ca.replaced = (int64_t)c->h_scal[S_CA_REPLACED];
+		ev.ca.absolute = (int64_t)c->h_scal[S_CA_ABSOLUTE];
 		c->ca_skipped = (int64_t)c->h_scal[S_CA_SKIPPED];
 		c->ca_walked = (int64_t)c->n_tile_pairs - c->ca_skipped;
-		if (c->run_mask == full_mask(c)) c->ca_accepted = c->ca_eval;
 	}
 	if (!out) return MPMC_OK;
 	std::memset(out, 0, sizeof(*out));
@@ -1318,14 +1318,15 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		out->lrc_pair = lrc ? c->h_static[0] : 0.0;
 		out->lrc_self = lrc ? c->h_static[1] : 0.0;
 	}
-	out->rd_energy = (out->lj_pairs + out->lrc_pair) + out->lrc_self;
+	RdForm form = RdForm::PLAIN; // (by what this evaluation RAN: a component call's mask need not follow the switches)
 	if (c->run_mask & RUN_CRYSTAL) { // the lattice sum replaces the LJ sum of the pair kernels; crystal_self joins in lj()'s order (:1011-1028)
 		out->lj_pairs = s[S_CRYSTAL];
-		out->rd_energy = ((out->lj_pairs + out->lrc_pair) + c->rc_self) + out->lrc_self;
+		form = RdForm::CRYSTAL_SELF;
+		ev.rc_terms = (int64_t)s[S_CRYSTAL_TERMS];
 		c->rc_info.order = c->rc_table_order;
 		c->rc_info.n_images = c->rc_par.n_img;
 		c->rc_info.cutoff = c->rc_cut;
-		c->rc_info.n_image_terms = (int64_t)s[S_CRYSTAL_TERMS];
+		c->rc_info.n_image_terms = ev.rc_terms;
 		c->rc_info.crystal_self = c->rc_self;
 	}
 	if (c->run_mask & RUN_RDM) { // the model's sum replaces the LJ sum of the pair kernels; the LJ form keeps lj()'s order of composition
@@ -1334,14 +1335,15 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 			const bool lrc = (c->run_mask & RUN_ATOMTERMS) && c->opts.rd_lrc;
 			out->lrc_pair = lrc ? c->rdm_lrc : 0.0;
 			out->lrc_self = lrc ? c->h_static[1] : 0.0;
-			out->rd_energy = (out->lj_pairs + out->lrc_pair) + out->lrc_self;
+			form = RdForm::PLAIN;
 		} else { // (lj_buffered_14_7() and dreiding() have no long-range correction)
 			out->lrc_pair = out->lrc_self = 0.0;
-			out->rd_energy = out->lj_pairs;
+			form = RdForm::NO_CORRECTIONS;
 		}
+		ev.rdm_terms = (int64_t)s[S_RDM_TERMS];
 		c->rdm_info.form = c->kept.rdm_form;
 		c->rdm_info.mixing = c->kept.rdm_mix;
-		c->rdm_info.n_terms = (int64_t)s[S_RDM_TERMS];
+		c->rdm_info.n_terms = ev.rdm_terms;
 		c->rdm_info.n_tile_pairs = c->n_tile_pairs;
 		c->rdm_info.n_tile_pairs_skipped = (int64_t)s[S_RDM_SKIPPED];
 	}
@@ -1353,9 +1355,8 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	if (c->run_mask & RUN_SOLVE) c->palmo_correction = c->palmo_ran ? s[S_PALMO] : 0.0;
 	out->dipole_rrms = s[S_RRMS];
 	out->three_body_energy = (c->run_mask & RUN_THREE_BODY) ? s[S_THREE_BODY] : 0.0;
-	out->energy = out->rd_energy + out->coulombic_energy + out->polarization_energy + out->vdw_energy + out->three_body_energy; // :136
 	out->N = c->N_movable;
-	out->NU = out->N * out->energy; // :162
+	compose_totals(c, form, out);
 	out->n_pairs = (int64_t)c->n * (c->n - 1) / 2;
 	out->n_lj_in_cutoff = c->h_cnt[C_LJ_IN];
 	out->n_es_in_cutoff = c->h_cnt[C_ES_IN];
@@ -1365,13 +1366,18 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	out->n_frozen = c->static_cnt[3];
 	out->polar_iterations = c->iters;
 	out->iterator_failed = c->failed;
-	if (c->run_mask == full_mask(c)) { // a complete energy(): it re-bases the trial-move totals
-		c->last_full = *out;
-		c->cache_valid = true;
-		c->rc_terms_accepted = c->rc_info.n_image_terms;
-		c->rdm_terms_accepted = c->rdm_info.n_terms;
-	}
+	ev.res = *out; // (whether this re-bases the accepted record is the caller's decision: rebase_on_eval)
 	return MPMC_OK;
+}
+
+void mpmc::compose_totals(const mpmc_ctx *c, RdForm form, mpmc_result *r) {
+	switch (form) {
+	case RdForm::PLAIN: r->rd_energy = (r->lj_pairs + r->lrc_pair) + r->lrc_self; break;
+	case RdForm::CRYSTAL_SELF: r->rd_energy = ((r->lj_pairs + r->lrc_pair) + c->rc_self) + r->lrc_self; break;
+	case RdForm::NO_CORRECTIONS: r->rd_energy = r->lj_pairs; break;
+	}
+	r->energy = r->rd_energy + r->coulombic_energy + r->polarization_energy + r->vdw_energy + r->three_body_energy; // :136
+	r->NU = r->N * r->energy; // :162
 }
 
 unsigned mpmc::full_mask(const mpmc_ctx *c) {
@@ -1404,24 +1410,23 @@ extern "C" int mpmc_hint_in_flight(mpmc_ctx *c, int n) {
 	return MPMC_OK;
 }
 // What leaves the library under cavity_autoreject.  r is the unpenalised result of a configuration with the contact counts n: the sigma
-// rule's pairs get MAXVALUE in lj_pairs, and rd_energy, energy and NU follow in the order of wait_and_fill; the absolute rule stays out of
+// rule's pairs get MAXVALUE in lj_pairs, and rd_energy, energy and NU follow (compose_totals); the absolute rule stays out of
 // mpmc_result (it mirrors the observables) and shows in the info struct, which belongs to this delivery.
 void mpmc::contact_penalise(const mpmc_ctx *c, mpmc_result *r, int64_t n_replaced) {
 	if (!(c->kept.ca_rules & CA_RULE_SIGMA)) return;
 	r->lj_pairs = r->lj_pairs + (double)n_replaced * kMaxValue;
-	// (14-7 and DREIDING have no corrections: rd_energy = lj_pairs; disp-expansion composes like lj(); the sigma rule never meets rd_crystal: contact_ready)
-	r->rd_energy = (rd_model_on(c) && c->kept.rdm_form != RD_FORM_LJ) ? r->lj_pairs : (r->lj_pairs + r->lrc_pair) + r->lrc_self;
-	r->energy = r->rd_energy + r->coulombic_energy + r->polarization_energy + r->vdw_energy + r->three_body_energy;
-	r->NU = r->N * r->energy;
+	// (disp-expansion composes like lj(); the sigma rule never meets rd_crystal, contact_ready, so the form is never the one with crystal_self)
+	compose_totals(c, rd_form_of(c), r);
 }
-void mpmc::contact_deliver(mpmc_ctx *c, mpmc_result *r, const mpmc_ctx::ContactCounts &n, int64_t frozen_pairs) {
+void mpmc::contact_deliver(mpmc_ctx *c, mpmc_result *r, const ConfigTotals &t) {
 	if (!contact_on(c) || !r) return;
+	const ContactCounts &n = t.ca;
 	const bool sigma = (c->kept.ca_rules & CA_RULE_SIGMA) != 0, absolute = (c->kept.ca_rules & CA_RULE_ABSOLUTE) != 0;
 	struct mpmc_cavity_autoreject_info &info = c->ca_info;
 	info = {};
 	info.n_replaced = sigma ? n.replaced : 0;
 	info.n_absolute = absolute ? n.absolute : 0;
-	info.n_unmeasured_frozen = (absolute && !c->opts.polarization) ? (frozen_pairs >= 0 ? frozen_pairs : c->ca_frozen_pairs) : 0;
+	info.n_unmeasured_frozen = (absolute && !c->opts.polarization) ? (t.frozen_pairs >= 0 ? t.frozen_pairs : c->ca_frozen_pairs) : 0;
 	info.tile_pairs_walked = c->ca_walked;
 	info.tile_pairs_skipped = c->ca_skipped;
 	contact_penalise(c, r, info.n_replaced);
@@ -1432,7 +1437,9 @@ void mpmc::contact_deliver(mpmc_ctx *c, mpmc_result *r, const mpmc_ctx::ContactC
 extern "C" int mpmc_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	if (!c) return MPMC_ERR_ARG;
 	const int rc = wait_and_fill(c, out);
-	if (rc == MPMC_OK && (c->run_mask & RUN_CONTACT)) contact_deliver(c, out, c->ca_eval);
+	if (rc != MPMC_OK || !out) return rc;
+	if (c->run_mask == full_mask(c)) rebase_on_eval(c); // a complete energy(): it re-bases the trial-move totals
+	if (c->run_mask & RUN_CONTACT) contact_deliver(c, out, c->eval);
 	return rc;
 }
 extern "C" int mpmc_energy(mpmc_ctx *c, mpmc_result *out) {
@@ -1449,7 +1456,9 @@ static int run_piece(mpmc_ctx *c, unsigned mask, mpmc_result *r) {
 	if (!c) return MPMC_ERR_ARG;
 	int rc = enqueue(c, mask);
 	if (rc != MPMC_OK) return rc;
-	return wait_and_fill(c, r);
+	rc = wait_and_fill(c, r);
+	if (rc == MPMC_OK && c->run_mask == full_mask(c)) rebase_on_eval(c); // (a component call that is a complete energy(): lj() of an rd_only box)
+	return rc;
 }
 extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	mpmc_result r;
@@ -1457,7 +1466,7 @@ extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	// (cavity_autoreject: the sigma rule lives inside lj(); the absolute rule belongs to energy() alone)
 	const bool contact = (c->kept.ca_rules & CA_RULE_SIGMA) != 0 && !c->kept.de_enabled; // (under disp-expansion the rule is disp_expansion()'s: mpmc_disp_expansion)
 	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u) | (rd_model_on(c) ? RUN_RDM : 0u) | (contact ? RUN_CONTACT : 0u), &r);
-	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->ca_eval);
+	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->eval);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }
@@ -1508,7 +1517,7 @@ extern "C" int mpmc_disp_expansion(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	const bool contact = (c->kept.ca_rules & CA_RULE_SIGMA) != 0; // (cavity_autoreject: the sigma rule lives inside disp_expansion() too)
 	int rc = run_piece(c, RUN_DISP | (contact ? RUN_CONTACT : 0u), &r);
-	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->ca_eval);
+	if (rc == MPMC_OK && contact) contact_deliver(c, &r, c->eval);
 	if (rc == MPMC_OK && out) *out = r.rd_energy;
 	return rc;
 }

@@ -30,24 +30,30 @@ static int ensure_trial_buffers(mpmc_ctx *c) {
 	return c->d_sf_trial.reserve(c, (size_t)c->K);
 }
 
+// a trial of `count` atoms from `at` on is open: a displacement (kind 0), an insertion (+1) or a removal (-1); nothing of it is evaluated yet
+static void open_trial(mpmc_ctx *c, int kind, int at, int count) {
+	TrialState &t = c->trial;
+	t.xch_kind = kind;
+	t.xch_at = t.first = at;
+	t.count = count;
+	t.xch_saved.clear();
+	t.open = true;
+	t.evaluated = t.enqueued = t.noop = false;
+}
+
 extern "C" int mpmc_trial_begin(mpmc_ctx *c, int first, int count, const double *new_pos) {
 	if (!c || !new_pos || first < 0 || count <= 0) return MPMC_ERR_ARG;
 	if (!c->atoms_set || first + count > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_begin: range outside the atom list");
-	if (c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_begin: a trial move is already open (accept or reject it first)");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_begin: a trial move is already open (accept or reject it first)");
 	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, "mpmc_trial_begin: no accepted configuration (call mpmc_energy first)");
 	for (int t = 0; t < 3 * count; t++)
 		if (!std::isfinite(new_pos[t])) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_begin: non-finite position");
-	c->xch_kind = 0;
-	c->trial_first = first;
-	c->trial_count = count;
-	c->trial_new.assign(new_pos, new_pos + 3 * (size_t)count);
-	c->trial_old.assign(c->h_pos.begin() + 3 * (size_t)first, c->h_pos.begin() + 3 * (size_t)(first + count));
-	c->trial_open = true;
-	c->trial_evaluated = false;
-	c->trial_enqueued = false;
+	open_trial(c, 0, first, count);
+	c->trial.pos_new.assign(new_pos, new_pos + 3 * (size_t)count);
+	c->trial.pos_old.assign(c->h_pos.begin() + 3 * (size_t)first, c->h_pos.begin() + 3 * (size_t)(first + count));
 	// a "move" that leaves every coordinate as it is (e.g. the box a two-box move does not touch): the trial totals ARE the accepted
 	// totals, nothing is evaluated.  (The reference's bead moves re-centre the whole chain, so they do touch every image.)
-	c->trial_noop = (std::memcmp(new_pos, c->h_pos.data() + 3 * (size_t)first, 3 * (size_t)count * sizeof(double)) == 0);
+	c->trial.noop = (std::memcmp(new_pos, c->h_pos.data() + 3 * (size_t)first, 3 * (size_t)count * sizeof(double)) == 0);
 	return MPMC_OK;
 }
 
@@ -55,7 +61,7 @@ extern "C" int mpmc_trial_begin(mpmc_ctx *c, int first, int count, const double 
 static int xch_begin_checks(mpmc_ctx *c, const char *who) {
 	const std::string w(who);
 	if (!c->atoms_set) return fail(c, MPMC_ERR_ARG, w + ": no atoms set");
-	if (c->trial_open) return fail(c, MPMC_ERR_ARG, w + ": a trial move is already open (accept or reject it first)");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, w + ": a trial move is already open (accept or reject it first)");
 	// (the per-atom coefficients of these two terms belong to one atom list, and an exchange trial has no way to hand over the new atoms';
 	// in front of the accepted-configuration check: switching either term on drops the accepted totals, and the answer to an exchange trial
 	// on such a context is "never", not "call mpmc_energy first")
@@ -63,14 +69,6 @@ static int xch_begin_checks(mpmc_ctx *c, const char *who) {
 		return fail(c, MPMC_ERR_UNSUPPORTED, w + ": a context with Axilrod-Teller or disp-expansion coefficients changes its composition through mpmc_set_atoms");
 	if (!c->cache_valid) return fail(c, MPMC_ERR_ARG, w + ": no accepted configuration (call mpmc_energy first)");
 	return MPMC_OK;
-}
-static void xch_open(mpmc_ctx *c, int kind, int at, int count) {
-	c->xch_kind = kind;
-	c->xch_at = c->trial_first = at;
-	c->trial_count = count;
-	c->xch_saved.clear();
-	c->trial_open = true;
-	c->trial_evaluated = c->trial_enqueued = c->trial_noop = false;
 }
 
 // an inserted molecule's data, `n_poses` poses of it: finite positions, sane parameters, masses where the list has them
@@ -120,8 +118,8 @@ extern "C" int mpmc_trial_insert_begin(mpmc_ctx *c, int at_index, int count, con
 	if ((rc = xch_molecule_checks(c, "mpmc_trial_insert_begin", count, 1, pos, charge, polarizability, epsilon, sigma, mass)) != MPMC_OK) return rc;
 	const int32_t id = xch_largest_mol_id(c);
 	if (id == INT32_MAX) return fail(c, MPMC_ERR_ARG, "mpmc_trial_insert_begin: no molecule id left");
-	xch_fill_molecule(c, c->xch_mol, id + 1, count, pos, charge, polarizability, epsilon, sigma, frozen, has_disp, mass);
-	xch_open(c, +1, at_index, count);
+	xch_fill_molecule(c, c->trial.xch_mol, id + 1, count, pos, charge, polarizability, epsilon, sigma, frozen, has_disp, mass);
+	open_trial(c, +1, at_index, count);
 	return MPMC_OK;
 }
 
@@ -134,18 +132,18 @@ extern "C" int mpmc_trial_remove_begin(mpmc_ctx *c, int first, int count) {
 	for (int i = first + 1; i < first + count; i++) whole = whole && c->h_mol[i] == c->h_mol[first];
 	if (!whole) return fail(c, MPMC_ERR_ARG, "mpmc_trial_remove_begin: the range is not exactly one whole molecule");
 	if (count == c->n) return fail(c, MPMC_ERR_ARG, "mpmc_trial_remove_begin: the last molecule cannot be removed");
-	copy_atom_run(c, first, count, c->xch_mol);
-	xch_open(c, -1, first, count);
+	copy_atom_run(c, first, count, c->trial.xch_mol);
+	open_trial(c, -1, first, count);
 	return MPMC_OK;
 }
 
 // the trial list: the accepted one with the molecule in or out
 static void xch_trial_list(const mpmc_ctx *c, const AtomRun &acc, AtomRun &out) {
 	out = acc;
-	const size_t at = (size_t)c->xch_at, m = (size_t)c->trial_count;
-	const AtomRun &mol = c->xch_mol;
+	const size_t at = (size_t)c->trial.xch_at, m = (size_t)c->trial.count;
+	const AtomRun &mol = c->trial.xch_mol;
 	auto edit = [&](auto &v, const auto &ins, size_t per) {
-		if (c->xch_kind > 0) v.insert(v.begin() + per * at, ins.begin(), ins.end());
+		if (c->trial.xch_kind > 0) v.insert(v.begin() + per * at, ins.begin(), ins.end());
 		else v.erase(v.begin() + per * at, v.begin() + per * (at + m));
 	};
 	edit(out.pos, mol.pos, 3);
@@ -159,24 +157,19 @@ static void xch_trial_list(const mpmc_ctx *c, const AtomRun &acc, AtomRun &out) 
 	if (!out.mass.empty()) edit(out.mass, mol.mass, 1);
 }
 
-// mpmc_set_atoms may rebuild the context in place (growth): the open trial's own state crosses the call in the caller's hands
+// mpmc_set_atoms closes the open trial and may rebuild the context in place (growth): the trial state, the accepted record and the
+// diagnostic of the last trial cross the call in the caller's hands, each as a whole (cache_valid does not: the caller sets it again)
 static int xch_replace_list(mpmc_ctx *c, const AtomRun &list, AtomRun &&saved) {
-	const int kind = c->xch_kind, at = c->xch_at, count = c->trial_count, last_kind = c->trial_last_kind;
-	const bool evaluated = c->trial_evaluated, was_full = c->trial_was_full;
-	const mpmc_result keep = c->trial_keep, res = c->trial_res;
-	const int64_t rc_terms = c->rc_terms_accepted, rdm_terms = c->rdm_terms_accepted;
-	const mpmc_ctx::ContactCounts ca_acc = c->ca_accepted, ca_tr = c->ca_trial;
-	AtomRun mol = std::move(c->xch_mol);
+	TrialState trial = std::move(c->trial);
+	const ConfigTotals accepted = c->accepted;
+	const int last_kind = c->trial_last_kind;
 	const int rc = set_atoms_from(c, list);
-	c->xch_mol = std::move(mol);
-	c->xch_saved = std::move(saved);
-	c->xch_kind = kind, c->xch_at = c->trial_first = at, c->trial_count = count, c->trial_last_kind = last_kind;
-	c->trial_evaluated = evaluated, c->trial_was_full = was_full;
-	c->trial_keep = keep, c->trial_res = res;
-	c->rc_terms_accepted = rc_terms, c->rdm_terms_accepted = rdm_terms;
-	c->ca_accepted = ca_acc, c->ca_trial = ca_tr;
-	c->trial_open = true;
-	c->trial_enqueued = c->trial_noop = false;
+	c->trial = std::move(trial);
+	c->accepted = accepted;
+	c->trial_last_kind = last_kind;
+	c->trial.xch_saved = std::move(saved);
+	c->trial.open = true;
+	c->trial.enqueued = c->trial.noop = false;
 	return rc;
 }
 
@@ -213,21 +206,20 @@ static void xch_species_terms(mpmc_ctx *c, int kind, const AtomRun &mol, XchSums
 static int xch_energy_async(mpmc_ctx *c) {
 	const mpmc_options &o = c->opts;
 	const bool polar = o.polarization && !o.rd_only;
-	const int m = c->trial_count, kind = c->xch_kind;
-	c->trial_polar_delta = false;
-	c->trial_inline = false;
+	const int m = c->trial.count, kind = c->trial.xch_kind;
+	c->trial.polar_delta = false;
+	c->trial.inline_move = false;
 	if (polar || m > MPMC_TRIAL_MAX_ATOMS || crystal_on(c) || rd_model_on(c)) {
 		// the dipole solve couples every atom, and the further terms have no exchange delta: the trial composition is evaluated in full
 		AtomRun acc, list;
 		copy_atom_run(c, 0, c->n, acc);
 		xch_trial_list(c, acc, list);
-		c->trial_keep = c->last_full;
 		int rc = xch_replace_list(c, list, std::move(acc));
 		if (rc != MPMC_OK) return rc;
 		if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) return rc;
-		c->trial_was_full = true;
+		c->trial.was_full = true;
 		c->trial_last_kind = 1;
-		c->trial_enqueued = true;
+		c->trial.enqueued = true;
 		c->kept.n_xch_full++;
 		return MPMC_OK;
 	}
@@ -241,18 +233,15 @@ static int xch_energy_async(mpmc_ctx *c) {
 	if ((rc = c->d_block_part.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
 	if ((rc = c->d_block_cnt.reserve(c, 2 * ((size_t)c->n_tiles + 1))) != MPMC_OK) return rc;
 	const double sg = kind > 0 ? 1.0 : -1.0;
-	xch_species_terms(c, kind, c->xch_mol, c->xs_trial, c->xch_static, c->xch_N, c->h_xch_mol);
+	xch_species_terms(c, kind, c->trial.xch_mol, c->xs_trial, c->trial.xch_static, c->trial.xch_N, c->h_xch_mol);
 	hipStream_t st = c->stream;
 	HIP_TRY(c, hipMemcpyAsync(c->d_xch_mol, c->h_xch_mol, (size_t)m * sizeof(XchAtom), hipMemcpyHostToDevice, st));
 	const int do_es = o.rd_only ? 0 : 1;
 	if (contact_on(c)) {
 		// cavity_autoreject: the molecule's contacts with the residents, signed, into D_CA_REPLACED and D_CA_ABSOLUTE of the delta result block,
-		// which k_delta_finish posts with everything else; the unmeasured frozen pairs of the trial composition from the host's counts
+		// which k_delta_finish posts with everything else (the unmeasured frozen pairs of the trial composition: the wait, from the host's counts)
 		if ((rc = contact_ready(c)) != MPMC_OK) return rc;
 		if ((rc = c->d_ca_xpart.reserve(c, 2 * (size_t)c->n_tiles)) != MPMC_OK) return rc;
-		int64_t fm = 0;
-		for (int k = 0; k < m; k++) fm += c->xch_mol.frozen[k] ? 1 : 0;
-		c->ca_frozen_pairs_trial = c->ca_frozen_pairs + (kind > 0 ? fm * c->ca_frozen_atoms : -fm * (c->ca_frozen_atoms - fm));
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_exchange_contact(st, atoms_view(c), c->box, contact_params(c), c->d_xch_mol, m, 1, sg, c->d_ca_xpart, c->d_delta_out + D_CA_REPLACED, nullptr);
 	}
@@ -265,9 +254,9 @@ static int xch_energy_async(mpmc_ctx *c) {
 		                c->d_delta_cnt, c->h_delta_out, (c->trial_seq += 1.0));
 	}
 	HIP_TRY(c, hipGetLastError());
-	c->trial_was_full = false;
+	c->trial.was_full = false;
 	c->trial_last_kind = 0;
-	c->trial_enqueued = true;
+	c->trial.enqueued = true;
 	c->kept.n_xch_delta++;
 	return MPMC_OK;
 }
@@ -302,12 +291,11 @@ static void xch_pair_counts(const mpmc_ctx *c, const AtomRun &mol, const long lo
 static void xch_compose(const mpmc_ctx *c, int kind, int m, const InsCandOut &p, const double st[3], double N, const long long d[4], mpmc_result &r) {
 	const mpmc_options &o = c->opts;
 	const int do_es = o.rd_only ? 0 : 1;
-	const mpmc_result &a = c->last_full;
+	const mpmc_result &a = c->accepted.res;
 	r = a;
 	r.lj_pairs = a.lj_pairs + p.lj;
 	r.lrc_pair = o.rd_lrc ? st[0] : 0.0;
 	r.lrc_self = o.rd_lrc ? st[1] : 0.0;
-	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + p.n_lj;
 	if (do_es) {
 		r.es_real = a.es_real + (p.es_real - p.es_intra);
@@ -316,9 +304,8 @@ static void xch_compose(const mpmc_ctx *c, int kind, int m, const InsCandOut &p,
 		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
 		r.n_es_in_cutoff = a.n_es_in_cutoff + p.n_es;
 	}
-	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
 	r.N = N;
-	r.NU = r.N * r.energy;
+	compose_totals(c, RdForm::PLAIN, &r); // (rd_crystal and the rd models have no exchange delta: xch_energy_async)
 	const int64_t n_new = (int64_t)c->n + (kind > 0 ? m : -m);
 	r.n_pairs = n_new * (n_new - 1) / 2;
 	const long long sgn = kind > 0 ? 1 : -1;
@@ -339,37 +326,32 @@ static void xch_result(mpmc_ctx *c, mpmc_result &r) {
 	p.n_lj = c->h_delta_cnt[0];
 	p.n_es = c->h_delta_cnt[1];
 	long long d[4];
-	xch_pair_counts(c, c->xch_mol, (c->xch_kind > 0) ? c->xs_acc.cls : c->xs_trial.cls, d);
-	xch_compose(c, c->xch_kind, c->trial_count, p, c->xch_static, c->xch_N, d, r);
+	xch_pair_counts(c, c->trial.xch_mol, (c->trial.xch_kind > 0) ? c->xs_acc.cls : c->xs_trial.cls, d);
+	xch_compose(c, c->trial.xch_kind, c->trial.count, p, c->trial.xch_static, c->trial.xch_N, d, r);
 }
 
-// accept of the delta path: the list is edited in place; a context that has to grow is rebuilt around the new list and re-based
+// accept of the delta path: the list is edited in place; a context that has to grow is rebuilt around the new list and evaluated once
+// (the accepted record is the caller's: mpmc_trial_accept makes it the trial's)
 static int xch_accept_delta(mpmc_ctx *c) {
-	const int m = c->trial_count, kind = c->xch_kind;
+	const int m = c->trial.count, kind = c->trial.xch_kind;
 	const int n_new = c->n + (kind > 0 ? m : -m);
 	if (n_new > c->max_atoms) { // (rare: the capacity grows by a quarter each time)
-		const mpmc_result res = c->trial_res;
 		AtomRun acc, list;
 		copy_atom_run(c, 0, c->n, acc);
 		xch_trial_list(c, acc, list);
 		int rc = xch_replace_list(c, list, AtomRun{});
-		c->trial_open = false;
+		c->trial.open = false;
 		mpmc_result tmp;
-		if (rc == MPMC_OK) rc = mpmc_energy(c, &tmp); // the fresh context's structure factors and position-independent terms
-		if (rc != MPMC_OK) return rc;
-		c->last_full = res; // the accepted totals are the trial's
-		c->cache_valid = true;
-		return MPMC_OK;
+		if (rc == MPMC_OK) rc = mpmc_energy(c, &tmp); // the fresh context's structure factors and position-independent terms (it re-bases, cache_valid with it)
+		return rc;
 	}
 	std::swap(c->d_sf, c->d_sf_trial); // (each buffer with its own capacity)
-	const int rc = splice_atoms(c, c->xch_at, kind < 0 ? m : 0, kind > 0 ? &c->xch_mol : nullptr);
+	const int rc = splice_atoms(c, c->trial.xch_at, kind < 0 ? m : 0, kind > 0 ? &c->trial.xch_mol : nullptr);
 	if (rc != MPMC_OK) return rc;
-	for (int k = 0; k < 3; k++) c->h_static[k] = c->xch_static[k];
+	for (int k = 0; k < 3; k++) c->h_static[k] = c->trial.xch_static[k];
 	c->static_dirty = false;
 	c->xs_acc = c->xs_trial;
 	c->xs_edits++;
-	c->last_full = c->trial_res;
-	c->cache_valid = true;
 	return MPMC_OK;
 }
 
@@ -377,18 +359,18 @@ static int xch_accept_delta(mpmc_ctx *c) {
 // path-integral move overlap on the device when a driver enqueues all of them before the first wait)
 extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	if (!c) return MPMC_ERR_ARG;
-	if (!c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy: no trial move is open");
-	if (c->trial_enqueued) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy_async: already enqueued");
-	if (c->trial_noop) {
-		c->trial_was_full = false;
-		c->trial_enqueued = true;
+	if (!c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy: no trial move is open");
+	if (c->trial.enqueued) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy_async: already enqueued");
+	if (c->trial.noop) {
+		c->trial.was_full = false;
+		c->trial.enqueued = true;
 		return MPMC_OK;
 	}
-	if (c->xch_kind) return xch_energy_async(c);
+	if (c->trial.xch_kind) return xch_energy_async(c);
 	const mpmc_options &o = c->opts;
 	const bool polar = o.polarization && !o.rd_only;
-	const int m = c->trial_count;
-	c->trial_polar_delta = false;
+	const int m = c->trial.count;
+	c->trial.polar_delta = false;
 	const bool no_polar_delta = c->kept.tune.no_polar_delta;
 	// (Wolf electrostatics and the Feynman-Hibbs corrections are per-pair terms like the others: the delta kernels carry them; a
 	// polarizable box under Wolf keeps the full evaluation -- its static field is the Ewald one, outside the reference's own combinations;
@@ -397,13 +379,12 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	const bool polar_delta = polar && c->e_real_valid && !no_polar_delta && m <= MPMC_TRIAL_MAX_ATOMS && !o.wolf && !direct_solve(c) && !ewald_full_on(c) && !gs_ranked_on(c);
 	if ((polar && !polar_delta) || m > MPMC_TRIAL_MAX_ATOMS) {
 		// the dipole solve couples every atom: evaluate the trial configuration in full (still on the device)
-		c->trial_keep = c->last_full;
-		int rc = mpmc_update_positions(c, c->trial_first, m, c->trial_new.data());
+		int rc = mpmc_update_positions(c, c->trial.first, m, c->trial.pos_new.data());
 		if (rc != MPMC_OK) return rc;
 		if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) return rc; // (eager: an accepted trial's dipoles are its caller's at once)
-		c->trial_was_full = true;
+		c->trial.was_full = true;
 		c->trial_last_kind = 1;
-		c->trial_enqueued = true;
+		c->trial.enqueued = true;
 		return MPMC_OK;
 	}
 	drop_pending_dipoles(c); // (the delta path swaps positions and rewrites the field and the store under an open on-demand solve)
@@ -415,13 +396,13 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->kept.tune.no_inline_move;
 	// (the three-body, disp-expansion, rd_crystal, rd-model and contact deltas read the moved atoms from the device lists: a box with one of them always stages its move)
-	c->trial_inline = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c) && !contact_on(c);
-	if (c->trial_inline) {
+	c->trial.inline_move = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c) && !contact_on(c);
+	if (c->trial.inline_move) {
 		for (int t = 0; t < m; t++) {
-			const int i = c->trial_first + t;
+			const int i = c->trial.first + t;
 			c->mv_inline.orig[t] = i;
 			c->mv_inline.slot[t] = c->slot_of[i];
-			for (int d = 0; d < 3; d++) c->mv_inline.nw[t][d] = c->trial_new[3 * t + d];
+			for (int d = 0; d < 3; d++) c->mv_inline.nw[t][d] = c->trial.pos_new[3 * t + d];
 			c->mv_inline.nw[t][3] = c->h_q[i];
 		}
 		for (int t = m; t < kMvInline; t++) { // (unused entries: defined values, never selected)
@@ -433,10 +414,10 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		int *slots = reinterpret_cast<int *>(c->h_mv_blob + MPMC_TRIAL_MAX_ATOMS * sizeof(double4));
 		int *origs = slots + MPMC_TRIAL_MAX_ATOMS;
 		for (int t = 0; t < m; t++) {
-			const int i = c->trial_first + t;
+			const int i = c->trial.first + t;
 			origs[t] = i;
 			slots[t] = c->slot_of[i];
-			nw[t] = make_double4(c->trial_new[3 * t], c->trial_new[3 * t + 1], c->trial_new[3 * t + 2], c->h_q[i]);
+			nw[t] = make_double4(c->trial.pos_new[3 * t], c->trial.pos_new[3 * t + 1], c->trial.pos_new[3 * t + 2], c->h_q[i]);
 		}
 		HIP_TRY(c, hipMemcpyAsync(c->d_mv_blob, c->h_mv_blob, kMvBlobBytes, hipMemcpyHostToDevice, st));
 	}
@@ -489,10 +470,10 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_delta(st, atoms_view(c), c->d_slot_of, c->box, recip_view(c), fp, do_es, c->d_mv_slot, c->d_mv_orig, c->d_mv_new, m,
 		             c->d_moved_idx, c->d_sf_trial, c->d_block_part, c->d_block_cnt, c->d_delta_out, c->d_delta_cnt, c->h_delta_out,
-		             (c->trial_seq += 1.0), c->trial_inline ? &c->mv_inline : nullptr);
+		             (c->trial_seq += 1.0), c->trial.inline_move ? &c->mv_inline : nullptr);
 	}
 	HIP_TRY(c, hipGetLastError()); // (k_delta_finish posts the result into h_delta_out itself)
-	c->trial_was_full = false;
+	c->trial.was_full = false;
 	c->trial_last_kind = 0;
 	if (polar_delta) {
 		// Polarizable box: the pair energies and structure factors above are O(m N); the static field follows the same way -- real part:
@@ -524,17 +505,17 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 			                      polar_moments_apply(c) ? c->d_dk_ring.p : nullptr);
 		}
 		HIP_TRY(c, hipGetLastError());
-		c->trial_polar_delta = true;
+		c->trial.polar_delta = true;
 		if (zodid_on(c)) { // `polar_zodid`: the dipoles are the start vector just written: no classes, no store, no iteration -- the reduction closes the move
 			if ((rc = enqueue(c, RUN_SOLVE)) != MPMC_OK) return rc;
-			c->trial_enqueued = true;
+			c->trial.enqueued = true;
 			return MPMC_OK;
 		}
 		// the store-only sweep rebuilds the tile pairs of the tiles the moved atoms live in, and of the tiles a rejected trial left behind:
 		// no other tile pair's geometry (or class) changed
 		c->trial_tiles.clear();
 		for (int t = 0; t < m; t++) {
-			const int tile = c->slot_of[c->trial_first + t] / kTile;
+			const int tile = c->slot_of[c->trial.first + t] / kTile;
 			if (std::find(c->trial_tiles.begin(), c->trial_tiles.end(), tile) == c->trial_tiles.end()) c->trial_tiles.push_back(tile);
 		}
 		std::vector<int> touch = c->trial_tiles;
@@ -547,45 +528,37 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		if (rc != MPMC_OK) return rc;
 		c->store_dirty_tiles = c->trial_tiles; // until accepted: these tiles hold the TRIAL geometry's tensors
 	}
-	c->trial_enqueued = true;
+	c->trial.enqueued = true;
 	return MPMC_OK;
 }
 
 extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
-	if (!c->trial_open || !c->trial_enqueued) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy_wait: nothing enqueued");
-	c->trial_enqueued = false;
-	if (c->trial_noop) {
-		c->trial_res = c->last_full;
-		c->ca_trial = c->ca_accepted;
-		c->trial_evaluated = true;
-		*out = c->trial_res;
-		contact_deliver(c, out, c->ca_trial);
+	if (!c->trial.open || !c->trial.enqueued) return fail(c, MPMC_ERR_ARG, "mpmc_trial_energy_wait: nothing enqueued");
+	c->trial.enqueued = false;
+	ConfigTotals &tr = c->trial.totals;
+	if (c->trial.noop) {
+		tr = c->accepted;
+		c->trial.evaluated = true;
+		*out = tr.res;
+		contact_deliver(c, out, tr);
 		return MPMC_OK;
 	}
-	if (c->trial_was_full) {
-		const int64_t terms_keep = c->rc_terms_accepted, rdm_terms_keep = c->rdm_terms_accepted;
-		const mpmc_ctx::ContactCounts ca_keep = c->ca_accepted;
+	if (c->trial.was_full) {
 		int rc = wait_and_fill(c, out); // (the unpenalised result: what leaves is penalised below)
 		if (rc != MPMC_OK) return rc;
-		c->trial_res = *out;
-		c->ca_trial = c->ca_eval; // (cavity_autoreject: the full walk's counts are the trial's; the accepted ones stay until mpmc_trial_accept)
-		c->ca_accepted = ca_keep;
-		contact_deliver(c, out, c->ca_trial);
-		c->last_full = c->trial_keep; // still the ACCEPTED configuration's totals until mpmc_trial_accept
-		c->rc_terms_trial = c->rc_info.n_image_terms; // (rd_crystal: the same for the image-term count)
-		c->rc_terms_accepted = terms_keep;
-		c->rdm_terms_trial = c->rdm_info.n_terms; // (the rd model: the same for its kept terms)
-		c->rdm_terms_accepted = rdm_terms_keep;
-		c->trial_evaluated = true;
+		// the evaluation's record is the TRIAL's; the accepted one stays until mpmc_trial_accept.  The update of the positions or of the atom
+		// list in front of the evaluation cleared cache_valid: the accepted record still holds, and from here on the flag says so again
+		tr = c->eval;
+		c->cache_valid = true;
+		contact_deliver(c, out, tr);
+		c->trial.evaluated = true;
 		return MPMC_OK;
 	}
 	HIP_TRY(c, hipSetDevice(c->device));
 	mpmc_result solved{};
-	if (c->trial_polar_delta) { // the solve half went through enqueue(): its scalars (polarization energy, rrms, iterations) arrive the usual way
-		const mpmc_result keep = c->last_full;
+	if (c->trial.polar_delta) { // the solve half went through enqueue(): its scalars (polarization energy, rrms, iterations) arrive the usual way
 		int rc = wait_and_fill(c, &solved);
-		c->last_full = keep;
 		if (rc != MPMC_OK) return rc;
 	} else {
 		// the finish kernel posts its launch number behind the result: poll for it (a trial is a few tens of microseconds; the stream
@@ -602,35 +575,39 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		}
 		prof_harvest(c);
 	}
-	if (c->xch_kind) {
-		xch_result(c, c->trial_res);
-		c->trial_evaluated = true;
-		*out = c->trial_res;
-		if (contact_on(c)) { // (cavity_autoreject: the accepted counts plus or minus the molecule's contacts with the residents)
-			const double *dh = c->h_delta_out.p;
-			c->ca_trial.replaced = c->ca_accepted.replaced + (int64_t)dh[delta_host_index(D_CA_REPLACED)];
-			c->ca_trial.absolute = c->ca_accepted.absolute + (int64_t)dh[delta_host_index(D_CA_ABSOLUTE)];
-			contact_deliver(c, out, c->ca_trial, c->ca_frozen_pairs_trial);
+	// the delta paths: the trial record is the accepted one plus what the device posted (the D_* slots at delta_host_index)
+	const ConfigTotals &acc = c->accepted;
+	const double *dh = c->h_delta_out.p;
+	tr = acc;
+	if (contact_on(c)) { // (cavity_autoreject: the accepted counts plus the signed change of the moved atoms' or the molecule's pairs)
+		tr.ca.replaced = acc.ca.replaced + (int64_t)dh[delta_host_index(D_CA_REPLACED)];
+		tr.ca.absolute = acc.ca.absolute + (int64_t)dh[delta_host_index(D_CA_ABSOLUTE)];
+	}
+	if (c->trial.xch_kind) {
+		xch_result(c, tr.res);
+		if (contact_on(c)) { // (the unmeasured frozen pairs of the trial composition, from the host's counts of the accepted list: contact_ready)
+			int64_t fm = 0;
+			for (int k = 0; k < c->trial.count; k++) fm += c->trial.xch_mol.frozen[k] ? 1 : 0;
+			tr.frozen_pairs = c->ca_frozen_pairs + (c->trial.xch_kind > 0 ? fm * c->ca_frozen_atoms : -fm * (c->ca_frozen_atoms - fm));
 		}
+		c->trial.evaluated = true;
+		*out = tr.res;
+		contact_deliver(c, out, tr);
 		return MPMC_OK;
 	}
 	const int do_es = c->opts.rd_only ? 0 : 1;
-	const mpmc_result &a = c->last_full;
-	const double *dh = c->h_delta_out.p; // (the D_* slots at delta_host_index)
-	mpmc_result r = a;
+	const mpmc_result &a = acc.res;
+	mpmc_result &r = tr.res;
 	r.lj_pairs = a.lj_pairs + (c->kept.de_enabled ? dh[delta_host_index(D_DISP)] : dh[delta_host_index(D_LJ)]); // (with the disp-expansion term lj_pairs holds its pair sum)
-	r.rd_energy = (r.lj_pairs + r.lrc_pair) + r.lrc_self;
 	if (crystal_on(c)) { // (lj_pairs holds the lattice sum; crystal_self and the corrections do not move with the atoms)
 		r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_RD)];
-		r.rd_energy = ((r.lj_pairs + r.lrc_pair) + c->rc_self) + r.lrc_self;
-		c->rc_terms_trial = c->rc_terms_accepted + (int64_t)dh[delta_host_index(D_RD_TERMS)];
-		c->rc_info.n_image_terms = c->rc_terms_trial;
+		tr.rc_terms = acc.rc_terms + (int64_t)dh[delta_host_index(D_RD_TERMS)];
+		c->rc_info.n_image_terms = tr.rc_terms;
 	}
 	if (rd_model_on(c)) { // (lj_pairs holds the model's sum; the corrections do not move with the atoms)
 		r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_RD)];
-		r.rd_energy = (c->kept.rdm_form == RD_FORM_LJ) ? (r.lj_pairs + r.lrc_pair) + r.lrc_self : r.lj_pairs;
-		c->rdm_terms_trial = c->rdm_terms_accepted + (int64_t)dh[delta_host_index(D_RD_TERMS)];
-		c->rdm_info.n_terms = c->rdm_terms_trial;
+		tr.rdm_terms = acc.rdm_terms + (int64_t)dh[delta_host_index(D_RD_TERMS)];
+		c->rdm_info.n_terms = tr.rdm_terms;
 	}
 	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
@@ -639,23 +616,17 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		r.coulombic_energy = (r.es_real + r.es_recip) + r.es_self;
 		r.n_es_in_cutoff = a.n_es_in_cutoff + c->h_delta_cnt[1];
 	}
-	if (c->trial_polar_delta) {
+	if (c->trial.polar_delta) {
 		r.polarization_energy = solved.polarization_energy;
 		r.dipole_rrms = solved.dipole_rrms;
 		r.polar_iterations = solved.polar_iterations;
 		r.iterator_failed = solved.iterator_failed;
 	}
 	if (c->kept.tb_enabled) r.three_body_energy = a.three_body_energy + dh[delta_host_index(D_THREE_BODY)];
-	r.energy = r.rd_energy + r.coulombic_energy + r.polarization_energy + r.vdw_energy + r.three_body_energy;
-	r.NU = r.N * r.energy;
-	if (contact_on(c)) { // (cavity_autoreject: the accepted counts plus the change of the moved atoms' pairs)
-		c->ca_trial.replaced = c->ca_accepted.replaced + (int64_t)dh[delta_host_index(D_CA_REPLACED)];
-		c->ca_trial.absolute = c->ca_accepted.absolute + (int64_t)dh[delta_host_index(D_CA_ABSOLUTE)];
-	}
-	c->trial_res = r;
-	c->trial_evaluated = true;
+	compose_totals(c, rd_form_of(c), &r);
+	c->trial.evaluated = true;
 	*out = r;
-	contact_deliver(c, out, c->ca_trial);
+	contact_deliver(c, out, tr);
 	return MPMC_OK;
 }
 
@@ -668,113 +639,92 @@ extern "C" int mpmc_trial_energy(mpmc_ctx *c, mpmc_result *out) {
 
 extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 	if (!c) return MPMC_ERR_ARG;
-	if (!c->trial_open || !c->trial_evaluated) return fail(c, MPMC_ERR_ARG, "mpmc_trial_accept: no evaluated trial move");
+	if (!c->trial.open || !c->trial.evaluated) return fail(c, MPMC_ERR_ARG, "mpmc_trial_accept: no evaluated trial move");
 	HIP_TRY(c, hipSetDevice(c->device));
-	const int m = c->trial_count;
-	if (c->trial_noop) {
-		c->trial_open = false;
+	const int m = c->trial.count;
+	if (c->trial.noop) {
+		c->trial.open = false;
 		return MPMC_OK;
 	}
-	if (c->xch_kind) { // an exchange: the full evaluation left the trial list resident; the delta path edits the list now
-		if (!c->trial_was_full) {
+	if (c->trial.xch_kind) { // an exchange: the full evaluation left the trial list resident; the delta path edits the list now
+		if (!c->trial.was_full) {
 			const int rc_x = xch_accept_delta(c);
 			if (rc_x != MPMC_OK) return rc_x;
-			if (contact_on(c)) c->ca_accepted = c->ca_trial;
-		} else {
-			c->last_full = c->trial_res;
-			c->cache_valid = true;
-			if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
-			if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
-			if (contact_on(c)) c->ca_accepted = c->ca_trial;
 		}
-		c->xch_saved.clear();
-		c->xch_kind = 0;
-		c->trial_open = false;
-		return MPMC_OK;
-	}
-	if (!c->trial_was_full) {
-		if (c->trial_polar_delta) { // the trial positions are already resident; the trial real-space field becomes the accepted one
+		c->trial.xch_saved.clear();
+		c->trial.xch_kind = 0;
+	} else if (!c->trial.was_full) {
+		if (c->trial.polar_delta) { // the trial positions are already resident; the trial real-space field becomes the accepted one
 			std::swap(c->d_e_real, c->d_e_real_trial);
 			c->store_dirty_tiles.clear(); // ... and so is the store
 		} else {
-			if (c->trial_inline) launch_commit_positions_inline(c->stream, c->d_xyzq, c->mv_inline, m);
+			if (c->trial.inline_move) launch_commit_positions_inline(c->stream, c->d_xyzq, c->mv_inline, m);
 			else launch_commit_positions(c->stream, c->d_xyzq, c->d_mv_slot, c->d_mv_new, m);
 		}
 		HIP_TRY(c, hipGetLastError());
 		std::swap(c->d_sf, c->d_sf_trial); // the trial structure factors become the accepted ones (each buffer with its own capacity)
 		// (no wait: whatever comes next on this context is enqueued behind the commit on the same stream, and the host mirrors below are
 		// the host's own -- the stream synchronisation that stood here cost 13 us of a 41 us accepted move)
-		for (int t = 0; t < 3 * m; t++) c->h_pos[3 * (size_t)c->trial_first + t] = c->trial_new[t];
+		for (int t = 0; t < 3 * m; t++) c->h_pos[3 * (size_t)c->trial.first + t] = c->trial.pos_new[t];
 		c->pos_gen++;
 		{
 			const int rc_g = mirror_guard(c);
 			if (rc_g != MPMC_OK) return rc_g;
 		}
 		for (int t = 0; t < m; t++) { // the slot-ordered mirror follows (a later position update uploads it as a whole)
-			double4 &v = c->h_xyzq[c->slot_of[c->trial_first + t]];
-			v.x = c->trial_new[3 * t], v.y = c->trial_new[3 * t + 1], v.z = c->trial_new[3 * t + 2];
+			double4 &v = c->h_xyzq[c->slot_of[c->trial.first + t]];
+			v.x = c->trial.pos_new[3 * t], v.y = c->trial.pos_new[3 * t + 1], v.z = c->trial.pos_new[3 * t + 2];
 		}
 	}
-	c->last_full = c->trial_res;
+	// the trial becomes the accepted configuration, whichever way it was evaluated.  (The whole record: a count whose term is off is read by
+	// nobody until the term is switched on, which drops cache_valid and this record with it.  Its frozen pairs are the resident list's own.)
+	c->accepted = c->trial.totals;
+	c->accepted.frozen_pairs = -1;
 	c->cache_valid = true;
-	if (crystal_on(c)) c->rc_terms_accepted = c->rc_terms_trial;
-	if (rd_model_on(c)) c->rdm_terms_accepted = c->rdm_terms_trial;
-	if (contact_on(c)) c->ca_accepted = c->ca_trial;
-	c->trial_open = false;
-	c->trial_polar_delta = false;
+	c->trial.open = false;
+	c->trial.polar_delta = false;
 	return MPMC_OK;
+}
+
+// behind a rejected full-evaluation trial, once the accepted configuration is resident again
+static int rebase_after_restore(mpmc_ctx *c) {
+	c->cache_valid = true;   // (the accepted record, which the trial never touched, describes the configuration that is back)
+	c->e_real_valid = false; // (the real-space field on the device is the rejected configuration's: the next polarizable trial evaluates in full)
+	if ((c->opts.polarization && !c->opts.rd_only) || c->opts.wolf) return MPMC_OK;
+	mpmc_result tmp; // the resident structure factors are the trial ones: re-base on the restored configuration
+	return mpmc_energy(c, &tmp);
 }
 
 extern "C" int mpmc_trial_reject(mpmc_ctx *c) {
 	if (!c) return MPMC_ERR_ARG;
-	if (!c->trial_open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_reject: no trial move is open");
-	if (c->trial_enqueued) { // enqueued but never waited for: drain it first
+	if (!c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_reject: no trial move is open");
+	if (c->trial.enqueued) { // enqueued but never waited for: drain it first
 		mpmc_result drop;
 		int rc = mpmc_trial_energy_wait(c, &drop);
 		if (rc != MPMC_OK) return rc;
 	}
-	if (c->xch_kind) { // an exchange: the delta path left nothing behind; after a full evaluation the accepted list goes back
-		if (c->xch_saved.size() > 0) {
-			const mpmc_result keep = c->trial_keep;
-			AtomRun acc = std::move(c->xch_saved);
-			int rc = xch_replace_list(c, acc, AtomRun{});
-			c->xch_kind = 0;
-			c->trial_open = false;
-			if (rc != MPMC_OK) return rc;
-			c->last_full = keep;
-			c->cache_valid = true;
-			c->e_real_valid = false;
-			const bool polar = c->opts.polarization && !c->opts.rd_only;
-			if (!polar && !c->opts.wolf) { // the resident structure factors are the trial ones: re-base on the restored list
-				mpmc_result tmp;
-				if ((rc = mpmc_energy(c, &tmp)) != MPMC_OK) return rc;
-			}
-			return MPMC_OK;
+	if (c->trial.xch_kind) { // an exchange: the delta path left nothing behind; after a full evaluation the accepted list goes back
+		const bool restore = c->trial.xch_saved.size() > 0;
+		int rc = MPMC_OK;
+		if (restore) {
+			AtomRun acc = std::move(c->trial.xch_saved);
+			rc = xch_replace_list(c, acc, AtomRun{});
 		}
-		c->xch_kind = 0;
-		c->trial_open = false;
-		return MPMC_OK;
+		c->trial.xch_kind = 0;
+		c->trial.open = false;
+		return (restore && rc == MPMC_OK) ? rebase_after_restore(c) : rc;
 	}
-	c->trial_open = false;
-	if (c->trial_polar_delta) { // (enqueued or evaluated) the device holds the trial positions: swap the accepted ones back
+	c->trial.open = false;
+	if (c->trial.polar_delta) { // (enqueued or evaluated) the device holds the trial positions: swap the accepted ones back
 		HIP_TRY(c, hipSetDevice(c->device));
-		launch_swap_positions(c->stream, c->d_xyzq, c->d_mv_slot, c->d_mv_new, c->trial_count);
+		launch_swap_positions(c->stream, c->d_xyzq, c->d_mv_slot, c->d_mv_new, c->trial.count);
 		HIP_TRY(c, hipGetLastError()); // (stream-ordered in front of whatever comes next: nothing to wait for)
-		c->trial_polar_delta = false;
+		c->trial.polar_delta = false;
 		return MPMC_OK; // (the store, classes and dipoles describe the rejected geometry; the next trial or energy() rebuilds them)
 	}
-	if (c->trial_evaluated && c->trial_was_full) { // the resident configuration is the trial one: put the old positions back
-		const mpmc_result keep = c->last_full;
-		int rc = mpmc_update_positions(c, c->trial_first, c->trial_count, c->trial_old.data());
-		if (rc != MPMC_OK) return rc;
-		c->last_full = keep;
-		c->cache_valid = true;
-		c->e_real_valid = false; // (the real-space field on the device is the rejected configuration's: the next polarizable trial evaluates in full)
-		const bool polar = c->opts.polarization && !c->opts.rd_only;
-		if (!polar && !c->opts.wolf) { // the resident structure factors are the trial ones: re-base on the restored configuration
-			mpmc_result tmp;
-			if ((rc = mpmc_energy(c, &tmp)) != MPMC_OK) return rc;
-		}
+	if (c->trial.evaluated && c->trial.was_full) { // the resident configuration is the trial one: put the old positions back
+		const int rc = mpmc_update_positions(c, c->trial.first, c->trial.count, c->trial.pos_old.data());
+		return rc != MPMC_OK ? rc : rebase_after_restore(c);
 	}
 	return MPMC_OK;
 }
@@ -879,8 +829,8 @@ extern "C" int mpmc_insert_candidates(mpmc_ctx *c, int count, int n_cand, const 
 	// (cavity_autoreject: the counts of each candidate's trial composition, and the sigma rule's penalty on out[q] as the single trial delivers it)
 	c->ins_ca.assign(2 * (size_t)n_cand, 0);
 	for (int q = 0; contact && q < n_cand; q++) {
-		c->ins_ca[2 * (size_t)q] = (c->kept.ca_rules & CA_RULE_SIGMA) ? c->ca_accepted.replaced + c->h_ins_ca[2 * (size_t)q] : 0;
-		c->ins_ca[2 * (size_t)q + 1] = (c->kept.ca_rules & CA_RULE_ABSOLUTE) ? c->ca_accepted.absolute + c->h_ins_ca[2 * (size_t)q + 1] : 0;
+		c->ins_ca[2 * (size_t)q] = (c->kept.ca_rules & CA_RULE_SIGMA) ? c->accepted.ca.replaced + c->h_ins_ca[2 * (size_t)q] : 0;
+		c->ins_ca[2 * (size_t)q + 1] = (c->kept.ca_rules & CA_RULE_ABSOLUTE) ? c->accepted.ca.absolute + c->h_ins_ca[2 * (size_t)q + 1] : 0;
 		contact_penalise(c, &out[q], c->ins_ca[2 * (size_t)q]);
 	}
 	c->ins_ca_n = n_cand;
