@@ -91,15 +91,20 @@ int main(int argc, char **argv) {
 		}
 		const double e = s.energy();
 		const mpmc::observables_t *o = s.observables;
-		if (s.polarization && !s.rd_only && !s.polar_iterative) { // the dipoles were solved directly: say how the solve went
+		if (s.polarization && !s.rd_only && !s.use_sg && !s.polar_iterative) { // the dipoles were solved directly: say how the solve went
 			mpmc_direct_info di;
 			if (mpmc_polar_direct_info(s.context(), &di) == MPMC_OK)
 				std::printf("direct dipole solve: %lld unknowns, status %lld, residual %.3e, factor %.1f MB\n", (long long)di.n_unknowns,
 				            (long long)di.status, di.residual, (double)di.factor_bytes / 1048576.0);
 		}
-		if (s.polarization && !s.rd_only && s.polar_palmo) { // the Palmo-Krimm correction that is part of "polar" below
+		if (s.polarization && !s.rd_only && !s.use_sg && s.polar_palmo) { // the Palmo-Krimm correction that is part of "polar" below
 			double corr = 0;
 			if (mpmc_polar_palmo_info(s.context(), &corr, nullptr) == MPMC_OK) std::printf("polar_palmo: correction %.17g K\n", corr);
+		}
+		if (s.use_sg) { // the Silvera-Goldman potential: how many pairs lay inside the cutoff
+			struct mpmc_silvera_goldman_info gi;
+			if (mpmc_silvera_goldman_info(s.context(), &gi) == MPMC_OK)
+				std::printf("silvera_goldman: %lld pairs inside %.6g A%s\n", (long long)gi.n_terms, gi.cutoff, gi.feynman_hibbs ? ", Feynman-Hibbs" : "");
 		}
 		std::printf("{\"natoms\": %d, \"total\": %.17g, \"rd\": %.17g, \"es\": %.17g, \"polar\": %.17g, \"es_real\": %.17g, \"es_recip\": %.17g, "
 		            "\"es_self\": %.17g, \"three_body\": %.17g, \"n_lj_in_cutoff\": %lld, \"n_es_in_cutoff\": %lld, \"polar_iterations\": %d, \"mu0\": [%.17g, %.17g, %.17g]}\n",

@@ -400,6 +400,40 @@ struct mpmc_rd_model_info {
 int mpmc_set_rd_model(mpmc_ctx *ctx, int form, int mixing);
 int mpmc_rd_model_info(mpmc_ctx *ctx, struct mpmc_rd_model_info *out);
 
+/* ---- `sg`: the Silvera-Goldman molecular hydrogen potential ------------------------------------------------------------------------------
+ * (System::sg src/System.Energy.cpp:1763-1867, dispatch :115-116; the constants of :1763-1770)
+ * enabled != 0: System::energy() of a system with `sg on`.  rd_energy = lj_pairs = sg(), the sum over EVERY pair i < j of the atom list
+ * with rimg < cutoff (strict: a pair at exactly the cutoff is out) of (V [+ V_FH]) * 3.15774655e5 K, with x = rimg / 0.529177249 and
+ *   V = exp(ALPHA - BETA x - GAMMA x^2) - (C6 / x^6 + C8 / x^8 + C10 / x^10 - C9 / x^9) f(x),  f = exp(-(RM / x - 1)^2) for x < RM, else 1.
+ * sg() tests neither the exclusions nor the frozen flags: pairs inside one molecule count, atoms with sigma = 0 or epsilon = 0 count, and
+ * sigma, epsilon and the charge play no part.  Under feynman_hibbs V_FH is the expression of :1831-1845 as the reference writes it
+ * (110 C10 / x^10 in the second derivative; derivatives in bohr under a prefactor in Angstrom^2; the mass of the molecule of the atom that
+ * comes FIRST in the caller's atom list, not a reduced mass -- so with two species the value depends on the order of the list, as in the
+ * reference); feynman_hibbs_order plays no part.  Masses and a positive temperature are required as for the Lennard-Jones corrections.
+ *   With the term on there are no electrostatics and no polarization whatever the options say (:46): es_*, coulombic_energy,
+ * polarization_energy, n_es_in_cutoff and polar_iterations are 0, no static field and no dipole solve run, and every entry point that reads
+ * dipoles or fields behaves as on a box with polarization off.  lrc_pair = lrc_self = 0 whatever rd_lrc says, and mpmc_set_rd_crystal is
+ * ignored (result unchanged to the bit).  No Lennard-Jones pass runs: n_lj_in_cutoff is 0; n_terms below counts the pairs kept.  The
+ * Axilrod-Teller term is still added when on; the absolute rule of mpmc_set_cavity_autoreject works as it is.  mpmc_lj returns this rd_energy.
+ *   Refused at the evaluation, with a message: MPMC_ERR_INCOMPATIBLE together with a non-default mpmc_set_rd_model or with
+ * mpmc_set_disp_expansion; MPMC_ERR_UNSUPPORTED with the sigma rule of mpmc_set_cavity_autoreject (it lives inside lj()) and for a list with
+ * two or more frozen atoms (the reference never measures a pair of two frozen atoms here: its value is inf - inf, not finite).
+ *   Trial moves: a displacement of m <= MPMC_TRIAL_MAX_ATOMS atoms is the O(m N) delta with n_terms carried as a difference; longer moves,
+ * insertions and removals evaluate the trial in full; mpmc_insert_candidates is refused with MPMC_ERR_UNSUPPORTED.
+ *   The setting has the lifetime of mpmc_set_rd_model's: it survives mpmc_set_atoms, mpmc_set_box, mpmc_set_options, position updates,
+ * accepted trials and capacity growth; it is refused while an evaluation or a trial move is open; it drops the accepted totals; enabled = 0
+ * returns the bits of a context that never made the call.  MPMC_FLAG_USE_SG in unsupported_flags is still refused: this call alone
+ * switches the term on.  Cost O(N^2) per evaluation; time is counted in MPMC_K_PAIR. */
+/* (a struct tag, not a typedef: the entry point below carries the same name) */
+struct mpmc_silvera_goldman_info {
+	int32_t enabled;        /* the setting                                                                                          */
+	int32_t feynman_hibbs;  /* of the last evaluation (complete, component or trial) with the term: V_FH was added                  */
+	int64_t n_terms;        /* ... its pairs with rimg < cutoff; 0: none has run                                                    */
+	double cutoff;          /* ... and its cutoff (Angstrom)                                                                        */
+};
+int mpmc_set_silvera_goldman(mpmc_ctx *ctx, int enabled);
+int mpmc_silvera_goldman_info(mpmc_ctx *ctx, struct mpmc_silvera_goldman_info *out);
+
 /* ---- `cavity_autoreject`, `cavity_autoreject_absolute`, `cavity_autoreject_scale`: contact rejection of uVT moves ---------------------------
  * (System::lj src/System.Energy.cpp:1001-1004, lj_buffered_14_7 :1237-1239, dreiding :2182-2185; System::cavity_absolute_check
  * src/System.Cavity.cpp:211-228, called at :167; validation SimulationControl.cpp:2139-2154)

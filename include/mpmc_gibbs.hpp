@@ -51,6 +51,7 @@ public:
 		if (uses_polar_wolf_or_palmo(*systems[0], 0) || uses_polar_wolf_or_palmo(*systems[1], 0)) throw 4004; // (nor polar_wolf / polar_palmo)
 		if (uses_polar_ewald_full(*systems[0], 0) || uses_polar_ewald_full(*systems[1], 0)) throw 4004; // (nor polar_ewald_full)
 		if (uses_rd_model(*systems[0], 0) || uses_rd_model(*systems[1], 0)) throw 4004; // (nor a non-default rd model)
+		if (uses_sg(*systems[0], 0) || uses_sg(*systems[1], 0)) throw 4004; // (nor the Silvera-Goldman potential)
 		systems[0]->energy_async();
 		systems[1]->energy_async();
 		final_energy[0] = systems[0]->energy_wait();

@@ -122,7 +122,7 @@ inline std::string read_input(const std::string &path, System &s) {
 	if (!f) throw 1000;
 	static const std::map<std::string, uint64_t> unsupported = {
 	    {"rd_crystal", MPMC_FLAG_RD_CRYSTAL}, {"spectre", MPMC_FLAG_SPECTRE},
-	    {"gwp", MPMC_FLAG_GWP}, {"sg", MPMC_FLAG_USE_SG}, {"polarvdw", MPMC_FLAG_POLARVDW}, {"cdvdw", MPMC_FLAG_POLARVDW},
+	    {"gwp", MPMC_FLAG_GWP}, {"polarvdw", MPMC_FLAG_POLARVDW}, {"cdvdw", MPMC_FLAG_POLARVDW},
 	    {"polar_ewald_full", MPMC_FLAG_POLAR_EWALD_FULL}, {"polar_wolf_full", MPMC_FLAG_POLAR_WOLF},
 	    {"polar_wolf_alpha_lookup", MPMC_FLAG_POLAR_WOLF}, {"polar_gs_ranked", MPMC_FLAG_POLAR_GS_RANKED},
 	    {"cdvdw_exp_repulsion", MPMC_FLAG_OTHER_RD},
@@ -188,6 +188,8 @@ inline std::string read_input(const std::string &path, System &s) {
 		else if (k == "c6_mixing") { need(1); s.c6_mixing = onoff(t[1]); }
 		else if (k == "lj_buffered_14_7") { need(1); s.using_lj_buffered_14_7 = onoff(t[1]) != 0; }
 		else if (k == "dreiding") { need(1); s.use_dreiding = onoff(t[1]); }
+		// (the Silvera-Goldman potential: read into a field, no flag; the facade hands it to mpmc_set_silvera_goldman)
+		else if (k == "sg") { need(1); s.use_sg = onoff(t[1]); }
 		// (the cavity-bias grid: read into fields, no flag; the facade hands them to mpmc_set_cavity_grid.  `cavity_grid` is the reference's
 		// keyword for cavity_grid_size, SimulationControl.cpp:608-624)
 		else if (k == "cavity_bias") { need(1); s.cavity_bias = onoff(t[1]); }

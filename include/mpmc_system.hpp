@@ -83,6 +83,10 @@ template <class T>
 auto uses_rd_model(const T &s, int) -> decltype(bool(s.rd_model_form() || s.rd_model_mixing())) { return s.rd_model_form() || s.rd_model_mixing(); }
 template <class T>
 bool uses_rd_model(const T &, long) { return false; }
+template <class T>
+auto uses_sg(const T &s, int) -> decltype(bool(s.use_sg)) { return s.use_sg != 0; }
+template <class T>
+bool uses_sg(const T &, long) { return false; }
 
 // one row of the flattened atom list (reference src/Atom.h:21-56, the fields the path reads / writes)
 struct Atom {
@@ -123,6 +127,7 @@ public:
 	int rd_model_mixing() const {
 		return waldmanhagler ? MPMC_RD_MIX_WALDMAN_HAGLER : halgren_mixing ? MPMC_RD_MIX_HALGREN : c6_mixing ? MPMC_RD_MIX_C6 : MPMC_RD_MIX_LB;
 	}
+	int use_sg = 0;                      // the Silvera-Goldman H2 potential in place of lj(), no electrostatics and no polarization (mpmc_set_silvera_goldman), src/System.h: use_sg
 	int polar_sor = 0, polar_esor = 0;   // relaxed dipole updates by polar_gamma (mpmc_set_polar_relax), src/System.h: polar_sor, polar_esor
 	int polar_zodid = 0;                 // zeroth-order dipoles, mu = alpha E0 (mpmc_set_polar_relax)
 	int polar_gs_ranked = 0;             // Gauss-Seidel sweeps in ranked order (mpmc_set_polar_gs_ranked), src/System.h: polar_gs_ranked
@@ -452,7 +457,7 @@ public:
 	}
 
 	void update_dipoles() { // atoms[].mu / ef_static / ef_induced of the last evaluation
-		if (polarization && !rd_only && ctx_) fetch_dipoles();
+		if (polarization && !rd_only && !use_sg && ctx_) fetch_dipoles(); // (no polarization under sg: System::energy :46)
 	}
 
 	mpmc_ctx *context() {
@@ -476,6 +481,7 @@ private:
 	int rd_crystal_on_ = 0, rd_crystal_order_ = 0; // ... and its rd_crystal setting
 	int ewald_full_on_ = 0, ewald_full_flags_ = 0; // ... and its polar_ewald_full setting
 	int rd_model_form_ = 0, rd_model_mixing_ = 0;  // ... and its rd model
+	int sg_on_ = 0;                                // ... and its Silvera-Goldman switch
 	int relax_scheme_ = 0, zodid_on_ = 0;          // ... and its polar_sor / polar_esor / polar_zodid setting
 	int gs_ranked_on_ = 0;                         // ... and its polar_gs_ranked setting
 	int cavity_grid_ = 0;                          // ... and its cavity grid (0: off)
@@ -529,6 +535,7 @@ private:
 			rd_crystal_on_ = rd_crystal_order_ = 0;
 			ewald_full_on_ = ewald_full_flags_ = 0;
 			rd_model_form_ = rd_model_mixing_ = 0;
+			sg_on_ = 0;
 			relax_scheme_ = zodid_on_ = 0;
 			gs_ranked_on_ = 0;
 			cavity_grid_ = 0;
@@ -624,6 +631,10 @@ private:
 			rd_model_form_ = rd_model_form();
 			rd_model_mixing_ = rd_model_mixing();
 		}
+		if ((use_sg != 0) != (sg_on_ != 0)) {
+			check(mpmc_set_silvera_goldman(ctx_, use_sg ? 1 : 0), "mpmc_set_silvera_goldman");
+			sg_on_ = use_sg ? 1 : 0;
+		}
 		const int pef_flags = polar_ewald_full_vector_kweight ? MPMC_PEF_VECTOR_KWEIGHT : 0;
 		if ((polar_ewald_full != 0) != (ewald_full_on_ != 0) || (polar_ewald_full && pef_flags != ewald_full_flags_)) {
 			check(mpmc_set_polar_ewald_full(ctx_, polar_ewald_full ? 1 : 0, pef_flags), "mpmc_set_polar_ewald_full");
@@ -698,7 +709,7 @@ private:
 		stats_.polarization_iterations = (double)r.polar_iterations;
 		iterator_failed = r.iterator_failed;
 		last_volume = pbc.volume;
-		if (polarization && !rd_only && eager_dipoles) fetch_dipoles();
+		if (polarization && !rd_only && !use_sg && eager_dipoles) fetch_dipoles();
 	}
 
 	double piece(int (*fn)(mpmc_ctx *, double *)) {

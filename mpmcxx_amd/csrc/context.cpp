@@ -291,7 +291,15 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 		if (!(o->temperature > 0)) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: feynman_hibbs requires positive temperature"); // SimulationControl.cpp:2509
 		if (o->wolf && !o->rd_only) return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_options: FH + es_wolf is not implemented"); // System.Energy.cpp:1448-1450
 	}
-	if (c->opts_set && std::memcmp(&c->opts, o, sizeof(mpmc_options)) == 0) return MPMC_OK; // unchanged: keep the accepted configuration's totals
+	if (c->opts_set && std::memcmp(&c->opts_user, o, sizeof(mpmc_options)) == 0) return MPMC_OK; // unchanged: keep the accepted configuration's totals
+	c->opts_user = *o;
+	apply_options(c, effective_options(c, *o));
+	return MPMC_OK;
+}
+
+// the options the evaluations read change (mpmc_set_options; mpmc_set_silvera_goldman, under which they differ from the caller's)
+void mpmc::apply_options(mpmc_ctx *c, const mpmc_options &eff) {
+	const mpmc_options *o = &eff;
 	// Gauss-Seidel sweeps run in the reference's atom order (System.Energy.cpp:3569): whenever "this evaluation sweeps in atom order"
 	// changes -- through polar_gs, polarization, rd_only or polar_iterative (the ranked sweeps), or on the first options after an upload
 	// under the defaults -- re-upload (not under `polar_ewald_full`, where polar_gs changes nothing: the spatial order stays)
@@ -303,7 +311,6 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 	c->static_dirty = true;
 	c->static_gen++;
 	c->cache_valid = false;
-	return MPMC_OK;
 }
 
 // ---- atoms -----------------------------------------------------------------------------------------------
@@ -567,6 +574,7 @@ int mpmc::upload_atoms(mpmc_ctx *c) {
 	if (c->de_have) c->de_dirty = true; // (so do the disp-expansion coefficients)
 	c->rdm_dirty = true;                // (and the rd model's per-atom table)
 	c->ca_dirty = true;                 // (and what cavity_autoreject takes from the list)
+	c->sg_frozen_atoms = -1;            // (and the Silvera-Goldman term's count of frozen atoms)
 	return MPMC_OK;
 }
 
@@ -582,13 +590,14 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	int rc = mpmc_ctx_create(c->device, cap, &f);
 	if (rc != MPMC_OK) return fail(c, rc, "mpmc_set_atoms: cannot grow the context to " + std::to_string(cap) + " atoms: " + g_create_error);
 	if (c->box_set) rc = mpmc_set_box(f, c->box.b, c->box.r, c->box.volume, c->box.cutoff);
-	if (rc == MPMC_OK && c->opts_set) rc = mpmc_set_options(f, &c->opts);
+	if (rc == MPMC_OK && c->opts_set) rc = mpmc_set_options(f, &c->opts_user);
 	if (rc != MPMC_OK) {
 		c->err = "mpmc_set_atoms: growing the context failed: " + f->err;
 		mpmc_ctx_destroy(f);
 		return rc;
 	}
 	f->kept = c->kept; // (the switched-on terms survive, their coefficients go with the atom list that is being replaced; the new context sorts)
+	if (f->opts_set && sg_on(f)) apply_options(f, effective_options(f, f->opts_user)); // (the Silvera-Goldman term reads its own view of the options)
 	std::swap(*c, *f);
 	mpmc_ctx_destroy(f); // now owns the old, smaller buffers
 	return MPMC_OK;
@@ -1012,6 +1021,59 @@ extern "C" int mpmc_rd_model_info(mpmc_ctx *c, struct mpmc_rd_model_info *out) {
 	if (!c || !out) return MPMC_ERR_ARG;
 	*out = c->rdm_info;
 	return MPMC_OK;
+}
+
+// ---- `sg`: the Silvera-Goldman potential (System::sg, src/System.Energy.cpp:1763-1867) -----------------------------------------------------------
+extern "C" int mpmc_set_silvera_goldman(mpmc_ctx *c, int enabled) {
+	if (!c) return MPMC_ERR_ARG;
+	if (c->pending || c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_set_silvera_goldman: an evaluation or a trial move is open");
+	const bool on = enabled != 0;
+	if (on == c->kept.sg_enabled) return MPMC_OK;
+	c->kept.sg_enabled = on;
+	c->cache_valid = false; // (the accepted totals carry the other term)
+	if (c->kept.rc_enabled) c->static_dirty = true, c->static_gen++; // (sg() ignores rd_crystal: the long-range corrections move between the crystal cutoff and the box cutoff, lrc_box)
+	if (!on) c->sg_info = {};
+	// no electrostatics and no polarization under the term (System::energy :46): the evaluations read the caller's options with rd_only on
+	// and polarization off
+	if (c->opts_set) apply_options(c, effective_options(c, c->opts_user));
+	return MPMC_OK;
+}
+extern "C" int mpmc_silvera_goldman_info(mpmc_ctx *c, struct mpmc_silvera_goldman_info *out) {
+	if (!c || !out) return MPMC_ERR_ARG;
+	*out = c->sg_info;
+	out->enabled = c->kept.sg_enabled ? 1 : 0;
+	return MPMC_OK;
+}
+
+int mpmc::sg_ready(mpmc_ctx *c) {
+	if (!sg_on(c)) return fail(c, MPMC_ERR_INVALID_SETTING, "the Silvera-Goldman term is off (mpmc_set_silvera_goldman)");
+	if (rd_model_on(c))
+		return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_silvera_goldman with a non-default mpmc_set_rd_model: sg() mixes nothing and comes before dreiding and lj_buffered_14_7 "
+		                                      "in the reference's dispatch (System.Energy.cpp:113-127); choose one");
+	if (c->kept.de_enabled)
+		return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_silvera_goldman with mpmc_set_disp_expansion: sg() comes before disp_expansion() in the reference's dispatch "
+		                                      "(System.Energy.cpp:113-127); choose one");
+	if (c->kept.ca_rules & CA_RULE_SIGMA)
+		return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_set_silvera_goldman with the sigma rule of cavity_autoreject: the rule lives inside lj(), which sg() replaces; use the absolute rule");
+	if (c->sg_frozen_atoms < 0) { // (the flags change with the atom list only: one scan per upload, none per trial move)
+		int nf = 0;
+		for (int i = 0; i < c->n; i++) nf += c->h_frozen[i] ? 1 : 0;
+		c->sg_frozen_atoms = nf;
+	}
+	if (c->sg_frozen_atoms >= 2)
+		return fail(c, MPMC_ERR_UNSUPPORTED, "Silvera-Goldman with two or more frozen atoms: the reference never measures a pair of two frozen atoms here, and the reference's "
+		                                     "value is not finite (inf - inf)");
+	return c->d_sg_part.reserve(c, (size_t)2 * kSgBlocks);
+}
+
+SgParams mpmc::sg_params(const mpmc_ctx *c) {
+	SgParams sp{};
+	sp.fh = c->opts.feynman_hibbs ? 1 : 0;
+	if (sp.fh) { // System::sg :1845: M2A^2 hBar^2 / (24 kB T AMU2KG mass), with hBar itself squared (constants.h:15)
+		const double hBar = 1.054571e-34, kB = 1.3806503e-23, amu = 1.66053873e-27;
+		sp.fh_c = 1.0e20 * (hBar * hBar / (24.0 * kB * c->opts.temperature * amu));
+	}
+	return sp;
 }
 
 // ---- cavity_autoreject (System.Energy.cpp:1001-1004, 1237-1239, 2182-2185; System.Cavity.cpp:211-228; SimulationControl.cpp:2139-2154) ----------

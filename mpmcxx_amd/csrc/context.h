@@ -139,6 +139,7 @@ struct mpmc_kept {
 	bool rc_enabled = false;                // `rd_crystal` (mpmc_set_rd_crystal), kept across mpmc_set_box and mpmc_set_options too
 	int rc_order = 0;                       // rd_crystal_order
 	int rdm_form = 0, rdm_mix = 0;          // the rd model (mpmc_set_rd_model), likewise: MPMC_RD_FORM_*, MPMC_RD_MIX_*; (0, 0) = the plain term
+	bool sg_enabled = false;                // the Silvera-Goldman potential (mpmc_set_silvera_goldman), likewise
 	bool pef_enabled = false;               // `polar_ewald_full` (mpmc_set_polar_ewald_full), likewise
 	int pef_flags = 0;                      // MPMC_PEF_*
 	int relax_scheme = 0;                   // `polar_sor` / `polar_esor` (mpmc_set_polar_relax), likewise: MPMC_POLAR_RELAX_*
@@ -178,6 +179,7 @@ struct ConfigTotals {
 	                           // cavity_autoreject is put on the copy that leaves the library (contact_deliver, evaluate.cpp)
 	int64_t rc_terms = 0;      // rd_crystal: image terms (mpmc_rd_crystal_info's n_image_terms)
 	int64_t rdm_terms = 0;     // the rd model: kept terms (mpmc_rd_model_info's n_terms)
+	int64_t sg_terms = 0;      // Silvera-Goldman: kept terms (mpmc_silvera_goldman_info's n_terms)
 	ContactCounts ca;          // cavity_autoreject: the contact counts
 	int64_t frozen_pairs = -1; // cavity_autoreject: unmeasured pairs of two frozen atoms of this composition; -1: the resident list's own (ca_frozen_pairs)
 };
@@ -345,7 +347,8 @@ struct mpmc_ctx {
 	double box_in[20] = {0}; // what mpmc_set_box was last called with (basis, reciprocal, volume, cutoff): an identical call is a no-op
 	bool box_in_has_recip = false;
 	bool box_set = false, atoms_set = false, opts_set = false, k_dirty = true;
-	mpmc_options opts{};
+	mpmc_options opts{};      // what the evaluations read: opts_user, and under the Silvera-Goldman term rd_only on and polarization off (effective_options)
+	mpmc_options opts_user{}; // what mpmc_set_options was last called with
 	double ewald_alpha = 0, polar_ewald_alpha = 0;
 
 	// results of the last evaluation
@@ -445,6 +448,13 @@ struct mpmc_ctx {
 	double rdm_lrc = 0, rdm_lrc_volume = 0, rdm_lrc_cutoff = 0;
 	int rdm_lrc_rd_lrc = 0, rdm_lrc_mix = -1;
 	struct mpmc_rd_model_info rdm_info{};   // of the last evaluation with a non-default model (mpmc_rd_model_info)
+
+	// the Silvera-Goldman H2 potential (mpmc_set_silvera_goldman, kernels_sg.hip; kept.sg_enabled): sg() in place of lj(), and no electrostatics
+	// and no polarization whatever the options say (System::energy :46) -- the context's `opts` are the caller's with rd_only on and
+	// polarization off while the term is on, so every reader of the options behaves as on such a box.
+	int sg_frozen_atoms = -1;               // frozen atoms of the current list (-1: not counted since the last upload)
+	DevBuf<double> d_sg_part;               // [2 kSgBlocks] per-workgroup partials: energies, kept terms
+	struct mpmc_silvera_goldman_info sg_info{}; // of the last evaluation with the term (mpmc_silvera_goldman_info)
 
 	// cavity_autoreject (mpmc_set_cavity_autoreject, kernels_contact.hip; kept.ca_rules, kept.ca_scale); the contact counts of a configuration
 	// travel in its record, next to the UNPENALISED result they belong to (ConfigTotals: accepted, trial.totals, eval)
@@ -687,7 +697,8 @@ enum : unsigned {
 	RUN_DISP = 512,       // the disp-expansion sum (contexts with the term switched on: it replaces the LJ part of rd_energy)
 	RUN_CRYSTAL = 1024,   // the rd_crystal lattice sum (contexts with the term switched on and disp-expansion off: it replaces the LJ sum)
 	RUN_RDM = 2048,       // the rd-model sum (contexts with a non-default model: it replaces the LJ part of rd_energy)
-	RUN_CONTACT = 4096    // the contact walk of cavity_autoreject (contexts with a rule on; never the single-launch form)
+	RUN_CONTACT = 4096,   // the contact walk of cavity_autoreject (contexts with a rule on; never the single-launch form)
+	RUN_SG = 8192         // the Silvera-Goldman sum (contexts with the term switched on: it is the whole of rd_energy, and no pair pass runs beside it)
 };
 // 3 x the unit factor of System::axilrod_teller (hartree bohr^9 -> K A^9, src/System.Energy.cpp:1709): the mixing rule's 3 and the units,
 // applied once to the sum of the per-triple terms
@@ -697,7 +708,18 @@ int disp_ready(mpmc_ctx *c);       // the same for the disp-expansion term, and 
 DispParams disp_params(const mpmc_ctx *c);
 inline bool rd_model_on(const mpmc_ctx *c) { return c->kept.rdm_form != 0 || c->kept.rdm_mix != 0; }
 // (disp_expansion() ignores rd_crystal, and so do lj_buffered_14_7() and dreiding())
-inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled && c->kept.rdm_form == 0; }
+// (... and so does sg())
+inline bool crystal_on(const mpmc_ctx *c) { return c->kept.rc_enabled && !c->kept.de_enabled && c->kept.rdm_form == 0 && !c->kept.sg_enabled; }
+inline bool sg_on(const mpmc_ctx *c) { return c->kept.sg_enabled; }
+int sg_ready(mpmc_ctx *c);         // the term's combinations and the list are valid (no model, no disp-expansion, no sigma rule, fewer than two frozen atoms), the partials stand (context.cpp)
+SgParams sg_params(const mpmc_ctx *c); // feynman_hibbs and its constant at this temperature (context.cpp)
+// the options the evaluations read: the caller's, and under the Silvera-Goldman term rd_only on and polarization off (System::energy :46)
+inline mpmc_options effective_options(const mpmc_ctx *c, const mpmc_options &user) {
+	mpmc_options o = user;
+	if (c->kept.sg_enabled) o.rd_only = 1, o.polarization = 0;
+	return o;
+}
+void apply_options(mpmc_ctx *c, const mpmc_options &eff); // the evaluations' options change: the order rule, the open solve, the k tables, the static terms, the accepted totals (context.cpp)
 int rd_model_ready(mpmc_ctx *c);   // the model's combinations and atom parameters are valid, its table is on the device in the current slot order, its correction is current (context.cpp)
 RdModelParams rd_model_params(const mpmc_ctx *c); // form, rule, distance test and this evaluation's Feynman-Hibbs constants (evaluate.cpp)
 inline bool contact_on(const mpmc_ctx *c) { return c->kept.ca_rules != 0; }
@@ -714,10 +736,11 @@ void contact_penalise(const mpmc_ctx *c, mpmc_result *r, int64_t n_replaced); //
 enum class RdForm {
 	PLAIN,          // (lj_pairs + lrc_pair) + lrc_self
 	CRYSTAL_SELF,   // ((lj_pairs + lrc_pair) + crystal_self) + lrc_self: rd_crystal, in lj()'s order
-	NO_CORRECTIONS  // lj_pairs: lj_buffered_14_7() and dreiding() have no long-range correction
+	NO_CORRECTIONS  // lj_pairs: lj_buffered_14_7(), dreiding() and sg() have no long-range correction
 };
 void compose_totals(const mpmc_ctx *c, RdForm form, mpmc_result *r);
 inline RdForm rd_form_of(const mpmc_ctx *c) { // by the terms switched on (the trial paths, contact_penalise)
+	if (sg_on(c)) return RdForm::NO_CORRECTIONS;
 	if (rd_model_on(c)) return c->kept.rdm_form == RD_FORM_LJ ? RdForm::PLAIN : RdForm::NO_CORRECTIONS;
 	return crystal_on(c) ? RdForm::CRYSTAL_SELF : RdForm::PLAIN;
 }

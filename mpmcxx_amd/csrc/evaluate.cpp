@@ -1071,6 +1071,11 @@ static int stage_added_terms(mpmc_ctx *c, const EvalPlan &p, const AtomsDev &at,
 		const int *cls = (p.pair_pass && c->box.ortho && !c->kept.tune.no_classes) ? c->d_cls.p : nullptr;
 		launch_rd_model(st, at, c->d_rdm_sp, c->d_tile_pairs, cls, c->n_tile_pairs, c->box, rd_model_params(c), c->d_rdm_part, c->d_scal + S_RDM);
 	}
+	// ---- Silvera-Goldman, System::sg (:115-116, 1763-1867): the pair sum and its kept terms into their two slots ------------------------
+	if (p.mask & RUN_SG) {
+		ProfScope ps(c, MPMC_K_PAIR);
+		launch_sg(st, at, c->d_perm, c->d_tile_pairs, c->n_tile_pairs, c->box, sg_params(c), c->d_sg_part, c->d_scal + S_SG);
+	}
 	// ---- cavity_autoreject: the contact counts and the tile pairs it skipped into their three slots.  Its own tile-pair classes come from
 	// this evaluation's tile bounding boxes, where the pairwise pass made them and the cell is orthorhombic ----------------------------------
 	if (p.mask & RUN_CONTACT) {
@@ -1117,6 +1122,7 @@ int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
 	if ((mask & RUN_DISP) && (rc = disp_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CRYSTAL) && (rc = crystal_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_RDM) && (rc = rd_model_ready(c)) != MPMC_OK) return rc;
+	if ((mask & RUN_SG) && (rc = sg_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_CONTACT) && (rc = contact_ready(c)) != MPMC_OK) return rc;
 	if ((mask & RUN_SOLVE) && ewald_full_on(c)) {
 		if (c->kept.palmo_enabled)
@@ -1347,6 +1353,15 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 		c->rdm_info.n_tile_pairs = c->n_tile_pairs;
 		c->rdm_info.n_tile_pairs_skipped = (int64_t)s[S_RDM_SKIPPED];
 	}
+	if (c->run_mask & RUN_SG) { // sg() is the whole of rd_energy (:115-116): no long-range correction, no rd_crystal sum
+		out->lj_pairs = s[S_SG];
+		out->lrc_pair = out->lrc_self = 0.0;
+		form = RdForm::NO_CORRECTIONS;
+		ev.sg_terms = (int64_t)s[S_SG_TERMS];
+		c->sg_info.feynman_hibbs = c->opts.feynman_hibbs ? 1 : 0;
+		c->sg_info.n_terms = ev.sg_terms;
+		c->sg_info.cutoff = c->box.cutoff;
+	}
 	out->es_real = s[S_ES_REAL] - s[S_ES_INTRA];
 	out->es_recip = s[S_ES_RECIP];
 	out->es_self = (c->run_mask & RUN_RECIP) ? c->h_static[2] : 0.0;
@@ -1358,7 +1373,7 @@ int mpmc::wait_and_fill(mpmc_ctx *c, mpmc_result *out) {
 	out->N = c->N_movable;
 	compose_totals(c, form, out);
 	out->n_pairs = (int64_t)c->n * (c->n - 1) / 2;
-	out->n_lj_in_cutoff = c->h_cnt[C_LJ_IN];
+	out->n_lj_in_cutoff = (c->run_mask & RUN_SG) ? 0 : c->h_cnt[C_LJ_IN]; // (no Lennard-Jones pass under Silvera-Goldman: mpmc_silvera_goldman_info counts its pairs)
 	out->n_es_in_cutoff = c->h_cnt[C_ES_IN];
 	out->n_intra = c->static_cnt[0];
 	out->n_rd_excluded = c->static_cnt[1];
@@ -1381,6 +1396,8 @@ void mpmc::compose_totals(const mpmc_ctx *c, RdForm form, mpmc_result *r) {
 }
 
 unsigned mpmc::full_mask(const mpmc_ctx *c) {
+	if (sg_on(c)) // (:46, :115-116: sg() alone, no electrostatics, no polarization, no pair pass; Axilrod-Teller and the absolute contacts on top)
+		return RUN_SG | (c->kept.tb_enabled ? RUN_THREE_BODY : 0u) | (contact_on(c) ? RUN_CONTACT : 0u);
 	unsigned m = RUN_PAIR | RUN_ATOMTERMS;
 	if (!c->opts.rd_only) {
 		m |= RUN_PAIR_ES;
@@ -1463,6 +1480,11 @@ static int run_piece(mpmc_ctx *c, unsigned mask, mpmc_result *r) {
 extern "C" int mpmc_lj(mpmc_ctx *c, double *out) {
 	mpmc_result r;
 	if (!c) return MPMC_ERR_ARG;
+	if (sg_on(c)) { // (sg() in place of lj(): a complete energy() when nothing else is on, and then it re-bases like one)
+		int rc = run_piece(c, RUN_SG, &r);
+		if (rc == MPMC_OK && out) *out = r.rd_energy;
+		return rc;
+	}
 	// (cavity_autoreject: the sigma rule lives inside lj(); the absolute rule belongs to energy() alone)
 	const bool contact = (c->kept.ca_rules & CA_RULE_SIGMA) != 0 && !c->kept.de_enabled; // (under disp-expansion the rule is disp_expansion()'s: mpmc_disp_expansion)
 	int rc = run_piece(c, RUN_PAIR | RUN_ATOMTERMS | (crystal_on(c) ? RUN_CRYSTAL : 0u) | (rd_model_on(c) ? RUN_RDM : 0u) | (contact ? RUN_CONTACT : 0u), &r);

@@ -62,6 +62,7 @@ enum : int {
 	S_CRYSTAL, S_CRYSTAL_TERMS,                  // rd_crystal pair sum and its image-term count (a double: exact) (kernels_crystal.hip)
 	S_RDM, S_RDM_TERMS, S_RDM_SKIPPED,           // rd-model pair sum, its kept terms and the tile pairs it skipped (doubles: exact) (kernels_rd_model.hip)
 	S_CA_REPLACED, S_CA_ABSOLUTE, S_CA_SKIPPED,  // cavity_autoreject: pairs replaced by MAXVALUE, absolute contacts, tile pairs not walked (doubles: exact) (kernels_contact.hip)
+	S_SG, S_SG_TERMS,                            // Silvera-Goldman pair sum and its kept terms (a double: exact) (kernels_sg.hip)
 	S_COUNT = 24
 };
 enum : int { C_LJ_IN = 0, C_ES_IN, C_INTRA, C_RDX, C_ESX, C_FROZEN, C_COUNT = 8 };
@@ -71,13 +72,13 @@ enum : int {
 	D_CNT_LJ, D_CNT_ES,                                   // the two int64 counts
 	D_THREE_BODY,                                         // Axilrod-Teller (kernels_three_body.hip)
 	D_DISP,                                               // disp-expansion (kernels_disp.hip)
-	D_RD, D_RD_TERMS,                                     // rd_crystal's lattice sum and image terms, OR the rd model's sum and kept terms
+	D_RD, D_RD_TERMS,                                     // rd_crystal's lattice sum and image terms, OR the rd model's OR Silvera-Goldman's sum and kept terms
 	D_CA_REPLACED, D_CA_ABSOLUTE,                         // cavity_autoreject: change of the replaced pairs and of the absolute contacts (kernels_contact.hip)
 	D_COUNT
 };
 // rd_crystal and the rd model share D_RD and D_RD_TERMS.  They never meet: a context with a model is not `rd_crystal on` (crystal_on is false
 // for it, context.h) and rd_model_ready refuses the combination, so at most one of launch_crystal_delta and launch_rd_model_delta runs
-// per move; each writes both slots.
+// per move; each writes both slots.  The Silvera-Goldman term shares them too: it is refused together with a model and ignores rd_crystal.
 static_assert(D_RD_TERMS == D_RD + 1, "the delta launchers of the rd terms write { sum, terms } side by side");
 // the pinned host mirror (h_delta_out) holds the same slots with the launch number of k_delta_finish, which the host polls, in between:
 // that slot stays where it was before the later terms came
@@ -461,6 +462,20 @@ void launch_rd_model_lrc(hipStream_t st, const AtomsDev &at, const double4 *sp, 
 // out2 = { change of the pair sum, change of the kept terms }
 void launch_rd_model_delta(hipStream_t st, const AtomsDev &at, const double4 *sp, const Box &bx, const RdModelParams &rp, const int *mv_slot,
                            const double4 *mv_new, int m, int *moved_idx, double *part, double *out2);
+
+// ---- the Silvera-Goldman H2 potential: a pair function of the distance alone over EVERY pair inside the cutoff (kernels_sg.hip) -----
+// perm[slot] = the atom's index in the caller's list (Feynman-Hibbs: the molecule mass of the pair's FIRST atom there).  part: [2 kSgBlocks].
+constexpr int kSgBlocks = 4096;
+struct SgParams {
+	int fh;      // feynman_hibbs: the second-order term of System::sg :1829-1847 (feynman_hibbs_order plays no part)
+	double fh_c; // M2A^2 hBar^2 / (24 kB T amu): times 1 / (molecule mass, amu)
+};
+// out2 = { pair sum, kept terms }
+void launch_sg(hipStream_t st, const AtomsDev &at, const int *perm, const int2 *tile_pairs, int n_tile_pairs, const Box &bx, const SgParams &sp, double *part,
+               double *out2);
+// out2 = { change of the pair sum, change of the kept terms }
+void launch_sg_delta(hipStream_t st, const AtomsDev &at, const int *perm, const Box &bx, const SgParams &sp, const int *mv_slot, const double4 *mv_new, int m,
+                     int *moved_idx, double *part, double *out2);
 
 // ---- cavity_autoreject: the contact counts of mpmc_set_cavity_autoreject (kernels_contact.hip) -------------------------------------------
 // Integer pair sums carried as doubles (exact).  sp: the rd model's per-atom table when `model` is set, the disp-expansion term's

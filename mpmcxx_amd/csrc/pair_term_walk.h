@@ -1,5 +1,5 @@
 // pair_term_walk.h -- the two walks of the energy terms that are sums over atom pairs (disp-expansion, rd_crystal, the rd model and its pair
-// correction), written once.  Included after kernels.h by kernels_disp.hip, kernels_crystal.hip and kernels_rd_model.hip; a term's file holds
+// correction, Silvera-Goldman), written once.  Included after kernels.h by kernels_disp.hip, kernels_crystal.hip, kernels_rd_model.hip and kernels_sg.hip; a term's file holds
 // its Term and its launchers, nothing of the walks.
 //
 // k_pair_term_sum: all tile pairs I <= J of the 64-atom tiles, one 64-lane wave per item, items in a fixed stride over the grid.  Lanes own
@@ -13,7 +13,7 @@
 // move list: O(m N).  launch_mark_moved in front, the map-clearing k_sum_partials behind.
 //
 // A Term (passed by value, like PairField of k_field_delta) states:
-//   kDoubles, load(slot, v)   the per-atom payload, as doubles; the walks lay it into LDS as s_v[kDoubles][64] and read it back
+//   kDoubles, load(slot, v)   the per-atom payload, as doubles (0: none); the walks lay it into LDS as s_v[kDoubles][64] and read it back
 //   kGeometry                 false: a sum over the parameters alone -- no positions, no molecule ids (the rd model's pair correction)
 //   admits(PairFlags)         which pairs count
 //   pair<ORTHO>(...)          one pair at the raw displacement pos_a - pos_b with both payloads and flag words; cnt += the terms it kept
@@ -37,9 +37,9 @@ inline int pair_term_grid(long long work_items, int blocks) { return (int)std::m
 template <bool ORTHO, class Term>
 __global__ __launch_bounds__(64) void k_pair_term_sum(Term term, const double4 *__restrict__ xyzq, const int2 *__restrict__ mf, const int2 *__restrict__ tile_pairs,
                                                       const int *__restrict__ cls, int n, int n_items, int jsplit, Box bx, double *__restrict__ part) {
-	constexpr int D = Term::kDoubles;
+	constexpr int D = Term::kDoubles, DA = D > 0 ? D : 1; // (a term without payload: arrays of one unused element, which take no register and no LDS)
 	constexpr bool G = Term::kGeometry;
-	__shared__ double s_pos[3][kTile], s_v[D][kTile];
+	__shared__ double s_pos[3][kTile], s_v[DA][kTile];
 	__shared__ int s_mol[kTile], s_fl[kTile]; // (an instantiation without geometry never touches s_pos and s_mol: they take no LDS there)
 	const int l = threadIdx.x;
 	if (!Term::kJSplit) jsplit = 1;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void k_pair_term_sum(Term term, const double4 *
 		double4 pi = {}, pj = {};
 		if (G) pi = xyzq[i], pj = xyzq[jl];
 		const int2 mi = mf[i], mj = mf[jl];
-		double vi[D], vj[D];
+		double vi[DA], vj[DA];
 		term.load(i, vi);
 		term.load(jl, vj);
 		const int nj = min(kTile, n - J * kTile);
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64) void k_pair_term_sum(Term term, const double4 *
 		for (int jj = q * jw; jj < j1; ++jj) {
 			const PairFlags f = pair_flags(mi.x, mi.y, G ? s_mol[jj] : mi.x, s_fl[jj]); // (without geometry only the flag words speak)
 			if (i_in && (I != J || jj > l) && Term::admits(f)) {
-				double vb[D];
+				double vb[DA];
 				for (int d = 0; d < D; d++) vb[d] = s_v[d][jj];
 				acc += term.template pair<ORTHO>(bx, G ? pi.x - s_pos[0][jj] : 0.0, G ? pi.y - s_pos[1][jj] : 0.0, G ? pi.z - s_pos[2][jj] : 0.0, vi, vb, mi.y,
 				                                 s_fl[jj], f, cnt);
@@ -94,7 +94,7 @@ template <bool ORTHO, class Term>
 __global__ __launch_bounds__(64) void k_pair_term_delta(Term term, const double4 *__restrict__ xyzq, const int2 *__restrict__ mf, int n, int n_tiles, Box bx,
                                                         const int *__restrict__ mv_slot, const double4 *__restrict__ mv_new, int m,
                                                         const int *__restrict__ moved_idx, double *__restrict__ part) {
-	constexpr int D = Term::kDoubles;
+	constexpr int D = Term::kDoubles, DA = D > 0 ? D : 1;
 	const int l = threadIdx.x;
 	term.prepare();
 	// a skewed cell's reciprocal basis in vector registers: with the pointers, the parameters and the loop state the 18 doubles of the two
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64) void k_pair_term_delta(Term term, const double4
 		const int sa = mv_slot[t];
 		double4 pao = xyzq[sa], pan = mv_new[t];
 		const int2 ma = mf[sa];
-		double va[D];
+		double va[DA];
 		term.load(sa, va);
 		// (the moved atom's values are wave-uniform: kept in vector registers, the box and the pointers fill the scalar ones; an orthorhombic
 		// cell leaves room for the new position)
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void k_pair_term_delta(Term term, const double4
 		const double4 pjo = xyzq[j];
 		const double4 pjn = (mv_j >= 0) ? mv_new[mv_j] : pjo;
 		const int2 mj = mf[j];
-		double vj[D];
+		double vj[DA];
 		term.load(j, vj);
 		const PairFlags f = pair_flags(ma.x, ma.y, mj.x, mj.y);
 		// partners of the moved atom t: every other atom the term admits, a moved one only when it comes later in the move list

@@ -209,7 +209,7 @@ static int xch_energy_async(mpmc_ctx *c) {
 	const int m = c->trial.count, kind = c->trial.xch_kind;
 	c->trial.polar_delta = false;
 	c->trial.inline_move = false;
-	if (polar || m > MPMC_TRIAL_MAX_ATOMS || crystal_on(c) || rd_model_on(c)) {
+	if (polar || m > MPMC_TRIAL_MAX_ATOMS || crystal_on(c) || rd_model_on(c) || sg_on(c)) {
 		// the dipole solve couples every atom, and the further terms have no exchange delta: the trial composition is evaluated in full
 		AtomRun acc, list;
 		copy_atom_run(c, 0, c->n, acc);
@@ -396,7 +396,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 	// call saved is ~5 us of a ~25 us move).  The polarizable path keeps the device lists (its field / store kernels read them).
 	const bool no_inline = c->kept.tune.no_inline_move;
 	// (the three-body, disp-expansion, rd_crystal, rd-model and contact deltas read the moved atoms from the device lists: a box with one of them always stages its move)
-	c->trial.inline_move = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c) && !contact_on(c);
+	c->trial.inline_move = !polar_delta && m <= kMvInline && !no_inline && !c->kept.tb_enabled && !c->kept.de_enabled && !crystal_on(c) && !rd_model_on(c) && !sg_on(c) && !contact_on(c);
 	if (c->trial.inline_move) {
 		for (int t = 0; t < m; t++) {
 			const int i = c->trial.first + t;
@@ -454,6 +454,14 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		ProfScope p(c, MPMC_K_PAIR);
 		launch_rd_model_delta(st, atoms_view(c), c->d_rdm_sp, c->box, rd_model_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_rdm_part,
 		                      c->d_delta_out + D_RD);
+	}
+	if (sg_on(c)) {
+		// Silvera-Goldman: the change of the pairs with a moved atom, O(m N), old positions still resident; into D_RD and D_RD_TERMS of the
+		// delta result block (no model and no rd_crystal sum beside it: sg_ready, crystal_on).  It replaces the LJ delta of launch_delta,
+		// which runs without electrostatics here (no structure-factor update) and posts the block.
+		if ((rc = sg_ready(c)) != MPMC_OK) return rc;
+		ProfScope p(c, MPMC_K_PAIR);
+		launch_sg_delta(st, atoms_view(c), c->d_perm, c->box, sg_params(c), c->d_mv_slot, c->d_mv_new, m, c->d_moved_idx, c->d_sg_part, c->d_delta_out + D_RD);
 	}
 	if (contact_on(c)) {
 		// cavity_autoreject: the change of the contact counts of the pairs with a moved atom, O(m N), old positions still resident; into
@@ -609,7 +617,12 @@ extern "C" int mpmc_trial_energy_wait(mpmc_ctx *c, mpmc_result *out) {
 		tr.rdm_terms = acc.rdm_terms + (int64_t)dh[delta_host_index(D_RD_TERMS)];
 		c->rdm_info.n_terms = tr.rdm_terms;
 	}
-	r.n_lj_in_cutoff = a.n_lj_in_cutoff + c->h_delta_cnt[0];
+	if (sg_on(c)) { // (lj_pairs holds sg()'s sum; n_lj_in_cutoff stays 0 under the term)
+		r.lj_pairs = a.lj_pairs + dh[delta_host_index(D_RD)];
+		tr.sg_terms = acc.sg_terms + (int64_t)dh[delta_host_index(D_RD_TERMS)];
+		c->sg_info.n_terms = tr.sg_terms;
+	}
+	r.n_lj_in_cutoff = sg_on(c) ? 0 : a.n_lj_in_cutoff + c->h_delta_cnt[0];
 	if (do_es) {
 		r.es_real = a.es_real + (dh[delta_host_index(D_ES_REAL)] - dh[delta_host_index(D_ES_INTRA)]);
 		r.es_recip = dh[delta_host_index(D_ES_RECIP)];
@@ -749,6 +762,7 @@ extern "C" int mpmc_insert_candidates(mpmc_ctx *c, int count, int n_cand, const 
 	if (o.polarization && !o.rd_only) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: a polarizable box has no insertion delta (use single trials)");
 	if (crystal_on(c)) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: rd_crystal has no insertion delta (use single trials)");
 	if (rd_model_on(c)) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: a non-default rd model has no insertion delta (use single trials)");
+	if (sg_on(c)) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: the Silvera-Goldman term has no insertion delta (use single trials)");
 	if (count > MPMC_TRIAL_MAX_ATOMS) return fail(c, MPMC_ERR_UNSUPPORTED, "mpmc_insert_candidates: count > MPMC_TRIAL_MAX_ATOMS (use single trials)");
 	if ((rc = xch_molecule_checks(c, "mpmc_insert_candidates", count, n_cand, pos, charge, polarizability, epsilon, sigma, mass)) != MPMC_OK) return rc;
 	const int32_t id = xch_largest_mol_id(c);

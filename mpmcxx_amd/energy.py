@@ -79,6 +79,11 @@ class RdModelInfo(C.Structure):
     _fields_ = [("form", C.c_int32), ("mixing", C.c_int32), ("n_terms", C.c_int64), ("n_tile_pairs", C.c_int64), ("n_tile_pairs_skipped", C.c_int64)]
 
 
+class SilveraGoldmanInfo(C.Structure):
+    """mpmc_silvera_goldman_info: the setting, and the last evaluation of a context with the Silvera-Goldman term."""
+    _fields_ = [("enabled", C.c_int32), ("feynman_hibbs", C.c_int32), ("n_terms", C.c_int64), ("cutoff", C.c_double)]
+
+
 # MPMC_RD_FORM_* / MPMC_RD_MIX_* and the reference keywords that select them
 RD_FORM = {"lj": 0, "lj_buffered_14_7": 1, "dreiding": 2}
 RD_MIX = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}
@@ -248,6 +253,9 @@ def lib():
     if hasattr(L, "mpmc_set_rd_model") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the rd model)
         L.mpmc_set_rd_model.argtypes = [vp, C.c_int, C.c_int]
         L.mpmc_rd_model_info.argtypes = [vp, C.POINTER(RdModelInfo)]
+    if hasattr(L, "mpmc_set_silvera_goldman") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for the Silvera-Goldman potential)
+        L.mpmc_set_silvera_goldman.argtypes = [vp, C.c_int]
+        L.mpmc_silvera_goldman_info.argtypes = [vp, C.POINTER(SilveraGoldmanInfo)]
     if hasattr(L, "mpmc_set_cavity_autoreject") or not os.environ.get("MPMC_ENERGY_LIB"):  # (likewise for cavity_autoreject)
         L.mpmc_set_cavity_autoreject.argtypes = [vp, C.c_int, C.c_double, C.c_double]
         L.mpmc_cavity_autoreject_info.argtypes = [vp, C.POINTER(AutorejectInfo)]
@@ -477,6 +485,10 @@ class System:
         if any(k in options for k in RD_MODEL_KEYS) or getattr(self, "_rd_model_set", False):
             self._rd_model_set = True
             self.set_rd_model(*rd_model_of(options))
+        # `sg` likewise: the Silvera-Goldman potential
+        if "sg" in options or getattr(self, "_sg_set", False):
+            self._sg_set = True
+            self.set_silvera_goldman(bool(options.get("sg")))
         # cavity_autoreject likewise: `cavity_autoreject`, `cavity_autoreject_absolute`, `cavity_autoreject_scale`, `cavity_autoreject_repulsion`
         if any(k in options for k in AUTOREJECT_KEYS) or getattr(self, "_autoreject_set", False):
             self._autoreject_set = True
@@ -602,6 +614,16 @@ class System:
         v = RdModelInfo()
         self._check(self._L.mpmc_rd_model_info(self._h, C.byref(v)))
         return {k: getattr(v, k) for k, _ in RdModelInfo._fields_}
+
+    def set_silvera_goldman(self, enabled: bool = True):
+        """The Silvera-Goldman H2 potential (mpmc_set_silvera_goldman): sg() in place of lj(), no electrostatics, no polarization."""
+        self._check(self._L.mpmc_set_silvera_goldman(self._h, 1 if enabled else 0))
+
+    def silvera_goldman_info(self) -> Dict[str, object]:
+        """enabled, and feynman_hibbs, n_terms and cutoff of the last evaluation with the term (mpmc_silvera_goldman_info)"""
+        v = SilveraGoldmanInfo()
+        self._check(self._L.mpmc_silvera_goldman_info(self._h, C.byref(v)))
+        return {k: getattr(v, k) for k, _ in SilveraGoldmanInfo._fields_}
 
     def set_cavity_autoreject(self, rules: int = 0, scale: float = 0.0, repulsion: float = 0.0):
         """cavity_autoreject (mpmc_set_cavity_autoreject): rules = AUTOREJECT_SIGMA | AUTOREJECT_ABSOLUTE (0: off), scale in (0, 1]."""

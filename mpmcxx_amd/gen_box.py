@@ -416,6 +416,8 @@ def fixture(name: str):
         return _ewald_full_fixture(name)
     if name in RD_MODEL_FIXTURES:
         return _rd_model_fixture(name)
+    if name in SG_FIXTURES:
+        return _sg_fixture(name)
     if name in RELAX_FIXTURES:
         return _relax_fixture(name)
     if name in GS_RANKED_FIXTURES:
@@ -867,6 +869,92 @@ def rd_model_golden(golden_dir: str, name: str) -> Dict[str, object]:
         return json.load(f)[name]
 
 
+# ---- `sg on`: the Silvera-Goldman H2 potential (reference src/System.Energy.cpp:1763-1867) ------------------------------------------------------
+# Hydrogen at about the liquid's density (3.75 A between lattice sites, +-10 % jitter): the cutoff, half the shortest cell edge, lies beyond
+# RM = 8.321 bohr = 4.40 A, so every box has pairs on both sides of the switch of the damping function.  sigma, epsilon and the charge play
+# no part in sg(); the rows carry hydrogen's usual values.
+#   h2_64_sg, h2_216_sg        single-site molecules in cubic cells of 15 and 22.5 A
+#   h2_64_sg_ortho             64 sites in a 14 x 16 x 18 A cell;  h2_216_sg_tri: 216 sites in a skewed cell
+#   h2_2site_sg                32 molecules of two sites 2.4 A apart: sg() counts the pairs inside a molecule
+#   h2d2_64_sg_fh_a / _b       H2 and D2 alternating, feynman_hibbs on at 30 K: the correction takes the mass of the molecule of the pair's
+#                              FIRST atom in the list; _b lists the same atoms in reverse order
+#   h2_64_sg_lrc               rd_lrc on and rd_crystal on (order 2): sg() ignores both
+#   h2_64_sg_polar             charges, polarizabilities and polarization on: energy() skips electrostatics and polarization under sg
+SG_MASS = {"H2": 2.016, "D2": 4.028}
+SG_FIXTURES = ["h2_64_sg", "h2_216_sg", "h2_64_sg_ortho", "h2_216_sg_tri", "h2_2site_sg", "h2d2_64_sg_fh_a", "h2d2_64_sg_fh_b", "h2_64_sg_lrc",
+               "h2_64_sg_polar"]
+SG_GOLDEN = "sg.json"  # under tests/golden/: every fixture's scalars
+SG_TRI_BASIS = [[22.5, 0.0, 0.0], [3.0, 22.0, 0.0], [-2.0, 4.0, 21.5]]
+
+
+def _h2_rows(rows: List[AtomRow], charged: bool = False) -> List[AtomRow]:
+    for r in rows:
+        r.atomtype, r.moltype, r.mass, r.eps, r.sigma = "H2G", "H2", SG_MASS["H2"], 34.2, 2.96
+        if not charged:
+            r.charge_e, r.alpha = 0.0, 0.0
+    return rows
+
+
+def _sg_fixture(name: str):
+    o = {"sg": "on"}
+    if name == "h2_216_sg":
+        return _h2_rows(lattice_box(216, 22.5, 31)), cubic(22.5), o
+    if name == "h2_64_sg_ortho":
+        basis = [[14.0, 0.0, 0.0], [0.0, 16.0, 0.0], [0.0, 0.0, 18.0]]
+        return _h2_rows(lattice_box_cell(64, basis, 32)), basis, o
+    if name == "h2_216_sg_tri":
+        return _h2_rows(lattice_box_cell(216, SG_TRI_BASIS, 33)), SG_TRI_BASIS, o
+    if name == "h2_2site_sg":  # the second site 2.4 A from the first, in a seeded direction
+        rng = random.Random(34)
+        rows = []
+        for k, r in enumerate(_h2_rows(lattice_box(32, 15.0, 35))):
+            ux, uy, uz = _rot(rng)[0]
+            rows.append(AtomRow(2 * k + 1, "H2G", "H2", "M", k + 1, r.x, r.y, r.z, 1.008, 0.0, 0.0, 34.2, 2.96))
+            rows.append(AtomRow(2 * k + 2, "H2E", "H2", "M", k + 1, r.x + 2.4 * ux, r.y + 2.4 * uy, r.z + 2.4 * uz, 1.008, 0.0, 0.0, 0.0, 0.0))
+        return rows, cubic(15.0), o
+    if name.startswith("h2d2_64_sg_fh_"):
+        rows = _h2_rows(lattice_box(64, 15.0, 36))
+        for r in rows[1::2]:
+            r.atomtype, r.moltype, r.mass = "D2G", "D2", SG_MASS["D2"]
+        if name.endswith("_b"):
+            rows = rows[::-1]
+            for k, r in enumerate(rows):
+                r.atom_id = r.mol_id = k + 1
+        return rows, cubic(15.0), dict(o, feynman_hibbs="on", temperature=30.0)
+    if name == "h2_64_sg_lrc":
+        return _h2_rows(lattice_box(64, 15.0, 30)), cubic(15.0), dict(o, rd_lrc="on", rd_crystal="on", rd_crystal_order=2)
+    if name == "h2_64_sg_polar":
+        rows = _h2_rows(lattice_box(64, 15.0, 30, alpha=0.8), charged=True)
+        return rows, cubic(15.0), dict(POLAR_OPTS, **o)
+    return _h2_rows(lattice_box(64, 15.0, 30)), cubic(15.0), o  # h2_64_sg
+
+
+def keep_sg_golden(golden_dir: str, names: Optional[List[str]] = None) -> None:
+    """After `python oracle/make_golden.py <SG_FIXTURES>`: the per-fixture files are folded into SG_GOLDEN (scalars and cell only) and
+    removed, the box text too (the tests regenerate it with `materialize`, which writes the same bytes the reference read)."""
+    import json
+
+    out = {}
+    for name in (names or SG_FIXTURES):
+        with open(os.path.join(golden_dir, f"{name}.json")) as f:
+            res = json.load(f)
+        out[name] = {k: v for k, v in res.items() if not isinstance(v, list) or k in ("basis", "reciprocal_basis")}
+    with open(os.path.join(golden_dir, SG_GOLDEN), "w") as f:
+        json.dump(out, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    for name in (names or SG_FIXTURES):
+        for ext in (".json", ".in", ".pqr"):
+            if os.path.exists(os.path.join(golden_dir, name + ext)):
+                os.remove(os.path.join(golden_dir, name + ext))
+
+
+def sg_golden(golden_dir: str, name: str) -> Dict[str, object]:
+    import json
+
+    with open(os.path.join(golden_dir, SG_GOLDEN)) as f:
+        return json.load(f)[name]
+
+
 # ---- `polar_ewald_full on` (reference src/System.Energy.cpp:2785-2830, 2944-3143) -------------------------------------------------------------
 # NAME = BASE_pef[_VARIANT]: the box BASE with the fully periodic dipole solve.  Variants: it3 = polar_max_iter 3 (4 passes); prec =
 # polar_precision 1e-8 and no polar_max_iter.  Bases that exist only here:
@@ -1175,6 +1263,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-rd-model-golden"]:
         keep_rd_model_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+        sys.exit(0)
+    if sys.argv[1:2] == ["--keep-sg-golden"]:
+        keep_sg_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
         sys.exit(0)
     if sys.argv[1:2] == ["--keep-ewald-full-golden"]:
         keep_ewald_full_golden(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))

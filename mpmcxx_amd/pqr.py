@@ -21,7 +21,7 @@ E2REDUCED = 408.7816  # reference src/constants.h:35
 
 # keywords that select physics outside SURVEY §8 -- the replacement must refuse them (§8a note 7)
 UNSUPPORTED_ON = [
-    "spectre", "gwp", "sg", "polarvdw", "cdvdw",
+    "spectre", "gwp", "polarvdw", "cdvdw",
     "polar_wolf_full", "polar_wolf_alpha_lookup", "polar_gs_ranked",
     "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion",
     "disp_expansion_mbvdw", "rd_anharmonic", "cavity_autoreject", "cavity_autoreject_absolute", "cuda", "opencl",
@@ -143,6 +143,8 @@ def read_input(path: str) -> Dict[str, object]:
             elif k in ("polar_sor", "polar_esor", "polar_zodid"):  # (likewise; relaxed dipole updates and zeroth-order dipoles, mpmc_set_polar_relax)
                 opts[k] = _onoff(v[0])
             elif k in ("waldmanhagler", "halgren_mixing", "c6_mixing", "lj_buffered_14_7", "dreiding"):  # (likewise; the rd model, mpmc_set_rd_model)
+                opts[k] = _onoff(v[0])
+            elif k == "sg":  # (likewise; the Silvera-Goldman potential, mpmc_set_silvera_goldman)
                 opts[k] = _onoff(v[0])
             elif k == "cavity_bias":  # (likewise; the cavity-bias grid of uVT moves, mpmc_set_cavity_grid)
                 opts[k] = _onoff(v[0])
