@@ -272,6 +272,46 @@ int mpmc_trial_insert_begin(mpmc_ctx *ctx, int at_index, int count, const double
 /* trial removal of the whole molecule that occupies atoms [first, first+count) */
 int mpmc_trial_remove_begin(mpmc_ctx *ctx, int first, int count);
 
+/* ---- volume trials: the volume change of NPT and of the Gibbs ensemble's volume exchange as a trial --------------------------------------
+ * System::volume_change / volume_change_Gibbs with revert_volume_change as its rejection (src/System.MonteCarlo.cpp:1235-1340, 1690-1727).
+ * The same five calls carry it: mpmc_trial_energy (or _async / _wait), then mpmc_trial_accept or mpmc_trial_reject.
+ *   The move, in the reference's arithmetic: every basis element times basis_scale_factor; reciprocal, volume and cutoff from
+ * mpmc_pbc_compute on the product; ewald_alpha and polar_ewald_alpha follow the new cutoff where the options leave them to the cell; every
+ * molecule (frozen ones too) shifted rigidly by com * s - com, com its centre of mass of the ACCEPTED positions (mass += m_i, cm[p] += m_i *
+ * pos_i[p] atom by atom in list order, cm[p] /= mass, as mpmc_update_com).  The positions are scaled on the device, on the context's stream,
+ * into a second position buffer (MPMC_K_CLASSES); the atoms keep their slots, nothing is sorted or uploaded.
+ *   The trial cell and positions get the full evaluation of whatever terms the context has on (mpmc_debug_last_trial_was_full answers 1);
+ * every field of the mpmc_result is the trial configuration's.
+ *   accept: cell, positions, the host mirrors behind mpmc_update_com / mpmc_cavity_update and the totals become the accepted ones with no
+ * further evaluation; the host computes its mirrors with the same expressions, nothing is copied back.  The next displacement or exchange
+ * trial is a delta on the new cell; a cavity grid is stale, as after mpmc_set_box; a later mpmc_set_box with the scaled basis is a no-op.
+ *   reject: cell, k tables, structure factors, positions, position-independent terms and accepted totals are the accepted configuration's
+ * again without an evaluation (the trial was evaluated into alternate buffers, which trade places back).  In a polarizable box the next
+ * trial evaluates in full, as after any rejected full trial.
+ *   basis_scale_factor == 1.0 is a trial that launches nothing.  MPMC_ERR_ARG with a text: no accepted configuration; a trial already
+ * open; mpmc_set_atoms was called without masses; the accepted cell was set with a caller-supplied reciprocal, volume or cutoff (there is
+ * no rule for scaling an override).  MPMC_ERR_INVALID_DATUM: basis_scale_factor not finite or <= 0; a molecule whose masses sum to 0.
+ * mpmc_set_box, mpmc_set_options, mpmc_set_atoms and mpmc_update_positions close an open volume trial as a rejection before they act. */
+int mpmc_trial_volume_begin(mpmc_ctx *ctx, double basis_scale_factor);
+/* the open volume trial's cell and positions (any pointer may be NULL); valid from _begin until accept / reject */
+int mpmc_trial_volume_get(mpmc_ctx *ctx, double basis[9], double reciprocal[9], double *volume, double *cutoff, double *pos /*[n][3]*/);
+/* diagnostics: out4 = { volume trials evaluated, accepted, rejected, evaluations enqueued from inside mpmc_trial_reject for them } */
+int mpmc_debug_volume_trial_counts(mpmc_ctx *ctx, long long out4[4]);
+/* diagnostics: out3 = { exchange trials on the delta path, exchange trials evaluated in full, summations of the host sums over the whole list } */
+int mpmc_debug_exchange_counts(mpmc_ctx *ctx, long long out3[3]);
+/* diagnostics: the positions resident on the device, original atom order (the trial's while an evaluated volume trial is open); a blocking
+ * copy.  MPMC_ERR_ARG while an upload of the atom list is pending. */
+int mpmc_debug_device_positions(mpmc_ctx *ctx, double *pos /*[n][3]*/);
+/* The ENSEMBLE_NPT branch of System::boltzmann_factor (:1441-1457) in the reference's operand order, host only:
+ *   MPMC_MOVETYPE_VOLUME    exp(-(dE + pressure * ATM2REDUCED * (v_new - v_old) - (N + 1) * T * log(v_new / v_old)) / T), dE = final - init
+ *   MPMC_MOVETYPE_DISPLACE  exp(-dE / T)
+ * anything else: MPMC_ERR_UNSUPPORTED.  N = observables->N of the trial configuration, pressure in atm. */
+typedef struct mpmc_npt_move {
+	int32_t movetype, reserved;
+	double temperature, pressure, N, init_energy, final_energy, volume_old, volume_new;
+} mpmc_npt_move;
+int mpmc_npt_boltzmann_factor(const mpmc_npt_move *move, double *boltzmann_factor);
+
 /* ---- batched insertion candidates: many trial insertions of one molecule in one launch chain ---------------------------------------------
  * Widom test-particle insertion, orientational-bias / multiple-try insertion at one site and energy-biased site selection ask the same
  * question many times against an unchanged accepted configuration: what is the energy with this molecule at this pose?  out[c] is the

@@ -114,6 +114,10 @@ struct GibbsSettings {
 	double temperature = 0, move_factor = 1.0, rot_factor = 1.0; // src/System.h:526-538
 	double volume_probability = 0, transfer_probability = 0, volume_change_factor = 0.25;
 	std::string pqr_input, pqr_input_B;
+	// every move as a device trial (energy_trial_async / energy_trial_insert_async + energy_trial_remove_async / energy_trial_volume_async,
+	// then accept_trial / reject_trial per box) instead of a full energy() of both boxes per step; off: the path of before, untouched.
+	// Needs a System type with the trial methods (the oracle-backed evaluator of tests/cpp/gibbs_check.cpp has none: 4004).
+	bool device_trials = false;
 };
 
 // the Monte Carlo keywords of a reference nvt_gibbs input file (src/SimulationControl.cpp:204-267, :801-863, :1351)
@@ -199,6 +203,10 @@ public:
 
 	// one pass of the main loop of Gibbs_mc (:166-272)
 	void mc_step() {
+		if (cfg.device_trials) {
+			mc_step_trials_select(*systems[0], 0);
+			return;
+		}
 		step++;
 		double init[2], fin[2];
 		init[0] = systems[0]->observables->energy;
@@ -268,6 +276,203 @@ public:
 	}
 
 private:
+	// ---- the same step on device trials (GibbsSettings::device_trials) ------------------------------------------------------------------
+	// The moves are PROPOSED, with the random draws of make_move_Gibbs in its order and from its engines, without touching the boxes' lists;
+	// each box gets one trial, both enqueued before either wait; N, the volumes and iterator_failed come from the trial results; accepted
+	// trials edit the lists (accept_trial), rejected ones leave nothing to restore.  No energy() after the initial one.  One deviation from
+	// the reference: its revert of a volume change scales the rejected cell back and so leaves a round trip's rounding (1e-16 relative) in
+	// positions and centres of mass; a rejected trial keeps the accepted bits.
+	template <class T>
+	auto mc_step_trials_select(T &s, int) -> decltype(s.energy_trial_volume_async(1.0), void()) {
+		mc_step_trials<T>();
+	}
+	template <class T>
+	void mc_step_trials_select(T &, long) {
+		throw 4004; // unsupported_setting: this evaluator has no trial moves
+	}
+	static void com_of(const std::vector<Atom> &atoms, int first, int last, std::array<double, 3> &c) { // Molecule::update_COM over any list
+		double mass = 0;
+		c = {{0, 0, 0}};
+		for (int k = first; k < last; k++) {
+			mass += atoms[k].mass;
+			c[0] += atoms[k].mass * atoms[k].pos[0];
+			c[1] += atoms[k].mass * atoms[k].pos[1];
+			c[2] += atoms[k].mass * atoms[k].pos[2];
+		}
+		c[0] /= mass;
+		c[1] /= mass;
+		c[2] /= mass;
+	}
+	template <class T>
+	void mc_step_trials() {
+		step++;
+		double init[2], fin[2] = {0, 0}, trial_volume[2];
+		init[0] = systems[0]->observables->energy;
+		init[1] = systems[1]->observables->energy;
+		Record r{};
+		r.movetype[0] = movetype[0];
+		r.movetype[1] = movetype[1];
+		bool open[2] = {false, false};
+		std::vector<Atom> moved[2];       // displacement: the moved molecule; transfer: the inserted one
+		std::array<double, 3> ins_com{{0, 0, 0}};
+		try {
+			switch (movetype[0]) {
+			case MPMC_MOVETYPE_DISPLACE: {
+				std::vector<double> pos[2];
+				for (int i = 0; i < 2; i++) { // System::displace on a copy of the molecule: 6 draws of the box's own engine, then the global one
+					const int m = altered[i], first = mol_first[i][m], last = mol_first[i][m + 1];
+					double dice[6];
+					for (int k = 0; k < 6; k++) dice[k] = dist(mt_rand[i]);
+					double tx = cfg.move_factor * dice[0] * systems[i]->pbc.cutoff;
+					double ty = cfg.move_factor * dice[1] * systems[i]->pbc.cutoff;
+					double tz = cfg.move_factor * dice[2] * systems[i]->pbc.cutoff;
+					if (dice[3] < 0.5) tx *= -1.0;
+					if (dice[4] < 0.5) ty *= -1.0;
+					if (dice[5] < 0.5) tz *= -1.0;
+					moved[i].assign(systems[i]->atoms.begin() + first, systems[i]->atoms.begin() + last);
+					for (Atom &a : moved[i]) {
+						a.pos[0] += tx;
+						a.pos[1] += ty;
+						a.pos[2] += tz;
+					}
+					std::array<double, 3> c;
+					com_of(moved[i], 0, (int)moved[i].size(), c);
+					rotate_rand(moved[i], 0, (int)moved[i].size(), c, cfg.rot_factor);
+					for (const Atom &a : moved[i])
+						for (int p = 0; p < 3; p++) pos[i].push_back(a.pos[p]);
+				}
+				for (int i = 0; i < 2; i++) {
+					systems[i]->energy_trial_async(mol_first[i][altered[i]], (int)moved[i].size(), pos[i].data());
+					open[i] = true;
+				}
+				break;
+			}
+			case MPMC_MOVETYPE_VOLUME: { // volume_change_Gibbs: the draws and the two factors, the scaling itself is the trial's
+				double new_volume[2];
+				do {
+					const double log_new_volume = std::log(systems[0]->pbc.volume) + (get_rand(0) - 0.5) * cfg.volume_change_factor;
+					new_volume[0] = std::exp(log_new_volume);
+					new_volume[1] = systems[1]->pbc.volume + systems[0]->pbc.volume - new_volume[0];
+				} while (new_volume[1] <= 0.0);
+				for (int s = 0; s < 2; s++) {
+					systems[s]->energy_trial_volume_async(std::pow(new_volume[s] / systems[s]->pbc.volume, 1.0 / 3.0));
+					open[s] = true;
+				}
+				break;
+			}
+			case MPMC_MOVETYPE_INSERT:
+			case MPMC_MOVETYPE_REMOVE:
+				for (int s = 0; s < 2; s++) {
+					if (movetype[s] != MPMC_MOVETYPE_INSERT) continue;
+					double rnd[3], c[3];
+					for (int p = 0; p < 3; p++) rnd[p] = 0.5 - get_rand(s);
+					for (int p = 0; p < 3; p++) {
+						c[p] = 0;
+						for (int q = 0; q < 3; q++) c[p] += systems[s]->pbc.basis[q][p] * rnd[q];
+					}
+					moved[s] = backup[s];
+					for (Atom &a : moved[s])
+						for (int p = 0; p < 3; p++) a.pos[p] += c[p] - backup_com[s][p];
+					ins_com = {{c[0], c[1], c[2]}};
+					rotate_rand(moved[s], 0, (int)moved[s].size(), ins_com, 1.0);
+					const int o = 1 - s;
+					systems[s]->energy_trial_insert_async(mol_first[s][altered[s]], moved[s]);
+					open[s] = true;
+					systems[o]->energy_trial_remove_async(mol_first[o][altered[o]], mol_first[o][altered[o] + 1] - mol_first[o][altered[o]]);
+					open[o] = true;
+				}
+				break;
+			default:
+				throw (int)MPMC_ERR_INVALID_MC_MOVE_KIND;
+			}
+			for (int i = 0; i < 2; i++) {
+				open[i] = false; // (energy_trial_wait closes the trial itself when it throws)
+				fin[i] = systems[i]->energy_trial_wait();
+				open[i] = true;
+			}
+		} catch (...) { // no box keeps a trial open, or an evaluation in flight, behind a throw
+			for (int i = 0; i < 2; i++)
+				if (open[i]) {
+					try {
+						systems[i]->reject_trial();
+					} catch (...) {
+					}
+				}
+			throw;
+		}
+		int failed[2];
+		double bf[2] = {stored_bf[0], stored_bf[1]}, en[2];
+		mpmc_gibbs_move m{};
+		for (int i = 0; i < 2; i++) {
+			const mpmc_result &t = systems[i]->trial_result();
+			trial_volume[i] = (movetype[0] == MPMC_MOVETYPE_VOLUME) ? systems[i]->trial_volume() : systems[i]->observables->volume;
+			failed[i] = t.iterator_failed;
+			en[i] = t.energy;
+			m.movetype[i] = movetype[i];
+			m.init_energy[i] = init[i];
+			m.final_energy[i] = fin[i];
+			m.N[i] = t.N;
+			m.volume[i] = trial_volume[i];
+		}
+		m.temperature = systems[0]->temperature;
+		m.checkpoint_volume_0 = ckpt_obs[0].volume;
+		const int rc = mpmc_gibbs_boltzmann_factor(&m, bf, en);
+		if (rc != MPMC_OK) {
+			for (int i = 0; i < 2; i++) systems[i]->reject_trial();
+			throw rc;
+		}
+		for (int i = 0; i < 2; i++) {
+			stored_bf[i] = bf[i];
+			r.final_energy[i] = fin[i];
+			r.boltzmann_factor[i] = bf[i];
+		}
+		bool take[2];
+		if (move == MPMC_MOVETYPE_DISPLACE || move == MPMC_MOVETYPE_SPINFLIP) { // independent Metropolis tests (:196-226)
+			for (int i = 0; i < 2; i++) take[i] = (rng.rand() < stored_bf[i]) && !failed[i];
+		} else { // transfers and volume exchanges stand or fall together (:228-270)
+			take[0] = take[1] = (rng.rand() < stored_bf[0]) && !failed[0] && !failed[1];
+		}
+		for (int i = 0; i < 2; i++) {
+			if (!take[i]) {
+				systems[i]->reject_trial();
+				systems[i]->iterator_failed = 0;
+				*systems[i]->observables = ckpt_obs[i];
+				reject[i]++;
+				continue;
+			}
+			systems[i]->accept_trial(); // (the observables take the trial's totals; the lists, and for a volume change the cell, follow)
+			systems[i]->observables->energy = en[i];
+			systems[i]->observables->volume = trial_volume[i];
+			r.accepted[i] = 1;
+			accept[i]++;
+			switch (movetype[i]) {
+			case MPMC_MOVETYPE_DISPLACE:
+				update_COM(i, altered[i], com[i][altered[i]]);
+				break;
+			case MPMC_MOVETYPE_VOLUME:
+				for (int k = 0; k < n_molecules(i); k++) update_COM(i, k, com[i][k]);
+				break;
+			case MPMC_MOVETYPE_INSERT:
+				com[i].insert(com[i].begin() + altered[i], ins_com);
+				rebuild_molecules(i);
+				update_COM(i, altered[i], com[i][altered[i]]);
+				break;
+			default: // REMOVE
+				com[i].erase(com[i].begin() + altered[i]);
+				rebuild_molecules(i);
+			}
+		}
+		for (int i = 0; i < 2; i++) {
+			r.energy[i] = systems[i]->observables->energy;
+			r.N[i] = systems[i]->observables->N;
+			r.volume[i] = systems[i]->pbc.volume;
+			r.natoms[i] = (int)systems[i]->atoms.size();
+		}
+		trace.push_back(r);
+		for (int i = 0; i < 2; i++) ckpt_obs[i] = *systems[i]->observables; // backup_observables_SYS_VECTOR (:274)
+		move = pick_Gibbs_move();
+	}
+
 	static constexpr double kGibbsMaxValue = 1.0e40; // MAXVALUE, src/constants.h:53
 	int move = 0, movetype[2] = {0, 0};
 	double stored_bf[2] = {0, 0};                  // nodestats->boltzmann_factor (entries the acceptance rule leaves alone keep their value)

@@ -25,6 +25,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <random>
 #include <string>
@@ -287,8 +288,59 @@ public:
 		return returned(r);
 	}
 	const mpmc_result &trial_result() const { return trial_result_; } // the trial configuration's totals (observables keep the accepted ones)
+	// ---- volume trials: System::volume_change / volume_change_Gibbs as a trial (mpmc_trial_volume_begin) ----
+	// energy of the configuration with every basis element times basis_scale_factor and every molecule shifted rigidly by com * s - com, then
+	// accept_trial() -- which scales pbc.basis, calls update_pbc() and shifts `atoms` with the library's expressions, so that the host list
+	// equals the device's bit for bit and the next energy() uploads nothing -- or reject_trial(), which leaves both alone.  Needs a prior
+	// energy() of the accepted state, masses on the atoms, and a cell whose reciprocal, volume and cutoff are update_pbc()'s own.
+	// trial_result() holds the trial configuration's totals; trial_volume() its cell volume.
+	double energy_trial_volume(double basis_scale_factor) {
+		energy_trial_volume_async(basis_scale_factor);
+		return energy_trial_wait();
+	}
+	void energy_trial_volume_async(double basis_scale_factor) {
+		check(mpmc_trial_volume_begin(ctx_, basis_scale_factor), "mpmc_trial_volume_begin");
+		trial_kind_ = 2, trial_first_ = 0, trial_scale_ = basis_scale_factor;
+		trial_pos_.clear();
+		exchange_enqueue();
+		check(mpmc_trial_volume_get(ctx_, nullptr, nullptr, &trial_volume_, nullptr, nullptr), "mpmc_trial_volume_get");
+	}
+	double trial_volume() const { return trial_volume_; }
+	// (diagnostics) mpmc_debug_exchange_counts and mpmc_debug_volume_trial_counts of this System's context; zeros before the first evaluation
+	void trial_counts(long long exchange3[3], long long volume4[4]) const {
+		for (int k = 0; k < 3; k++) exchange3[k] = 0;
+		for (int k = 0; k < 4; k++) volume4[k] = 0;
+		if (!ctx_) return;
+		(void)mpmc_debug_exchange_counts(ctx_, exchange3);
+		(void)mpmc_debug_volume_trial_counts(ctx_, volume4);
+	}
 	void accept_trial() {
 		check(mpmc_trial_accept(ctx_), "mpmc_trial_accept");
+		if (trial_kind_ == 2) { // the cell and the list follow the library's, in its arithmetic: the context is not told again
+			const double s = trial_scale_;
+			trial_kind_ = 0;
+			if (s != 1.0) {
+				for (int p = 0; p < 3; p++)
+					for (int q = 0; q < 3; q++) pbc.basis[p][q] *= s;
+				update_pbc();
+				for (size_t a0 = 0; a0 < atoms.size();) {
+					size_t a1 = a0;
+					double m = 0, c[3] = {0, 0, 0};
+					for (; a1 < atoms.size() && atoms[a1].molecule == atoms[a0].molecule; a1++) {
+						m += atoms[a1].mass;
+						for (int d = 0; d < 3; d++) c[d] += atoms[a1].mass * atoms[a1].pos[d];
+					}
+					for (int d = 0; d < 3; d++) {
+						c[d] /= m;
+						const double delta = c[d] * s - c[d];
+						for (size_t k = a0; k < a1; k++) atoms[k].pos[d] += delta;
+					}
+					a0 = a1;
+				}
+			}
+			absorb(trial_result_);
+			return;
+		}
 		if (trial_kind_ > 0) { // the list follows the library's: the context is not told again
 			int id = 0;
 			for (const Atom &a : atoms) id = a.molecule >= id ? a.molecule + 1 : id;
@@ -498,7 +550,8 @@ private:
 	double cavity_radius_ = 0;
 	double polar_wolf_alpha_ = 0;
 	int trial_first_ = 0;
-	int trial_kind_ = 0, trial_count_ = 0; // the open trial: 0 a displacement, +1 an insertion (trial_mol_), -1 a removal
+	int trial_kind_ = 0, trial_count_ = 0; // the open trial: 0 a displacement, +1 an insertion (trial_mol_), -1 a removal, 2 a volume change (trial_scale_)
+	double trial_scale_ = 1.0, trial_volume_ = 0.0;
 	std::vector<Atom> trial_mol_;
 	void exchange_enqueue() {
 		const int rc = mpmc_trial_energy_async(ctx_);
@@ -544,7 +597,13 @@ private:
 			autoreject_scale_ = autoreject_repulsion_ = 0;
 		}
 		if (box_dirty_) {
-			check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
+			// a cell whose reciprocal, volume and cutoff are PeriodicBoundary::update's own goes over as the basis alone: the library computes
+			// the same bits from it, and only a cell without overrides can be scaled by a volume trial
+			double R[9], vol = 0, cut = 0;
+			const bool own = mpmc_pbc_compute(&pbc.basis[0][0], R, &vol, &cut) == MPMC_OK && std::memcmp(R, &pbc.reciprocal_basis[0][0], sizeof(R)) == 0 &&
+			                 vol == pbc.volume && cut == pbc.cutoff;
+			if (own) check(mpmc_set_box(ctx_, &pbc.basis[0][0], nullptr, 0.0, 0.0), "mpmc_set_box");
+			else check(mpmc_set_box(ctx_, &pbc.basis[0][0], &pbc.reciprocal_basis[0][0], pbc.volume, pbc.cutoff), "mpmc_set_box");
 			box_dirty_ = false;
 		}
 		mpmc_options o;
@@ -567,8 +626,10 @@ private:
 		o.polar_precision = polar_precision;
 		o.polar_gamma = polar_gamma;
 		o.polar_damp = polar_damp;
-		o.ewald_alpha = ewald_alpha;
-		o.polar_ewald_alpha = polar_ewald_alpha;
+		// (an alpha that update_pbc() derived from the cutoff is left to the library, which derives the same bits from the same cutoff -- and
+		// goes on doing so for the cell of a volume trial, as update_pbc() does after a volume change)
+		o.ewald_alpha = (ewald_alpha_set != 1 && ewald_alpha == 3.5 / pbc.cutoff) ? 0.0 : ewald_alpha;
+		o.polar_ewald_alpha = (polar_ewald_alpha_set != 1 && polar_ewald_alpha == 3.5 / pbc.cutoff) ? 0.0 : polar_ewald_alpha;
 		// (polar_iterative off is the library's direct dipole solve: no flag; `rd_crystal on` goes to mpmc_set_rd_crystal below: the reader's
 		// flag for the keyword is cleared here, a caller's flag without the field is still refused)
 		// (`polar_ewald_full on` likewise, to mpmc_set_polar_ewald_full, `polar_gs_ranked on` to mpmc_set_polar_gs_ranked and

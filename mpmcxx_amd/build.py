@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, ".obj")
 LIB = os.path.join(HERE, "libmpmc_energy.so")
-SOURCES = ["kernels.hip", "kernels_sym.hip", "kernels_panel.hip", "kernels_pair.hip", "erfc_table.cpp", "kernels_delta.hip", "kernels_exchange.hip", "kernels_insert_batch.hip", "kernels_gs.hip", "kernels_gs_rank.hip", "kernels_dense.hip", "kernels_chol.hip", "kernels_three_body.hip", "kernels_disp.hip", "kernels_crystal.hip", "kernels_rd_model.hip", "kernels_sg.hip", "kernels_contact.hip", "kernels_wolf_field.hip", "kernels_ewald_full.hip", "kernels_cavity.hip", "context.cpp", "evaluate.cpp",
+SOURCES = ["kernels.hip", "kernels_sym.hip", "kernels_panel.hip", "kernels_pair.hip", "erfc_table.cpp", "kernels_delta.hip", "kernels_exchange.hip", "kernels_insert_batch.hip", "kernels_gs.hip", "kernels_gs_rank.hip", "kernels_dense.hip", "kernels_chol.hip", "kernels_three_body.hip", "kernels_disp.hip", "kernels_crystal.hip", "kernels_rd_model.hip", "kernels_sg.hip", "kernels_contact.hip", "kernels_wolf_field.hip", "kernels_ewald_full.hip", "kernels_cavity.hip", "kernels_volume.hip", "context.cpp", "evaluate.cpp",
            "trial.cpp", "pi.cpp", "comm.cpp", "gibbs.cpp", "cavity.cpp"]
 HEADERS = ["kernels.h", "context.h", "pair_math.h", "erfcx_coeffs.h", "device_math.h", "trial_kernels.h", "exchange_kernels.h", "pair_term_walk.h", "erfc_table.inc", os.path.join("..", "..", "include", "mpmc_energy.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function"]

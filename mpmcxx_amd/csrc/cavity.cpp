@@ -76,6 +76,24 @@ extern "C" int mpmc_uvt_boltzmann_factor(const mpmc_uvt_move *m, double *boltzma
 	}
 }
 
+// the ENSEMBLE_NPT branch (:1441-1457), operand for operand
+extern "C" int mpmc_npt_boltzmann_factor(const mpmc_npt_move *m, double *boltzmann_factor) {
+	if (!m || !boltzmann_factor) return MPMC_ERR_ARG;
+	constexpr double ATM2REDUCED = 0.0073389366; // src/constants.h
+	const double delta_energy = m->final_energy - m->init_energy;
+	const double temperature = m->temperature, pressure = m->pressure, N = m->N, v_old = m->volume_old, v_new = m->volume_new;
+	switch (m->movetype) {
+	case MPMC_MOVETYPE_VOLUME:
+		*boltzmann_factor = std::exp(-(delta_energy + pressure * ATM2REDUCED * (v_new - v_old) - (N + 1) * temperature * std::log(v_new / v_old)) / temperature);
+		return MPMC_OK;
+	case MPMC_MOVETYPE_DISPLACE:
+		*boltzmann_factor = std::exp(-delta_energy / temperature);
+		return MPMC_OK;
+	default:
+		return MPMC_ERR_UNSUPPORTED;
+	}
+}
+
 // ---- the setting --------------------------------------------------------------------------------------------------------------------------
 extern "C" int mpmc_set_cavity_grid(mpmc_ctx *c, int grid_size, double radius) {
 	if (!c) return MPMC_ERR_ARG;

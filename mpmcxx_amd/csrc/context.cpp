@@ -226,6 +226,21 @@ extern "C" int mpmc_ctx_destroy(mpmc_ctx *c) {
 }
 
 // ---- box / options ---------------------------------------------------------------------------------------
+void mpmc::box_from_cell(const double basis[9], const double R[9], double vol, double cut, Box &out) {
+	std::memcpy(out.b, basis, sizeof(out.b));
+	std::memcpy(out.r, R, sizeof(out.r));
+	out.volume = vol;
+	out.cutoff = cut;
+	// squared-distance forms of the reference's cutoff predicates (see pair_math.h Box)
+	out.t_lj = bisect_threshold(cut, [cut](double t) { return std::sqrt(t) - kSmallDR < cut; });
+	out.t_es = bisect_threshold(cut, [cut](double t) { return !(std::sqrt(t) > cut); });
+	out.t_wolf = bisect_threshold(cut, [cut](double t) { return std::sqrt(t) < cut; });
+	out.ortho = 1;
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++)
+			if (i != j && (basis[3 * i + j] != 0.0 || R[3 * i + j] != 0.0)) out.ortho = 0;
+}
+
 extern "C" int mpmc_set_box(mpmc_ctx *c, const double basis[9], const double *reciprocal, double volume, double cutoff) {
 	if (!c || !basis) return MPMC_ERR_ARG;
 	// the same cell again (a caller that hands the box over before every evaluation): nothing to invalidate
@@ -243,19 +258,9 @@ extern "C" int mpmc_set_box(mpmc_ctx *c, const double basis[9], const double *re
 	if (volume > 0) vol = volume;
 	if (cutoff > 0) cut = cutoff;
 	if (!(vol > 0) || !(cut > 0)) return fail(c, MPMC_ERR_BOX, "mpmc_set_box: invalid volume / cutoff");
+	vol_abandon(c);          // (an open volume trial belongs to the old cell too)
 	drop_pending_dipoles(c); // (an open on-demand solve belongs to the old cell)
-	std::memcpy(c->box.b, basis, sizeof(R));
-	std::memcpy(c->box.r, R, sizeof(R));
-	c->box.volume = vol;
-	c->box.cutoff = cut;
-	// squared-distance forms of the reference's cutoff predicates (see pair_math.h Box)
-	c->box.t_lj = bisect_threshold(cut, [cut](double t) { return std::sqrt(t) - kSmallDR < cut; });
-	c->box.t_es = bisect_threshold(cut, [cut](double t) { return !(std::sqrt(t) > cut); });
-	c->box.t_wolf = bisect_threshold(cut, [cut](double t) { return std::sqrt(t) < cut; });
-	c->box.ortho = 1;
-	for (int i = 0; i < 3; i++)
-		for (int j = 0; j < 3; j++)
-			if (i != j && (basis[3 * i + j] != 0.0 || R[3 * i + j] != 0.0)) c->box.ortho = 0;
+	box_from_cell(basis, R, vol, cut, c->box);
 	c->box_set = true;
 	std::memcpy(c->box_in, in, sizeof(in)); // (only a call that was accepted is remembered)
 	c->box_in_has_recip = (reciprocal != nullptr);
@@ -304,6 +309,7 @@ void mpmc::apply_options(mpmc_ctx *c, const mpmc_options &eff) {
 	// changes -- through polar_gs, polarization, rd_only or polar_iterative (the ranked sweeps), or on the first options after an upload
 	// under the defaults -- re-upload (not under `polar_ewald_full`, where polar_gs changes nothing: the spatial order stays)
 	if ((c->opts_set && sweeps_keep_atom_order(c, c->opts)) != sweeps_keep_atom_order(c, *o)) c->atoms_dirty = c->atoms_dirty_order = true;
+	vol_abandon(c);
 	drop_pending_dipoles(c); // (... and to the old options)
 	c->opts = *o;
 	c->opts_set = true;
@@ -643,6 +649,7 @@ static int size_tile_tables(mpmc_ctx *c) {
 extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const double *charge, const double *polarizability, const double *epsilon,
                               const double *sigma, const int32_t *mol_id, const int32_t *frozen, const int32_t *has_disp, const double *mass) {
 	if (!c || n <= 0 || !pos || !charge || !polarizability || !epsilon || !sigma || !mol_id || !frozen) return MPMC_ERR_ARG;
+	vol_abandon(c); // (an open volume trial: the accepted device state goes back in place before the list is replaced)
 	const bool solve_open = c->polar_pending != mpmc_ctx::PEND_NONE;
 	if (n > c->max_atoms) { // insertions (uVT / Gibbs callers) outgrew the capacity hint given at creation
 		const int rc_grow = grow_capacity(c, n);
@@ -672,6 +679,7 @@ extern "C" int mpmc_set_atoms(mpmc_ctx *c, int n, const double *pos, const doubl
 	c->order_carried = carry_spatial_order(c, pos, n);
 	c->h_pos.assign(pos, pos + 3 * (size_t)n);
 	c->pos_gen++;
+	c->list_gen++;
 	c->h_q.assign(charge, charge + n);
 	c->h_alpha.assign(polarizability, polarizability + n);
 	c->h_eps.assign(epsilon, epsilon + n);
@@ -752,6 +760,7 @@ int mpmc::splice_atoms(mpmc_ctx *c, int at, int n_remove, const AtomRun *ins) {
 	c->order_carried = carry_spatial_order(c, np_.data(), n_new); // (before the old positions go)
 	c->h_pos.swap(np_);
 	c->pos_gen++;
+	c->list_gen++;
 	splice_vec(c->h_q, (size_t)at, (size_t)n_remove, ins ? &ins->q : nullptr);
 	splice_vec(c->h_alpha, (size_t)at, (size_t)n_remove, ins ? &ins->alpha : nullptr);
 	splice_vec(c->h_eps, (size_t)at, (size_t)n_remove, ins ? &ins->eps : nullptr);
@@ -1468,6 +1477,7 @@ extern "C" int mpmc_update_positions(mpmc_ctx *c, int first, int count, const do
 	if (!c->atoms_set || first + count > c->n) return fail(c, MPMC_ERR_ARG, "mpmc_update_positions: range outside the atom list");
 	if (count == 0) return MPMC_OK;
 	HIP_TRY(c, hipSetDevice(c->device));
+	vol_abandon(c);
 	for (int t = 0; t < count; t++) {
 		if (!std::isfinite(pos[3 * t]) || !std::isfinite(pos[3 * t + 1]) || !std::isfinite(pos[3 * t + 2]))
 			return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_update_positions: non-finite position");

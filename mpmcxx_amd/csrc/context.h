@@ -130,6 +130,7 @@ struct mpmc_kept {
 	long long n_uploads_carried = 0, n_uploads_sorted = 0; // (diagnostics: mpmc_debug_upload_counts)
 	long long n_xch_delta = 0, n_xch_full = 0, n_xch_resums = 0; // (diagnostics: mpmc_debug_exchange_counts)
 	long long n_ins_calls = 0, n_ins_cands = 0;                  // (diagnostics: mpmc_debug_insert_batch_counts)
+	long long n_vol[4] = {0, 0, 0, 0}; // (diagnostics: mpmc_debug_volume_trial_counts) evaluated, accepted, rejected, evaluations made by a reject
 	bool tb_enabled = false, tb_mk = false; // Axilrod-Teller term switched on; Midzuno-Kihara c9 (mpmc_set_axilrod_teller)
 	bool de_enabled = false;                // disp-expansion term switched on (mpmc_set_disp_expansion); the atoms' dispersion flag is AF_DISP_RD then
 	int de_flags = 0;                       // MPMC_DISP_*
@@ -198,6 +199,16 @@ struct TrialState {
 	AtomRun xch_saved;           // full-evaluation trials: the accepted atom list, which a rejection puts back
 	double xch_static[3] = {0, 0, 0}, xch_N = 0; // lrc_pair, lrc_self, es_self and countN of the evaluated trial composition
 	ConfigTotals totals;         // of the evaluated trial
+	// volume trials (mpmc_trial_volume_begin): every basis element times vol_s, every molecule shifted rigidly by com * vol_s - com
+	bool volume = false;         // the open trial is one
+	bool vol_swapped = false;    // the trial cell, positions, k tables and structure factors are the resident ones (vol_restore trades them back)
+	bool vol_host_pos = false;   // pos_new holds the trial positions [n][3] and pos_old the shift of every molecule [n_molecules][3] (vol_host_positions)
+	double vol_s = 1.0;
+	Box vol_box{};               // the trial cell
+	Box vol_acc_box{};           // what the evaluation of the trial replaced: the accepted cell, its two alphas, its position-independent terms
+	double vol_acc_alpha[2] = {0, 0}, vol_acc_static[3] = {0, 0, 0};
+	bool vol_acc_static_dirty = false;
+	unsigned vol_acc_gen = 0;    // ... and the static_gen they belonged to
 };
 
 struct mpmc_ctx {
@@ -392,6 +403,18 @@ struct mpmc_ctx {
 	XchSums xs_acc, xs_trial;
 	unsigned xs_gen = 0;         // static_gen of xs_acc (0: none)
 	int xs_edits = 0;            // accepted exchanges since xs_acc was summed over the list
+
+	// volume trials (mpmc_trial_volume_begin, kernels_volume.hip): all allocated by the first one.  The trial is evaluated into the
+	// alternates -- d_vol_xyzq, the d_vol_k* tables, d_sf_trial -- which trade places with the accepted ones for as long as it is open
+	// (d_xyzq is a pointer into the atom block: it points at d_vol_xyzq meanwhile, d_xyzq_acc keeps the block's own)
+	DevBuf<double4> d_vol_xyzq;        // [max_pad] trial positions and charges, slot order
+	double4 *d_xyzq_acc = nullptr;
+	DevBuf<double4> d_vol_kvec, d_vol_kw; // the k tables of the other cell
+	DevBuf<double> d_vol_w_en;
+	DevBuf<double> d_vol_mass;         // [max_atoms] per-atom masses, ORIGINAL order (a re-sort does not touch them)
+	DevBuf<int> d_vol_first;           // [n_molecules + 1] first atom of every molecule, original order; the last entry is n
+	unsigned list_gen = 1, vol_list_gen = 0; // counts the atom lists (mpmc_set_atoms, accepted exchanges) / the one the two arrays above were made from (0: none)
+	bool vol_zero_mass = false;        // ... and it has a molecule without mass: no centre
 
 	// batched insertion candidates (mpmc_insert_candidates, kernels_insert_batch.hip): all allocated by the first call.  The staging block
 	// holds one pass of candidates (kInsStageRecords records at the most), the device scratch one launch chain (kInsBatchChunk candidates).
@@ -810,6 +833,9 @@ void ext_params(const mpmc_ctx *c, FusedParams &fp, bool wolf_on); // Wolf / Fey
 AtomsDev atoms_view(const mpmc_ctx *c);
 RecipDev recip_view(const mpmc_ctx *c);
 int upload_atoms(mpmc_ctx *c);                   // spatial order + device atom arrays (context.cpp)
+// the Box of a cell: basis, reciprocal, volume, cutoff, the squared-distance thresholds of the cutoff predicates, ortho (context.cpp)
+void box_from_cell(const double basis[9], const double R[9], double volume, double cutoff, Box &out);
+void vol_abandon(mpmc_ctx *c); // an open volume trial is closed and the accepted device state put back in place (trial.cpp); nothing to do otherwise
 // the AF_* word of one atom as upload_atoms packs it
 inline int atom_flag_word(const mpmc_ctx *c, int frozen, double eps, double sigma, int disp, double q, double alpha) {
 	int fl = 0;

@@ -579,6 +579,12 @@ void launch_cavity_compact(hipStream_t st, const int *part, int slices, int poin
 void launch_cavity_darts(hipStream_t st, const double *grid, const int *open, const double *dart_frac, int n_darts, int slices, const double basis[9], double t2,
                          unsigned long long *mask, long long *res);
 
+// ---- volume-change trial moves (kernels_volume.hip; System::volume_change, src/System.MonteCarlo.cpp:1235-1340) --------------------------
+// out[slot] = the atom of that slot shifted by its molecule's com * s - com (charge copied; the padding slots copied): mass [n] and
+// mol_first [n_mol + 1] in ORIGINAL atom order, every molecule's sums sequential in that order
+void launch_volume_scale(hipStream_t st, const double4 *xyzq, const int *slot_of, const double *mass, const int *mol_first, int n_mol, int n, int n_pad, double s,
+                         double4 *out);
+
 // device-resident positions [n][3] in original atom order -> xyzq[slot].xyz (perm[slot] = original index)
 void launch_set_positions(hipStream_t st, const double *pos_dev, const int *perm, double4 *xyzq, int n);
 

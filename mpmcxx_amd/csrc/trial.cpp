@@ -37,6 +37,7 @@ static void open_trial(mpmc_ctx *c, int kind, int at, int count) {
 	t.xch_at = t.first = at;
 	t.count = count;
 	t.xch_saved.clear();
+	t.volume = t.vol_swapped = t.vol_host_pos = false;
 	t.open = true;
 	t.evaluated = t.enqueued = t.noop = false;
 }
@@ -355,6 +356,246 @@ static int xch_accept_delta(mpmc_ctx *c) {
 	return MPMC_OK;
 }
 
+// ---- volume trials: System::volume_change / volume_change_Gibbs / revert_volume_change (src/System.MonteCarlo.cpp:1235-1340, 1690-1727) -----
+// The trial is a full evaluation of the scaled cell and the scaled positions, made in the ALTERNATES of everything the accepted
+// configuration keeps on the device: a second position buffer (kernels_volume.hip writes it), a second set of k tables, and d_sf_trial for
+// the structure factors.  They trade places with the accepted ones in front of the evaluation; reject trades them back and restores the
+// host's cell, alphas and position-independent terms, so nothing is evaluated again; accept keeps them and brings the host mirrors up with
+// the same expressions the kernel ran.
+extern "C" int mpmc_trial_volume_begin(mpmc_ctx *c, double s) {
+	if (!c) return MPMC_ERR_ARG;
+	if (!c->atoms_set || !c->box_set || !c->cache_valid) return fail(c, MPMC_ERR_ARG, "mpmc_trial_volume_begin: no accepted configuration (call mpmc_energy first)");
+	if (c->trial.open) return fail(c, MPMC_ERR_ARG, "mpmc_trial_volume_begin: a trial move is already open (accept or reject it first)");
+	if (c->h_mass.empty()) return fail(c, MPMC_ERR_ARG, "mpmc_trial_volume_begin: mpmc_set_atoms was called without masses");
+	if (!std::isfinite(s) || s <= 0.0) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_volume_begin: the scale factor must be finite and positive");
+	if (c->box_in_has_recip || c->box_in[18] > 0 || c->box_in[19] > 0)
+		return fail(c, MPMC_ERR_ARG, "mpmc_trial_volume_begin: the cell was set with a caller-supplied reciprocal, volume or cutoff (there is no rule for scaling an override)");
+	double basis[9], R[9], vol = 0, cut = 0;
+	for (int k = 0; k < 9; k++) basis[k] = c->box.b[k] * s;
+	if (mpmc_pbc_compute(basis, R, &vol, &cut) != MPMC_OK || !(vol > 0) || !(cut > 0) || !std::isfinite(vol))
+		return fail(c, MPMC_ERR_BOX, "mpmc_trial_volume_begin: the scaled cell has no positive finite volume");
+	open_trial(c, 0, 0, c->n);
+	TrialState &t = c->trial;
+	t.volume = true;
+	t.vol_s = s;
+	box_from_cell(basis, R, vol, cut, t.vol_box);
+	t.noop = (s == 1.0); // (the same cell and the same positions: the trial totals are the accepted totals, nothing is launched)
+	return MPMC_OK;
+}
+
+// the host's restatement of k_volume_scale over its own mirror: trial positions into pos_new, every molecule's shift into pos_old
+static void vol_host_positions(mpmc_ctx *c) {
+	TrialState &t = c->trial;
+	if (t.vol_host_pos) return;
+	const double s = t.vol_s;
+	t.pos_new.resize(3 * (size_t)c->n);
+	t.pos_old.assign(3 * (size_t)c->n_molecules, 0.0);
+	int m = 0;
+	for (int i0 = 0; i0 < c->n; m++) {
+		int i1 = i0;
+		while (i1 + 1 < c->n && c->h_mol[i1 + 1] == c->h_mol[i0]) i1++;
+		double cm[3] = {0, 0, 0}, mass = 0;
+		for (int i = i0; i <= i1; i++) {
+			mass += c->h_mass[i];
+			for (int p = 0; p < 3; p++) cm[p] += c->h_mass[i] * c->h_pos[3 * (size_t)i + p];
+		}
+		for (int p = 0; p < 3; p++) {
+			cm[p] /= mass;
+			t.pos_old[3 * (size_t)m + p] = cm[p] * s - cm[p];
+		}
+		for (int i = i0; i <= i1; i++)
+			for (int p = 0; p < 3; p++) t.pos_new[3 * (size_t)i + p] = c->h_pos[3 * (size_t)i + p] + t.pos_old[3 * (size_t)m + p];
+		i0 = i1 + 1;
+	}
+	t.vol_host_pos = true;
+}
+
+extern "C" int mpmc_trial_volume_get(mpmc_ctx *c, double basis[9], double reciprocal[9], double *volume, double *cutoff, double *pos) {
+	if (!c) return MPMC_ERR_ARG;
+	if (!c->trial.open || !c->trial.volume) return fail(c, MPMC_ERR_ARG, "mpmc_trial_volume_get: no volume trial is open");
+	const TrialState &t = c->trial;
+	if (basis) std::memcpy(basis, t.vol_box.b, 9 * sizeof(double));
+	if (reciprocal) std::memcpy(reciprocal, t.vol_box.r, 9 * sizeof(double));
+	if (volume) *volume = t.vol_box.volume;
+	if (cutoff) *cutoff = t.vol_box.cutoff;
+	if (pos) {
+		if (!t.noop) vol_host_positions(c);
+		std::memcpy(pos, t.noop ? c->h_pos.data() : t.pos_new.data(), 3 * (size_t)c->n * sizeof(double));
+	}
+	return MPMC_OK;
+}
+
+extern "C" int mpmc_debug_volume_trial_counts(mpmc_ctx *c, long long *out4) {
+	if (!c || !out4) return -1;
+	for (int k = 0; k < 4; k++) out4[k] = c->kept.n_vol[k];
+	return 0;
+}
+
+// diagnostics only: the positions RESIDENT on the device, in original atom order -- the trial's while an evaluated volume trial is open.
+// A blocking copy behind everything enqueued on the context's stream.
+extern "C" int mpmc_debug_device_positions(mpmc_ctx *c, double *pos) {
+	if (!c || !pos) return MPMC_ERR_ARG;
+	if (!c->atoms_set || c->atoms_dirty || !c->d_xyzq) return fail(c, MPMC_ERR_ARG, "mpmc_debug_device_positions: the atom list is not on the device");
+	HIP_TRY(c, hipSetDevice(c->device));
+	std::vector<double4> tmp((size_t)c->n_pad);
+	HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->d_xyzq, tmp.size() * sizeof(double4), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	for (int i = 0; i < c->n; i++) {
+		const double4 &v = tmp[(size_t)c->slot_of[i]];
+		pos[3 * (size_t)i] = v.x, pos[3 * (size_t)i + 1] = v.y, pos[3 * (size_t)i + 2] = v.z;
+	}
+	return MPMC_OK;
+}
+
+// the buffers of a volume trial, and the masses and molecule boundaries of the current atom list on the device
+static int vol_ensure(mpmc_ctx *c) {
+	int rc;
+	if ((rc = c->d_vol_xyzq.reserve(c, (size_t)c->max_pad)) != MPMC_OK) return rc;
+	if ((rc = c->d_sf_trial.reserve(c, (size_t)c->K)) != MPMC_OK) return rc;
+	if (c->vol_list_gen != c->list_gen) { // (once per atom list: mpmc_set_atoms, an accepted exchange)
+		std::vector<int> first;
+		first.reserve((size_t)c->n_molecules + 1);
+		c->vol_zero_mass = false;
+		double mass = 0;
+		for (int i = 0; i < c->n; i++) {
+			if (i == 0 || c->h_mol[i] != c->h_mol[i - 1]) {
+				if (i > 0 && !(mass > 0.0 && std::isfinite(mass))) c->vol_zero_mass = true;
+				first.push_back(i);
+				mass = 0;
+			}
+			mass += c->h_mass[i];
+		}
+		if (!(mass > 0.0 && std::isfinite(mass))) c->vol_zero_mass = true;
+		first.push_back(c->n);
+		if ((rc = c->d_vol_mass.reserve(c, (size_t)c->n, (size_t)c->max_atoms)) != MPMC_OK) return rc;
+		if ((rc = c->d_vol_first.reserve(c, first.size(), (size_t)c->max_atoms + 1)) != MPMC_OK) return rc;
+		HIP_TRY(c, hipMemcpyAsync(c->d_vol_mass, c->h_mass.data(), (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(c->d_vol_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream)); // (pageable sources; `first` dies here)
+		c->vol_list_gen = c->list_gen;
+	}
+	if (c->vol_zero_mass) return fail(c, MPMC_ERR_INVALID_DATUM, "mpmc_trial_energy: a molecule without mass has no centre of mass to scale");
+	return MPMC_OK;
+}
+
+// the accepted and the alternate device state trade places (both ways: the same three swaps and the position pointer)
+static void vol_swap_device(mpmc_ctx *c, bool to_trial) {
+	std::swap(c->d_sf, c->d_sf_trial); // (each buffer with its own capacity)
+	std::swap(c->d_kvec, c->d_vol_kvec);
+	std::swap(c->d_kw, c->d_vol_kw);
+	std::swap(c->d_w_en, c->d_vol_w_en);
+	if (to_trial) c->d_xyzq_acc = c->d_xyzq, c->d_xyzq = c->d_vol_xyzq;
+	else c->d_xyzq = c->d_xyzq_acc;
+}
+
+// the accepted configuration is the resident one again, on the device and on the host, without an evaluation
+static void vol_restore(mpmc_ctx *c) {
+	TrialState &t = c->trial;
+	if (!t.vol_swapped) return;
+	vol_swap_device(c, false);
+	c->box = t.vol_acc_box;
+	c->ewald_alpha = t.vol_acc_alpha[0];
+	c->polar_ewald_alpha = t.vol_acc_alpha[1];
+	for (int k = 0; k < 3; k++) c->h_static[k] = t.vol_acc_static[k];
+	c->static_dirty = t.vol_acc_static_dirty;
+	c->k_dirty = false; // (the accepted cell's tables are back in place)
+	// what was made for the trial cell (the rd_crystal image table, a ranked view) is stale again; what was made for the accepted cell and
+	// not touched meanwhile (the host sums of the exchange trials, a cavity grid) is valid again
+	c->static_gen++;
+	if (c->xs_gen == t.vol_acc_gen) c->xs_gen = c->static_gen;
+	if (c->cav_static_gen == t.vol_acc_gen) c->cav_static_gen = c->static_gen;
+	t.vol_swapped = false;
+}
+
+// a call that replaces the cell, the options, the atom list or positions while a volume trial is open closes it first: the accepted state
+// goes back into place (the caller's call then drops the accepted totals as it always does)
+void mpmc::vol_abandon(mpmc_ctx *c) {
+	if (!c->trial.open || !c->trial.volume) return;
+	vol_restore(c);
+	c->trial.open = c->trial.volume = c->trial.enqueued = false;
+}
+
+static int vol_energy_async(mpmc_ctx *c) {
+	TrialState &t = c->trial;
+	drop_pending_dipoles(c);
+	int rc = prepare(c); // (the pending upload behind an accepted exchange: the kernel below reads the accepted positions in their slots)
+	if (rc != MPMC_OK) return rc;
+	if ((rc = vol_ensure(c)) != MPMC_OK) return rc;
+	{
+		ProfScope p(c, MPMC_K_CLASSES); // (geometry in front of the evaluation, like the tile bounds)
+		launch_volume_scale(c->stream, c->d_xyzq, c->d_slot_of, c->d_vol_mass, c->d_vol_first, c->n_molecules, c->n, c->n_pad, t.vol_s, c->d_vol_xyzq);
+	}
+	HIP_TRY(c, hipGetLastError());
+	t.vol_acc_box = c->box;
+	t.vol_acc_alpha[0] = c->ewald_alpha, t.vol_acc_alpha[1] = c->polar_ewald_alpha;
+	for (int k = 0; k < 3; k++) t.vol_acc_static[k] = c->h_static[k];
+	t.vol_acc_static_dirty = c->static_dirty;
+	t.vol_acc_gen = c->static_gen;
+	vol_swap_device(c, true);
+	c->box = t.vol_box;
+	c->k_dirty = true;      // (prepare: the alphas follow the new cutoff, the k tables are built into the alternates)
+	c->static_dirty = true; // (the position-independent terms ride along with the evaluation)
+	c->static_gen++;
+	t.vol_swapped = true;
+	if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) {
+		vol_restore(c);
+		return rc;
+	}
+	t.was_full = true;
+	t.polar_delta = t.inline_move = false;
+	c->trial_last_kind = 1;
+	t.enqueued = true;
+	c->kept.n_vol[0]++;
+	return MPMC_OK;
+}
+
+static int vol_accept(mpmc_ctx *c) {
+	TrialState &t = c->trial;
+	HIP_TRY(c, hipSetDevice(c->device));
+	const size_t n = (size_t)c->n;
+	// the device: the trial positions go into the atom block (stream-ordered behind the evaluation; 32 bytes per atom), the cell, the k
+	// tables and the structure factors stay where the evaluation left them
+	HIP_TRY(c, hipMemcpyAsync(c->d_xyzq_acc, c->d_vol_xyzq, (size_t)c->n_pad * sizeof(double4), hipMemcpyDeviceToDevice, c->stream));
+	c->d_xyzq = c->d_xyzq_acc;
+	t.vol_swapped = false;
+	// the host: the same expressions over its own mirrors, no copy back
+	vol_host_positions(c);
+	if (c->h_pos_sorted.size() == 3 * n) // (where every atom stood at the last sort, in the new cell: the drift check measures from there)
+		for (int i = 0, m = 0; i < c->n; i++) {
+			if (i > 0 && c->h_mol[i] != c->h_mol[i - 1]) m++;
+			for (int p = 0; p < 3; p++) c->h_pos_sorted[3 * (size_t)i + p] += t.pos_old[3 * (size_t)m + p];
+		}
+	c->h_pos.swap(t.pos_new);
+	c->pos_gen++;
+	const int rc_g = mirror_guard(c);
+	if (rc_g != MPMC_OK) return rc_g;
+	if (!c->atoms_dirty)
+		for (int i = 0; i < c->n; i++) {
+			double4 &v = c->h_xyzq[c->slot_of[i]];
+			v.x = c->h_pos[3 * (size_t)i], v.y = c->h_pos[3 * (size_t)i + 1], v.z = c->h_pos[3 * (size_t)i + 2];
+		}
+	std::memset(c->box_in, 0, sizeof(c->box_in)); // (what mpmc_set_box(basis, NULL, 0, 0) of the new cell would have left)
+	std::memcpy(c->box_in, t.vol_box.b, 9 * sizeof(double));
+	c->box_in_has_recip = false;
+	c->accepted = t.totals;
+	c->accepted.frozen_pairs = -1;
+	c->cache_valid = true;
+	t.open = t.volume = false;
+	c->kept.n_vol[1]++;
+	return MPMC_OK;
+}
+
+static int vol_reject(mpmc_ctx *c) {
+	TrialState &t = c->trial;
+	t.open = t.volume = false;
+	if (!t.vol_swapped) return MPMC_OK; // (never enqueued, or s == 1)
+	vol_restore(c);
+	c->cache_valid = true;   // (the accepted record, which the trial never touched, describes the configuration that is back)
+	c->e_real_valid = false; // (field, store and dipoles are the rejected configuration's: the next polarizable trial evaluates in full)
+	c->kept.n_vol[2]++;
+	return MPMC_OK;
+}
+
 // the two halves of mpmc_trial_energy: everything up to the last enqueue, then the wait + host arithmetic (P images of a
 // path-integral move overlap on the device when a driver enqueues all of them before the first wait)
 extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
@@ -366,6 +607,7 @@ extern "C" int mpmc_trial_energy_async(mpmc_ctx *c) {
 		c->trial.enqueued = true;
 		return MPMC_OK;
 	}
+	if (c->trial.volume) return vol_energy_async(c);
 	if (c->trial.xch_kind) return xch_energy_async(c);
 	const mpmc_options &o = c->opts;
 	const bool polar = o.polarization && !o.rd_only;
@@ -659,6 +901,7 @@ extern "C" int mpmc_trial_accept(mpmc_ctx *c) {
 		c->trial.open = false;
 		return MPMC_OK;
 	}
+	if (c->trial.volume) return vol_accept(c);
 	if (c->trial.xch_kind) { // an exchange: the full evaluation left the trial list resident; the delta path edits the list now
 		if (!c->trial.was_full) {
 			const int rc_x = xch_accept_delta(c);
@@ -716,6 +959,7 @@ extern "C" int mpmc_trial_reject(mpmc_ctx *c) {
 		int rc = mpmc_trial_energy_wait(c, &drop);
 		if (rc != MPMC_OK) return rc;
 	}
+	if (c->trial.volume) return vol_reject(c);
 	if (c->trial.xch_kind) { // an exchange: the delta path left nothing behind; after a full evaluation the accepted list goes back
 		const bool restore = c->trial.xch_saved.size() > 0;
 		int rc = MPMC_OK;

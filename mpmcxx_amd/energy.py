@@ -176,6 +176,12 @@ CAVITY_KEYS = ("cavity_bias", "cavity_grid_size", "cavity_radius")
 CAVITY_MAX_GRID = 128  # MPMC_CAVITY_MAX_GRID
 
 
+class NptMove(C.Structure):
+    """mpmc_npt_move: what the ENSEMBLE_NPT branch of System::boltzmann_factor reads (mpmc_npt_boltzmann_factor)."""
+    _fields_ = [("movetype", C.c_int32), ("reserved", C.c_int32), ("temperature", C.c_double), ("pressure", C.c_double), ("N", C.c_double),
+                ("init_energy", C.c_double), ("final_energy", C.c_double), ("volume_old", C.c_double), ("volume_new", C.c_double)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -296,6 +302,12 @@ def lib():
         L.mpmc_cavity_r2_threshold.restype = C.c_double
         L.mpmc_uvt_boltzmann_factor.argtypes = [C.POINTER(UvtMove), dp]
         L.mpmc_debug_cavity_times.argtypes = [vp, dp]
+    if hasattr(L, "mpmc_trial_volume_begin") or not os.environ.get("MPMC_ENERGY_LIB"):  # (an earlier build named by MPMC_ENERGY_LIB has no volume trials)
+        L.mpmc_trial_volume_begin.argtypes = [vp, C.c_double]
+        L.mpmc_trial_volume_get.argtypes = [vp, dp, dp, dp, dp, dp]
+        L.mpmc_debug_volume_trial_counts.argtypes = [vp, C.POINTER(C.c_longlong)]
+        L.mpmc_npt_boltzmann_factor.argtypes = [C.POINTER(NptMove), dp]
+        L.mpmc_debug_device_positions.argtypes = [vp, dp]
     L.mpmc_gibbs_energy.argtypes = [vp, vp, C.POINTER(Result), C.POINTER(Result)]
     L.mpmc_gibbs_boltzmann_factor.argtypes = [C.POINTER(GibbsMove), dp, dp]
     L.mpmc_rccl_version.argtypes = [C.POINTER(C.c_int)]
@@ -828,9 +840,46 @@ class System:
         self._exchange, self._move = (int(first), int(count), None), None
         return self._trial()
 
+    def trial_volume_energy(self, scale: float) -> float:
+        """energy of the configuration with every basis element times `scale` and every molecule shifted rigidly by com * scale - com
+        (System::volume_change); follow with accept() or reject().  The atoms need masses."""
+        self._check(self._L.mpmc_trial_volume_begin(self._h, float(scale)))
+        self._exchange, self._move, self._volume = None, None, True
+        try:
+            return self._trial()
+        except MpmcError:
+            self._volume = False
+            raise
+
+    def trial_volume_state(self) -> Dict[str, object]:
+        """the open volume trial's cell and positions (mpmc_trial_volume_get): basis (3, 3), reciprocal (3, 3), volume, cutoff, pos (n, 3)"""
+        b, r, pos = np.zeros(9), np.zeros(9), np.zeros((self.n, 3))
+        vol, cut = C.c_double(), C.c_double()
+        self._check(self._L.mpmc_trial_volume_get(self._h, _dp(b), _dp(r), C.byref(vol), C.byref(cut), _dp(pos)))
+        return {"basis": b.reshape(3, 3), "reciprocal": r.reshape(3, 3), "volume": vol.value, "cutoff": cut.value, "pos": pos}
+
+    def device_positions(self) -> np.ndarray:
+        """(diagnostics) the positions resident on the device, original atom order: the trial's while an evaluated volume trial is open"""
+        pos = np.zeros((self.n, 3))
+        self._check(self._L.mpmc_debug_device_positions(self._h, _dp(pos)))
+        return pos
+
+    def volume_trial_counts(self) -> Dict[str, int]:
+        """volume trials evaluated, accepted and rejected, and evaluations made from inside a reject (mpmc_debug_volume_trial_counts)"""
+        v = (C.c_longlong * 4)()
+        if self._L.mpmc_debug_volume_trial_counts(self._h, v) != 0:
+            raise MpmcError(-1, "mpmc_debug_volume_trial_counts: no context")
+        return {"evaluated": int(v[0]), "accepted": int(v[1]), "rejected": int(v[2]), "reject_evaluations": int(v[3])}
+
     def accept(self):
+        vol_state = self.trial_volume_state() if getattr(self, "_volume", False) else None  # (valid until the accept)
         self._check(self._L.mpmc_trial_accept(self._h))
         self.observables = dict(self.trial_observables)
+        if vol_state is not None:  # the object's own cell and positions follow an accepted volume trial
+            self.basis = vol_state["basis"].copy()
+            if getattr(self, "_atoms", None) is not None:
+                self._atoms["pos"][:] = vol_state["pos"]
+            self._volume = False
         if getattr(self, "_exchange", None) is not None:  # the object's own atom arrays follow an accepted exchange
             at, n_remove, mol = self._exchange
             own = self.atoms
@@ -847,6 +896,7 @@ class System:
     def reject(self):
         self._check(self._L.mpmc_trial_reject(self._h))
         self._exchange = self._move = None
+        self._volume = False
 
     def _scalar(self, fn) -> float:
         v = C.c_double()
@@ -1081,6 +1131,18 @@ def uvt_boltzmann_factor(movetype, temperature, fugacity, volume, N, init_energy
     bf = C.c_double(float("nan"))
     rc = lib().mpmc_uvt_boltzmann_factor(C.byref(m), C.byref(bf))
     return rc, bf.value
+
+
+def npt_boltzmann_factor(movetype, temperature, pressure, N, init_energy, final_energy, volume_old, volume_new) -> float:
+    """the ENSEMBLE_NPT branch of System::boltzmann_factor (mpmc_npt_boltzmann_factor).  movetype: a MOVETYPE name or number; "volume" and "displace" have a factor"""
+    movetype = MOVETYPE[movetype] if isinstance(movetype, str) else int(movetype)
+    m = NptMove(movetype, 0, float(temperature), float(pressure), float(N), float(init_energy), float(final_energy), float(volume_old),
+                float(volume_new))
+    bf = C.c_double()
+    rc = lib().mpmc_npt_boltzmann_factor(C.byref(m), C.byref(bf))
+    if rc != MPMC_OK:
+        raise MpmcError(rc, f"mpmc_npt_boltzmann_factor: move type {int(movetype)} has no NPT acceptance factor")
+    return bf.value
 
 
 def pi_allreduce(beads: Sequence[System]):
