@@ -291,7 +291,16 @@ int mpmc_trial_remove_begin(mpmc_ctx *ctx, int first, int count);
  *   basis_scale_factor == 1.0 is a trial that launches nothing.  MPMC_ERR_ARG with a text: no accepted configuration; a trial already
  * open; mpmc_set_atoms was called without masses; the accepted cell was set with a caller-supplied reciprocal, volume or cutoff (there is
  * no rule for scaling an override).  MPMC_ERR_INVALID_DATUM: basis_scale_factor not finite or <= 0; a molecule whose masses sum to 0.
- * mpmc_set_box, mpmc_set_options, mpmc_set_atoms and mpmc_update_positions close an open volume trial as a rejection before they act. */
+ * mpmc_set_box, mpmc_set_options, mpmc_set_atoms and mpmc_update_positions close an open volume trial as a rejection before they act
+ * (mpmc_set_box with the accepted cell and mpmc_set_options with unchanged options too: they are no-ops only while no volume trial is open); a
+ * trial enqueued with mpmc_trial_energy_async and never waited for is drained first, as mpmc_trial_reject drains it.  What they leave is what
+ * they leave without a trial: the accepted cell, tables and positions back in place, no accepted totals (call mpmc_energy), and
+ * mpmc_trial_reject answers that no trial move is open.
+ *   While a volume trial is open, every call that evaluates (mpmc_energy, mpmc_energy_async, the component calls mpmc_lj ... mpmc_polar,
+ * mpmc_thole_field, the bead loops) is refused with MPMC_ERR_ARG and a text, and the trial stays open: the resident cell and positions
+ * are the trial's, and a complete evaluation would re-base the accepted totals on them.  Accept or reject first.
+ *   A context that outgrew its capacity (mpmc_set_atoms, an accepted insertion) keeps the cell as the caller gave it: a basis handed over
+ * alone can still be scaled. */
 int mpmc_trial_volume_begin(mpmc_ctx *ctx, double basis_scale_factor);
 /* the open volume trial's cell and positions (any pointer may be NULL); valid from _begin until accept / reject */
 int mpmc_trial_volume_get(mpmc_ctx *ctx, double basis[9], double reciprocal[9], double *volume, double *cutoff, double *pos /*[n][3]*/);

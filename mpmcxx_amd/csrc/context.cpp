@@ -250,7 +250,9 @@ extern "C" int mpmc_set_box(mpmc_ctx *c, const double basis[9], const double *re
 	else std::memset(in + 9, 0, 9 * sizeof(double));
 	in[18] = volume;
 	in[19] = cutoff;
-	if (c->box_set && c->box_in_has_recip == (reciprocal != nullptr) && std::memcmp(in, c->box_in, sizeof(in)) == 0) return MPMC_OK;
+	// (not while a volume trial is open: the call closes it, and the accepted totals go as with any other cell)
+	const bool vol_open = c->trial.open && c->trial.volume;
+	if (!vol_open && c->box_set && c->box_in_has_recip == (reciprocal != nullptr) && std::memcmp(in, c->box_in, sizeof(in)) == 0) return MPMC_OK;
 	double R[9], vol = 0, cut = 0;
 	int rc = mpmc_pbc_compute(basis, R, &vol, &cut);
 	if (rc != MPMC_OK) return fail(c, MPMC_ERR_BOX, "mpmc_set_box: non-positive cell volume");
@@ -296,7 +298,8 @@ extern "C" int mpmc_set_options(mpmc_ctx *c, const mpmc_options *o) {
 		if (!(o->temperature > 0)) return fail(c, MPMC_ERR_INVALID_SETTING, "mpmc_set_options: feynman_hibbs requires positive temperature"); // SimulationControl.cpp:2509
 		if (o->wolf && !o->rd_only) return fail(c, MPMC_ERR_INCOMPATIBLE, "mpmc_set_options: FH + es_wolf is not implemented"); // System.Energy.cpp:1448-1450
 	}
-	if (c->opts_set && std::memcmp(&c->opts_user, o, sizeof(mpmc_options)) == 0) return MPMC_OK; // unchanged: keep the accepted configuration's totals
+	// unchanged: keep the accepted configuration's totals (not while a volume trial is open: the call closes it, as with changed options)
+	if (!(c->trial.open && c->trial.volume) && c->opts_set && std::memcmp(&c->opts_user, o, sizeof(mpmc_options)) == 0) return MPMC_OK;
 	c->opts_user = *o;
 	apply_options(c, effective_options(c, *o));
 	return MPMC_OK;
@@ -595,7 +598,9 @@ static int grow_capacity(mpmc_ctx *c, int n) {
 	const int cap = n + n / 4 + kTile;
 	int rc = mpmc_ctx_create(c->device, cap, &f);
 	if (rc != MPMC_OK) return fail(c, rc, "mpmc_set_atoms: cannot grow the context to " + std::to_string(cap) + " atoms: " + g_create_error);
-	if (c->box_set) rc = mpmc_set_box(f, c->box.b, c->box.r, c->box.volume, c->box.cutoff);
+	// (the cell as the caller gave it, box_in: a basis alone stays a basis alone, which a volume trial can scale; handing over the derived
+	// reciprocal, volume and cutoff made every volume trial behind a growth "a caller-supplied override".  The derived values are the same bits.)
+	if (c->box_set) rc = mpmc_set_box(f, c->box_in, c->box_in_has_recip ? c->box_in + 9 : nullptr, c->box_in[18], c->box_in[19]);
 	if (rc == MPMC_OK && c->opts_set) rc = mpmc_set_options(f, &c->opts_user);
 	if (rc != MPMC_OK) {
 		c->err = "mpmc_set_atoms: growing the context failed: " + f->err;

@@ -773,7 +773,8 @@ Box lrc_box(const mpmc_ctx *c);    // the cell as the long-range corrections see
 int prepare(mpmc_ctx *c, bool defer_static = false); // uploads what is dirty, (re)builds the k tables; the position-independent terms unless deferred (evaluate.cpp)
 // one evaluation (the pieces in `mask`) on the context's streams (evaluate.cpp: a plan, the room it needs, then the stages); on_demand: where
 // the energy comes from the moments of the first half of the iterations, stop there and leave the rest to finish_pending_dipoles
-int enqueue(mpmc_ctx *c, unsigned mask, bool on_demand = false);
+// (volume_trial: the one caller that evaluates while a volume trial is open, the trial's own evaluation; every other is refused)
+int enqueue(mpmc_ctx *c, unsigned mask, bool on_demand = false, bool volume_trial = false);
 // waits for it and assembles the result into *out and c->eval (evaluate.cpp).  It FILLS: the accepted record and cache_valid are its
 // callers' -- mpmc_energy_wait and the component entry points re-base (where run_mask == full_mask), the trial paths do not
 int wait_and_fill(mpmc_ctx *c, mpmc_result *out);

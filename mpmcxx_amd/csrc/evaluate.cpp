@@ -1111,9 +1111,14 @@ static constexpr Stage kStages[] = {stage_clear_and_static_terms, stage_side_wor
                                     stage_palmo,
                                     stage_added_terms,            stage_post};
 
-int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand) {
+int mpmc::enqueue(mpmc_ctx *c, unsigned mask, bool on_demand, bool volume_trial) {
 	// one evaluation per context at a time: a second enqueue would overwrite the scalar block and the result slots under the first
 	if (c->pending) return fail(c, MPMC_ERR_ARG, "an evaluation of this context is still in flight (mpmc_energy_wait first)");
+	// While a volume trial is open the resident cell, tables and positions may be the trial's: an evaluation would describe the trial
+	// configuration, and a complete one would re-base the accepted totals on it, which a following reject then declares valid for the
+	// accepted cell.  Refused, like the setters; the trial stays open.
+	if (c->trial.open && c->trial.volume && !volume_trial)
+		return fail(c, MPMC_ERR_ARG, "an evaluation was asked for while a volume trial is open (mpmc_trial_accept or mpmc_trial_reject first)");
 	drop_pending_dipoles(c); // (its tables, slots and dipole vectors are this evaluation's from here on)
 	// stale position-independent terms ride along with this evaluation (an insertion / removal makes them stale every time)
 	int rc = prepare(c, true);

@@ -511,7 +511,12 @@ static void vol_restore(mpmc_ctx *c) {
 // goes back into place (the caller's call then drops the accepted totals as it always does)
 void mpmc::vol_abandon(mpmc_ctx *c) {
 	if (!c->trial.open || !c->trial.volume) return;
+	if (c->trial.enqueued) { // enqueued and never waited for: drain it first, as mpmc_trial_reject does (the evaluation holds `pending` and the scalar block)
+		mpmc_result drop;
+		(void)mpmc_trial_energy_wait(c, &drop); // (a wait that fails leaves the context idle all the same: wait_and_fill)
+	}
 	vol_restore(c);
+	c->e_real_valid = false; // (as in vol_reject: field, store and dipoles are the abandoned cell's, whether or not the caller's call then goes through)
 	c->trial.open = c->trial.volume = c->trial.enqueued = false;
 }
 
@@ -537,7 +542,7 @@ static int vol_energy_async(mpmc_ctx *c) {
 	c->static_dirty = true; // (the position-independent terms ride along with the evaluation)
 	c->static_gen++;
 	t.vol_swapped = true;
-	if ((rc = enqueue(c, full_mask(c))) != MPMC_OK) {
+	if ((rc = enqueue(c, full_mask(c), false, /*volume_trial*/ true)) != MPMC_OK) {
 		vol_restore(c);
 		return rc;
 	}

@@ -473,14 +473,26 @@ class System:
         return "sweep" if self._L.mpmc_debug_last_pair_kernel(self._h) == 1 else "fused"
 
     # -- state ------------------------------------------------------------------------------------------------
+    def _volume_closed(self):
+        """the four state calls close an open volume trial in the library (also where they then refuse their arguments): the object's flag
+        takes the library's own answer"""
+        if getattr(self, "_volume", False):
+            self._volume = self._L.mpmc_trial_volume_get(self._h, None, None, None, None, None) == MPMC_OK
+
     def set_box(self, basis: np.ndarray):
         b = np.ascontiguousarray(basis, dtype=np.float64).reshape(9)
-        self._check(self._L.mpmc_set_box(self._h, _dp(b), None, 0.0, 0.0))
+        try:
+            self._check(self._L.mpmc_set_box(self._h, _dp(b), None, 0.0, 0.0))
+        finally:
+            self._volume_closed()
         self.basis = b.reshape(3, 3).copy()
 
     def set_options(self, options: Dict[str, object]):
         self._opts = make_options(options)
-        self._check(self._L.mpmc_set_options(self._h, C.byref(self._opts)))
+        try:
+            self._check(self._L.mpmc_set_options(self._h, C.byref(self._opts)))
+        finally:
+            self._volume_closed()
         self.options = dict(options)
         # `polar_wolf` / `polar_palmo` are switches of their own in the library and follow the options here (only when some options named them:
         # a library of before this term, named by MPMC_ENERGY_LIB, is never asked)
@@ -532,8 +544,11 @@ class System:
         n = pos.size // 3
         disp = g("has_disp") if "has_disp" in atoms else None
         mass = f("mass") if "mass" in atoms else None
-        self._check(self._L.mpmc_set_atoms(self._h, n, _dp(pos), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
-                                           _dp(f("sigma")), _ip(g("mol_id")), _ip(g("frozen")), _ip(disp), _dp(mass)))
+        try:
+            self._check(self._L.mpmc_set_atoms(self._h, n, _dp(pos), _dp(f("charge")), _dp(f("polarizability")), _dp(f("epsilon")),
+                                               _dp(f("sigma")), _ip(g("mol_id")), _ip(g("frozen")), _ip(disp), _dp(mass)))
+        finally:
+            self._volume_closed()
         self.n = n
         # the object's own copy of the list: accepted trials and update_positions keep it current (set_positions_device does not: the positions
         # stay on the device)
@@ -732,7 +747,10 @@ class System:
 
     def update_positions(self, first: int, pos: np.ndarray):
         p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
-        self._check(self._L.mpmc_update_positions(self._h, int(first), p.size // 3, _dp(p)))
+        try:
+            self._check(self._L.mpmc_update_positions(self._h, int(first), p.size // 3, _dp(p)))
+        finally:
+            self._volume_closed()
         if getattr(self, "_atoms", None) is not None:
             self._atoms["pos"][int(first):int(first) + p.size // 3] = p.reshape(-1, 3)
 
@@ -894,9 +912,11 @@ class System:
         self._move = None
 
     def reject(self):
-        self._check(self._L.mpmc_trial_reject(self._h))
-        self._exchange = self._move = None
-        self._volume = False
+        try:
+            self._check(self._L.mpmc_trial_reject(self._h))
+        finally:  # (whatever the library answers, "no trial move is open" included, the object holds no trial afterwards)
+            self._exchange = self._move = None
+            self._volume = False
 
     def _scalar(self, fn) -> float:
         v = C.c_double()

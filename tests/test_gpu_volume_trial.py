@@ -18,6 +18,7 @@ import pytest
 
 import util
 from mpmcxx_amd import energy
+from volume_trial_cases import TERM_FIXTURES, host_scale  # (the one restatement of the move; shared with the follow-up tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +28,6 @@ ERR_ARG, ERR_INVALID_DATUM = -3, 6001
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def host_scale(atoms, basis, s):
-    """System::volume_change in Python floats: per molecule mass += m_i, cm[p] += m_i * pos_i[p] in atom order, cm[p] /= mass,
-    delta[p] = cm[p] * s - cm[p], pos_i[p] += delta[p]; every basis element times s"""
-    pos, mass = np.asarray(atoms["pos"], dtype=np.float64), np.asarray(atoms["mass"], dtype=np.float64)
-    new = pos.copy()
-    for a, b in util.molecules(atoms):
-        m, cm = 0.0, [0.0, 0.0, 0.0]
-        for i in range(a, b):
-            mi = float(mass[i])
-            m += mi
-            for p in range(3):
-                cm[p] += mi * float(pos[i, p])
-        for p in range(3):
-            cm[p] /= m
-            d = cm[p] * s - cm[p]
-            for i in range(a, b):
-                new[i, p] = float(pos[i, p]) + d
-    return new, np.asarray(basis, dtype=np.float64) * s
 
 
 def long_molecules():
@@ -132,10 +113,6 @@ def test_energy_against_oracle_and_fresh_context(boxes, name, s):
         S.reject()
     finally:
         S.close()
-
-
-TERM_FIXTURES = ["lj64_rc2", "ion216_triclinic_rdm_ljwh", "h2_64_sg", "water64_at", "water64_disp", "water64_polar_pef", "ion216_gs",
-                 "water64_polar_direct", "ion216_wolf"]
 
 
 @pytest.mark.parametrize("name", TERM_FIXTURES + ["ion64_es+autoreject"])
