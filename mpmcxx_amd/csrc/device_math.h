@@ -75,7 +75,10 @@ __device__ __forceinline__ double hstep(double p, double t, double c) {
 }
 
 // exp(x) = 2^k exp(r), k = rint(x log2 e), r = x - k ln2 (two-part ln2), exp(r) by the degree-11 polynomial of
-// tools/fit_erfcx.py on [-ln2/2, ln2/2] (rel. err 1.6e-15).  Arguments here are <= 0 (Gaussian, Thole damping).
+// tools/fit_erfcx.py on [-ln2/2, ln2/2] (rel. err 1.6e-15).  Arguments of either sign: <= 0 for the Gaussian and the Thole damping (down to
+// -1849 under polar_wolf, where ldexp returns 0), up to +1.7 for Silvera-Goldman's repulsion at contact and +7.2 for DREIDING's
+// exp(12 (1 - rho)) at rho = 0.4; nothing in the reduction depends on the sign.  tests/test_gpu_pair_scans.py walks these ranges on the device,
+// the points where rint switches included.
 __device__ __forceinline__ double exp_fast(double x) {
 	const double k = rint(x * 1.4426950408889634);
 	double r = fma(-k, 6.93147180369123816490e-01, x);

@@ -44,7 +44,7 @@ __device__ __forceinline__ double rdm_pair(const Box &bx, const RdModelParams &r
 	const double ri2 = min_image_sq<ORTHO>(bx, dx, dy, dz, ox, oy, oz);
 	if (!(ri2 <= rp.t_in)) return 0.0;
 	cnt += 1;
-	const RdMixed m = rd_mix<MIX>(a, b);
+	const RdMixed m = rd_mix<MIX, FORM>(a, b);
 	return rd_pair_energy<FORM>(m, ri2, FORM == RD_FORM_LJ ? rp.fh_order : 0, rp.fh_c2, rp.fh_c4, imu, ExpFast{});
 }
 

@@ -718,9 +718,12 @@ __device__ __forceinline__ void hyb_step(const Box &bx, const HybLds &L, const i
 		const double explr = exp_fast(-lr);
 		const double damp1 = fma(-explr, fma(lr, fma(0.5, lr, 1.0), 1.0), 1.0);
 		const double damp2 = fma(-explr, (lr * lr) * (lr * (1.0 / 6.0)), damp1);
-		const double live = (r2 > 0.0) ? mask * L.j[jl + 6 * kJ2] : 0.0;
-		t.x = live * (damp1 * ir3);
-		t.y = live * (3.0 * damp2 * ir5);
+		// coincident positions (a dummy site on an atom; an atom where the padding slots lie) give 1 / r = NaN: the entries are SELECTED to
+		// zero there, as the stored tensor's are (kernels_pair.hip) -- a product with a zero mask would keep the NaN
+		const bool apart = r2 > 0.0;
+		const double live = mask * L.j[jl + 6 * kJ2];
+		t.x = apart ? live * (damp1 * ir3) : 0.0;
+		t.y = apart ? live * (3.0 * damp2 * ir5) : 0.0;
 	}
 	const double mjx = L.j[jl + 3 * kJ2], mjy = L.j[jl + 4 * kJ2], mjz = L.j[jl + 5 * kJ2];
 	const double dj = t.y * fma(oz, mjz, fma(oy, mjy, ox * mjx));

@@ -197,20 +197,42 @@ constexpr double kDreidingGamma = 12.0; // DREIDING_GAMMA, System.Energy.cpp:209
 struct RdAtom {
 	double s, s2, s3, s6, sqe, e;
 };
-// The pair's mixed parameters.  No pow: Waldman-Hagler's sixth root is a square root and a cube root; one division (Halgren: one each for
+// The pair's mixed parameters.  No pow: Waldman-Hagler's sixth root is a square root and a cube root (DREIDING: and one correction, rd_sixth_root); one division (Halgren: one each for
 // sigma and epsilon, which keeps both within a few ulp of the reference's expressions); sqrt(e_i) sqrt(e_j) stands for the reference's
 // sqrt(e_i e_j) as in lj_mix.  A pair with a sigma of 0 gets sigma = 0 (rd_pair_energy returns 0 for it), never a division by zero.
 struct RdMixed {
 	double sigma, eps;
 };
-template <int MIX>
+// Waldman-Hagler's sigma as the reference gets it, pow(s6, 1. / 6.), from y = cbrt(sqrt(s6)): DREIDING tests r < 0.4 sigma (:2139), so a
+// sigma one ulp off moves a branch between MAXVALUE and a finite term.  y alone (two roundings, and the exact sixth root where the
+// reference's exponent is the double below 1 / 6) differs from pow in 64 % of 2e7 random pairs; one Newton step on y^6 = s6 with the
+// residual carried in two doubles, and the exponent's 9.25e-18 as a first-order factor, differs in 0.08 % (glibc's pow is not correctly
+// rounded either).  Only DREIDING takes it (rd_mix's FORM), the one FORM with a branch on sigma: under the LJ and 14-7 forms sigma stays y,
+// a value within an ulp of the reference's like every other mixed parameter here.  (Still open: the sigma rule of cavity_autoreject,
+// kernels_contact.hip, tests r < scale sigma with the LJ form's sigma, so under Waldman-Hagler that test can sit one ulp from the reference's.)
+MPMC_HD double rd_sixth_root(double x, double y) {
+	const double y2 = y * y, e2 = fma(y, y, -y2);
+	const double y3 = y2 * y, e3 = fma(y2, y, -y3) + e2 * y;
+	const double y6 = y3 * y3, e6 = fma(y3, y3, -y6) + 2.0 * (y3 * e3);
+	// x^(fl(1/6)) = x^(1/6) exp(-(1/6 - fl(1/6)) ln x): that factor is 6e-17 from 1, so a single-precision log2 is plenty (one instruction);
+	// 6 y^6 by additions and one literal in all: the triclinic walks have no scalar register to spare
+#if defined(__HIP_DEVICE_COMPILE__)
+	const double l2 = (double)__log2f((float)x);
+#else
+	const double l2 = (double)log2f((float)x);
+#endif
+	const double corr = y * (((x - y6) - e6) / (((y6 + y6) + y6) * 2.0) - 6.412899660930516e-18 * l2); // (1/6 - fl(1/6)) ln 2
+	return y + corr;
+}
+template <int MIX, int FORM = RD_FORM_LJ>
 MPMC_HD RdMixed rd_mix(const RdAtom &a, const RdAtom &b) {
 	RdMixed m;
 	const bool zero = (a.s == 0.0) || (b.s == 0.0);
 	const double ee = a.sqe * b.sqe;
 	if (MIX == RD_MIX_WALDMAN_HAGLER) { // :1072-1091: sigma^6 = (s_i^6 + s_j^6) / 2, eps = sqrt(e_i e_j) 2 s_i^3 s_j^3 / (s_i^6 + s_j^6)
 		const double s6 = 0.5 * (a.s6 + b.s6);
-		m.sigma = zero ? 0.0 : cbrt(sqrt(s6));
+		const double y = cbrt(sqrt(s6));
+		m.sigma = zero ? 0.0 : (FORM == RD_FORM_DREIDING ? rd_sixth_root(s6, y) : y);
 		m.eps = zero ? ee : (ee * (a.s3 * b.s3)) / s6;
 	} else if (MIX == RD_MIX_HALGREN) { // :1093-1106: sigma = (s_i^3 + s_j^3) / (s_i^2 + s_j^2), eps = 4 e_i e_j / (sqrt e_i + sqrt e_j)^2
 		const bool ezero = (a.e == 0.0) || (b.e == 0.0);

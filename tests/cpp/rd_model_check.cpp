@@ -19,7 +19,7 @@ struct HostExp {
 
 template <int FORM, int MIX>
 static void point(double si, double ei, double sj, double ej, double r) {
-	const RdMixed m = rd_mix<MIX>(atom(si, ei), atom(sj, ej));
+	const RdMixed m = rd_mix<MIX, FORM>(atom(si, ei), atom(sj, ej));
 	const double e = rd_pair_energy<FORM>(m, r * r, 0, 0.0, 0.0, 0.0, HostExp{});
 	std::printf("%d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", FORM, MIX, si, ei, sj, ej, r, m.sigma, m.eps, e);
 }
@@ -31,7 +31,7 @@ static void grid() {
 		for (int b = 0; b < 4; b++)
 			for (int c = 0; c < 4; c++) {
 				const double si = sig[a], ei = eps[a], sj = sig[b], ej = eps[c];
-				const RdMixed m = rd_mix<MIX>(atom(si, ei), atom(sj, ej));
+				const RdMixed m = rd_mix<MIX, FORM>(atom(si, ei), atom(sj, ej));
 				std::vector<double> rs = {0.9, 2.0, 3.0, 3.7, 5.0, 9.5, 12.0};
 				if (m.sigma > 0.0) { // the DREIDING contact threshold, from both sides
 					const double rc = 0.4 * m.sigma;
