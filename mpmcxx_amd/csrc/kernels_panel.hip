@@ -130,11 +130,24 @@ struct PanAcc {
 	double g[3];
 };
 
+// Skewed cell: what the image INDEX of a pair is made from.  The index is a predicate in all but name: the stored (a, b) of a pair come
+// from the sweep, which takes the reference's image, so the walk must contract them with the displacement of that very image.  On a
+// half-cell tie the reference's rint(((R[0][p] d0) + R[1][p] d1) + R[2][p] d2) is decided by the last bit of that sum: a fused sum, or the
+// sum of the pre-shifted displacement, lands on the other side of .5 for a few per cent of the ties.  So the index is rounded from the raw
+// displacement r (the i-atom where it lies) in the reference's association order, and the member's pre-shift is taken off as an integer:
+// n_shift[p] = (R sh)_p, the common index of direction p where the member has one and 0 where it has none.  Off a tie this is the integer
+// the fused sum of the pre-shifted displacement gave; the back-projection (values only) stays fused and keeps its operands.
+template <int NI>
+struct PanTri {
+	double r[NI][3];
+	double n_shift[NI][3];
+};
+
 // one step of the walk: every member against j = (lane + s) & 63 (LDS slot jl = lane + s, no wrap: the image holds every value twice)
 template <bool FAR, int NU, int NI, bool ROT, bool PAD, bool TRI>
 __device__ __forceinline__ void pan_step(const Box &bx, const double2 *__restrict__ s_xy, const double2 *__restrict__ s_zm, const double2 *__restrict__ s_mm,
                                          const double *__restrict__ s_valid, const int jl, const int src4, const double (&L)[3],
-                                         const double (&iL)[3], const double (&q)[NI][3], const double (&m)[NI][3], const double2 (&t)[NI],
+                                         const double (&iL)[3], const PanTri<NI> &T, const double (&q)[NI][3], const double (&m)[NI][3], const double2 (&t)[NI],
                                          PanAcc<NI> &A) {
 	const double2 xy = s_xy[jl], zm = s_zm[jl], mm = s_mm[jl];
 	const double xj = xy.x, yj = xy.y, zj = zm.x, mjx = zm.y, mjy = mm.x, mjz = mm.y;
@@ -144,18 +157,18 @@ __device__ __forceinline__ void pan_step(const Box &bx, const double2 *__restric
 	for (int k = 0; k < NI; ++k) {
 		double ox = q[k][0] - xj, oy = q[k][1] - yj, oz = q[k][2] - zj;
 		if (TRI) { // general cell: NU is the MASK of the lattice directions without a tile-pair-wide image index; each one costs the row of R,
-			// rint and the lattice vector (values only: nothing here is a predicate)
-			const double dx = ox, dy = oy, dz = oz;
+			// rint and the lattice vector.  The index is the reference's (PanTri); the back-projection is values only
+			const double dx = T.r[k][0] - xj, dy = T.r[k][1] - yj, dz = T.r[k][2] - zj;
 			if (NU & 1) {
-				const double n0 = rint(fma(bx.r[6], dz, fma(bx.r[3], dy, bx.r[0] * dx)));
+				const double n0 = rint(((bx.r[0] * dx) + bx.r[3] * dy) + bx.r[6] * dz) - T.n_shift[k][0];
 				ox = fma(-n0, bx.b[0], ox), oy = fma(-n0, bx.b[1], oy), oz = fma(-n0, bx.b[2], oz);
 			}
 			if (NU & 2) {
-				const double n1 = rint(fma(bx.r[7], dz, fma(bx.r[4], dy, bx.r[1] * dx)));
+				const double n1 = rint(((bx.r[1] * dx) + bx.r[4] * dy) + bx.r[7] * dz) - T.n_shift[k][1];
 				ox = fma(-n1, bx.b[3], ox), oy = fma(-n1, bx.b[4], oy), oz = fma(-n1, bx.b[5], oz);
 			}
 			if (NU & 4) {
-				const double n2 = rint(fma(bx.r[8], dz, fma(bx.r[5], dy, bx.r[2] * dx)));
+				const double n2 = rint(((bx.r[2] * dx) + bx.r[5] * dy) + bx.r[8] * dz) - T.n_shift[k][2];
 				ox = fma(-n2, bx.b[6], ox), oy = fma(-n2, bx.b[7], oy), oz = fma(-n2, bx.b[8], oz);
 			}
 		} else {
@@ -206,7 +219,7 @@ __device__ __forceinline__ void pan_step(const Box &bx, const double2 *__restric
 template <bool FAR, int NU, int NI, int PIPE, bool TRI>
 __device__ __forceinline__ void pan_walk(const Box &bx, const double2 *__restrict__ s_xy, const double2 *__restrict__ s_zm, const double2 *__restrict__ s_mm,
                                          const double *__restrict__ s_valid, const bool pad, const int lane, const int src4,
-                                         const double (&L)[3], const double (&iL)[3], const double (&q)[NI][3], const double (&m)[NI][3],
+                                         const double (&L)[3], const double (&iL)[3], const PanTri<NI> &T, const double (&q)[NI][3], const double (&m)[NI][3],
                                          const double2 *__restrict__ ab, const size_t (&ab_tile)[NI], const int s_first, const int n_steps,
                                          PanAcc<NI> &A) {
 	int jb = lane + s_first;
@@ -215,10 +228,10 @@ __device__ __forceinline__ void pan_walk(const Box &bx, const double2 *__restric
 #define MPMC_FAR_LOOP(P)                                                                                                               \
 	for (int kc = 0; kc < n_steps - 4; kc += 4, jb += 4) {                                                                             \
 		_Pragma("unroll") for (int u = 0; u < 4; ++u)                                                                                  \
-		    pan_step<true, NU, NI, true, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, q, m, none, A);                      \
+		    pan_step<true, NU, NI, true, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, T, q, m, none, A);                      \
 	}                                                                                                                                  \
-	_Pragma("unroll") for (int u = 0; u < 3; ++u) pan_step<true, NU, NI, true, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, q, m, none, A); \
-	pan_step<true, NU, NI, false, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + 3, src4, L, iL, q, m, none, A);
+	_Pragma("unroll") for (int u = 0; u < 3; ++u) pan_step<true, NU, NI, true, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, T, q, m, none, A); \
+	pan_step<true, NU, NI, false, P, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + 3, src4, L, iL, T, q, m, none, A);
 		if (pad) { // wave-uniform: only the panels whose j-tile is the padded last tile
 			MPMC_FAR_LOOP(true)
 		} else {
@@ -245,7 +258,7 @@ __device__ __forceinline__ void pan_walk(const Box &bx, const double2 *__restric
 			double2 t[NI];
 #pragma unroll
 			for (int k = 0; k < NI; ++k) t[k] = buf[k][u];
-			pan_step<false, NU, NI, true, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, q, m, t, A);
+			pan_step<false, NU, NI, true, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, T, q, m, t, A);
 #pragma unroll
 			for (int k = 0; k < NI; ++k) buf[k][u] = ld_stream<true>(ab + ab_tile[k] + voff + u * kTile); // refill in place
 			__builtin_amdgcn_sched_barrier(0);
@@ -256,8 +269,8 @@ __device__ __forceinline__ void pan_walk(const Box &bx, const double2 *__restric
 		double2 t[NI];
 #pragma unroll
 		for (int k = 0; k < NI; ++k) t[k] = buf[k][u];
-		if (u != PIPE - 1) pan_step<false, NU, NI, true, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, q, m, t, A);
-		else pan_step<false, NU, NI, false, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, q, m, t, A);
+		if (u != PIPE - 1) pan_step<false, NU, NI, true, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, T, q, m, t, A);
+		else pan_step<false, NU, NI, false, false, TRI>(bx, s_xy, s_zm, s_mm, s_valid, jb + u, src4, L, iL, T, q, m, t, A);
 		__builtin_amdgcn_sched_barrier(0);
 	}
 }
@@ -306,6 +319,7 @@ __device__ __forceinline__ void panel_block(const AtomsDev &at, const Box &bx, c
 		s_valid[lane] = s_valid[lane + kTile] = (at.mf[j0 + lane].y & AF_PAD) ? 0.0 : 1.0;
 	}
 	double q[NI][3], m[NI][3];
+	PanTri<NI> T = {};
 	size_t ab_tile[NI]; // wave-uniform element offset of each member's 64 x 64 block of the store
 	int Is[NI];
 #pragma unroll
@@ -322,6 +336,11 @@ __device__ __forceinline__ void panel_block(const AtomsDev &at, const Box &bx, c
 		q[k][0] = xp[0][a4] - pick(sx, sy, sz, p0);
 		q[k][1] = xp[1][a4] - pick(sx, sy, sz, p1);
 		q[k][2] = xp[2][a4] - pick(sx, sy, sz, p2);
+		if (!ORTHO) { // (p0, p1, p2 = x, y, z here) the raw position and the integers of the shift, for the image index: PanTri
+			T.r[k][0] = xp[0][a4], T.r[k][1] = xp[1][a4], T.r[k][2] = xp[2][a4];
+#pragma unroll
+			for (int p = 0; p < 3; ++p) T.n_shift[k][p] = rint(((bx.r[p] * sh.x) + bx.r[3 + p] * sh.y) + bx.r[6 + p] * sh.z);
+		}
 		m[k][0] = mp[0][a3];
 		m[k][1] = mp[1][a3];
 		m[k][2] = mp[2][a3];
@@ -332,8 +351,8 @@ __device__ __forceinline__ void panel_block(const AtomsDev &at, const Box &bx, c
 	// the waves split the walk: 64 / kPanelWaves steps each of the 64 of an off-diagonal tile pair (s = 0..63), 32 / kPanelWaves of the 32 of a diagonal one (s = 1..32)
 	const int n_steps = (diag ? 32 : 64) / kPanelWaves, s_first = (diag ? 1 : 0) + w * n_steps;
 	PanAcc<NI> A = {};
-#define MPMC_PWALK(F, N) pan_walk<F, N, NI, PIPE, false>(bx, s_xy, s_zm, s_mm, s_valid, pad, lane, src4, L, iL, q, m, ab, ab_tile, s_first, n_steps, A)
-#define MPMC_PWALK_TRI(F, M) pan_walk<F, M, NI, PIPE, true>(bx, s_xy, s_zm, s_mm, s_valid, pad, lane, src4, L, iL, q, m, ab, ab_tile, s_first, n_steps, A)
+#define MPMC_PWALK(F, N) pan_walk<F, N, NI, PIPE, false>(bx, s_xy, s_zm, s_mm, s_valid, pad, lane, src4, L, iL, T, q, m, ab, ab_tile, s_first, n_steps, A)
+#define MPMC_PWALK_TRI(F, M) pan_walk<F, M, NI, PIPE, true>(bx, s_xy, s_zm, s_mm, s_valid, pad, lane, src4, L, iL, T, q, m, ab, ab_tile, s_first, n_steps, A)
 	if (!ORTHO && nu > 0) { // skewed cell: the far-field walk per mask of directions without a common index; the (few) stored ones take all three
 		if (far) {
 			switch (nonuni) {

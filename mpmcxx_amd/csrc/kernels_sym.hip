@@ -599,7 +599,8 @@ __global__ __launch_bounds__(256) void k_classify(const double *__restrict__ tb,
 			}
 			// B^T img over the lattice directions with a common index, summed as the reference sums it (x + 0.0 = x: with all three common
 			// this IS the reference's translation, which is what the pair sweep needs -- it uses a skewed tile pair's shift only then; the
-			// Jacobi walk, values only, takes the partial sums too and rounds the remaining indices per pair)
+			// Jacobi panel walk takes the partial sums too, as a pre-shift of the VALUES only: the remaining indices it rounds per pair from
+			// the raw displacement, as the reference does, and takes rint(R sh) off them -- kernels_panel.hip, PanTri)
 			for (int p = 0; p < 3; ++p) sh[p] = ((bx.b[p] * img[0]) + bx.b[3 + p] * img[1]) + bx.b[6 + p] * img[2];
 		}
 		tp_shift[t] = make_double4(sh[0], sh[1], sh[2], band);

@@ -11,15 +11,16 @@ of eps rather than cond(A) eps.  Atoms with alpha == 0 are left out of the syste
 import numpy as np
 
 from oracle import OracleSystem, pbc_update
+from three_body_ref import min_image
 
 
 def minimum_image(pos, basis):
-    """d[i, j] = minimum image of pos[i] - pos[j] the reference's way: d - basis^T rint(recip^T d) (System.cpp:1231-1241)"""
+    """d[i, j] = minimum image of pos[i] - pos[j] the reference's way: d - basis^T rint(recip^T d) (System.cpp:1231-1241), each sum in
+    the reference's association order (three_body_ref.min_image).  A matrix product leaves the order, and whether the sums are fused,
+    to the BLAS: at a half-cell tie of a skewed cell that is another image (test_lattice_tie_preconditions)."""
     R, _, _ = pbc_update(basis)
     b = np.asarray(basis, dtype=np.float64).reshape(3, 3)
-    d = pos[:, None, :] - pos[None, :, :]
-    img = np.rint(d @ np.asarray(R).reshape(3, 3))
-    return d - img @ b
+    return min_image(b, np.asarray(R, dtype=np.float64).reshape(3, 3), pos[:, None, :] - pos[None, :, :])
 
 
 def amatrix(atoms, basis, opts, dtype=np.float64):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """One system at a time (what System::mc sees): wall time per evaluation of BASELINE configs[2] / configs[3] under a list of
-mpmc_debug_configure variants, interleaved three times.  usage: python tools/alone_ab.py "label:key=v,key=v" ..."""
+mpmc_debug_configure variants, interleaved three times.  usage: python tools/alone_ab.py [--box NAME[:REPS]] ... "label:key=v,key=v" ...
+--box: a gen_box fixture in place of the two BASELINE boxes (e.g. --box ion8000_triclinic:60); the library is the one MPMC_ENERGY_LIB
+names, so two builds are compared by two runs in one session."""
 import os
 import sys
 import tempfile
@@ -10,9 +12,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from mpmcxx_amd import energy, gen_box, pqr  # noqa: E402
 
-specs = sys.argv[1:] or ["default:"]
+args = sys.argv[1:]
+boxes = []
+while "--box" in args:
+    k = args.index("--box")
+    name, _, reps = args[k + 1].partition(":")
+    boxes.append((name, int(reps or 60)))
+    del args[k:k + 2]
+specs = args or ["default:"]
 wd = tempfile.mkdtemp()
-for name, reps in (("ion10k_es", 300), ("ion10k_polar", 60)):
+for name, reps in boxes or (("ion10k_es", 300), ("ion10k_polar", 60)):
     inp, _ = gen_box.materialize(name, wd)
     atoms, basis, opts = pqr.load_case(inp)
     systems = {}
